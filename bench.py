@@ -6,13 +6,24 @@ all-reduce + clip 1.0 + RAdamScheduleFree + bf16 weight refresh), synthetic 64x6
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  value = line-images/s of the whole job (all ranks), inputs resident in HBM.
+Prints ONE JSON line (rank 0).  value = line-images/s of the whole job (all ranks), inputs resident in HBM;
+ms_per_step = wall time of one timed step.  A plain run sets up, warms up, times --steps steps and prints the line;
+`roofline`, `cpu_baseline` and `config.untrimmed` are null in it.
+
+--full adds the side measurements (the headline is then timed with the roofline's events in place):
 roofline: the bf16 MFMA GEMM family gemm_nt_kernel<*> (every nn.Linear forward and input-gradient), timed live
 with HIP events inside the timed region (kzv_prof_*: every s-th launch is bracketed -- a bracket costs ~2 us of stream
 time; s is the first of 4, 5, 3, 7 co-prime to the family's launches per step, counted in one untimed step, so that every
 launch site is sampled equally often), priced by its
-algorithmic 2*M*N*K FLOPs against the 2.5 PFLOP/s dense bf16 peak of /opt/skills/guides/MI355X_MICROARCH.md.
+algorithmic 2*M*N*K FLOPs against the 2.5 PFLOP/s dense bf16 peak of the MI355X.
+untrimmed: the same step with every decoder position computed, a few steps after the timed region (one GPU).
 cpu_baseline: oracle/trocr_oracle.py (a port, not the reference) timed on this box's host cores, rank 0, N=1.
+
+--dump-outputs DIR (rank 0) writes what the LAST timed step computed, before anything else runs on the model:
+loss.npy (float32 [1]), grad_norm.npy (float64 [1], the norm the clip saw), and params.npy / grads.npy (float32, the
+flat parameters after the optimizer step and the step's gradients) -- whole if they fit DUMP_SAMPLE elements, else at
+the same DUMP_SAMPLE sorted positions drawn with numpy's default_rng(DUMP_SEED).  Inputs, initial weights and dropout
+seeds are fixed by the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -32,6 +43,8 @@ for p in (ROOT, os.path.join(ROOT, "kuzushiji-vision_amd")):
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA, MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_FP8_TFLOPS = 5000.0    # dense fp8 (block-scaled MFMA), same table
+DUMP_SAMPLE = 1 << 22       # elements per sampled --dump-outputs array (16 MB of float32)
+DUMP_SEED = 0
 
 
 def train_flops_per_image(cfg, T):
@@ -159,6 +172,27 @@ def pick_stride(launches_per_step: int) -> int:
     return next((c for c in (4, 5, 3, 7, 9, 11) if math.gcd(c, max(launches_per_step, 1)) == 1), 1)
 
 
+def dump_outputs(out_dir, model, opt, loss):
+    """--dump-outputs: the last timed step's results as float32 / float64 .npy files (module docstring)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = model.flat_params.numel()
+    pos = None
+    if n > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        pos = torch.from_numpy(pos).to(model.flat_params.device)
+
+    def pick(t):
+        return (t if pos is None else t.index_select(0, pos)).float().cpu().numpy()
+    arrays = {"loss": loss.detach().float().cpu().numpy().reshape(1),
+              "grad_norm": np.array([opt.grad_norm()], dtype=np.float64),
+              "params": pick(model.flat_params),
+              "grads": pick(model.flat_grads)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -176,7 +210,12 @@ def main():
                     help="side measurement (configs[4], second half): the encoder's QKV / fc1 / fc2 forward GEMMs on e4m3 operands; "
                          "NOT the benchmark line, which is bf16")
     ap.add_argument("--label-len", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (events inside the timed region + one untimed step), the untrimmed step and the "
+                         "CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, gradient norm and (sampled) parameters / gradients to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-batch", type=int, default=16, help="the survey probe's batch (BASELINE.md section 2)")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--dp-rehearsal", action="store_true",
@@ -236,7 +275,7 @@ def main():
     barrier()
     # Timed region: HIP events bracket every launch of the reported kernel family only (each bracket costs ~2 us of
     # stream time; gemm_tn / attention are measured in one extra, untimed step below).
-    events = not os.environ.get("KZV_BENCH_NO_EVENTS")     # dev knob: step time without any per-launch events
+    events = args.full and not os.environ.get("KZV_BENCH_NO_EVENTS")     # dev knob: step time without any per-launch events
     stride = int(os.environ.get("KZV_BENCH_EVENT_STRIDE", "0"))
     if events and stride <= 0:
         # every s-th launch is bracketed; s must be coprime with the family's launches per step, or the sample only ever sees the
@@ -258,10 +297,14 @@ def main():
         loss = stepper.step(batch, i)
     barrier()
     dt = time.perf_counter() - t0
-    L.check(lib.kzv_prof_enable(0, 0), "prof_disable")
     nt_ms, nt_fl, nt_n = C.c_double(), C.c_double(), C.c_int64()
-    L.check(lib.kzv_prof_collect(0, C.byref(nt_ms), C.byref(nt_fl), C.byref(nt_n)), "prof_collect")
-    nt_seen = int(lib.kzv_prof_seen(0))
+    nt_seen = 0
+    if args.full:
+        L.check(lib.kzv_prof_enable(0, 0), "prof_disable")
+        L.check(lib.kzv_prof_collect(0, C.byref(nt_ms), C.byref(nt_fl), C.byref(nt_n)), "prof_collect")
+        nt_seen = int(lib.kzv_prof_seen(0))
+    if args.dump_outputs and rank == 0:                    # before any other step touches the model
+        dump_outputs(args.dump_outputs, model, opt, loss)
     if events:                                             # untimed: one more step for the other kernel families
         L.check(lib.kzv_prof_sample(1), "prof_sample")
         L.check(lib.kzv_prof_select((1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)), "prof_select")
@@ -273,7 +316,7 @@ def main():
     # The reference computes every decoder position (trocr_model.py:274-292); the headline skips the columns that are padding in
     # every sample of the batch (exact).  The same step with the trim off, a few steps outside the headline's timed region:
     untrimmed = None
-    if world == 1 and getattr(model, "trim_padding", False) and not os.environ.get("KZV_BENCH_NO_UNTRIMMED"):
+    if args.full and world == 1 and getattr(model, "trim_padding", False) and not os.environ.get("KZV_BENCH_NO_UNTRIMMED"):
         t_trim = getattr(model, "last_active_length", args.label_len - 1)
         model.trim_padding = False
         for i in range(2):
@@ -322,34 +365,46 @@ def main():
     if rank == 0:
         imgs = args.batch * world * args.steps
         T = args.label_len - 1
-        ms, fl, n = nt_ms.value, nt_fl.value, nt_n.value
-        ach = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
         t_act = getattr(model, "last_active_length", T)     # decoder positions actually computed (trailing all-pad columns trimmed)
-        step_flops = train_flops_per_image(cfg, t_act) * args.batch
-        others = {}
-        for kind, name in ((1, "gemm_tn_kernel"), (2, "attn_fwd_kernel"), (3, "attn_bwd_kernel")):
-            m2, f2, n2 = collect(kind)
-            others[name] = {"ms_per_step": m2, "TFLOP/s": (f2 / (m2 * 1e-3) / 1e12) if m2 > 0 else 0.0,
-                            "launches_per_step": n2, "measured": "one extra step outside the timed region"}
-        if args.fp8:
-            m2, f2, n2 = collect(4)
-            others["gemm_nt_fp8_kernel"] = {"ms_per_step": m2, "TFLOP/s": (f2 / (m2 * 1e-3) / 1e12) if m2 > 0 else 0.0, "launches_per_step": n2,
-                                            "peak": PEAK_FP8_TFLOPS, "frac": (f2 / (m2 * 1e-3) / 1e12 / PEAK_FP8_TFLOPS) if m2 > 0 else 0.0,
-                                            "measured": "one extra step outside the timed region"}
         DECPOS = (f"{t_act} of {T} computed: columns that are padding in every sample of the batch are skipped (exact: masked "
                   "keys, ignored targets); labels hold U{8..60} characters (BASELINE.md section 4)")
-        # HBM-side bytes per launch come from rocprofv3 PMC passes (they cannot be collected from inside this process):
-        # quoted only from a profile of THIS workload taken on THESE kernel sources (tools/hbm_traffic.py records their hash),
-        # null otherwise -- never from a stale file
-        traffic, traffic_src = None, None
-        import glob
-        for tj in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True):
-            j = json.load(open(tj))
-            if j.get("source_sha16") == source_sha16() and args.batch == 256 and args.dec_layers == 6 and args.encoder == "vit_b" and not args.fp8 and not args.wide_decoder:
-                k = j["kernels"].get("gemm_nt_kernel<*>")
-                if k:
-                    traffic, traffic_src = k["fetch_bytes_per_launch"] + k["write_bytes_per_launch"], os.path.relpath(tj, ROOT)
-                    break
+        roofline = None
+        if args.full:
+            ms, fl, n = nt_ms.value, nt_fl.value, nt_n.value
+            ach = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            step_flops = train_flops_per_image(cfg, t_act) * args.batch
+            others = {}
+            for kind, name in ((1, "gemm_tn_kernel"), (2, "attn_fwd_kernel"), (3, "attn_bwd_kernel")):
+                m2, f2, n2 = collect(kind)
+                others[name] = {"ms_per_step": m2, "TFLOP/s": (f2 / (m2 * 1e-3) / 1e12) if m2 > 0 else 0.0,
+                                "launches_per_step": n2, "measured": "one extra step outside the timed region"}
+            if args.fp8:
+                m2, f2, n2 = collect(4)
+                others["gemm_nt_fp8_kernel"] = {"ms_per_step": m2, "TFLOP/s": (f2 / (m2 * 1e-3) / 1e12) if m2 > 0 else 0.0, "launches_per_step": n2,
+                                                "peak": PEAK_FP8_TFLOPS, "frac": (f2 / (m2 * 1e-3) / 1e12 / PEAK_FP8_TFLOPS) if m2 > 0 else 0.0,
+                                                "measured": "one extra step outside the timed region"}
+            # HBM-side bytes per launch come from rocprofv3 PMC passes (they cannot be collected from inside this process):
+            # quoted only from a profile of THIS workload taken on THESE kernel sources (tools/hbm_traffic.py records their hash),
+            # null otherwise -- never from a stale file
+            traffic, traffic_src = None, None
+            import glob
+            for tj in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True):
+                j = json.load(open(tj))
+                if j.get("source_sha16") == source_sha16() and args.batch == 256 and args.dec_layers == 6 and args.encoder == "vit_b" and not args.fp8 and not args.wide_decoder:
+                    k = j["kernels"].get("gemm_nt_kernel<*>")
+                    if k:
+                        traffic, traffic_src = k["fetch_bytes_per_launch"] + k["write_bytes_per_launch"], os.path.relpath(tj, ROOT)
+                        break
+            roofline = {"bound": "mfma", "kernel": "gemm_nt_kernel<*> (bf16 MFMA 16x16x32, all nn.Linear fwd + dgrad)",
+                        "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
+                        "traffic": traffic, "traffic_unit": f"bytes/launch (L2-miss fetch x2-corrected + write, rocprofv3 PMC, {traffic_src}; null = no profile of these kernel sources)",
+                        "launches_per_step": nt_seen / args.steps, "avg_launch_us": (ms / n * 1e3) if n else None,
+                        "kernel_ms_per_step": (ms / n * nt_seen / args.steps) if n else None,
+                        "events": f"every {stride}th launch bracketed inside the timed region ({n} of {nt_seen} launches)",
+                        "source_sha16": source_sha16(),
+                        "whole_step_TFLOP/s": step_flops / (dt / args.steps) / 1e12,
+                        "whole_step_frac": step_flops / (dt / args.steps) / 1e12 / PEAK_BF16_TFLOPS,
+                        "other_kernels": others}
         out = {
             "metric": "line-images/sec (train)", "value": imgs / dt, "unit": "img/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -363,18 +418,9 @@ def main():
                        "decoder_positions": DECPOS,
                        "untrimmed": untrimmed,
                        "final_loss": final_loss},
-            "roofline": {"bound": "mfma", "kernel": "gemm_nt_kernel<*> (bf16 MFMA 16x16x32, all nn.Linear fwd + dgrad)",
-                         "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
-                         "traffic": traffic, "traffic_unit": f"bytes/launch (L2-miss fetch x2-corrected + write, rocprofv3 PMC, {traffic_src}; null = no profile of these kernel sources)",
-                         "launches_per_step": nt_seen / args.steps, "avg_launch_us": (ms / n * 1e3) if n else None,
-                         "kernel_ms_per_step": (ms / n * nt_seen / args.steps) if n else None,
-                         "events": f"every {stride}th launch bracketed inside the timed region ({n} of {nt_seen} launches)",
-                         "source_sha16": source_sha16(),
-                         "whole_step_TFLOP/s": step_flops / (dt / args.steps) / 1e12,
-                         "whole_step_frac": step_flops / (dt / args.steps) / 1e12 / PEAK_BF16_TFLOPS,
-                         "other_kernels": others},
+            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args.label_len, args.cpu_sample_batch, args.cpu_steps)
         else:
             out["cpu_baseline"] = None

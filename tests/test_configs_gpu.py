@@ -367,6 +367,39 @@ def test_bench_multi_rank_path_rehearsal(tmp_path):
     assert d["value"] > 0 and d["steps"] == 2 and np.isfinite(d["config"]["final_loss"]) and d["cpu_baseline"] is None
 
 
+def test_bench_plain_line_dump_outputs_and_full(tmp_path):
+    """A plain `bench.py` run times the headline only (roofline, untrimmed step and CPU baseline null); --dump-outputs writes
+    the last timed step's loss, gradient norm and the seeded parameter / gradient sample as float .npy files, the same for
+    two runs with the same arguments up to float-atomic order; --full adds the roofline and the untrimmed step."""
+    import json
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--batch", "16", *extra], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    dumps = []
+    for k in range(2):
+        d = run("--dump-outputs", str(tmp_path / f"plain{k}"))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["config"]["untrimmed"] is None
+        files = {f: np.load(tmp_path / f"plain{k}" / f"{f}.npy") for f in ("loss", "grad_norm", "params", "grads")}
+        assert sum(os.path.getsize(tmp_path / f"plain{k}" / f"{f}.npy") for f in files) < 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert files["loss"].shape == (1,) and float(files["loss"][0]) == d["config"]["final_loss"] and files["grad_norm"][0] > 0
+        assert files["params"].shape == files["grads"].shape and files["params"].size > 1 << 20
+        dumps.append(files)
+    a, b = dumps
+    assert abs(float(a["loss"][0]) - float(b["loss"][0])) < 1e-4
+    assert np.abs(a["grads"] - b["grads"]).max() <= 1e-2 * np.abs(a["grads"]).max()
+    assert np.abs(a["params"] - b["params"]).max() <= 1e-3 * np.abs(a["params"]).max()
+    d = run("--full", "--no-cpu-baseline")
+    assert d["steps"] == 2 and d["roofline"]["frac"] > 0 and d["roofline"]["other_kernels"] and d["config"]["untrimmed"]["value"] > 0
+
+
 def test_labels_longer_than_the_position_table_are_refused(tmp_path):
     """RoBERTa position ids run to (non-pad decoder inputs) + pad_id and index a [max_pos, H] table (HF
     modeling_roberta.py:142-155): the reference raises IndexError for longer labels.  The host mirror raises the same for

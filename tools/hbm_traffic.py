@@ -1,8 +1,8 @@
 """Turns two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of bench.py into per-kernel HBM-side bytes per launch.
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  python tools/hbm_traffic.py gpurun_out/pmc_fetch/*/*_counter_collection.csv gpurun_out/pmc_write/*/*_counter_collection.csv > profiles/rNN_hbm_traffic.json
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  python tools/hbm_traffic.py $OUT/pmc_fetch/*/*_counter_collection.csv $OUT/pmc_write/*/*_counter_collection.csv > profiles/rNN_hbm_traffic.json
 
 Corrections (MI355X_MICROARCH.md, HBM / rocprofv3 section): the counters are in KiB on gfx950 and FETCH_SIZE reads
 half the true value (x2).  The three gemm_nt kernels (gemm_nt_kernel, gemm_nt256_kernel, gemm_nt256p_kernel) are
@@ -65,7 +65,7 @@ def main():
             "write_bytes_per_launch": sum(out[k]["write_bytes_per_launch"] * out[k]["launches"] for k in fam) / nl}
     print(json.dumps({
         "source_sha16": source_sha16(),
-        "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline (two separate passes), tools/hbm_traffic.py",
+        "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (two separate passes), tools/hbm_traffic.py",
         "corrections": "counter unit KiB; FETCH_SIZE x2 on gfx950 (MI355X_MICROARCH.md, HBM section)",
         "note": "FETCH_SIZE counts L2-side fabric requests (Infinity-Cache hits included), i.e. L2 misses, an upper bound on HBM reads",
         "kernels": out}, indent=1))
