@@ -493,8 +493,9 @@ int kzv_debug_attn_dropout_mask(uint32_t key, float p, int64_t pairs, int32_t Sq
  * double their time when a concurrently running collective holds a few CUs.  With n > 0 the launchers leave n CUs
  * free: gemm_nt falls back to the one-tile-per-workgroup kernel (its workgroups flow to whatever CUs are free) and
  * gemm_tn256 sizes its token splits to (CUs - n) workgroups.  Default 0 (or KZV_CU_RESERVE); kzv/trainer.py sets it
- * when world_size > 1. */
+ * when world_size > 1.  kzv_get_cu_reserve returns the value in force (so that a caller can restore it). */
 int kzv_set_cu_reserve(int n);
+int kzv_get_cu_reserve(void);
 
 /* ------------------------------------------------------------------ N2: input pipeline on the device
  * Replaces ResizeWithPadding + ToTensor + Normalize(0.5, 0.5) (src/data/trocr_dataset.py:24-53, 97-104) for a batch of

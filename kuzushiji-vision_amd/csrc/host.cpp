@@ -62,6 +62,7 @@ extern "C" int kzv_set_cu_reserve(int n) {
     g_cu_reserve = n;
     return KZV_OK;
 }
+extern "C" int kzv_get_cu_reserve(void) { return kzv_cu_reserve(); }
 extern "C" int kzv_version(void) { return 1; }
 
 // ------------------------------------------------------------------------------------------ profiling

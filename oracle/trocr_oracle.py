@@ -1,7 +1,7 @@
 """ORACLE (test infrastructure -- never imported by the product path).
 
-CPU restatement, in plain torch ops (fp32 by default, fp64 on request), of the reference's
-TrOCR training path.  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
+Restatement, in plain torch ops (fp32 by default, fp64 on request), of the reference's
+TrOCR training path; it runs on the CPU (where the golden fixtures pin it) or on any torch device.  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 ``cpu_baseline`` leg may import this module.
 
 Parity status: PINNED for forward / loss / gradients by ``tests/golden/*.npz``, which were
@@ -228,9 +228,9 @@ def decoder_forward(cfg, sd, input_ids, enc, stages=None, masks=None):
     if stages is not None:
         stages["dec_embed"] = x
     neg = torch.finfo(x.dtype).min
-    causal = torch.ones(T, T, dtype=torch.bool).tril()
+    causal = torch.ones(T, T, dtype=torch.bool, device=input_ids.device).tril()
     keep = causal[None, None, :, :] & (input_ids != cfg.pad_id)[:, None, None, :]
-    mask = torch.zeros(B, 1, T, T, dtype=x.dtype).masked_fill(~keep, neg)
+    mask = torch.zeros(B, 1, T, T, dtype=x.dtype, device=x.device).masked_fill(~keep, neg)
     nh = cfg.dec_heads
     for i in range(cfg.dec_layers):
         p = r + f"encoder.layer.{i}."
@@ -272,29 +272,31 @@ def forward(cfg, sd, pixel_values, labels, stages=None, masks=None, fp8=None):
     return logits, loss
 
 
-def leaf_state_dict(sd_np, dtype=torch.float32, requires_grad=True):
-    """numpy HF-named dict -> torch leaves; tied aliases dropped (they share storage)."""
+def leaf_state_dict(sd_np, dtype=torch.float32, requires_grad=True, device="cpu"):
+    """numpy HF-named dict -> torch leaves on ``device``; tied aliases dropped (they share storage)."""
     out = {}
     for k, v in sd_np.items():
         if k.startswith("decoder.lm_head.decoder."):
             continue
-        t = torch.tensor(v, dtype=dtype)
+        t = torch.tensor(v, dtype=dtype, device=device)
         t.requires_grad_(requires_grad)
         out[k] = t
     return out
 
 
-def forward_backward(cfg, sd_np, pixel_values, labels, dtype=torch.float32, want_stages=False, masks=None, fp8=None):
-    """One teacher-forced step; returns dict(logits, loss, grads{hf_name: ndarray}, stages)."""
-    sd = leaf_state_dict(sd_np, dtype)
+def forward_backward(cfg, sd_np, pixel_values, labels, dtype=torch.float32, want_stages=False, masks=None, fp8=None, device="cpu"):
+    """One teacher-forced step on ``device`` (the same arithmetic on any device; the golden fixtures pin it on the CPU);
+    returns dict(logits, loss, grads{hf_name: ndarray}, stages), all on the host."""
+    sd = leaf_state_dict(sd_np, dtype, device=device)
     stages = {} if want_stages else None
     if masks is not None:
-        masks = {k: torch.as_tensor(v) for k, v in masks.items()}
-    logits, loss = forward(cfg, sd, torch.as_tensor(pixel_values).to(dtype), torch.as_tensor(labels), stages, masks, fp8)
+        masks = {k: torch.as_tensor(v).to(device) for k, v in masks.items()}
+    px = torch.as_tensor(pixel_values).to(device=device, dtype=dtype)
+    logits, loss = forward(cfg, sd, px, torch.as_tensor(labels).to(device), stages, masks, fp8)
     loss.backward()
-    grads = {k: (v.grad.detach().numpy() if v.grad is not None else None) for k, v in sd.items()}
-    return {"logits": logits.detach().numpy(), "loss": float(loss.detach()), "grads": grads,
-            "stages": {k: v.detach().numpy() for k, v in (stages or {}).items()}}
+    grads = {k: (v.grad.detach().cpu().numpy() if v.grad is not None else None) for k, v in sd.items()}
+    return {"logits": logits.detach().cpu().numpy(), "loss": float(loss.detach()), "grads": grads,
+            "stages": {k: v.detach().cpu().numpy() for k, v in (stages or {}).items()}}
 
 
 # ---- runtime policy restated: clip + optimizer --------------------------------

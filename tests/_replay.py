@@ -29,21 +29,21 @@ def _mask(seed: int, site: int, p: float, rows: int, cols: int, ld: int | None =
     return out
 
 
-def step_masks(cfg, seed: int, B: int, T: int) -> dict[str, torch.Tensor]:
-    """Masks of kzv_forward_loss(train=1, seed) for a batch of B crops and a decoder of T (= active) positions."""
+def step_masks(cfg, seed: int, B: int, T: int, device="cpu") -> dict[str, torch.Tensor]:
+    """Masks of kzv_forward_loss(train=1, seed) for a batch of B crops and a decoder of T (= active) positions, on ``device``."""
     Se, He, Hd, npatch = cfg.enc_seq, cfg.enc_hidden, cfg.dec_hidden, cfg.num_patches
     m: dict[str, torch.Tensor] = {}
 
     def hidden(name, site, p, rows, cols, shape):
         if p > 0:
-            m[name] = _mask(seed, site, p, rows, cols).reshape(shape).cpu()
+            m[name] = _mask(seed, site, p, rows, cols).reshape(shape).to(device)
 
     def probs(name, site, p, heads, sq, sk):       # attention-probability sites: the 4 x 4-block generator
         if p > 0:
             lib = L.load()
             out = torch.empty(B * heads * sq, sk, dtype=torch.float32, device="cuda")
             L.check(lib.kzv_debug_attn_dropout_mask(lib.kzv_drop_key(seed, site), p, B * heads, sq, sk, out.data_ptr(), L.stream_handle()), "attn mask")
-            m[name] = out.reshape(B, heads, sq, sk).cpu()
+            m[name] = out.reshape(B, heads, sq, sk).to(device)
 
     hidden("enc_emb", SITE_ENC_EMB, cfg.enc_hidden_dropout, B * Se, He, (B, Se, He))
     for i in range(cfg.enc_layers):
