@@ -356,12 +356,14 @@ int kzv_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
 int kzv_layernorm_bwd(const void* dy, int dy_is_f32, const float* x, const float* stats, const float* gamma,
                       float* dx, int accumulate_dx, float* dgamma, float* dbeta, int rows, int H, void* stream);
 
-/* Multi-head attention, one workgroup per (batch, head) on the MFMA kernels for head_dim 64 (the benchmark geometry and the
- * decoder); other head dimensions (multiples of 8 up to 128; the reference's CLI default ViT is 768 / 8 heads = 96,
- * scripts/train_trocr.py:41-43) take a plain fp32 kernel -- same results, several times slower (attention_generic.hip).
+/* Multi-head attention, one workgroup per (batch, head) on bf16 MFMA kernels for head_dim 64 (the benchmark geometry and the
+ * decoder; attention.hip) and for head_dim 96 in mode 0 with Sq, Sk <= 288 (the reference's CLI default ViT, 768 / 8 heads on
+ * 1024 x 64 columns: 257 tokens, scripts/train_trocr.py:39-44; attention_d96.hip).  Other head dimensions (multiples of 8 up to
+ * 128) and head_dim 96 beyond 288 keys take a plain fp32 kernel -- same results and dropout masks, several times slower
+ * (attention_generic.hip).  kzv_attn_impl reports which one serves a call.
  * mode 0: no mask (ViT self-attn / decoder cross-attn); mode 1: causal AND key-not-pad (decoder self; head_dim 64 only). */
 typedef struct kzv_attn_args {
-    const void* Q; const void* K; const void* V;   /* bf16, row strides ldq/ldk/ldv, head h at col h*64 */
+    const void* Q; const void* K; const void* V;   /* bf16, row strides ldq/ldk/ldv (multiples of 8), head h at col h*head_dim */
     void* O;                                        /* bf16 [B*Sq, ldo] */
     float* LSE;                                     /* fp32 [B, heads, Sq] */
     const void* dO; void* dQ; void* dK; void* dV;   /* backward only (same strides as O/Q/K/V) */
@@ -373,6 +375,13 @@ typedef struct kzv_attn_args {
 } kzv_attn_args;
 int kzv_attn_fwd(const kzv_attn_args* a, void* stream);
 int kzv_attn_bwd(const kzv_attn_args* a, void* stream);
+/* Which kernels kzv_attn_fwd (bwd = 0) / kzv_attn_bwd (bwd = 1) would run for these arguments, without launching anything or
+ * touching a GPU: KZV_ATTN_MFMA64, KZV_ATTN_MFMA96 or KZV_ATTN_VALU; for arguments the launch would refuse, its negative code and
+ * kzv_last_error() message.  The launches dispatch through it. */
+#define KZV_ATTN_MFMA64 1
+#define KZV_ATTN_MFMA96 2
+#define KZV_ATTN_VALU 3
+int kzv_attn_impl(const kzv_attn_args* a, int bwd);
 
 /* ------------------------------------------------------------- the ResNet / BiLSTM / CTC model of ocr_lightning/model.py
  * (SURVEY.md section 8(f), row N3).  Per-op entry points; the host mirror kzv/ocr_model.py strings them together the way

@@ -522,7 +522,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
     }
 }
 
-int fill(AttnP& p, const kzv_attn_args* a, bool bwd) {
+// what the head_dim-64 kernels refuse (kzv_attn_impl)
+int check64(const kzv_attn_args* a, bool bwd) {
     if (!a || !a->Q || !a->K || !a->V || !a->O) return kzv_fail(KZV_E_ARG, "attn: null operand");
     if (a->Sq <= 0 || a->Sk <= 0 || a->Sq > 288 || a->Sk > 288) return kzv_fail(KZV_E_ARG, "attn: Sq/Sk must be in 1..288");
     if (a->mode == 1 && a->Sq > 192) return kzv_fail(KZV_E_ARG, "attn: causal mode is built for <= 192 tokens");
@@ -530,6 +531,10 @@ int fill(AttnP& p, const kzv_attn_args* a, bool bwd) {
     if (a->mode != 0 && a->mode != 1) return kzv_fail(KZV_E_ARG, "attn: unknown mode");
     if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
     if (bwd && (!a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE)) return kzv_fail(KZV_E_ARG, "attn_bwd: null gradient operand");
+    return KZV_OK;
+}
+
+int fill(AttnP& p, const kzv_attn_args* a) {
     p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
     p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
     p.zero16 = kzv_zero_page();
@@ -552,6 +557,8 @@ extern "C" int kzv_debug_bwd_stamps(unsigned long long* host128) {
 #endif
 
 int kzv_attn_generic(const kzv_attn_args* a, int D, bool bwd, hipStream_t s);      // attention_generic.hip
+int kzv_attn_generic_check(const kzv_attn_args* a, int D);
+int kzv_attn_d96(const kzv_attn_args* a, bool bwd, hipStream_t s);                  // attention_d96.hip
 
 template <int MODE, int NKT, bool EXACT>
 static void launch_fwd(const AttnP& p, int blocks, hipStream_t s) {
@@ -568,15 +575,31 @@ static void launch_bwd(const AttnP& p, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((attn_bwd_kernel<MODE, NKT, NW, EXACT>), dim3(blocks), dim3(NW * 64), lds, s, p);
 }
 
-extern "C" int kzv_attn_fwd(const kzv_attn_args* a, void* stream) {
+// Which kernels serve a call (include/kzv.h): head_dim 0 / 64 -> attention.hip; head_dim 96, mode 0, Sq and Sk in 1..288 ->
+// attention_d96.hip; the other head dims the VALU kernel takes -> attention_generic.hip.  Arguments a launch would refuse give its
+// error code and message.  The launches below dispatch through this, so the report and the launch cannot disagree.
+extern "C" int kzv_attn_impl(const kzv_attn_args* a, int bwd) {
     if (a && a->head_dim != 0 && a->head_dim != 64) {
-        if (!a->Q || !a->K || !a->V || !a->O) return kzv_fail(KZV_E_ARG, "attn: null operand");
+        if (!bwd && (!a->Q || !a->K || !a->V || !a->O)) return kzv_fail(KZV_E_ARG, "attn: null operand");
+        if (bwd && (!a->Q || !a->K || !a->V || !a->O || !a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE)) return kzv_fail(KZV_E_ARG, "attn_bwd: null operand");
         if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
+        if (a->head_dim == 96 && a->mode == 0 && a->Sq >= 1 && a->Sq <= 288 && a->Sk >= 1 && a->Sk <= 288) return KZV_ATTN_MFMA96;
+        if (int rc = kzv_attn_generic_check(a, a->head_dim)) return rc;
+        return KZV_ATTN_VALU;
+    }
+    if (int rc = check64(a, bwd != 0)) return rc;
+    return KZV_ATTN_MFMA64;
+}
+
+extern "C" int kzv_attn_fwd(const kzv_attn_args* a, void* stream) {
+    const int impl = kzv_attn_impl(a, 0);
+    if (impl < 0) return impl;
+    if (impl != KZV_ATTN_MFMA64) {
         KzvProfScope prof(2, 4.0 * a->B * a->heads * (double)a->Sq * a->Sk * a->head_dim, (hipStream_t)stream);
-        return kzv_attn_generic(a, a->head_dim, false, (hipStream_t)stream);
+        return impl == KZV_ATTN_MFMA96 ? kzv_attn_d96(a, false, (hipStream_t)stream) : kzv_attn_generic(a, a->head_dim, false, (hipStream_t)stream);
     }
     AttnP p;
-    if (int rc = fill(p, a, false)) return rc;
+    if (int rc = fill(p, a)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int nkt = (a->Sk + 15) >> 4, nqt = (a->Sq + 15) >> 4, blocks = a->B * a->heads;
     KzvProfScope prof(2, 4.0 * a->B * a->heads * (double)a->Sq * a->Sk * 64, s);
@@ -590,14 +613,14 @@ extern "C" int kzv_attn_fwd(const kzv_attn_args* a, void* stream) {
 }
 
 extern "C" int kzv_attn_bwd(const kzv_attn_args* a, void* stream) {
-    if (a && a->head_dim != 0 && a->head_dim != 64) {
-        if (!a->Q || !a->K || !a->V || !a->O || !a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE) return kzv_fail(KZV_E_ARG, "attn_bwd: null operand");
-        if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
+    const int impl = kzv_attn_impl(a, 1);
+    if (impl < 0) return impl;
+    if (impl != KZV_ATTN_MFMA64) {
         KzvProfScope prof(3, 10.0 * a->B * a->heads * (double)a->Sq * a->Sk * a->head_dim, (hipStream_t)stream);
-        return kzv_attn_generic(a, a->head_dim, true, (hipStream_t)stream);
+        return impl == KZV_ATTN_MFMA96 ? kzv_attn_d96(a, true, (hipStream_t)stream) : kzv_attn_generic(a, a->head_dim, true, (hipStream_t)stream);
     }
     AttnP p;
-    if (int rc = fill(p, a, true)) return rc;
+    if (int rc = fill(p, a)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int nkt = (a->Sk + 15) >> 4, nqb = (a->Sq + 31) >> 5, blocks = a->B * a->heads;
     KzvProfScope prof(3, 10.0 * a->B * a->heads * (double)a->Sq * a->Sk * 64, s);

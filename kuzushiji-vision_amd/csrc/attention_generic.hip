@@ -18,6 +18,8 @@
 #include "kzv_host.h"
 #include <mutex>
 
+int kzv_attn_generic_check(const kzv_attn_args* a, int D);
+
 namespace {
 
 struct GenP {
@@ -198,9 +200,7 @@ bf16_t* scratch(size_t elems) {          // grow-only, process-global (one devic
 }
 
 int fill(GenP& p, const kzv_attn_args* a, int D, bool bwd) {
-    if (a->mode != 0) return kzv_fail(KZV_E_ARG, "attn: the causal / key-padding mode exists for head_dim 64 only");
-    if (D < 8 || D > 128 || D % 8) return kzv_fail(KZV_E_ARG, "attn: head_dim must be a multiple of 8 in 8..128 (got %d)", D);
-    if (a->Sq <= 0 || a->Sk <= 0 || a->Sk > 512) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): Sk must be in 1..512");
+    if (int rc = kzv_attn_generic_check(a, D)) return rc;
     p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
     p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
     p.dSs = nullptr; p.Pd = nullptr;
@@ -213,20 +213,28 @@ int fill(GenP& p, const kzv_attn_args* a, int D, bool bwd) {
     return KZV_OK;
 }
 
-size_t lds_bytes(const GenP& p) {
-    const size_t DP = p.D + 2, SkP = (p.Sk + 63) & ~63;
-    size_t kv = 2 * (size_t)p.Sk * DP * sizeof(bf16_t);
+}  // namespace
+
+static size_t lds_bytes(int D, int Sk) {
+    const size_t DP = D + 2, SkP = (Sk + 63) & ~63;
+    size_t kv = 2 * (size_t)Sk * DP * sizeof(bf16_t);
     kv = (kv + 3) & ~(size_t)3;
-    return kv + 4 + 4 * (2 * (size_t)p.D + SkP) * sizeof(float);
+    return kv + 4 + 4 * (2 * (size_t)D + SkP) * sizeof(float);
 }
 
-}  // namespace
+// what this path refuses (kzv_attn_impl asks it too, so the report and the launch give the same verdict and message)
+int kzv_attn_generic_check(const kzv_attn_args* a, int D) {
+    if (a->mode != 0) return kzv_fail(KZV_E_ARG, "attn: the causal / key-padding mode exists for head_dim 64 only");
+    if (D < 8 || D > 128 || D % 8) return kzv_fail(KZV_E_ARG, "attn: head_dim must be a multiple of 8 in 8..128 (got %d)", D);
+    if (a->Sq <= 0 || a->Sk <= 0 || a->Sk > 512) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): Sk must be in 1..512");
+    if (lds_bytes(D, a->Sk) > 160 * 1024) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): %d keys x head_dim %d do not fit the 160 KiB LDS", a->Sk, D);
+    return KZV_OK;
+}
 
 int kzv_attn_generic(const kzv_attn_args* a, int D, bool bwd, hipStream_t s) {
     GenP p;
     if (int rc = fill(p, a, D, bwd)) return rc;
-    const size_t lds = lds_bytes(p);
-    if (lds > 160 * 1024) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): %d keys x head_dim %d do not fit the 160 KiB LDS", p.Sk, D);
+    const size_t lds = lds_bytes(D, p.Sk);
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)attn_gen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -841,7 +841,7 @@ extern "C" int kzv_model_create(const kzv_config* cfg, kzv_model** out) {
     if (c.enc_heads <= 0 || c.dec_heads <= 0 || c.dec_hidden != 64 * c.dec_heads)
         return kzv_fail(KZV_E_ARG, "model_create: the decoder's head_dim must be 64 (hidden = 64 * heads)");
     if (c.enc_hidden % c.enc_heads || (c.enc_hidden / c.enc_heads) % 8 || c.enc_hidden / c.enc_heads > 128)
-        return kzv_fail(KZV_E_ARG, "model_create: the encoder's head_dim must be a multiple of 8 up to 128 (64 takes the MFMA attention kernels)");
+        return kzv_fail(KZV_E_ARG, "model_create: the encoder's head_dim must be a multiple of 8 up to 128 (64 and 96 take the MFMA attention kernels)");
     if (c.enc_ffn % 64 || c.dec_ffn % 64 || (c.channels * c.patch_h * c.patch_w) % 64 || c.patch_w % 8)
         return kzv_fail(KZV_E_ARG, "model_create: ffn sizes and C*ph*pw must be multiples of 64, patch_w of 8");
     const int np = (c.image_h / c.patch_h) * (c.image_w / c.patch_w);

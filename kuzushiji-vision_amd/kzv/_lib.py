@@ -78,6 +78,8 @@ class kzv_attn_args(C.Structure):
 
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU = range(5)
+ATTN_MFMA64, ATTN_MFMA96, ATTN_VALU = 1, 2, 3          # kzv_attn_impl
+ATTN_IMPL_NAMES = {ATTN_MFMA64: "mfma64", ATTN_MFMA96: "mfma96", ATTN_VALU: "valu"}
 
 # every symbol include/kzv.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -132,6 +134,7 @@ SYMBOLS = {
     "kzv_layernorm_bwd": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "kzv_attn_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_bwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
+    "kzv_attn_impl": (C.c_int, [C.POINTER(kzv_attn_args), C.c_int]),
     "kzv_drop_key": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "kzv_debug_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "kzv_debug_attn_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
@@ -215,6 +218,27 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().kzv_last_error().decode("utf-8", "replace")
         raise KzvError(f"{what or 'libkzv'} failed ({rc}): {msg}")
+
+
+def attention_impl(head_dim: int, Sq: int, Sk: int, heads: int = 1, mode: int = 0, bwd: bool = False,
+                   ldq: int | None = None, ldo: int | None = None) -> str:
+    """Which kernels kzv_attn_fwd (or, with bwd, kzv_attn_bwd) runs for this geometry: "mfma64" | "mfma96" | "valu".
+    Asks the library (kzv_attn_impl), which launches nothing and needs no GPU.  The strides default to the model's packed
+    QKV buffer [B * S, 3 * heads * head_dim] and its [B * S, heads * head_dim] output.  Raises KzvError for arguments the
+    launch would refuse, with the launch's message."""
+    lib = load()
+    width = heads * (head_dim or 64)
+    a = kzv_attn_args()
+    a.Q = a.K = a.V = a.O = a.LSE = a.dO = a.dQ = a.dK = a.dV = 16      # never dereferenced: only their presence is checked
+    a.ldq = a.ldk = a.ldv = 3 * width if ldq is None else ldq
+    a.ldo = width if ldo is None else ldo
+    a.ids = 16 if mode == 1 else None
+    a.ld_ids = Sk
+    a.B, a.heads, a.Sq, a.Sk, a.mode, a.head_dim = 1, heads, Sq, Sk, mode, head_dim
+    rc = lib.kzv_attn_impl(C.byref(a), int(bwd))
+    if rc < 0:
+        check(rc, "kzv_attn_impl")
+    return ATTN_IMPL_NAMES[rc]
 
 
 def ptr(t) -> int:

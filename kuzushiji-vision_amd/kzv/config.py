@@ -73,7 +73,7 @@ class ModelConfig:
         if self.dec_hidden // self.dec_heads != 64:
             raise ValueError("the decoder's attention / generation kernels are built for head_dim == 64")
         eh = self.enc_hidden // self.enc_heads
-        if eh % 8 or eh > 128:      # 64: MFMA kernels; others (the reference CLI's default 768 / 8 = 96): the plain fp32 kernel
+        if eh % 8 or eh > 128:      # 64 and 96 (the reference CLI's default 768 / 8): MFMA kernels; others: the plain fp32 kernel
             raise ValueError("the encoder's head_dim must be a multiple of 8 up to 128")
         for k in (self.enc_hidden, self.enc_ffn, self.dec_hidden, self.dec_ffn, self.patch_dim):
             if k % 64:
@@ -179,6 +179,14 @@ def vit_l_config(enc_layers: int = 24, dec_layers: int = 12, dec_hidden: int = 2
 def vit_l_wide_config(enc_layers: int = 24, dec_layers: int = 12) -> ModelConfig:
     """configs[3] as SURVEY.md section 8(d) prices it: ViT-L/16 + a 12-layer decoder at 1024 hidden / 16 heads / FFN 4096."""
     return vit_l_config(enc_layers, dec_layers, dec_hidden=1024, dec_heads=16, dec_ffn=4096)
+
+
+def reference_cli_config() -> ModelConfig:
+    """The model the reference's training command builds with its defaults (scripts/train_trocr.py:39-44, and `python -m kzv.train`):
+    ViT 768 / 12 layers / 8 heads (head_dim 96) / FFN 3072 on 1024 x 64 columns (256 patches + CLS = 257 tokens), the reference
+    decoder (256 / 4 heads / 12 layers / 768, labels up to 128)."""
+    return ModelConfig(image_h=1024, image_w=64, enc_hidden=768, enc_layers=12, enc_heads=8, enc_ffn=3072,
+                       dec_hidden=256, dec_layers=12, dec_heads=4, dec_ffn=768, vocab=4300, max_pos=128)
 
 
 def small_config() -> ModelConfig:

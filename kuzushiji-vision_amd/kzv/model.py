@@ -21,6 +21,16 @@ class _Cfg(types.SimpleNamespace):
     pass
 
 
+def encoder_attention_impl(cfg: ModelConfig) -> str:
+    """Which attention kernels the encoder of `cfg` runs on, forward and backward: "mfma64" | "mfma96" | "valu" (kzv_attn_impl:
+    no GPU needed)."""
+    hd, S = cfg.enc_hidden // cfg.enc_heads, cfg.enc_seq
+    fwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads)
+    bwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads, bwd=True)
+    assert fwd == bwd, (fwd, bwd)
+    return fwd
+
+
 class TrOCRModel:
     """TrOCR Model with ViT Encoder and RoBERTa Decoder (MI355X engine).
 
@@ -184,6 +194,11 @@ class TrOCRModel:
 
     def num_parameters(self) -> int:
         return P.num_parameters(self.cfg)
+
+    @property
+    def encoder_attention_impl(self) -> str:
+        """"mfma64" | "mfma96" | "valu": the attention kernels of this model's encoder."""
+        return encoder_attention_impl(self.cfg)
 
     def train(self, mode: bool = True):
         self.training = mode

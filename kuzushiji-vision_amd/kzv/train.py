@@ -31,8 +31,8 @@ def parse_args(argv=None):
     p.add_argument("--encoder_hidden_size", type=int, default=768)
     p.add_argument("--encoder_num_layers", type=int, default=12)
     p.add_argument("--encoder_num_heads", type=int, default=8,
-                   help="reference default 8 = head_dim 96 (scripts/train_trocr.py:43), which runs on the plain fp32 attention kernel; "
-                        "hidden_size / 64 heads (12 for ViT-B/16) take the MFMA attention kernels, several times faster")
+                   help="reference default 8 = head_dim 96 (scripts/train_trocr.py:43); head_dim 64 and 96 (up to 287 patches) run on the "
+                        "MFMA attention kernels, other multiples of 8 up to 128 on a plain fp32 kernel, several times slower")
     p.add_argument("--max_length", type=int, default=128)
     # training (:47-54)
     p.add_argument("--batch_size", type=int, default=64)
@@ -216,6 +216,9 @@ def main(argv=None):
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
                        fp8=args.precision == "fp8-mixed")
     model._step_seed = 1_000_003 * rank
+    if rank == 0:
+        c = model.cfg
+        print(f"encoder attention: {model.encoder_attention_impl} (head_dim {c.enc_hidden // c.enc_heads}, {c.enc_seq} tokens)")
     if args.synthetic:
         n_val = max(args.batch_size, args.synthetic // 10)
         train_ds = SyntheticLineDataset(model.cfg, args.synthetic, args.max_length, seed=args.seed)
