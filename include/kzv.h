@@ -51,6 +51,13 @@ typedef struct kzv_model kzv_model;
 
 /* TrOCRModel.__init__ (trocr_model.py:208-256): validates geometry, builds the parameter table. */
 int kzv_model_create(const kzv_config* cfg, kzv_model** out);
+/* kzv_model_create with flags (kzv_model_create(cfg, out) == kzv_model_create_ex(cfg, 0, out)).
+ * KZV_MODEL_LONG_SEQ: encoders with head_dim 64 or 96 take up to 4,097 tokens (4,096 patches + CLS); attention launches whose
+ * key or query count exceeds 288 run the K/V-streaming kernels (kzv_attn_impl_ex), shorter ones the whole-head kernels as before.
+ * Other encoder head dims keep the 288-token cap.  kzv_model_bind then also refuses batches whose attention-dropout block index
+ * B * heads * ceil(Sq / 4) * ceil(Sk / 4) would pass 2^32 (the generator's block word is 32-bit). */
+#define KZV_MODEL_LONG_SEQ 1u
+int kzv_model_create_ex(const kzv_config* cfg, unsigned flags, kzv_model** out);
 int kzv_model_destroy(kzv_model* m);
 
 /* Parameter table = the reference's state_dict, fused/flattened (kzv/params.py documents the
@@ -382,6 +389,18 @@ int kzv_attn_bwd(const kzv_attn_args* a, void* stream);
 #define KZV_ATTN_MFMA96 2
 #define KZV_ATTN_VALU 3
 int kzv_attn_impl(const kzv_attn_args* a, int bwd);
+
+/* Long sequences: K/V-streaming (flash-style) kernels for head_dim 64 and 96, mode 0, Sq and Sk in 1..4,097
+ * (attention_stream.hip).  Same contract as kzv_attn_fwd / kzv_attn_bwd (arguments, natural-log LSE [B, heads, Sq], dropout masks,
+ * written outputs), so a streaming forward's LSE feeds a whole-head backward and vice versa; no buffer grows with Sq * Sk and no
+ * float atomics (bitwise reproducible).  These two run the streaming kernels at any length, short ones included. */
+int kzv_attn_stream_fwd(const kzv_attn_args* a, void* stream);
+int kzv_attn_stream_bwd(const kzv_attn_args* a, void* stream);
+/* kzv_attn_impl with flags.  KZV_MODEL_LONG_SEQ: head_dim 0 / 64 / 96 calls in mode 0 with Sq or Sk above 288 (up to 4,097) report
+ * KZV_ATTN_STREAM64 / KZV_ATTN_STREAM96; every other call, and every call without the flag, gets kzv_attn_impl's answer. */
+#define KZV_ATTN_STREAM64 4
+#define KZV_ATTN_STREAM96 5
+int kzv_attn_impl_ex(const kzv_attn_args* a, int bwd, unsigned flags);
 
 /* ------------------------------------------------------------- the ResNet / BiLSTM / CTC model of ocr_lightning/model.py
  * (SURVEY.md section 8(f), row N3).  Per-op entry points; the host mirror kzv/ocr_model.py strings them together the way

@@ -591,6 +591,19 @@ extern "C" int kzv_attn_impl(const kzv_attn_args* a, int bwd) {
     return KZV_ATTN_MFMA64;
 }
 
+int kzv_attn_stream_check(const kzv_attn_args* a, bool bwd);                      // attention_stream.hip
+
+// With KZV_MODEL_LONG_SEQ the calls the whole-head kernels cannot take (head_dim 0 / 64 / 96, mode 0, Sq or Sk above 288) go to the
+// streaming kernels; everything else is kzv_attn_impl's answer, so a short launch of a long-sequence model is unchanged.
+extern "C" int kzv_attn_impl_ex(const kzv_attn_args* a, int bwd, unsigned flags) {
+    if ((flags & KZV_MODEL_LONG_SEQ) && a && a->mode == 0 && (a->head_dim == 0 || a->head_dim == 64 || a->head_dim == 96) &&
+        (a->Sq > 288 || a->Sk > 288)) {
+        if (int rc = kzv_attn_stream_check(a, bwd != 0)) return rc;
+        return a->head_dim == 96 ? KZV_ATTN_STREAM96 : KZV_ATTN_STREAM64;
+    }
+    return kzv_attn_impl(a, bwd);
+}
+
 extern "C" int kzv_attn_fwd(const kzv_attn_args* a, void* stream) {
     const int impl = kzv_attn_impl(a, 0);
     if (impl < 0) return impl;

@@ -435,6 +435,96 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
     }
 }
 
+// More than 320 keys (cross-attention over long encoder sequences; no cache append, no row table): the lane layout of
+// attn_decode_kernel, but the keys are swept in chunks of 64 (8 wave-instructions of 8 rows) with a running max and sum per
+// sequence, so nothing is held per key.  The output accumulators are rescaled when the max moves.
+template <int G>
+__global__ __launch_bounds__(256) void attn_decode_long_kernel(const DecAttnP p, const int nunits) {
+    const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= nunits) return;
+    const int b0 = (unit / p.heads) * G, h = unit - (unit / p.heads) * p.heads, lane = threadIdx.x & 63;
+    const bf16_t* Kb = p.K + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
+    const bf16_t* Vb = p.V + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
+    const int nkeys = p.nkeys, r = lane >> 3, c = lane & 7;
+    float qc[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bf16x8 q8 = *(const bf16x8*)(p.q + (int64_t)(b0 + g) * p.ldq + h * 64 + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qc[g][e] = bf2f((bf16_t)q8[e]) * p.scale;
+    }
+    constexpr int CH = 8;
+    float mx[G], sum[G], o[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        mx[g] = -INFINITY; sum[g] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+    }
+    for (int j0 = 0; j0 < nkeys; j0 += 8 * CH) {
+        bf16x8 kk[CH], vv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int j = min(j0 + 8 * u + r, nkeys - 1);          // clamped rows: their scores are masked below
+            kk[u] = *(const bf16x8*)(Kb + (int64_t)j * p.kj + c * 8);
+            vv[u] = *(const bf16x8*)(Vb + (int64_t)j * p.kj + c * 8);
+        }
+        bool kok[G][CH];
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int u = 0; u < CH; ++u) kok[g][u] = j0 + 8 * u + r < nkeys;
+        if (p.valid) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+#pragma unroll
+                for (int u = 0; u < CH; ++u)
+                    kok[g][u] = kok[g][u] && p.valid[(int64_t)(b0 + g) * p.ldvalid + min(j0 + 8 * u + r, (int)p.ldvalid - 1)] != 0;
+        }
+        float sc[G][CH];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            float cm = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                float a = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) a += qc[g][e] * bf2f((bf16_t)kk[u][e]);
+                a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64);
+                sc[g][u] = kok[g][u] ? a : -INFINITY;
+                cm = fmaxf(cm, sc[g][u]);
+            }
+            cm = wave_max(cm);
+            const float mn = fmaxf(mx[g], cm);
+            if (mn == -INFINITY) continue;                          // nothing usable yet (wave-uniform)
+            const float alpha = __expf(mx[g] - mn);                 // 0 on the first usable chunk (mx = -inf)
+            mx[g] = mn;
+            sum[g] *= alpha;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const float pr = __expf(sc[g][u] - mn);
+                sum[g] += pr;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[g][e] += pr * bf2f((bf16_t)vv[u][e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool dead = mx[g] == -INFINITY;                       // no usable key: output zeros
+        const float iv = dead ? 0.f : 1.f / (wave_sum(sum[g]) * 0.125f);   // every key is counted by the 8 lanes of its row
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { o[g][e] += __shfl_xor(o[g][e], 8, 64); o[g][e] += __shfl_xor(o[g][e], 16, 64); o[g][e] += __shfl_xor(o[g][e], 32, 64); }
+        if (r == 0) {
+            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+            const u32x4 pk = (u32x4){pack_bf2(o[g][0] * iv, o[g][1] * iv), pack_bf2(o[g][2] * iv, o[g][3] * iv), pack_bf2(o[g][4] * iv, o[g][5] * iv), pack_bf2(o[g][6] * iv, o[g][7] * iv)};
+            *(u32x4*)(p.out + (int64_t)(b0 + g) * p.ldo + h * 64 + c * 8) = pk;
+        }
+    }
+}
+
 // inputs of decoder step t from the token table: newest token, its RoBERTa position id (HF modeling_roberta.py:142-155: t + 1 +
 // pad_id for a real token, pad_id for padding) and the key-usable flag of column t -- six small torch kernels otherwise
 __global__ void decode_prep_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int t, int pad, int B, int64_t* __restrict__ tok,
@@ -504,7 +594,8 @@ int kzv_step_inc(int* d_t, hipStream_t s) {
 int kzv_attn_decode(const bf16_t* q, int64_t ldq, const bf16_t* knew, const bf16_t* vnew, int64_t ldnew, bf16_t* K, bf16_t* V, int64_t kb,
                     int64_t kj, const unsigned char* valid, int64_t ldvalid, bf16_t* out, int64_t ldo, int B, int heads, int nkeys,
                     int append_at, hipStream_t s, const int* tptr, int group, int* rows, int64_t ldrows, int64_t kh) {
-    if (nkeys < 1 || nkeys > 320) return kzv_fail(KZV_E_ARG, "attn_decode: 1..320 keys");
+    if (nkeys < 1 || nkeys > 4097) return kzv_fail(KZV_E_ARG, "attn_decode: 1..4097 keys");
+    if (nkeys > 320 && (append_at >= 0 || tptr || rows)) return kzv_fail(KZV_E_ARG, "attn_decode: beyond 320 keys only without a cache append or row table");
     if (ldq % 8 || ldo % 8 || (knew && ldnew % 8)) return kzv_fail(KZV_E_ARG, "attn_decode: rows must be 16-byte aligned");
     if (group < 1 || (append_at >= 0 && group != 1)) return kzv_fail(KZV_E_ARG, "attn_decode: shared keys cannot be appended to");
     if (kj % 8) return kzv_fail(KZV_E_ARG, "attn_decode: key rows must be 16-byte aligned");
@@ -517,7 +608,11 @@ int kzv_attn_decode(const bf16_t* q, int64_t ldq, const bf16_t* knew, const bf16
     const int nunits = (B / G) * heads;
 #define KZV_AD(NI, GG) hipLaunchKernelGGL((attn_decode_kernel<NI, GG>), dim3((nunits + 3) / 4), dim3(256), 0, s, p, nunits)
 #define KZV_AD_G(NI) do { if (G == 4) KZV_AD(NI, 4); else if (G == 3) KZV_AD(NI, 3); else if (G == 2) KZV_AD(NI, 2); else KZV_AD(NI, 1); } while (0)
-    if (nkeys <= 192) KZV_AD_G(24); else KZV_AD_G(40);
+#define KZV_ADL(GG) hipLaunchKernelGGL((attn_decode_long_kernel<GG>), dim3((nunits + 3) / 4), dim3(256), 0, s, p, nunits)
+    if (nkeys <= 192) KZV_AD_G(24);
+    else if (nkeys <= 320) KZV_AD_G(40);
+    else if (G == 4) KZV_ADL(4); else if (G == 3) KZV_ADL(3); else if (G == 2) KZV_ADL(2); else KZV_ADL(1);
+#undef KZV_ADL
 #undef KZV_AD_G
 #undef KZV_AD
     return kzv_check_launch("attn_decode");

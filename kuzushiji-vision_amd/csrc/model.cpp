@@ -47,6 +47,7 @@ struct kzv_model {
     int np, Se, PD, He, Fe, Hd, Fd, V, Vp, Le, Ld;
     int npa = 0, Sa = 0, img_w = 0;   // ACTIVE geometry (kzv_set_image_width): img_w <= c.image_w, npa patches, Sa = npa + 1 tokens
     bool has_proj;
+    bool long_seq = false;            // KZV_MODEL_LONG_SEQ: launches beyond 288 tokens take the streaming attention kernels
     std::vector<PEntry> table;
     int64_t total = 0;
     // parameter offsets
@@ -467,6 +468,11 @@ int attn(const kzv_model* m, bool bwd, int mode, const bf16_t* Q, int64_t ldq, c
     a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
     a.ids = m->labels; a.ld_ids = m->L; a.pad_id = m->c.pad_id;
     a.B = batch > 0 ? batch : m->B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.head_dim = head_dim; a.mode = mode; a.drop_p = drop_p; a.drop_key = drop_key;
+    if (m->long_seq) {        // the key / query count alone picks the structure, per launch
+        const int impl = kzv_attn_impl_ex(&a, bwd ? 1 : 0, KZV_MODEL_LONG_SEQ);
+        if (impl < 0) return impl;
+        if (impl == KZV_ATTN_STREAM64 || impl == KZV_ATTN_STREAM96) return bwd ? kzv_attn_stream_bwd(&a, s) : kzv_attn_stream_fwd(&a, s);
+    }
     return bwd ? kzv_attn_bwd(&a, s) : kzv_attn_fwd(&a, s);
 }
 
@@ -833,8 +839,11 @@ int backward_embed(kzv_model* m, hipStream_t s) {
 }  // namespace
 
 // ================================================================================================== C ABI
-extern "C" int kzv_model_create(const kzv_config* cfg, kzv_model** out) {
+extern "C" int kzv_model_create(const kzv_config* cfg, kzv_model** out) { return kzv_model_create_ex(cfg, 0, out); }
+
+extern "C" int kzv_model_create_ex(const kzv_config* cfg, unsigned flags, kzv_model** out) {
     if (!cfg || !out) return kzv_fail(KZV_E_ARG, "model_create: null");
+    if (flags & ~KZV_MODEL_LONG_SEQ) return kzv_fail(KZV_E_ARG, "model_create: unknown flags 0x%x", flags);
     const kzv_config& c = *cfg;
     if (c.patch_h <= 0 || c.patch_w <= 0 || c.image_h % c.patch_h || c.image_w % c.patch_w)
         return kzv_fail(KZV_E_ARG, "model_create: image %dx%d not divisible by patch %dx%d", c.image_h, c.image_w, c.patch_h, c.patch_w);
@@ -845,7 +854,15 @@ extern "C" int kzv_model_create(const kzv_config* cfg, kzv_model** out) {
     if (c.enc_ffn % 64 || c.dec_ffn % 64 || (c.channels * c.patch_h * c.patch_w) % 64 || c.patch_w % 8)
         return kzv_fail(KZV_E_ARG, "model_create: ffn sizes and C*ph*pw must be multiples of 64, patch_w of 8");
     const int np = (c.image_h / c.patch_h) * (c.image_w / c.patch_w);
-    if (np + 1 > 288) return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 288-token attention kernels", np);
+    const int ehd = c.enc_hidden / c.enc_heads;
+    if (np + 1 > 288) {
+        if (!(flags & KZV_MODEL_LONG_SEQ))
+            return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 288-token attention kernels", np);
+        if (ehd != 64 && ehd != 96)
+            return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 288-token attention kernels: the streaming kernels that take "
+                                       "longer sequences serve encoder head_dim 64 and 96 only (this encoder's is %d)", np, ehd);
+        if (np + 1 > 4097) return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 4,097-token streaming attention kernels", np);
+    }
     if (c.vocab < 8 || c.max_pos < 4 || c.type_vocab < 1 || c.pad_id < 0 || c.pad_id >= c.vocab)
         return kzv_fail(KZV_E_ARG, "model_create: bad vocabulary geometry");
     if (c.enc_layers < 1 || c.dec_layers < 1) return kzv_fail(KZV_E_ARG, "model_create: encoder and decoder need at least one layer each");
@@ -856,6 +873,7 @@ extern "C" int kzv_model_create(const kzv_config* cfg, kzv_model** out) {
     m->He = c.enc_hidden; m->Fe = c.enc_ffn; m->Hd = c.dec_hidden; m->Fd = c.dec_ffn;
     m->V = c.vocab; m->Vp = (int)align_up(c.vocab, 64); m->Le = c.enc_layers; m->Ld = c.dec_layers;
     m->has_proj = m->He != m->Hd;
+    m->long_seq = (flags & KZV_MODEL_LONG_SEQ) != 0;
     build_param_table(m);
     *out = m;
     return KZV_OK;
@@ -907,6 +925,11 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
                               int batch, int label_len) {
     if (!m || !d_params || !d_workspace) return kzv_fail(KZV_E_ARG, "model_bind: null");
     KZV_TRY(check_batch(m, batch, label_len));
+    if (m->long_seq) {       // the attention-dropout block index (kzv_common.h) is a 32-bit word: beyond it the masks would repeat
+        const auto blocks = [](int64_t B, int64_t heads, int64_t Sq, int64_t Sk) { return B * heads * ((Sq + 3) / 4) * ((Sk + 3) / 4); };
+        if (blocks(batch, m->c.enc_heads, m->Se, m->Se) > (1ll << 32) || blocks(batch, m->c.dec_heads, label_len - 1, m->np) > (1ll << 32))
+            return kzv_fail(KZV_E_ARG, "model_bind: batch %d x %d tokens exceeds the 2^32 attention-dropout blocks of one launch", batch, m->Se);
+    }
     if (((uintptr_t)d_params | (uintptr_t)d_grads | (uintptr_t)d_workspace) & 255) return kzv_fail(KZV_E_ARG, "model_bind: buffers must be 256-byte aligned");
     m->P = d_params; m->G = d_grads;
     const int64_t need = plan(m, (char*)d_workspace, batch, label_len);

@@ -79,7 +79,9 @@ class kzv_attn_args(C.Structure):
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU = range(5)
 ATTN_MFMA64, ATTN_MFMA96, ATTN_VALU = 1, 2, 3          # kzv_attn_impl
-ATTN_IMPL_NAMES = {ATTN_MFMA64: "mfma64", ATTN_MFMA96: "mfma96", ATTN_VALU: "valu"}
+ATTN_STREAM64, ATTN_STREAM96 = 4, 5                    # kzv_attn_impl_ex with MODEL_LONG_SEQ
+ATTN_IMPL_NAMES = {ATTN_MFMA64: "mfma64", ATTN_MFMA96: "mfma96", ATTN_VALU: "valu", ATTN_STREAM64: "stream64", ATTN_STREAM96: "stream96"}
+MODEL_LONG_SEQ = 1                                     # kzv_model_create_ex flag
 
 # every symbol include/kzv.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -93,6 +95,7 @@ SYMBOLS = {
     "kzv_last_error": (C.c_char_p, []),
     "kzv_version": (C.c_int, []),
     "kzv_model_create": (C.c_int, [C.POINTER(kzv_config), C.POINTER(_P)]),
+    "kzv_model_create_ex": (C.c_int, [C.POINTER(kzv_config), C.c_uint, C.POINTER(_P)]),
     "kzv_model_destroy": (C.c_int, [_P]),
     "kzv_param_count": (C.c_int, [_P]),
     "kzv_param_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
@@ -135,6 +138,9 @@ SYMBOLS = {
     "kzv_attn_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_bwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_impl": (C.c_int, [C.POINTER(kzv_attn_args), C.c_int]),
+    "kzv_attn_stream_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
+    "kzv_attn_stream_bwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
+    "kzv_attn_impl_ex": (C.c_int, [C.POINTER(kzv_attn_args), C.c_int, C.c_uint]),
     "kzv_drop_key": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "kzv_debug_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "kzv_debug_attn_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
@@ -221,9 +227,10 @@ def check(rc: int, what: str = "") -> None:
 
 
 def attention_impl(head_dim: int, Sq: int, Sk: int, heads: int = 1, mode: int = 0, bwd: bool = False,
-                   ldq: int | None = None, ldo: int | None = None) -> str:
-    """Which kernels kzv_attn_fwd (or, with bwd, kzv_attn_bwd) runs for this geometry: "mfma64" | "mfma96" | "valu".
-    Asks the library (kzv_attn_impl), which launches nothing and needs no GPU.  The strides default to the model's packed
+                   ldq: int | None = None, ldo: int | None = None, long_sequences: bool = False) -> str:
+    """Which kernels kzv_attn_fwd (or, with bwd, kzv_attn_bwd) runs for this geometry: "mfma64" | "mfma96" | "valu"; with
+    long_sequences, what a model created with MODEL_LONG_SEQ runs (kzv_attn_impl_ex), which adds "stream64" | "stream96".
+    Asks the library, which launches nothing and needs no GPU.  The strides default to the model's packed
     QKV buffer [B * S, 3 * heads * head_dim] and its [B * S, heads * head_dim] output.  Raises KzvError for arguments the
     launch would refuse, with the launch's message."""
     lib = load()
@@ -235,9 +242,12 @@ def attention_impl(head_dim: int, Sq: int, Sk: int, heads: int = 1, mode: int = 
     a.ids = 16 if mode == 1 else None
     a.ld_ids = Sk
     a.B, a.heads, a.Sq, a.Sk, a.mode, a.head_dim = 1, heads, Sq, Sk, mode, head_dim
-    rc = lib.kzv_attn_impl(C.byref(a), int(bwd))
+    if long_sequences:
+        rc = lib.kzv_attn_impl_ex(C.byref(a), int(bwd), MODEL_LONG_SEQ)
+    else:
+        rc = lib.kzv_attn_impl(C.byref(a), int(bwd))
     if rc < 0:
-        check(rc, "kzv_attn_impl")
+        check(rc, "kzv_attn_impl_ex" if long_sequences else "kzv_attn_impl")
     return ATTN_IMPL_NAMES[rc]
 
 

@@ -67,7 +67,16 @@ class ModelConfig:
     def has_proj(self) -> bool:  # nn.Identity when equal (src/models/trocr_model.py:250-253)
         return self.enc_hidden != self.dec_hidden
 
-    def validate(self) -> None:
+    def validate(self, long_sequences: bool = False) -> None:
+        """Geometry checks of kzv_model_create; with long_sequences those of kzv_model_create_ex(KZV_MODEL_LONG_SEQ): more than
+        288 encoder tokens need head_dim 64 or 96 (the streaming attention kernels), at most 4,097."""
+        if long_sequences and self.enc_hidden % self.enc_heads == 0 and self.enc_seq > 288:
+            eh = self.enc_hidden // self.enc_heads
+            if eh not in (64, 96):
+                raise ValueError(f"{self.enc_seq} encoder tokens exceed the 288-token attention kernels: longer sequences run on "
+                                 f"the streaming kernels, which serve encoder head_dim 64 and 96 only (this one is {eh})")
+            if self.enc_seq > 4097:
+                raise ValueError(f"{self.enc_seq} encoder tokens exceed the 4,097-token streaming attention kernels")
         if self.enc_hidden % self.enc_heads or self.dec_hidden % self.dec_heads:
             raise ValueError("hidden size must be a multiple of the number of heads")
         if self.dec_hidden // self.dec_heads != 64:

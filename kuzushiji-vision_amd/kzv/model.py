@@ -21,12 +21,12 @@ class _Cfg(types.SimpleNamespace):
     pass
 
 
-def encoder_attention_impl(cfg: ModelConfig) -> str:
-    """Which attention kernels the encoder of `cfg` runs on, forward and backward: "mfma64" | "mfma96" | "valu" (kzv_attn_impl:
-    no GPU needed)."""
+def encoder_attention_impl(cfg: ModelConfig, long_sequences: bool = False) -> str:
+    """Which attention kernels the encoder of `cfg` runs on, forward and backward: "mfma64" | "mfma96" | "valu", and for a
+    model built with long_sequences also "stream64" | "stream96" (kzv_attn_impl / kzv_attn_impl_ex: no GPU needed)."""
     hd, S = cfg.enc_hidden // cfg.enc_heads, cfg.enc_seq
-    fwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads)
-    bwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads, bwd=True)
+    fwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads, long_sequences=long_sequences)
+    bwd = L.attention_impl(hd, S, S, heads=cfg.enc_heads, bwd=True, long_sequences=long_sequences)
     assert fwd == bwd, (fwd, bwd)
     return fwd
 
@@ -41,14 +41,17 @@ class TrOCRModel:
     def __init__(self, encoder_config: dict[str, Any], decoder_path: str, learning_rate: float = 1e-4,
                  beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, weight_decay: float = 0,
                  *, device: str = "cuda", init_seed: int = 42, load_tokenizer: bool = True, width_buckets=None,
-                 fp8: bool = False):
+                 fp8: bool = False, long_sequences: bool = False):
         import torch
         self.hparams = types.SimpleNamespace(encoder_config=encoder_config, decoder_path=decoder_path,
                                              learning_rate=learning_rate, beta1=beta1, beta2=beta2,
                                              epsilon=epsilon, weight_decay=weight_decay)
         dec_cfg = load_decoder_config(decoder_path)          # FileNotFoundError like scripts/train_trocr.py:88-89
         self.cfg = ModelConfig.from_reference(encoder_config, dec_cfg)
-        self.cfg.validate()
+        # long_sequences (include/kzv.h: KZV_MODEL_LONG_SEQ): encoders with head_dim 64 or 96 take up to 4,097 tokens, attention
+        # launches beyond 288 tokens running the K/V-streaming kernels.  Off by default: the library keeps the 288-token cap.
+        self.long_sequences = bool(long_sequences)
+        self.cfg.validate(long_sequences=self.long_sequences)
         self.tokenizer = None
         if load_tokenizer:
             from transformers import AutoTokenizer                      # trocr_model.py:222
@@ -82,7 +85,10 @@ class TrOCRModel:
             enc_hidden_dropout=c.enc_hidden_dropout, enc_attn_dropout=c.enc_attn_dropout,
             dec_hidden_dropout=c.dec_hidden_dropout, dec_attn_dropout=c.dec_attn_dropout, ln_eps=c.ln_eps)
         h = C.c_void_p()
-        L.check(lib.kzv_model_create(C.byref(self._ccfg), C.byref(h)), "kzv_model_create")
+        if self.long_sequences:
+            L.check(lib.kzv_model_create_ex(C.byref(self._ccfg), L.MODEL_LONG_SEQ, C.byref(h)), "kzv_model_create_ex")
+        else:
+            L.check(lib.kzv_model_create(C.byref(self._ccfg), C.byref(h)), "kzv_model_create")
         self._h = h
         # fp8 weight path (BASELINE.json configs[4]; an extension -- the reference trains in bf16 autocast): the encoder's QKV,
         # fc1 and fc2 forward GEMMs read e4m3 weights and activations (include/kzv.h: kzv_set_fp8); backward stays bf16.
@@ -197,8 +203,9 @@ class TrOCRModel:
 
     @property
     def encoder_attention_impl(self) -> str:
-        """"mfma64" | "mfma96" | "valu": the attention kernels of this model's encoder."""
-        return encoder_attention_impl(self.cfg)
+        """"mfma64" | "mfma96" | "valu" | "stream64" | "stream96": the attention kernels of this model's encoder (at its
+        widest crop)."""
+        return encoder_attention_impl(self.cfg, self.long_sequences)
 
     def train(self, mode: bool = True):
         self.training = mode

@@ -31,8 +31,9 @@ def parse_args(argv=None):
     p.add_argument("--encoder_hidden_size", type=int, default=768)
     p.add_argument("--encoder_num_layers", type=int, default=12)
     p.add_argument("--encoder_num_heads", type=int, default=8,
-                   help="reference default 8 = head_dim 96 (scripts/train_trocr.py:43); head_dim 64 and 96 (up to 287 patches) run on the "
-                        "MFMA attention kernels, other multiples of 8 up to 128 on a plain fp32 kernel, several times slower")
+                   help="reference default 8 = head_dim 96 (scripts/train_trocr.py:43); head_dim 64 and 96 run on MFMA attention kernels "
+                        "(whole-head up to 288 tokens, K/V-streaming up to 4,097 = 4,096 patches + CLS), other multiples of 8 up to 128 "
+                        "on a plain fp32 kernel, several times slower and for at most 287 patches")
     p.add_argument("--max_length", type=int, default=128)
     # training (:47-54)
     p.add_argument("--batch_size", type=int, default=64)
@@ -193,6 +194,15 @@ def main(argv=None):
     hd = args.encoder_hidden_size / max(1, args.encoder_num_heads)
     if hd != int(hd) or int(hd) % 8 or hd > 128:
         raise SystemExit(f"encoder head_dim {hd:g} is not supported: --encoder_hidden_size / --encoder_num_heads must be a multiple of 8 up to 128")
+    if len(args.patch_size) == 2 and min(args.patch_size) > 0 and args.image_size[0] % args.patch_size[0] == 0 and args.image_size[1] % args.patch_size[1] == 0:
+        tokens = (args.image_size[0] // args.patch_size[0]) * (args.image_size[1] // args.patch_size[1]) + 1
+        if tokens > 288 and int(hd) not in (64, 96):
+            raise SystemExit(f"--image_size {args.image_size[0]} {args.image_size[1]} with --patch_size {args.patch_size[0]} {args.patch_size[1]} "
+                             f"gives {tokens} encoder tokens; beyond 288 the attention runs on streaming kernels for head_dim 64 and 96 only, "
+                             f"and this encoder's is {int(hd)} (--encoder_hidden_size / --encoder_num_heads)")
+        if tokens > 4097:
+            raise SystemExit(f"--image_size {args.image_size[0]} {args.image_size[1]} with --patch_size {args.patch_size[0]} {args.patch_size[1]} "
+                             f"gives {tokens} encoder tokens; the attention kernels take at most 4,097 (4,096 patches + CLS)")
     rank, world, local = init_distributed()
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one process per GPU with torch.distributed.run")
@@ -214,7 +224,7 @@ def main(argv=None):
                       "hidden_dropout_prob": 0.1, "attention_probs_dropout_prob": 0.1}   # :111-121
     model = TrOCRModel(encoder_config, decoder_path, learning_rate=args.learning_rate, beta1=args.beta1, beta2=args.beta2,
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
-                       fp8=args.precision == "fp8-mixed")
+                       fp8=args.precision == "fp8-mixed", long_sequences=True)
     model._step_seed = 1_000_003 * rank
     if rank == 0:
         c = model.cfg

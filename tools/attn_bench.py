@@ -2,6 +2,12 @@
 """Times the encoder attention and the whole training step at the reference CLI's defaults; prints one JSON line.
 
   python tools/attn_bench.py [--B 64 --heads 8 --S 257 --D 96] [--step-batch 64] [--iters 20 --warmup 5]
+  python tools/attn_bench.py --long [--iters 20 --warmup 5] [--step-batch 64]
+
+--long measures the K/V-streaming kernels (kzv_attn_stream_fwd / _bwd) next to what kzv_attn_fwd / _bwd run on the same launch
+(the whole-head MFMA kernels at 257 tokens, the VALU kernel at head_dim 96 and 384 tokens), the streaming kernels alone at
+head_dim 64, B * heads = 32 * 12, 1,025 tokens, and the step of the reference CLI model built with long_sequences=True on
+1024 x 64, 1536 x 64 and 2048 x 64 columns (257, 385 and 513 tokens).
 
 * op: kzv_attn_fwd and kzv_attn_bwd on the model's packed strides (Q | K | V column blocks of one [B * S, 3 * heads * D]
   buffer, O / dO [B * S, heads * D]), dropout 0.1 as in training; device-event timing, mean per launch;
@@ -39,7 +45,7 @@ def load_tolerant():
     return L.load(), unbound
 
 
-def time_op(lib, B, heads, S, D, iters, warmup):
+def time_op(lib, B, heads, S, D, iters, warmup, stream=False):
     H = heads * D
     gen = torch.Generator(device="cuda")
     gen.manual_seed(0)
@@ -54,7 +60,8 @@ def time_op(lib, B, heads, S, D, iters, warmup):
                         head_dim=0 if D == 64 else D)
     st = torch.cuda.current_stream().cuda_stream
     res = {}
-    for name, fn in (("fwd", lib.kzv_attn_fwd), ("bwd", lib.kzv_attn_bwd)):
+    fns = (("fwd", lib.kzv_attn_stream_fwd), ("bwd", lib.kzv_attn_stream_bwd)) if stream else (("fwd", lib.kzv_attn_fwd), ("bwd", lib.kzv_attn_bwd))
+    for name, fn in fns:
         for _ in range(warmup):
             L.check(fn(C.byref(a), st), name)
         torch.cuda.synchronize()
@@ -70,15 +77,17 @@ def time_op(lib, B, heads, S, D, iters, warmup):
     return res
 
 
-def time_step(batch, iters, warmup):
+def time_step(batch, iters, warmup, image_h=1024, long_sequences=False):
+    import dataclasses
     from kzv.config import reference_cli_config
     from kzv.data import build_decoder_dir, synthetic_batch
     from kzv.model import TrOCRModel
     from kzv.trainer import Stepper
-    cfg = reference_cli_config()
+    cfg = dataclasses.replace(reference_cli_config(), image_h=image_h)
     with tempfile.TemporaryDirectory() as tmp:
+        kw = {"long_sequences": True} if long_sequences else {}
         m = TrOCRModel(cfg.encoder_config_dict(), build_decoder_dir(os.path.join(tmp, "dec"), cfg), device="cuda:0", init_seed=42,
-                       load_tokenizer=False)
+                       load_tokenizer=False, **kw)
     opt = m.configure_optimizers()
     m.train()
     stepper = Stepper(m, opt, world=1, max_grad_norm=1.0, dp_path=False)
@@ -92,8 +101,27 @@ def time_step(batch, iters, warmup):
         loss = stepper.step(b, warmup + i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return {"batch": batch, "ms_per_step": round(dt * 1e3 / iters, 2), "img_per_s": round(batch * iters / dt, 1),
-            "loss": round(float(loss), 4)}
+    out = {"batch": batch, "ms_per_step": round(dt * 1e3 / iters, 2), "img_per_s": round(batch * iters / dt, 1),
+           "loss": round(float(loss), 4)}
+    del stepper, opt, m
+    torch.cuda.empty_cache()
+    return out
+
+
+def long_table(lib, iters, warmup, step_batch, step_iters):
+    """--long: streaming against whole-head / VALU on the same launches, the 1,025-token throughput, the long-column steps."""
+    ops = []
+    for B, heads, S, D, other in ((64, 8, 257, 96, True), (64, 12, 257, 64, True), (64, 8, 384, 96, True), (32, 12, 1025, 64, False)):
+        row = {"B": B, "heads": heads, "S": S, "D": D, "stream": time_op(lib, B, heads, S, D, iters, warmup, stream=True)}
+        if other:
+            row["impl"] = L.attention_impl(D, S, S, heads=heads)
+            row[row["impl"]] = time_op(lib, B, heads, S, D, iters if row["impl"] != "valu" else max(2, iters // 5), warmup, stream=False)
+        ops.append(row)
+    steps = []
+    if step_batch > 0:
+        for h in (1024, 1536, 2048):
+            steps.append(dict(image=f"{h}x64", tokens=h // 16 * 4 + 1, **time_step(step_batch, step_iters, 2, image_h=h, long_sequences=True)))
+    return {"op": ops, "step": steps}
 
 
 def main():
@@ -106,12 +134,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--step-batch", type=int, default=64)
     ap.add_argument("--step-iters", type=int, default=10)
+    ap.add_argument("--long", action="store_true", help="the streaming-kernel table (see above)")
+    ap.add_argument("--stream", action="store_true", help="time kzv_attn_stream_fwd / _bwd instead of kzv_attn_fwd / _bwd")
     args = ap.parse_args()
     lib, unbound = load_tolerant()
+    if args.long:
+        print(json.dumps({"lib": L.LIB_PATH, **long_table(lib, args.iters, args.warmup, args.step_batch, args.step_iters)}), flush=True)
+        return
     out = {"lib": L.LIB_PATH, "unbound": unbound, "geometry": {"B": args.B, "heads": args.heads, "S": args.S, "D": args.D}}
     if "kzv_attn_impl" not in unbound:
-        out["impl"] = L.attention_impl(args.D, args.S, args.S, heads=args.heads)
-    out["op"] = time_op(lib, args.B, args.heads, args.S, args.D, args.iters, args.warmup)
+        out["impl"] = L.attention_impl(args.D, args.S, args.S, heads=args.heads, long_sequences=args.stream)
+    out["op"] = time_op(lib, args.B, args.heads, args.S, args.D, args.iters, args.warmup, stream=args.stream)
     if args.step_batch > 0:
         out["step"] = time_step(args.step_batch, args.step_iters, 2)
     print(json.dumps(out), flush=True)
