@@ -367,7 +367,8 @@ int kzv_layernorm_bwd(const void* dy, int dy_is_f32, const float* x, const float
  * decoder; attention.hip) and for head_dim 96 in mode 0 with Sq, Sk <= 288 (the reference's CLI default ViT, 768 / 8 heads on
  * 1024 x 64 columns: 257 tokens, scripts/train_trocr.py:39-44; attention_d96.hip).  Other head dimensions (multiples of 8 up to
  * 128) and head_dim 96 beyond 288 keys take a plain fp32 kernel -- same results and dropout masks, several times slower
- * (attention_generic.hip).  kzv_attn_impl reports which one serves a call.
+ * (attention_generic.hip).  kzv_attn_impl reports which one serves a call; it, every other attention entry point and the
+ * one dispatch behind them live in attention_api.cpp, what the kernel files share in attention_common.h.
  * mode 0: no mask (ViT self-attn / decoder cross-attn); mode 1: causal AND key-not-pad (decoder self; head_dim 64 only). */
 typedef struct kzv_attn_args {
     const void* Q; const void* K; const void* V;   /* bf16, row strides ldq/ldk/ldv (multiples of 8), head h at col h*head_dim */

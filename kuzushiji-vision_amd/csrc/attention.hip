@@ -18,10 +18,12 @@
 //           dV^T += dO^T.P and dK^T += Q^T.dS; only dS crosses LDS (bf16, 32-query slab) for dQ.
 // Q / K / V / O / dO are read once per (batch, head): every LDS-DMA of this unit carries the streaming hint (kzv_common.h KZV_GLDS_NT):
 // attention forward 1.044 -> 1.012 ms per step, backward 2.63 -> 2.54, four same-box alternations (round 4)
-#define KZV_GLDS_NT
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+//
+// What this file shares with attention_d96.hip / attention_stream.hip / attention_generic.hip (LDS image layout, dropout bookkeeping,
+// the forward key-tile and backward element steps, the parameter filler, the limits) is in attention_common.h; the entry points and
+// the dispatch are in attention_api.cpp, which calls kzv_attn_mfma64 below with validated arguments.
+#define KZV_GLDS_NT      // must precede the first inclusion of kzv_common.h (attention_common.h includes it)
+#include "attention_common.h"
 
 namespace {
 
@@ -36,7 +38,8 @@ namespace {
 // per-lane constants + immediates, the softmax normalisation and 1 / P(keep) are applied to the 16 outputs instead of the
 // 44 probabilities, the dropout bits come from the packed 4 x 4-block generator of kzv_common.h, and dS crosses LDS as
 // packed 8-byte pieces of a [key][query] image that the dQ product reads back transposed (ds_read_b64_tr_b16).
-constexpr float LOG2E = 1.4426950408889634f;
+// Four sets of per-lane offsets (forward kA / kB and vT, backward tT and kT) keep the D = 64 layout written out instead of
+// img_off<64> / tr_off<64>: through the helpers the same values cost v_lshl_add_u32 for v_lshlrev_b32 and another allocation.
 
 struct AttnP {
     const bf16_t* Q; const bf16_t* K; const bf16_t* V; bf16_t* O; float* LSE;
@@ -55,24 +58,11 @@ __device__ __forceinline__ void stage_image(char* img, const bf16_t* src, int64_
     const int r8 = lane >> 3;
     for (int pc = w; pc < SP / 8; pc += NW) {
         const int row = pc * 8 + r8;
-        const int chunk = (lane & 7) ^ (row & 7);
+        const int chunk = (lane & 7) ^ swz<64>(row);
         const void* s = row < nvalid ? (const void*)(src + (int64_t)row * ld + chunk * 8) : zero16;
         glds16(s, img + pc * 1024);
     }
 }
-__device__ __forceinline__ bf16x8 frag_row(const char* img, int row, int chunk) {
-    return *(const bf16x8*)(img + row * 128 + ((chunk ^ (row & 7)) << 4));
-}
-// transposing read: block rows rb..rb+3 (supplied by lane groups of 4), 16 columns starting at chunk c2 (2 chunks)
-__device__ __forceinline__ bf16x4 frag_tr(const char* img, int rb, int c2, int l15) {
-    const int row = rb + (l15 >> 2);
-    const int chunk = c2 + ((l15 >> 1) & 1);
-    return lds_tr16(img + row * 128 + ((chunk ^ (row & 7)) << 4) + (l15 & 1) * 8);
-}
-__device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return (bf16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-__device__ __forceinline__ bf16x8 words8(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(bf16x8, (u32x4){a, b, c, d}); }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
 // ================================================================================================ forward
 // launch bounds = the occupancy the LDS images allow anyway (3 workgroups per CU at <= 192 key rows, 2 at 288)
@@ -117,8 +107,8 @@ __global__ __launch_bounds__(256, NKT <= 12 ? 3 : 2) void attn_fwd_kernel(const 
         for (int dt = 0; dt < 4; ++dt) vT[dt] = row * 128 + ((((dt * 2 + hb) ^ (row & 7))) << 4) + (l15 & 1) * 8;
     }
     const AttDropLane dl = att_drop_lane(l15 & 3, true);
-    const unsigned thrm1x2 = (unsigned)((p.thr16 - 32768 - 1) & 0xffff) * 0x10001u;
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
+    const unsigned thrm1x2 = att_thrm1x2(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     KZV_ASTAMP();
@@ -157,19 +147,11 @@ __global__ __launch_bounds__(256, NKT <= 12 ? 3 : 2) void attn_fwd_kernel(const 
         const float mref = dead ? 0.f : mx * sc;
         float sum = 0.f;
         unsigned pw[NKP * 4];                                 // bf16 pairs of the (dropped, un-normalised) probabilities
-        const unsigned xw0 = (((unsigned)(b * p.heads + h) * nQ4 + ((unsigned)q >> 2)) * nK4 + g) * KZV_ATT_GOLD + p.key;
+        const unsigned xw0 = att_block_word(b * p.heads + h, nQ4, (unsigned)q >> 2, nK4, g, p.key);
 #pragma unroll
         for (int kt = 0; kt < NKP * 2; ++kt) {
             if (kt < NKT && (EXACT || kt < nk)) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], sc, -mref)); sum += s[kt][r]; }
-                unsigned w01 = pack_bf2(s[kt][0], s[kt][1]), w23 = pack_bf2(s[kt][2], s[kt][3]);
-                if (p.thr16) {
-                    unsigned u01, u23;
-                    att_drop_u(dl, att_mix(xw0 + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
-                    w01 &= att_keep_mask(u01, thrm1x2); w23 &= att_keep_mask(u23, thrm1x2);
-                }
-                pw[kt * 2] = w01; pw[kt * 2 + 1] = w23;
+                att_fwd_tile(s[kt], sc, mref, sum, p.thr16, dl, xw0 + (unsigned)kt * (4u * KZV_ATT_GOLD), thrm1x2, pw + kt * 2);
             } else {
                 pw[kt * 2] = 0u; pw[kt * 2 + 1] = 0u;
             }
@@ -198,7 +180,7 @@ __global__ __launch_bounds__(256, NKT <= 12 ? 3 : 2) void attn_fwd_kernel(const 
             bf16_t* orow = p.O + ((int64_t)b * p.Sq + q) * p.ldo + h * 64 + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                *(uint2*)(orow + dt * 16) = make_uint2(pack_bf2(o[dt][0] * onorm, o[dt][1] * onorm), pack_bf2(o[dt][2] * onorm, o[dt][3] * onorm));
+                store_bf4(orow + dt * 16, o[dt], onorm);
         }
         KZV_ASTAMP();
     }
@@ -230,28 +212,21 @@ __device__ __forceinline__ void stage_slabs(char* qs, char* os, const bf16_t* Qb
     for (int pc = w; pc < npc; pc += NW) {
         const int pq = pc & 3;
         const int row = pq * 8 + (lane >> 3);
-        const unsigned chunk = (lane & 7) ^ (row & 7);
+        const unsigned chunk = (lane & 7) ^ swz<64>(row);
         const unsigned r = (unsigned)min(row0 + row, nvalid - 1);
-#ifdef KZV_ATT_M0_RESTORE
-        if (pc < 4) glds16_asm_soff(Qb, (r * ldq + chunk * 8) * 2, qs + pq * 1024);
-        else if (pc < 8) glds16_asm_soff(dOb, (r * ldo + chunk * 8) * 2, os + pq * 1024);
-        else glds16_asm_soff(Ob, (r * ldo + chunk * 8) * 2, oo + pq * 1024);
-#else       // every LDS-DMA of the backward kernel is issued from asm: M0 need not be handed back to the compiler
+        // every LDS-DMA of the backward kernel is issued from asm: M0 need not be handed back to the compiler (tools/check_m0.py)
         if (pc < 4) glds16_asm_soff_m0(Qb, (r * ldq + chunk * 8) * 2, qs + pq * 1024);
         else if (pc < 8) glds16_asm_soff_m0(dOb, (r * ldo + chunk * 8) * 2, os + pq * 1024);
         else glds16_asm_soff_m0(Ob, (r * ldo + chunk * 8) * 2, oo + pq * 1024);
-#endif
     }
 }
 // delta' of the 8 rows this wave staged itself (rows 8w .. 8w+7 of the slab): lane = (row, 16-byte chunk); its own DMA pieces are
 // visible to it after its vmcnt wait, no barrier needed
 __device__ __forceinline__ void slab_delta(const char* os, const char* oo, float* dlt_slab, float keep_p, int w, int lane) {
     const int row = w * 8 + (lane >> 3);
-    const unsigned off = row * 128 + ((((unsigned)lane & 7) ^ (row & 7)) << 4);
+    const unsigned off = img_off<64>(row, lane & 7);
     const bf16x8 a = *(const bf16x8*)(os + off), e = *(const bf16x8*)(oo + off);
-    float d = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d += bf2f((bf16_t)a[j]) * bf2f((bf16_t)e[j]);
+    float d = dot8(a, e);
     d += __shfl_xor(d, 1, 64);
     d += __shfl_xor(d, 2, 64);
     d += __shfl_xor(d, 4, 64);
@@ -263,12 +238,8 @@ __device__ __forceinline__ void stage_image_asm(char* img, const bf16_t* src, in
     const int r8 = lane >> 3;
     for (int pc = w; pc < SP / 8; pc += NW) {
         const int row = pc * 8 + r8;
-        const int chunk = (lane & 7) ^ (row & 7);
-#ifdef KZV_ATT_M0_RESTORE
-        glds16_asm(row < nvalid ? (const void*)(src + (int64_t)row * ld + chunk * 8) : zero16, img + pc * 1024);
-#else
+        const int chunk = (lane & 7) ^ swz<64>(row);
         glds16_asm_m0(row < nvalid ? (const void*)(src + (int64_t)row * ld + chunk * 8) : zero16, img + pc * 1024);
-#endif
     }
 }
 
@@ -337,15 +308,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
         const int row = (tid >> 2) + i * (NT / 4);
         float d = 0.f;
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d += bf2f((bf16_t)ov[i][c][j]) * bf2f((bf16_t)dv8[i][c][j]);
-        d += __shfl_xor(d, 1, 64);
-        d += __shfl_xor(d, 2, 64);
-        if ((tid & 3) == 0 && row < SP) {
-            lse[row] = row < p.Sq ? lv[i] * LOG2E : INFINITY;
-            dlt[row] = row < p.Sq ? d * keep_p : 0.f;
-        }
+        for (int c = 0; c < 2; ++c) d = dot8(ov[i][c], dv8[i][c], d);
+        att_row_stats(d, lv[i], keep_p, row, SP, p.Sq, tid, lse, dlt);
     }
     KZV_BSTAMP();
   }
@@ -365,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) { dk[a][d] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[a][d] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
     // per-lane LDS offsets (constant over the whole sweep)
-    const unsigned rA = l15 * 128 + ((g ^ (l15 & 7)) << 4), rB = l15 * 128 + (((4 + g) ^ (l15 & 7)) << 4);   // row fragments
+    const unsigned rA = img_off<64>(l15, g), rB = img_off<64>(l15, 4 + g);   // row fragments
     unsigned tT[4];                                                                                          // transposed fragments
     {
         const int row = 4 * g + (l15 >> 2), hb = (l15 >> 1) & 1;
@@ -373,10 +337,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
         for (int dt = 0; dt < 4; ++dt) tT[dt] = row * 128 + ((((dt * 2 + hb) ^ (row & 7))) << 4) + (l15 & 1) * 8;
     }
     const AttDropLane dl = att_drop_lane(l15 & 3, false);
-    const int thr_s = p.thr16 ? (int)p.thr16 - 32768 : -40000;          // no dropout: below every int16, everything is kept
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
+    const int thr_s = att_thr_s(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
     // pre-mix word of block (q >> 2 = g, k >> 2 = l15 >> 2) of slab 0; + per slab / 16-query half / key tile multiples of GOLD
-    unsigned xslab = (((unsigned)(b * p.heads + h) * nQ4 + g) * nK4 + (l15 >> 2)) * KZV_ATT_GOLD + p.key;
+    unsigned xslab = att_block_word(b * p.heads + h, nQ4, g, nK4, l15 >> 2, p.key);
     const unsigned xstep_t2 = 4u * nK4 * KZV_ATT_GOLD;
 
     for (int qb = 0; qb < nqb; ++qb) {
@@ -430,14 +394,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
                     att_drop_u(dl, att_mix(xslab + (unsigned)t2 * xstep_t2 + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
                 float pm[4], ds[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pr = __builtin_amdgcn_exp2f(fmaf(S[r], sc, -lq4[r]));      // lse = +inf for q >= Sq / dead rows
-                    if (MODE == 1) pr = key <= qb * 32 + t2 * 16 + 4 * g + r ? pr : 0.f;     // causal
-                    const unsigned ur = (r & 2) ? u23 : u01;
-                    const int us = (r & 1) ? (int)ur >> 16 : (int)(short)(ur & 0xffffu);
-                    pm[r] = us >= thr_s ? pr : 0.f;
-                    ds[r] = fmaf(pm[r], dP[r], -pr * dq4[r]);
-                }
+                for (int r = 0; r < 4; ++r)      // MODE 1: causal
+                    att_bwd_elem<MODE == 1>(r, S[r], dP[r], sc, lq4[r], dq4[r], key <= qb * 32 + t2 * 16 + 4 * g + r, u01, u23, thr_s, pm[r], ds[r]);
                 pdw[t2 * 2] = pack_bf2(pm[0], pm[1]); pdw[t2 * 2 + 1] = pack_bf2(pm[2], pm[3]);
                 dsw[t2 * 2] = pack_bf2(ds[0], ds[1]); dsw[t2 * 2 + 1] = pack_bf2(ds[2], ds[3]);
                 *(uint2*)(dsrow + (((t2 * 4 + g) ^ dsz) << 3)) = make_uint2(dsw[t2 * 2], dsw[t2 * 2 + 1]);
@@ -497,6 +455,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
 #pragma unroll
                 for (int u = 0; u < TB; ++u) {
                     const int dt = dt0 + u;
+                    // store_bf4 written out: through the helper, the four-wave instances schedule these two stores differently
                     *(uint2*)(row + dt * 16) = make_uint2(pack_bf2(acc[u][0] * osc, acc[u][1] * osc), pack_bf2(acc[u][2] * osc, acc[u][3] * osc));
                 }
             }
@@ -515,37 +474,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
         bf16_t* vrow = p.dV + ((int64_t)b * p.Sk + key) * p.ldv + h * 64 + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            *(uint2*)(krow + dt * 16) = make_uint2(pack_bf2(dk[a][dt][0] * ksc, dk[a][dt][1] * ksc), pack_bf2(dk[a][dt][2] * ksc, dk[a][dt][3] * ksc));
-            *(uint2*)(vrow + dt * 16) = make_uint2(pack_bf2(dv[a][dt][0] * p.inv_keep, dv[a][dt][1] * p.inv_keep),
-                                                   pack_bf2(dv[a][dt][2] * p.inv_keep, dv[a][dt][3] * p.inv_keep));
+            store_bf4(krow + dt * 16, dk[a][dt], ksc);
+            store_bf4(vrow + dt * 16, dv[a][dt], p.inv_keep);
         }
     }
-}
-
-// what the head_dim-64 kernels refuse (kzv_attn_impl)
-int check64(const kzv_attn_args* a, bool bwd) {
-    if (!a || !a->Q || !a->K || !a->V || !a->O) return kzv_fail(KZV_E_ARG, "attn: null operand");
-    if (a->Sq <= 0 || a->Sk <= 0 || a->Sq > 288 || a->Sk > 288) return kzv_fail(KZV_E_ARG, "attn: Sq/Sk must be in 1..288");
-    if (a->mode == 1 && a->Sq > 192) return kzv_fail(KZV_E_ARG, "attn: causal mode is built for <= 192 tokens");
-    if (a->mode == 1 && (!a->ids || a->Sq != a->Sk)) return kzv_fail(KZV_E_ARG, "attn: causal mode needs ids and Sq == Sk");
-    if (a->mode != 0 && a->mode != 1) return kzv_fail(KZV_E_ARG, "attn: unknown mode");
-    if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
-    if (bwd && (!a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE)) return kzv_fail(KZV_E_ARG, "attn_bwd: null gradient operand");
-    return KZV_OK;
-}
-
-int fill(AttnP& p, const kzv_attn_args* a) {
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
-    p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
-    p.zero16 = kzv_zero_page();
-    if (!p.zero16) return kzv_fail(KZV_E_HIP, "attn: zero page unavailable");
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.ids = a->ids; p.ld_ids = a->ld_ids; p.pad_id = a->pad_id;
-    p.B = a->B; p.heads = a->heads; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.scale = 0.125f;   // head_dim^-0.5, head_dim = 64
-    kzv_drop_params(a->drop_p, &p.thr16, &p.inv_keep);
-    p.key = a->drop_key;
-    return KZV_OK;
 }
 
 }  // namespace
@@ -555,10 +487,6 @@ extern "C" int kzv_debug_bwd_stamps(unsigned long long* host128) {
     return hipMemcpyFromSymbol(host128, HIP_SYMBOL(kzv_bwd_stamps), 128 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
 }
 #endif
-
-int kzv_attn_generic(const kzv_attn_args* a, int D, bool bwd, hipStream_t s);      // attention_generic.hip
-int kzv_attn_generic_check(const kzv_attn_args* a, int D);
-int kzv_attn_d96(const kzv_attn_args* a, bool bwd, hipStream_t s);                  // attention_d96.hip
 
 template <int MODE, int NKT, bool EXACT>
 static void launch_fwd(const AttnP& p, int blocks, hipStream_t s) {
@@ -575,68 +503,22 @@ static void launch_bwd(const AttnP& p, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((attn_bwd_kernel<MODE, NKT, NW, EXACT>), dim3(blocks), dim3(NW * 64), lds, s, p);
 }
 
-// Which kernels serve a call (include/kzv.h): head_dim 0 / 64 -> attention.hip; head_dim 96, mode 0, Sq and Sk in 1..288 ->
-// attention_d96.hip; the other head dims the VALU kernel takes -> attention_generic.hip.  Arguments a launch would refuse give its
-// error code and message.  The launches below dispatch through this, so the report and the launch cannot disagree.
-extern "C" int kzv_attn_impl(const kzv_attn_args* a, int bwd) {
-    if (a && a->head_dim != 0 && a->head_dim != 64) {
-        if (!bwd && (!a->Q || !a->K || !a->V || !a->O)) return kzv_fail(KZV_E_ARG, "attn: null operand");
-        if (bwd && (!a->Q || !a->K || !a->V || !a->O || !a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE)) return kzv_fail(KZV_E_ARG, "attn_bwd: null operand");
-        if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
-        if (a->head_dim == 96 && a->mode == 0 && a->Sq >= 1 && a->Sq <= 288 && a->Sk >= 1 && a->Sk <= 288) return KZV_ATTN_MFMA96;
-        if (int rc = kzv_attn_generic_check(a, a->head_dim)) return rc;
-        return KZV_ATTN_VALU;
-    }
-    if (int rc = check64(a, bwd != 0)) return rc;
-    return KZV_ATTN_MFMA64;
-}
-
-int kzv_attn_stream_check(const kzv_attn_args* a, bool bwd);                      // attention_stream.hip
-
-// With KZV_MODEL_LONG_SEQ the calls the whole-head kernels cannot take (head_dim 0 / 64 / 96, mode 0, Sq or Sk above 288) go to the
-// streaming kernels; everything else is kzv_attn_impl's answer, so a short launch of a long-sequence model is unchanged.
-extern "C" int kzv_attn_impl_ex(const kzv_attn_args* a, int bwd, unsigned flags) {
-    if ((flags & KZV_MODEL_LONG_SEQ) && a && a->mode == 0 && (a->head_dim == 0 || a->head_dim == 64 || a->head_dim == 96) &&
-        (a->Sq > 288 || a->Sk > 288)) {
-        if (int rc = kzv_attn_stream_check(a, bwd != 0)) return rc;
-        return a->head_dim == 96 ? KZV_ATTN_STREAM96 : KZV_ATTN_STREAM64;
-    }
-    return kzv_attn_impl(a, bwd);
-}
-
-extern "C" int kzv_attn_fwd(const kzv_attn_args* a, void* stream) {
-    const int impl = kzv_attn_impl(a, 0);
-    if (impl < 0) return impl;
-    if (impl != KZV_ATTN_MFMA64) {
-        KzvProfScope prof(2, 4.0 * a->B * a->heads * (double)a->Sq * a->Sk * a->head_dim, (hipStream_t)stream);
-        return impl == KZV_ATTN_MFMA96 ? kzv_attn_d96(a, false, (hipStream_t)stream) : kzv_attn_generic(a, a->head_dim, false, (hipStream_t)stream);
-    }
+// The launch: kzv_attn_launch (attention_api.cpp) sends here what kzv_attn_impl answered KZV_ATTN_MFMA64 for.
+int kzv_attn_mfma64(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     AttnP p;
-    if (int rc = fill(p, a)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int nkt = (a->Sk + 15) >> 4, nqt = (a->Sq + 15) >> 4, blocks = a->B * a->heads;
-    KzvProfScope prof(2, 4.0 * a->B * a->heads * (double)a->Sq * a->Sk * 64, s);
-    // exact-tile instances for the two hot shapes (a wave holds ceil(NKT / 4) query tiles: 12 for both)
-    if (a->mode == 1) launch_fwd<1, 12, false>(p, blocks, s);
-    else if (nkt == 11 && nqt <= 12) launch_fwd<0, 11, true>(p, blocks, s);
-    else if (nkt == 10 && nqt <= 12) launch_fwd<0, 10, true>(p, blocks, s);
-    else if (nkt <= 12 && nqt <= 12) launch_fwd<0, 12, false>(p, blocks, s);
-    else launch_fwd<0, 18, false>(p, blocks, s);
-    return kzv_check_launch("attn_fwd");
-}
-
-extern "C" int kzv_attn_bwd(const kzv_attn_args* a, void* stream) {
-    const int impl = kzv_attn_impl(a, 1);
-    if (impl < 0) return impl;
-    if (impl != KZV_ATTN_MFMA64) {
-        KzvProfScope prof(3, 10.0 * a->B * a->heads * (double)a->Sq * a->Sk * a->head_dim, (hipStream_t)stream);
-        return impl == KZV_ATTN_MFMA96 ? kzv_attn_d96(a, true, (hipStream_t)stream) : kzv_attn_generic(a, a->head_dim, true, (hipStream_t)stream);
+    kzv_attn_fill(p, a, 64);
+    if (int rc = kzv_attn_fill_zero(p, "attn")) return rc;
+    p.ids = a->ids; p.ld_ids = a->ld_ids; p.pad_id = a->pad_id;
+    const int nkt = (a->Sk + 15) >> 4, nqt = (a->Sq + 15) >> 4, nqb = (a->Sq + 31) >> 5, blocks = a->B * a->heads;
+    if (!bwd) {
+        // exact-tile instances for the two hot shapes (a wave holds ceil(NKT / 4) query tiles: 12 for both)
+        if (a->mode == 1) launch_fwd<1, 12, false>(p, blocks, s);
+        else if (nkt == 11 && nqt <= 12) launch_fwd<0, 11, true>(p, blocks, s);
+        else if (nkt == 10 && nqt <= 12) launch_fwd<0, 10, true>(p, blocks, s);
+        else if (nkt <= 12 && nqt <= 12) launch_fwd<0, 12, false>(p, blocks, s);
+        else launch_fwd<0, 18, false>(p, blocks, s);
+        return kzv_check_launch("attn_fwd");
     }
-    AttnP p;
-    if (int rc = fill(p, a)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int nkt = (a->Sk + 15) >> 4, nqb = (a->Sq + 31) >> 5, blocks = a->B * a->heads;
-    KzvProfScope prof(3, 10.0 * a->B * a->heads * (double)a->Sq * a->Sk * 64, s);
     // the per-row arrays (log-sum-exp, delta) hold 32 * ceil(NKT / 2) queries: 192 for every <= 12-tile instance
     if (a->mode == 1 && nkt <= 8) launch_bwd<1, 8, 4, false>(p, blocks, s);           // the decoder (<= 128 positions)
     else if (a->mode == 1) launch_bwd<1, 12, 4, false>(p, blocks, s);

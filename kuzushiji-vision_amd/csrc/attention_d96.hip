@@ -15,17 +15,16 @@
 //     workgroup per CU, so 8 waves keep two per SIMD.
 //   * Backward: Q and dO come in 32-query slabs through a 2-deep LDS ring, loaded into registers one slab ahead (plain loads,
 //     retired by an explicit vmcnt(0) before they are written to LDS); dS^T crosses LDS for dQ as in attention.hip.
+// The image layout (swz / img_off / tr_off<96>), the dropout bookkeeping and the per-tile / per-element steps are attention_common.h's.
 // Every global load is unconditional (rows past the end are clamped or read the zero page); K / V use the builtin LDS-DMA, whose
 // M0 the compiler owns.
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+#include "attention_common.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int NW = 8, NT = NW * 64;     // waves, threads per workgroup
 constexpr int NKT = 18, SP = NKT * 16;  // key tiles of 16 / image rows (288 tokens)
+static_assert(SP == KZV_ATTN_MAX_S, "the images hold the longest sequence the dispatch sends here");
 constexpr int NKP = NKT / 2;            // 32-key steps
 constexpr int ROW = 192;                // bytes per 96-wide bf16 row
 constexpr int SLAB = 32 * ROW;          // one 32-query slab of Q or dO
@@ -39,32 +38,16 @@ struct AttnP96 {
     float scale; unsigned thr16; float inv_keep; unsigned key;
 };
 
-__device__ __forceinline__ int swz(int r) { return (((r >> 2) & 1) << 1) | ((r >> 3) & 1); }
-__device__ __forceinline__ int img_off(int r, int c) { return r * ROW + ((c ^ swz(r)) << 4); }
-// per-lane offset of a transposed read: block rows 4g .. 4g + 3 (+ a 16-aligned base), 16 columns from chunk 2 * dt
-__device__ __forceinline__ int tr_off(int g, int l15, int dt) {
-    const int r = 4 * g + (l15 >> 2);
-    return img_off(r, 2 * dt + ((l15 >> 1) & 1)) + (l15 & 1) * 8;
-}
-
 // stage rows [0, SP) of one head's [S][96] operand into a swizzled image by LDS-DMA (lane-linear destination: the permutation is
 // on the source); rows >= nvalid read the zero page
 __device__ __forceinline__ void stage_image96(char* img, const bf16_t* src, int64_t ld, int nvalid, const void* zero16, int w, int lane) {
     constexpr int NPC = SP * 12 / 64;
     static_assert(SP * 12 % 64 == 0, "image must be a whole number of 1-KiB pieces");
     for (int pc = w; pc < NPC; pc += NW) {
-        const int P = pc * 64 + lane, r = P / 12, c = (P - r * 12) ^ swz(r);
+        const int P = pc * 64 + lane, r = P / 12, c = (P - r * 12) ^ swz<96>(r);
         glds16(r < nvalid ? (const void*)(src + (int64_t)r * ld + c * 8) : zero16, img + pc * 1024);
     }
 }
-
-__device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return (bf16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-__device__ __forceinline__ bf16x8 words8(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(bf16x8, (u32x4){a, b, c, d}); }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-__device__ __forceinline__ void pin(bf16x8& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin(u32x4& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 
 // ================================================================================================ forward
 __global__ __launch_bounds__(NT) void attn96_fwd_kernel(const AttnP96 p) {
@@ -85,10 +68,10 @@ __global__ __launch_bounds__(NT) void attn96_fwd_kernel(const AttnP96 p) {
         for (int i = 0; i < 3; ++i) qf[it][i] = *(const bf16x8*)(qrow + 32 * i);
     }
     // per-lane LDS offsets: chunk c ^ swz keeps c >> 2, so chunk groups 4i and 16-column tiles dt, dt + 2, dt + 4 are immediates
-    const int kA = img_off(l15, g), vT0 = tr_off(g, l15, 0), vT1 = tr_off(g, l15, 1);
+    const int kA = img_off<96>(l15, g), vT0 = tr_off<96>(g, l15, 0), vT1 = tr_off<96>(g, l15, 1);
     const AttDropLane dl = att_drop_lane(l15 & 3, true);
-    const unsigned thrm1x2 = (unsigned)((p.thr16 - 32768 - 1) & 0xffff) * 0x10001u;
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
+    const unsigned thrm1x2 = att_thrm1x2(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int it = 0; it < QI; ++it)
@@ -125,19 +108,11 @@ __global__ __launch_bounds__(NT) void attn96_fwd_kernel(const AttnP96 p) {
         const float mref = mx * sc;
         float sum = 0.f;
         unsigned pw[NKP * 4];                                 // bf16 pairs of the (dropped, un-normalised) probabilities
-        const unsigned xw0 = (((unsigned)(b * p.heads + h) * nQ4 + ((unsigned)q >> 2)) * nK4 + g) * KZV_ATT_GOLD + p.key;
+        const unsigned xw0 = att_block_word(b * p.heads + h, nQ4, (unsigned)q >> 2, nK4, g, p.key);
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             if (kt < nkt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], sc, -mref)); sum += s[kt][r]; }
-                unsigned w01 = pack_bf2(s[kt][0], s[kt][1]), w23 = pack_bf2(s[kt][2], s[kt][3]);
-                if (p.thr16) {
-                    unsigned u01, u23;
-                    att_drop_u(dl, att_mix(xw0 + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
-                    w01 &= att_keep_mask(u01, thrm1x2); w23 &= att_keep_mask(u23, thrm1x2);
-                }
-                pw[kt * 2] = w01; pw[kt * 2 + 1] = w23;
+                att_fwd_tile(s[kt], sc, mref, sum, p.thr16, dl, xw0 + (unsigned)kt * (4u * KZV_ATT_GOLD), thrm1x2, pw + kt * 2);
             } else {
                 pw[kt * 2] = 0u; pw[kt * 2 + 1] = 0u;
             }
@@ -167,7 +142,7 @@ __global__ __launch_bounds__(NT) void attn96_fwd_kernel(const AttnP96 p) {
             bf16_t* orow = p.O + ((int64_t)b * p.Sq + q) * p.ldo + h * 96 + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < 6; ++dt)
-                *(uint2*)(orow + dt * 16) = make_uint2(pack_bf2(o[dt][0] * onorm, o[dt][1] * onorm), pack_bf2(o[dt][2] * onorm, o[dt][3] * onorm));
+                store_bf4(orow + dt * 16, o[dt], onorm);
         }
     }
 }
@@ -194,7 +169,7 @@ __device__ __forceinline__ void slab_store(char* qs, char* os, const u32x4 v[2],
     for (int j = 0; j < 2; ++j) {
         const int idx = min(tid + NT * j, 767), op = idx >= 384, i = idx - 384 * op;
         const int r = i / 12, c = i - r * 12;
-        *(u32x4*)((op ? os : qs) + img_off(r, c)) = v[j];
+        *(u32x4*)((op ? os : qs) + img_off<96>(r, c)) = v[j];
     }
 }
 
@@ -244,10 +219,8 @@ __global__ __launch_bounds__(NT) void attn96_bwd_kernel(const AttnP96 p) {
         const int row = (tid >> 2) + i * (NT / 4);
         float d = 0.f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d += bf2f((bf16_t)ov[i][c][j]) * bf2f((bf16_t)dv8[i][c][j]);
-        d += __shfl_xor(d, 1, 64);
+        for (int c = 0; c < 3; ++c) d = dot8(ov[i][c], dv8[i][c], d);
+        d += __shfl_xor(d, 1, 64);      // att_row_stats written out: through the helper this kernel is allocated other registers
         d += __shfl_xor(d, 2, 64);
         if ((tid & 3) == 0 && row < SP) {
             lse[row] = row < p.Sq ? lv[i] * LOG2E : INFINITY;
@@ -265,16 +238,16 @@ __global__ __launch_bounds__(NT) void attn96_bwd_kernel(const AttnP96 p) {
 #pragma unroll
         for (int d = 0; d < 6; ++d) { dk[a][d] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[a][d] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
     // per-lane LDS offsets: chunk c ^ swz keeps c >> 2, so chunk groups 4i and 16-column tiles dt, dt + 2, dt + 4 are immediates
-    const int rA = img_off(l15, g), tT0 = tr_off(g, l15, 0), tT1 = tr_off(g, l15, 1);
+    const int rA = img_off<96>(l15, g), tT0 = tr_off<96>(g, l15, 0), tT1 = tr_off<96>(g, l15, 1);
     const AttDropLane dl = att_drop_lane(l15 & 3, false);
-    const int thr_s = p.thr16 ? (int)p.thr16 - 32768 : -40000;          // no dropout: below every int16, everything is kept
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
-    unsigned xslab = (((unsigned)(b * p.heads + h) * nQ4 + g) * nK4 + (l15 >> 2)) * KZV_ATT_GOLD + p.key;
+    const int thr_s = att_thr_s(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
+    unsigned xslab = att_block_word(b * p.heads + h, nQ4, g, nK4, l15 >> 2, p.key);
     const unsigned xstep_t2 = 4u * nK4 * KZV_ATT_GOLD;
     // phase B: wave w takes the 16 queries t2 = w & 1 and the output tiles dt0 = w >> 1 and dt0 + 4 (the latter for dt0 < 2)
     const int bt2 = w & 1, dt0 = w >> 1;
     const int dsA = (4 * g + (l15 >> 2)) * 64 + (((bt2 * 4 + (l15 & 3)) ^ ((g & 1) << 2)) << 3);
-    const int kT0 = tr_off(g, l15, dt0), kT1 = tr_off(g, l15, dt0 < 2 ? dt0 + 4 : dt0);
+    const int kT0 = tr_off<96>(g, l15, dt0), kT1 = tr_off<96>(g, l15, dt0 < 2 ? dt0 + 4 : dt0);
 
     for (int qb = 0; qb < nqb; ++qb) {
         const char* Qs = Qring + (qb & 1) * SLAB;
@@ -306,13 +279,7 @@ __global__ __launch_bounds__(NT) void attn96_bwd_kernel(const AttnP96 p) {
                     att_drop_u(dl, att_mix(xslab + (unsigned)t2 * xstep_t2 + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
                 float pm[4], ds[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = __builtin_amdgcn_exp2f(fmaf(S[r], sc, -lq4[r]));      // lse = +inf for q >= Sq
-                    const unsigned ur = (r & 2) ? u23 : u01;
-                    const int us = (r & 1) ? (int)ur >> 16 : (int)(short)(ur & 0xffffu);
-                    pm[r] = us >= thr_s ? pr : 0.f;
-                    ds[r] = fmaf(pm[r], dP[r], -pr * dq4[r]);
-                }
+                for (int r = 0; r < 4; ++r) att_bwd_elem<false>(r, S[r], dP[r], sc, lq4[r], dq4[r], true, u01, u23, thr_s, pm[r], ds[r]);
                 pdw[t2 * 2] = pack_bf2(pm[0], pm[1]); pdw[t2 * 2 + 1] = pack_bf2(pm[2], pm[3]);
                 dsw[t2 * 2] = pack_bf2(ds[0], ds[1]); dsw[t2 * 2 + 1] = pack_bf2(ds[2], ds[3]);
                 *(uint2*)(dsrow + (((t2 * 4 + g) ^ (key & 4)) << 3)) = make_uint2(dsw[t2 * 2], dsw[t2 * 2 + 1]);
@@ -355,9 +322,9 @@ __global__ __launch_bounds__(NT) void attn96_bwd_kernel(const AttnP96 p) {
             if (q < p.Sq) {
                 const float osc = p.scale * p.inv_keep;
                 bf16_t* row = p.dQ + ((int64_t)b * p.Sq + q) * p.ldq + h * 96 + 4 * g;
-                *(uint2*)(row + dt0 * 16) = make_uint2(pack_bf2(acc0[0] * osc, acc0[1] * osc), pack_bf2(acc0[2] * osc, acc0[3] * osc));
+                store_bf4(row + dt0 * 16, acc0, osc);
                 if (dt0 < 2)
-                    *(uint2*)(row + (dt0 + 4) * 16) = make_uint2(pack_bf2(acc1[0] * osc, acc1[1] * osc), pack_bf2(acc1[2] * osc, acc1[3] * osc));
+                    store_bf4(row + (dt0 + 4) * 16, acc1, osc);
             }
             // the other ring buffer was last read in the previous block's phase A (two barriers ago)
             slab_store(Qring + ((qb + 1) & 1) * SLAB, Oring + ((qb + 1) & 1) * SLAB, sv, tid);
@@ -374,9 +341,8 @@ __global__ __launch_bounds__(NT) void attn96_bwd_kernel(const AttnP96 p) {
         bf16_t* vrow = p.dV + ((int64_t)b * p.Sk + key) * p.ldv + h * 96 + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < 6; ++dt) {
-            *(uint2*)(krow + dt * 16) = make_uint2(pack_bf2(dk[a][dt][0] * ksc, dk[a][dt][1] * ksc), pack_bf2(dk[a][dt][2] * ksc, dk[a][dt][3] * ksc));
-            *(uint2*)(vrow + dt * 16) = make_uint2(pack_bf2(dv[a][dt][0] * p.inv_keep, dv[a][dt][1] * p.inv_keep),
-                                                   pack_bf2(dv[a][dt][2] * p.inv_keep, dv[a][dt][3] * p.inv_keep));
+            store_bf4(krow + dt * 16, dk[a][dt], ksc);
+            store_bf4(vrow + dt * 16, dv[a][dt], p.inv_keep);
         }
     }
 }
@@ -385,18 +351,11 @@ constexpr int FWD_LDS = 2 * SP * ROW;
 
 }  // namespace
 
-// The launch: arguments were checked by kzv_attn_impl (attention.hip), which sends head_dim 96, mode 0, Sq and Sk in 1..288 here.
+// The launch: arguments were checked by kzv_attn_impl (attention_api.cpp), which sends head_dim 96, mode 0, Sq and Sk in 1..288 here.
 int kzv_attn_d96(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     AttnP96 p;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
-    p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
-    p.zero16 = kzv_zero_page();
-    if (!p.zero16) return kzv_fail(KZV_E_HIP, "attn: zero page unavailable");
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.B = a->B; p.heads = a->heads; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.scale = 1.f / sqrtf(96.f);          // head_dim^-0.5 as attention_generic.hip computes it
-    kzv_drop_params(a->drop_p, &p.thr16, &p.inv_keep);
-    p.key = a->drop_key;
+    kzv_attn_fill(p, a, 96);
+    if (int rc = kzv_attn_fill_zero(p, "attn")) return rc;
     const int blocks = a->B * a->heads;
     if (!bwd) {
         static bool attr = false;

@@ -3,7 +3,7 @@
 // Why it exists: the reference's CLI defaults give the ViT encoder hidden 768 with 8 heads, i.e. head_dim 96
 // (scripts/train_trocr.py:41-43), while the MFMA kernels of attention.hip are built around 64-wide heads (two 32-deep MFMA
 // steps, 128-byte LDS rows).  This file is the FUNCTIONAL path for such geometries: plain fp32 VALU arithmetic on LDS-staged
-// K / V, same semantics and the same dropout element indexing as attention.hip (HF eager_attention_forward,
+// K / V, same semantics and the same dropout element indexing (att_block, attention_common.h) as attention.hip (HF eager_attention_forward,
 // modeling_vit.py:164-189: fp32 softmax of q.k^T * D^-0.5, probability dropout, P.V), several times slower than the MFMA path
 // and not part of any benchmark.  The decoder (4 heads of 64) never comes here.
 //
@@ -13,12 +13,8 @@
 //   backward  kernel A, same decomposition: recomputes P from the saved log-sum-exp, dP = dO.V^T, dS = P (dP keep - delta);
 //             writes dQ and parks dS * scale and P * keep (bf16) in a scratch matrix [pair][Sq][Sk_even];
 //             kernel B, one workgroup per (batch, head, 16 keys): dK = dS^T.Q, dV = (P keep)^T.dO, lane = dimension.
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+#include "attention_common.h"
 #include <mutex>
-
-int kzv_attn_generic_check(const kzv_attn_args* a, int D);
 
 namespace {
 
@@ -32,11 +28,12 @@ struct GenP {
 };
 
 constexpr int QT = 16;       // queries (or keys, kernel B) per workgroup
+static_assert(KZV_ATTN_VALU_MAX_SK == 8 * 64, "a lane of attn_gen_kernel holds the scores of 8 keys");
 
 __device__ __forceinline__ float keep_mul(const GenP& p, int pair, int q, int k) {
     if (!p.thr16) return 1.f;
     // the attention sites' 4 x 4-block generator (kzv_common.h), scalar form: same masks as attention.hip would draw
-    const unsigned block = ((unsigned)pair * ((unsigned)(p.Sq + 3) >> 2) + ((unsigned)q >> 2)) * ((unsigned)(p.Sk + 3) >> 2) + ((unsigned)k >> 2);
+    const unsigned block = att_block(pair, KZV_ATT_N4(p.Sq), (unsigned)q >> 2, KZV_ATT_N4(p.Sk), (unsigned)k >> 2);
     return att_keep1(p.key, block, q & 3, k & 3, (int)p.thr16) ? p.inv_keep : 0.f;
 }
 
@@ -199,42 +196,21 @@ bf16_t* scratch(size_t elems) {          // grow-only, process-global (one devic
     return g_scratch;
 }
 
-int fill(GenP& p, const kzv_attn_args* a, int D, bool bwd) {
-    if (int rc = kzv_attn_generic_check(a, D)) return rc;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
-    p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
-    p.dSs = nullptr; p.Pd = nullptr;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.B = a->B; p.heads = a->heads; p.Sq = a->Sq; p.Sk = a->Sk; p.D = D;
-    p.scale = 1.f / sqrtf((float)D);
-    kzv_drop_params(a->drop_p, &p.thr16, &p.inv_keep);
-    p.key = a->drop_key;
-    (void)bwd;
-    return KZV_OK;
-}
-
 }  // namespace
 
-static size_t lds_bytes(int D, int Sk) {
+size_t kzv_attn_generic_lds(int D, int Sk) {
     const size_t DP = D + 2, SkP = (Sk + 63) & ~63;
     size_t kv = 2 * (size_t)Sk * DP * sizeof(bf16_t);
     kv = (kv + 3) & ~(size_t)3;
     return kv + 4 + 4 * (2 * (size_t)D + SkP) * sizeof(float);
 }
 
-// what this path refuses (kzv_attn_impl asks it too, so the report and the launch give the same verdict and message)
-int kzv_attn_generic_check(const kzv_attn_args* a, int D) {
-    if (a->mode != 0) return kzv_fail(KZV_E_ARG, "attn: the causal / key-padding mode exists for head_dim 64 only");
-    if (D < 8 || D > 128 || D % 8) return kzv_fail(KZV_E_ARG, "attn: head_dim must be a multiple of 8 in 8..128 (got %d)", D);
-    if (a->Sq <= 0 || a->Sk <= 0 || a->Sk > 512) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): Sk must be in 1..512");
-    if (lds_bytes(D, a->Sk) > 160 * 1024) return kzv_fail(KZV_E_ARG, "attn (generic head_dim): %d keys x head_dim %d do not fit the 160 KiB LDS", a->Sk, D);
-    return KZV_OK;
-}
-
+// The launch: arguments were checked by kzv_attn_impl (attention_api.cpp: kzv_attn_generic_check).
 int kzv_attn_generic(const kzv_attn_args* a, int D, bool bwd, hipStream_t s) {
     GenP p;
-    if (int rc = fill(p, a, D, bwd)) return rc;
-    const size_t lds = lds_bytes(D, p.Sk);
+    kzv_attn_fill(p, a, D);
+    p.dSs = nullptr; p.Pd = nullptr; p.D = D;
+    const size_t lds = kzv_attn_generic_lds(D, p.Sk);
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)attn_gen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -19,17 +19,14 @@
 //             delta' = rowsum(dO . O) * P(keep) of every query row are computed once into LDS first.
 //             dQ: a workgroup owns 64 queries (a tile per wave) and sweeps K / V blocks like the forward; dS^T stays in
 //             registers (query on the lane) and feeds dQ^T = K^T.dS^T directly.
-// LDS images use the swizzles of the whole-head kernels: 128-byte rows with chunk c at c ^ (r & 7) (head_dim 64), 192-byte rows
-// with chunk c at c ^ swz(r) (head_dim 96, attention_d96.hip).  All LDS-DMA is issued from asm (glds16_asm): the waits are ours.
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+// LDS images use the layout of the whole-head kernels (attention_common.h: swz / img_off / tr_off<D>), and their dropout
+// bookkeeping and per-tile / per-element steps.  All LDS-DMA is issued from asm (glds16_asm): the waits are ours.
+// The entry points (kzv_attn_stream_fwd / _bwd) and kzv_attn_stream_check are in attention_api.cpp.
+#include "attention_common.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int KB = 64;                  // keys per K / V block (forward, dQ)
-constexpr int MAXS = 4097;              // 4,096 patches + CLS
 
 struct StreamP {
     const bf16_t* Q; const bf16_t* K; const bf16_t* V; bf16_t* O; float* LSE;
@@ -40,16 +37,6 @@ struct StreamP {
     float scale; unsigned thr16; float inv_keep; unsigned key;
 };
 
-template <int D> __device__ __forceinline__ int swz(int r) {
-    if constexpr (D == 64) return r & 7;
-    else return (((r >> 2) & 1) << 1) | ((r >> 3) & 1);
-}
-template <int D> __device__ __forceinline__ int img_off(int r, int c) { return r * (2 * D) + ((c ^ swz<D>(r)) << 4); }
-// per-lane offset of a transposed read: block rows 4g .. 4g + 3 (+ a 16-aligned base), 16 columns from chunk 2 * dt
-template <int D> __device__ __forceinline__ int tr_off(int g, int l15, int dt) {
-    const int r = 4 * g + (l15 >> 2);
-    return img_off<D>(r, 2 * dt + ((l15 >> 1) & 1)) + (l15 & 1) * 8;
-}
 // NR rows [row0, row0 + NR) of one head's [S][D] operand into a swizzled image by LDS-DMA (lane-linear destination, permuted
 // source); rows >= nvalid read the zero page (zero != 0) or are clamped to the last row (zero == 0)
 template <int D, int NR>
@@ -66,26 +53,10 @@ __device__ __forceinline__ void stage(char* img, const bf16_t* src, int64_t ld, 
     }
 }
 
-__device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return (bf16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-__device__ __forceinline__ bf16x8 words8(unsigned a, unsigned b, unsigned c, unsigned d) { return __builtin_bit_cast(bf16x8, (u32x4){a, b, c, d}); }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-__device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b) {
-    float d = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d += bf2f((bf16_t)a[j]) * bf2f((bf16_t)b[j]);
-    return d;
-}
 __device__ __forceinline__ void lds_wait_barrier() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 }
-// Values loaded before the sweep are "used" here, after the prologue's vmcnt(0): hipcc cannot see the asm LDS-DMAs, so a first
-// use inside the K / V loop would get a compiler wait (vmcnt(0)..(3)) that also drains the next block's DMA issued in the same
-// iteration.  With every prologue load consumed up front, the loops carry no vmcnt but the one per block.
-__device__ __forceinline__ void pin(bf16x8& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin(AttDropLane& d) { asm volatile("" : "+v"(d.c01), "+v"(d.c23), "+v"(d.m01), "+v"(d.m23), "+v"(d.rot)); }
 
 // ================================================================================================ forward
 template <int D>
@@ -114,13 +85,13 @@ __global__ __launch_bounds__(256, 2) void stream_fwd_kernel(const StreamP p) {
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) vT[dt] = tr_off<D>(g, l15, dt);
     AttDropLane dl = att_drop_lane(l15 & 3, true);
-    const unsigned thrm1x2 = (unsigned)((p.thr16 - 32768 - 1) & 0xffff) * 0x10001u;
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
+    const unsigned thrm1x2 = att_thrm1x2(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
     unsigned xw0[QT];
 #pragma unroll
     for (int it = 0; it < QT; ++it) {
         const int q = (qblk * 4 * QT + w * QT + it) * 16 + l15;
-        xw0[it] = (((unsigned)bh * nQ4 + ((unsigned)q >> 2)) * nK4 + g) * KZV_ATT_GOLD + p.key;
+        xw0[it] = att_block_word(bh, nQ4, (unsigned)q >> 2, nK4, g, p.key);
     }
     const float sc = p.scale * LOG2E;
     float m[QT], l[QT];
@@ -177,15 +148,9 @@ __global__ __launch_bounds__(256, 2) void stream_fwd_kernel(const StreamP p) {
             const unsigned xw = xw0[it] + (unsigned)kb * (16u * KZV_ATT_GOLD);
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], sc, -mref)); l[it] += s[kt][r]; }
-                unsigned w01 = pack_bf2(s[kt][0], s[kt][1]), w23 = pack_bf2(s[kt][2], s[kt][3]);
-                if (p.thr16) {
-                    unsigned u01, u23;
-                    att_drop_u(dl, att_mix(xw + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
-                    w01 &= att_keep_mask(u01, thrm1x2); w23 &= att_keep_mask(u23, thrm1x2);
-                }
-                pw[kt * 2] = w01; pw[kt * 2 + 1] = w23;
+                float lsum = l[it];                           // a scalar local: see att_fwd_tile
+                att_fwd_tile(s[kt], sc, mref, lsum, p.thr16, dl, xw + (unsigned)kt * (4u * KZV_ATT_GOLD), thrm1x2, pw + kt * 2);
+                l[it] = lsum;
             }
 #pragma unroll
             for (int kp = 0; kp < 2; ++kp) {
@@ -212,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void stream_fwd_kernel(const StreamP p) {
             bf16_t* orow = p.O + ((int64_t)b * p.Sq + q) * p.ldo + h * D + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
-                *(uint2*)(orow + dt * 16) = make_uint2(pack_bf2(o[it][dt][0] * onorm, o[it][dt][1] * onorm), pack_bf2(o[it][dt][2] * onorm, o[it][dt][3] * onorm));
+                store_bf4(orow + dt * 16, o[it][dt], onorm);
         }
     }
 }
@@ -265,16 +230,7 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_kv_kernel(const StreamP p) 
             lv[u] = p.LSE[(int64_t)bh * p.Sq + row];
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float d = dv[u];
-            d += __shfl_xor(d, 1, 64);
-            d += __shfl_xor(d, 2, 64);
-            const int row = r0 + u * 64 + (tid >> 2);
-            if ((tid & 3) == 0 && row < SqP) {
-                lse[row] = row < p.Sq ? lv[u] * LOG2E : INFINITY;
-                dlt[row] = row < p.Sq ? d * keep_p : 0.f;
-            }
-        }
+        for (int u = 0; u < 4; ++u) att_row_stats(dv[u], lv[u], keep_p, r0 + u * 64 + (tid >> 2), SqP, p.Sq, tid, lse, dlt);
     }
     const float sc = p.scale * LOG2E;
     f32x4 dk[KT][NDT], dvv[KT][NDT];
@@ -288,10 +244,10 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_kv_kernel(const StreamP p) 
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) tT[dt] = tr_off<D>(g, l15, dt);
     AttDropLane dl = att_drop_lane(l15 & 3, false);
-    const int thr_s = p.thr16 ? (int)p.thr16 - 32768 : -40000;          // no dropout: below every int16, everything is kept
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
+    const int thr_s = att_thr_s(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
     // pre-mix word of block (q >> 2 = g, k >> 2 = l15 >> 2) of slab 0, key tile 0; + per slab / 16-query half / key tile multiples of GOLD
-    unsigned xslab = (((unsigned)bh * nQ4 + g) * nK4 + (l15 >> 2)) * KZV_ATT_GOLD + p.key;
+    unsigned xslab = att_block_word(bh, nQ4, g, nK4, l15 >> 2, p.key);
     const unsigned xstep_t2 = 4u * nK4 * KZV_ATT_GOLD;
     lds_wait_barrier();
 #pragma unroll
@@ -338,13 +294,7 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_kv_kernel(const StreamP p) 
                     att_drop_u(dl, att_mix(xslab + (unsigned)t2 * xstep_t2 + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
                 float pm[4], ds[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = __builtin_amdgcn_exp2f(fmaf(S[r], sc, -lq4[r]));      // lse = +inf for q >= Sq
-                    const unsigned ur = (r & 2) ? u23 : u01;
-                    const int us = (r & 1) ? (int)ur >> 16 : (int)(short)(ur & 0xffffu);
-                    pm[r] = us >= thr_s ? pr : 0.f;
-                    ds[r] = fmaf(pm[r], dP[r], -pr * dq4[r]);
-                }
+                for (int r = 0; r < 4; ++r) att_bwd_elem<false>(r, S[r], dP[r], sc, lq4[r], dq4[r], true, u01, u23, thr_s, pm[r], ds[r]);
                 pdw[t2 * 2] = pack_bf2(pm[0], pm[1]); pdw[t2 * 2 + 1] = pack_bf2(pm[2], pm[3]);
                 dsw[t2 * 2] = pack_bf2(ds[0], ds[1]); dsw[t2 * 2 + 1] = pack_bf2(ds[2], ds[3]);
             }
@@ -369,9 +319,8 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_kv_kernel(const StreamP p) 
         bf16_t* vrow = p.dV + ((int64_t)b * p.Sk + key) * p.ldv + h * D + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
-            *(uint2*)(krow + dt * 16) = make_uint2(pack_bf2(dk[a][dt][0] * ksc, dk[a][dt][1] * ksc), pack_bf2(dk[a][dt][2] * ksc, dk[a][dt][3] * ksc));
-            *(uint2*)(vrow + dt * 16) = make_uint2(pack_bf2(dvv[a][dt][0] * p.inv_keep, dvv[a][dt][1] * p.inv_keep),
-                                                   pack_bf2(dvv[a][dt][2] * p.inv_keep, dvv[a][dt][3] * p.inv_keep));
+            store_bf4(krow + dt * 16, dk[a][dt], ksc);
+            store_bf4(vrow + dt * 16, dvv[a][dt], p.inv_keep);
         }
     }
 }
@@ -411,9 +360,9 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_q_kernel(const StreamP p) {
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) kT[dt] = tr_off<D>(g, l15, dt);
     AttDropLane dl = att_drop_lane(l15 & 3, true);
-    const int thr_s = p.thr16 ? (int)p.thr16 - 32768 : -40000;
-    const unsigned nQ4 = (unsigned)(p.Sq + 3) >> 2, nK4 = (unsigned)(p.Sk + 3) >> 2;
-    const unsigned xw0 = (((unsigned)bh * nQ4 + ((unsigned)q >> 2)) * nK4 + g) * KZV_ATT_GOLD + p.key;
+    const int thr_s = att_thr_s(p.thr16);
+    const unsigned nQ4 = KZV_ATT_N4(p.Sq), nK4 = KZV_ATT_N4(p.Sk);
+    const unsigned xw0 = att_block_word(bh, nQ4, (unsigned)q >> 2, nK4, g, p.key);
     const float sc = p.scale * LOG2E;
     f32x4 acc[NDT];
 #pragma unroll
@@ -447,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_q_kernel(const StreamP p) {
                 if (p.thr16) att_drop_u(dl, att_mix(xw + (unsigned)kt * (4u * KZV_ATT_GOLD)), &u01, &u23);
                 float ds[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < 4; ++r) {      // att_bwd_elem written out: its mask as an argument (!last || key < Sk) turns 15 selects into s_or
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[r], sc, -lq));
                     if (last) pr = kb * KB + kt * 16 + 4 * g + r < p.Sk ? pr : 0.f;
                     const unsigned ur = (r & 2) ? u23 : u01;
@@ -476,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_q_kernel(const StreamP p) {
         bf16_t* row = p.dQ + ((int64_t)b * p.Sq + q) * p.ldq + h * D + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
-            *(uint2*)(row + dt * 16) = make_uint2(pack_bf2(acc[dt][0] * osc, acc[dt][1] * osc), pack_bf2(acc[dt][2] * osc, acc[dt][3] * osc));
+            store_bf4(row + dt * 16, acc[dt], osc);
     }
 }
 
@@ -490,18 +439,11 @@ void launch(K kernel, bool& attr, int max_lds, int blocks, int lds, hipStream_t 
 template <int D>
 int run(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     StreamP p;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O; p.LSE = a->LSE;
-    p.dO = (const bf16_t*)a->dO; p.dQ = (bf16_t*)a->dQ; p.dK = (bf16_t*)a->dK; p.dV = (bf16_t*)a->dV;
-    p.zero16 = kzv_zero_page();
-    if (!p.zero16) return kzv_fail(KZV_E_HIP, "attn_stream: zero page unavailable");
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.B = a->B; p.heads = a->heads; p.Sq = a->Sq; p.Sk = a->Sk;
-    p.scale = D == 64 ? 0.125f : 1.f / sqrtf((float)D);     // head_dim^-0.5 as the whole-head kernels compute it
-    kzv_drop_params(a->drop_p, &p.thr16, &p.inv_keep);
-    p.key = a->drop_key;
+    kzv_attn_fill(p, a, D);
+    if (int rc = kzv_attn_fill_zero(p, "attn_stream")) return rc;
     const int bh = a->B * a->heads;
     constexpr int IMG2 = 2 * 2 * KB * 2 * D;                  // two buffers of a K and a V block
-    constexpr int KV_MAX = kv_ring_bytes<D>() + 2 * ((MAXS + 31) / 32 * 32) * 4;
+    constexpr int KV_MAX = kv_ring_bytes<D>() + 2 * ((KZV_ATTN_STREAM_MAX_S + 31) / 32 * 32) * 4;
     static bool attr_fwd = false, attr_kv = false, attr_q = false;
     if (!bwd) {
         p.nblk = (a->Sq + 127) / 128;
@@ -518,33 +460,7 @@ int run(const kzv_attn_args* a, bool bwd, hipStream_t s) {
 
 }  // namespace
 
-// what the streaming kernels refuse (kzv_attn_stream_fwd / _bwd, kzv_attn_impl_ex)
-int kzv_attn_stream_check(const kzv_attn_args* a, bool bwd) {
-    if (!a || !a->Q || !a->K || !a->V || !a->O) return kzv_fail(KZV_E_ARG, "attn_stream: null operand");
-    if (a->head_dim != 0 && a->head_dim != 64 && a->head_dim != 96) return kzv_fail(KZV_E_ARG, "attn_stream: head_dim must be 64 or 96");
-    if (a->mode != 0) return kzv_fail(KZV_E_ARG, "attn_stream: only mode 0 (no mask)");
-    if (a->Sq < 1 || a->Sk < 1 || a->Sq > MAXS || a->Sk > MAXS) return kzv_fail(KZV_E_ARG, "attn_stream: Sq/Sk must be in 1..4097");
-    if (a->B < 1 || a->heads < 1 || (int64_t)a->B * a->heads * (((a->Sq > a->Sk ? a->Sq : a->Sk) + 63) / 64) >= (1ll << 31))
-        return kzv_fail(KZV_E_ARG, "attn_stream: B and heads must be positive and the grid within 2^31 workgroups");
-    if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8) return kzv_fail(KZV_E_ARG, "attn: row strides must be multiples of 8");
-    if (bwd && (!a->dO || !a->dQ || !a->dK || !a->dV || !a->LSE)) return kzv_fail(KZV_E_ARG, "attn_stream_bwd: null gradient operand");
-    return KZV_OK;
-}
-
+// The launch: arguments were checked by kzv_attn_stream_check (attention_api.cpp); head_dim 96, else 64.
 int kzv_attn_stream(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     return a->head_dim == 96 ? run<96>(a, bwd, s) : run<64>(a, bwd, s);
-}
-
-extern "C" int kzv_attn_stream_fwd(const kzv_attn_args* a, void* stream) {
-    if (int rc = kzv_attn_stream_check(a, false)) return rc;
-    const int D = a->head_dim == 96 ? 96 : 64;
-    KzvProfScope prof(2, 4.0 * a->B * a->heads * (double)a->Sq * a->Sk * D, (hipStream_t)stream);
-    return kzv_attn_stream(a, false, (hipStream_t)stream);
-}
-
-extern "C" int kzv_attn_stream_bwd(const kzv_attn_args* a, void* stream) {
-    if (int rc = kzv_attn_stream_check(a, true)) return rc;
-    const int D = a->head_dim == 96 ? 96 : 64;
-    KzvProfScope prof(3, 10.0 * a->B * a->heads * (double)a->Sq * a->Sk * D, (hipStream_t)stream);
-    return kzv_attn_stream(a, true, (hipStream_t)stream);
 }

@@ -13,6 +13,7 @@
 #include "../../include/kzv.h"
 #include "gemm_nt.h"
 #include "gemm_tn.h"
+#include "attention_common.h"
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -468,12 +469,9 @@ int attn(const kzv_model* m, bool bwd, int mode, const bf16_t* Q, int64_t ldq, c
     a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
     a.ids = m->labels; a.ld_ids = m->L; a.pad_id = m->c.pad_id;
     a.B = batch > 0 ? batch : m->B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.head_dim = head_dim; a.mode = mode; a.drop_p = drop_p; a.drop_key = drop_key;
-    if (m->long_seq) {        // the key / query count alone picks the structure, per launch
-        const int impl = kzv_attn_impl_ex(&a, bwd ? 1 : 0, KZV_MODEL_LONG_SEQ);
-        if (impl < 0) return impl;
-        if (impl == KZV_ATTN_STREAM64 || impl == KZV_ATTN_STREAM96) return bwd ? kzv_attn_stream_bwd(&a, s) : kzv_attn_stream_fwd(&a, s);
-    }
-    return bwd ? kzv_attn_bwd(&a, s) : kzv_attn_fwd(&a, s);
+    // decided (and validated) once; in a long-sequence model the key / query count alone picks the structure, per launch
+    const int impl = kzv_attn_impl_ex(&a, bwd ? 1 : 0, m->long_seq ? KZV_MODEL_LONG_SEQ : 0);
+    return impl < 0 ? impl : kzv_attn_launch(&a, impl, bwd, s);
 }
 
 // ================================================================================================ forward
@@ -855,13 +853,13 @@ extern "C" int kzv_model_create_ex(const kzv_config* cfg, unsigned flags, kzv_mo
         return kzv_fail(KZV_E_ARG, "model_create: ffn sizes and C*ph*pw must be multiples of 64, patch_w of 8");
     const int np = (c.image_h / c.patch_h) * (c.image_w / c.patch_w);
     const int ehd = c.enc_hidden / c.enc_heads;
-    if (np + 1 > 288) {
+    if (np + 1 > KZV_ATTN_MAX_S) {
         if (!(flags & KZV_MODEL_LONG_SEQ))
             return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 288-token attention kernels", np);
         if (ehd != 64 && ehd != 96)
             return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 288-token attention kernels: the streaming kernels that take "
                                        "longer sequences serve encoder head_dim 64 and 96 only (this encoder's is %d)", np, ehd);
-        if (np + 1 > 4097) return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 4,097-token streaming attention kernels", np);
+        if (np + 1 > KZV_ATTN_STREAM_MAX_S) return kzv_fail(KZV_E_ARG, "model_create: %d patches + CLS exceed the 4,097-token streaming attention kernels", np);
     }
     if (c.vocab < 8 || c.max_pos < 4 || c.type_vocab < 1 || c.pad_id < 0 || c.pad_id >= c.vocab)
         return kzv_fail(KZV_E_ARG, "model_create: bad vocabulary geometry");
@@ -909,7 +907,7 @@ extern "C" int kzv_param_info(const kzv_model* m, int i, const char** name, int6
 static int check_batch(const kzv_model* m, int batch, int label_len) {
     if (batch <= 0) return kzv_fail(KZV_E_ARG, "batch must be positive");
     if (label_len < 2) return kzv_fail(KZV_E_ARG, "labels need at least 2 columns");
-    if (label_len - 1 > 192) return kzv_fail(KZV_E_ARG, "decoder length %d exceeds the 192-token attention kernels", label_len - 1);
+    if (label_len - 1 > KZV_ATTN_MAX_CAUSAL) return kzv_fail(KZV_E_ARG, "decoder length %d exceeds the 192-token attention kernels", label_len - 1);
     if ((int64_t)batch * m->Se * (int64_t)m->Fe >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "batch too large for 32-bit element indices");
     return KZV_OK;
 }
