@@ -21,7 +21,6 @@
 #include "kzv_host.h"
 #include "gemm_nt.h"
 #include "gemm_tn.h"
-#include <cstdlib>
 
 namespace {
 
@@ -407,13 +406,13 @@ static int g_nt_schedule = -1;
 static int g_nt_half_mask = -1;
 static int nt_schedule() {
     if (g_nt_schedule < 0) {
-        const char* e = getenv("KZV_NT_FREE"); g_nt_schedule = e ? (atoi(e) != 0) : 0;
-        const char* h = getenv("KZV_NT_HALF"); if (h && atoi(h)) g_nt_schedule |= 2;
+        g_nt_schedule = kzv_env_int("KZV_NT_FREE", 0) != 0;
+        if (kzv_env_int("KZV_NT_HALF", 0)) g_nt_schedule |= 2;
     }
     return g_nt_schedule;
 }
 static int nt_half_mask() {
-    if (g_nt_half_mask < 0) { const char* e = getenv("KZV_NT_HALF_EPIS"); g_nt_half_mask = e ? atoi(e) : 0x3f; }
+    if (g_nt_half_mask < 0) g_nt_half_mask = kzv_env_int("KZV_NT_HALF_EPIS", 0x3f);
     return g_nt_half_mask;
 }
 extern "C" int kzv_set_nt_schedule(int n) { g_nt_schedule = n < 0 ? -1 : (n & 3); return KZV_OK; }
@@ -451,13 +450,13 @@ extern "C" int kzv_gemm_nt(const kzv_gemm_nt_args* a, int epilogue, void* stream
     // store per element: -2..-10 % vs the one-tile-per-workgroup kernel); the two-store GELU epilogues are faster through
     // the workgroup-wide LDS epilogue of gemm_nt256.hip (512-B / 1-KiB row segments).
     static int use_p = -1;
-    if (use_p < 0) { const char* e = getenv("KZV_NT256P"); use_p = e ? atoi(e) : 1; }
+    if (use_p < 0) use_p = kzv_env_int("KZV_NT256P", 1);
     if (kzv_rows_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");      // M <= 1024: the generation step's GEMMs
     static int p_gelu = -1;      // dev knob: the two-store GELU epilogues on the persistent kernel too (A/B; default off)
-    if (p_gelu < 0) { const char* e = getenv("KZV_NT256P_GELU"); p_gelu = e ? atoi(e) : 0; }
+    if (p_gelu < 0) p_gelu = kzv_env_int("KZV_NT256P_GELU", 0);
     const bool two_store = !p_gelu && (epilogue == KZV_EPI_GELU || epilogue == KZV_EPI_GELU_F32);
     static int half_maxk = -1;   // the four-wave kernel's K loop is latency-bound (three-group ring): it pays only where the drain is a large part of a tile
-    if (half_maxk < 0) { const char* e = getenv("KZV_NTH_MAX_K"); half_maxk = e ? atoi(e) : 1 << 30; }
+    if (half_maxk < 0) half_maxk = kzv_env_int("KZV_NTH_MAX_K", 1 << 30);
     if ((nt_schedule() & 2) && ((nt_half_mask() >> epilogue) & 1) && p.K <= half_maxk && kzv_cu_reserve() == 0 && kzv_nt256h_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
     if ((nt_schedule() & 1) && use_p && !two_store && kzv_cu_reserve() == 0 && kzv_nt256f_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
     if (use_p && !two_store && kzv_cu_reserve() == 0 && kzv_nt256p_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
@@ -465,10 +464,8 @@ extern "C" int kzv_gemm_nt(const kzv_gemm_nt_args* a, int epilogue, void* stream
 #define KZV_NT_CASE(E, WM, WN, NS, KB, AD)                                                                \
     case E: {                                                                                             \
         constexpr int lds = NS * (WM + WN) * 64 * KB * 2;                                                 \
-        static bool attr_done = false;                                                                    \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<E, WM, WN, NS, KB, AD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; } \
         const int grid = ((a->M + WM * 64 - 1) / (WM * 64)) * ((a->N + WN * 64 - 1) / (WN * 64));         \
-        hipLaunchKernelGGL((gemm_nt_kernel<E, WM, WN, NS, KB, AD>), dim3(grid), dim3(WM * WN * 64), lds, s, p); \
+        kzv_launch_lds<gemm_nt_kernel<E, WM, WN, NS, KB, AD>>(dim3(grid), dim3(WM * WN * 64), lds, s, p); \
     } break;
 #define KZV_NT_VARIANT(WM, WN, NS, KB, AD)                                                                \
     switch (epilogue) {                                                                                   \
@@ -551,7 +548,7 @@ static int tn_fill(const kzv_gemm_tn_args* a, TnParams& p) {
 // contended when many splits hit one small output) stay a small share.  Returns the workgroup count.
 static int tn_plan(TnParams& p, int target) {
     static int min_steps = -1;
-    if (min_steps < 0) { const char* e = getenv("KZV_TN_MINSTEPS"); min_steps = e ? atoi(e) : 16; }
+    if (min_steps < 0) min_steps = kzv_env_int("KZV_TN_MINSTEPS", 16);
     const int tiles = ((p.N + 127) / 128) * ((p.K + 127) / 128);
     const int tok_tiles = (p.Mtok + 63) / 64;
     int splits = target / tiles;
@@ -565,7 +562,7 @@ static int tn_plan(TnParams& p, int target) {
 }
 static int tn_target() {
     static int target = -1;
-    if (target < 0) { const char* e = getenv("KZV_TN_BLOCKS"); target = e ? atoi(e) : 512; }
+    if (target < 0) target = kzv_env_int("KZV_TN_BLOCKS", 512);
     return target;
 }
 
@@ -576,9 +573,7 @@ extern "C" int kzv_gemm_tn(const kzv_gemm_tn_args* a, void* stream) {
     KzvProfScope prof(1, 2.0 * a->Mtok * p.n_store * a->K, (hipStream_t)stream);
     if (kzv_tn256_launch(p, (hipStream_t)stream)) return kzv_check_launch("gemm_tn");     // >= 9 tiles of 256x256: eight-phase kernel
     const int blocks = tn_plan(p, tn_target());
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS); attr_done = true; }
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(blocks), dim3(256), NT_LDS, (hipStream_t)stream, p);
+    kzv_launch_lds<gemm_tn_kernel>(dim3(blocks), dim3(256), NT_LDS, (hipStream_t)stream, p);
     return kzv_check_launch("gemm_tn");
 }
 
@@ -620,8 +615,6 @@ int kzv_gemm_tn_group(const kzv_gemm_tn_args* a, int n, hipStream_t s) {
         blocks += tn_plan(g.p[i], share);
     }
     g.start[g.n] = blocks;
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS); attr_done = true; }
-    hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(blocks), dim3(256), NT_LDS, s, g);
+    kzv_launch_lds<gemm_tn_group_kernel>(dim3(blocks), dim3(256), NT_LDS, s, g);
     return kzv_check_launch("gemm_tn_group");
 }

@@ -1,5 +1,6 @@
-// Shared between the two gemm_nt kernels (gemm.hip: 128x128 two-stage; gemm_nt256.hip: 256x256 eight-phase):
-// launch parameters and the fused per-row epilogue.
+// Shared by the gemm_nt kernels -- gemm.hip (128x128 two-stage, and the dispatch), gemm_nt256.hip (256x256 eight-phase), gemm_nt256p.hip
+// (persistent; bf16 and fp8), gemm_nt256f.hip (free-running), gemm_nt256h.hip (four waves, 256x128), gemm_rows.hip (few rows) and the
+// pair kernel of gemm_tn256.hip: launch parameters, the fused per-row epilogue, the tile walk and the launchers' contracts.
 #pragma once
 #include "kzv_common.h"
 #include "../../include/kzv.h"
@@ -93,6 +94,12 @@ __device__ __forceinline__ void nt_tile_coords(int id, int tilesM, int tilesN, i
     tn = st * strip + (rem - tm * w);
 }
 int kzv_nt_strip();      // KZV_NT_STRIP (default 3)
+
+// The 256x256 kernels address their operands as a wave-uniform 64-bit base + a 32-bit per-lane byte offset (LDS-DMA): the A row panel of a
+// tile and all valid rows of B must lie within 4 GiB of their bases.  `es` = bytes per operand element (2: bf16, 1: e4m3).
+inline bool nt_dma_offsets_fit(const NtParams& p, int es) {
+    return (uint64_t)256 * (uint64_t)p.lda * es <= 0xffffffffull && (uint64_t)p.n_valid * (uint64_t)p.ldb * es <= 0xffffffffull;
+}
 
 // gemm_nt256.hip: returns 1 when it took the launch, 0 when the shape is left to the 128x128 kernel.
 int kzv_nt256_launch(const NtParams& p, int epilogue, hipStream_t s);

@@ -29,26 +29,9 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "gemm_nt.h"
-#include <cstdlib>
+#include "gemm256_common.h"
 
 namespace {
-
-constexpr int HT_BYTES = 128 * 128;        // half-tile: 128 rows x 64 bf16
-constexpr int BUF_BYTES = 4 * HT_BYTES;    // A-h0, A-h1, B-h0, B-h1
-constexpr int LDS_BYTES = 2 * BUF_BYTES;   // 128 KiB
-constexpr int KA0 = 0, KA1 = 1, KB0 = 2, KB1 = 3;
-
-// LDS-DMA, 16 B per lane: source = sbase (wave-uniform) + voff (per lane), destination = lds_dst + 16*lane.
-__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
-}
 
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
@@ -84,7 +67,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
     const unsigned ldsw = __builtin_amdgcn_readfirstlane((unsigned)(__SIZE_TYPE__)((KZV_LDS char*)smem) + (unsigned)w * 1024u);
     auto stage = [&](int buf, int kind, int kt) {
         const char* sb = (kind < 2 ? baseA : baseB) + (int64_t)kt * 128;
-        const unsigned d = ldsw + (unsigned)(buf * BUF_BYTES + kind * HT_BYTES);
+        const unsigned d = ldsw + (unsigned)(buf * NT256_BUF_BYTES + kind * NT256_HT_BYTES);
         glds16_s(voff[kind][0], sb, d);
         glds16_s(voff[kind][1], sb, d + 8192u);
     };
@@ -102,7 +85,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
     const int a_off = (wr * 64 + l15) * 128, b_off = (wc * 32 + l15) * 128;
     bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
     auto readA = [&](int buf, int mh) {
-        const char* b = smem + buf * BUF_BYTES + (KA0 + mh) * HT_BYTES + a_off;
+        const char* b = smem + buf * NT256_BUF_BYTES + (KA0 + mh) * NT256_HT_BYTES + a_off;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             fa[i][0] = *(const bf16x8*)(b + i * 2048 + slot0);
@@ -110,7 +93,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
         }
     };
     auto readB = [&](int buf, int nh, bf16x8 (&fb)[2][2]) {
-        const char* b = smem + buf * BUF_BYTES + (KB0 + nh) * HT_BYTES + b_off;
+        const char* b = smem + buf * NT256_BUF_BYTES + (KB0 + nh) * NT256_HT_BYTES + b_off;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             fb[j][0] = *(const bf16x8*)(b + j * 2048 + slot0);
@@ -241,7 +224,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
 
 int nt256_min_tiles() {
     static int v = -1;
-    if (v < 0) { const char* e = getenv("KZV_NT256_MIN_TILES"); v = e ? atoi(e) : 384; }
+    if (v < 0) v = kzv_env_int("KZV_NT256_MIN_TILES", 384);
     return v;
 }
 
@@ -251,13 +234,8 @@ int kzv_nt256_launch(const NtParams& p, int epilogue, hipStream_t s) {
     const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
     // below ~1.5 rounds of the 256 CUs the 128x128 kernel (4x the tiles, 2 workgroups per CU) fills the chip better
     if (p.K < 128 || tiles < nt256_min_tiles()) return 0;
-    if ((uint64_t)256 * (uint64_t)p.lda * 2 > 0xffffffffull || (uint64_t)p.n_valid * (uint64_t)p.ldb * 2 > 0xffffffffull) return 0;   // 32-bit DMA offsets
-#define KZV_NT256_CASE(E)                                                                                           \
-    case E: {                                                                                                       \
-        static bool attr_done = false;                                                                              \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr_done = true; } \
-        hipLaunchKernelGGL((gemm_nt256_kernel<E>), dim3(tiles), dim3(512), LDS_BYTES, s, p);                        \
-    } break;
+    if (!nt_dma_offsets_fit(p, 2)) return 0;
+#define KZV_NT256_CASE(E) case E: kzv_launch_lds<gemm_nt256_kernel<E>>(dim3(tiles), dim3(512), NT256_RING_BYTES, s, p); break;
     switch (epilogue) {
         KZV_NT256_CASE(KZV_EPI_BF16) KZV_NT256_CASE(KZV_EPI_F32) KZV_NT256_CASE(KZV_EPI_GELU)
         KZV_NT256_CASE(KZV_EPI_RESID) KZV_NT256_CASE(KZV_EPI_DGELU) KZV_NT256_CASE(KZV_EPI_GELU_F32)

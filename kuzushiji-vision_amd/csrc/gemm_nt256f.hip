@@ -1,7 +1,7 @@
 // gemm_nt, persistent 256x256 kernel with a FREE-RUNNING schedule for gfx950 (MI355X).
 //
 // Same tile, LDS ring (2 K-tiles x 4 half-tiles of 16 KiB), DMA pieces, swizzle, tile stream and per-wave drain as
-// gemm_nt256p.hip (read its header and gemm_nt256.hip's first).  What changes is the K loop: gemm_nt256p is the eight-phase
+// gemm_nt256p.hip (read gemm_nt256p_body.h's header and gemm_nt256.hip's first).  What changes is the K loop: gemm_nt256p is the eight-phase
 // ping-pong (waves 4..7 one barrier behind, every phase = [reads + DMA issue] barrier [16 MFMA] barrier: while one wave of a
 // SIMD multiplies, its partner loads), whose barrier interval measured 362 cycles where the 16 MFMAs are 256 (the
 // load half is a 247-cycle latency chain of its own).  Here all eight waves run the SAME stream with TWO barriers per K-tile,
@@ -26,43 +26,24 @@
 // Tile boundaries: the last K-tile of an output tile skips p4's reads (the fragments would be live across the drain); the
 // first K-tile's A0 / B0 are read after the drain (their half-tiles were retired at the barrier in p3 of the previous K-tile).
 // Eight DMAs (h0(u+2), h1(u+2)) are in flight across a drain; the first three waits after a credited drain are widened by the
-// drain's own operation count (vmcnt bookkeeping as in gemm_nt256p.hip).  A stream that has run past its last tile keeps
+// drain's own operation count (vmcnt bookkeeping: gemm256_common.h, drain_ops).  A stream that has run past its last tile keeps
 // issuing (it re-reads tile 0 into slots nobody reads again), so the loop has no tail case and every count stays exact; the
 // kernel ends on vmcnt(0).
 #include "kzv_common.h"
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "gemm_nt.h"
-#include <cstdlib>
+#include "gemm256_common.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int HT_BYTES = 128 * 128;        // half-tile: 128 rows x 64 bf16
-constexpr int RING_BYTES = 8 * HT_BYTES;   // 128 KiB: A [buf][h] in the first 64 KiB, B [buf][h] in the second
-constexpr int LDS_BYTES = RING_BYTES + 8 * 4096;   // + one 4-KiB drain patch per wave = 160 KiB
-
-__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 40) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-    else if constexpr (N == 63) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
-}
-constexpr int cmin(int a, int b) { return a < b ? a : b; }
 #define KZV_SB() __builtin_amdgcn_sched_barrier(0)
 #ifdef KZV_F_NOBAR
 #define KZV_F_BARRIER() do {} while (0)
 #else
 #define KZV_F_BARRIER() __builtin_amdgcn_s_barrier()
 #endif
-
-// VMEM operations one wave issues while draining an interior tile (32 four-column groups per lane)
-template <int EPI> constexpr int drain_ops() { return (EPI == KZV_EPI_BF16 || EPI == KZV_EPI_F32) ? 32 : 64; }
 
 struct TileSrc {            // where the next half-tiles of one half index come from: wave-uniform (SGPRs) throughout
     const char* a; const char* b;      // tile row panel of A, tile column panel of B, both at the stream's current K-tile
@@ -124,14 +105,14 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
         return;
 #endif
         const unsigned v = min(qA + (unsigned)(j * 128 + h * 64) * lda2, s.limA);
-        glds16_s(v, s.a, ldsw + (unsigned)((buf * 2 + h) * HT_BYTES + j * 8192));
+        glds16_s(v, s.a, ldsw + (unsigned)((buf * 2 + h) * NT256_HT_BYTES + j * 8192));
     };
     auto stageB1 = [&](const TileSrc& s, int buf, int h, int j) {
 #ifdef KZV_F_NODMA
         return;
 #endif
         const unsigned v = min(qB + (unsigned)(j * 128 + h * 32) * ldb2, s.limB);
-        glds16_s(v, s.b, ldsw + (unsigned)(65536 + (buf * 2 + h) * HT_BYTES + j * 8192));
+        glds16_s(v, s.b, ldsw + (unsigned)(65536 + (buf * 2 + h) * NT256_HT_BYTES + j * 8192));
     };
 
     f32x4 acc[8][4];
@@ -158,12 +139,12 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
     bool rd_on = true;
     auto rdA = [&](int buf, int mh, int i) {
         if (!rd_on) return;
-        const int o = (buf * 2 + mh) * HT_BYTES + i * 2048;
+        const int o = (buf * 2 + mh) * NT256_HT_BYTES + i * 2048;
         fa[i].k[0] = *(const KZV_LDS bf16x8*)(pA0 + o); fa[i].k[1] = *(const KZV_LDS bf16x8*)(pA1 + o);
     };
     auto rdB = [&](int buf, int nh, int j, Frag (&fb)[2]) {
         if (!rd_on) return;
-        const int o = (buf * 2 + nh) * HT_BYTES + j * 2048;
+        const int o = (buf * 2 + nh) * NT256_HT_BYTES + j * 2048;
         fb[j].k[0] = *(const KZV_LDS bf16x8*)(pB0 + o); fb[j].k[1] = *(const KZV_LDS bf16x8*)(pB1 + o);
     };
     // two MFMAs: accumulator row block i of half mh against both column blocks of half nh, K-chunk kh
@@ -180,7 +161,7 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
 
     const bool late = w >= 4;          // wave-uniform: which half of a barrier interval this wave issues its DMAs in
     TileSrc s0, s1;                    // s0 feeds A-h0 / B-h0, s1 feeds B-h1 / A-h1; both stand at stream K-tile u + 2 when K-tile u starts
-    constexpr int D = drain_ops<EPI>();
+    constexpr int D = drain_ops<EPI, false>();
     constexpr int W8 = cmin(63, 8 + D);
 
     // One K-tile of the stream (header).  Bf: the B set holding B0(u) (p1, p4), Bs: the set B1(u) is read into (p2, p3) and,
@@ -239,13 +220,15 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
 
     // ---- drain: this wave's 128x64 accumulators -> global, through its private LDS patch ----
+    // (kept in step BY HAND with the copy in gemm_nt256p_body.h, whose residual / derivative loads are nontemporal: sharing it moved the
+    // register allocation of the default kernels, which sit at the 256-VGPR edge)
     // bf16 output without a second operand (the BF16 epilogue of interior tiles): bias added and converted BEFORE the transposition,
     // so a row block is 2 KiB in the patch and two of them alternate -- block i + 1 is written while block i is read back.  The
     // fp32 drain below is one LDS write -> read round trip per row block, 8 in a row (2.2 us per tile, all of it latency).
     auto drain_bf16 = [&](int tm, int tn) {
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        char* patch = smem + RING_BYTES + w * 4096;                 // [2][16 rows][128 B], 8-byte chunks XOR row
+        char* patch = smem + NT256_RING_BYTES + w * 4096;                 // [2][16 rows][128 B], 8-byte chunks XOR row
         const int l15 = ln & 15, g = ln >> 4;
         const int prow = ln >> 4, pchunk = ln & 15;                 // read-back: 4 rows x 128 B per wave-instruction
         const int nb0 = tn * 256 + wc * 64;
@@ -279,7 +262,7 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
         int ln = lane;
         asm volatile("" : "+v"(ln));       // as in set_tile: keep the drain's address terms out of the K loop's live set
         // patch = one accumulator row block: [16 rows][64 cols] fp32 (256-B rows), 16-B chunks XOR (row & 15)
-        float* patch = (float*)(smem + RING_BYTES + w * 4096);
+        float* patch = (float*)(smem + NT256_RING_BYTES + w * 4096);
         const int prow = ln >> 4, pchunk = ln & 15;           // read-back: 4 rows x 256 B per wave-instruction
         const int l15 = ln & 15, g = ln >> 4;
         // wave columns: accumulator column block j (nh = j >> 1) sits at wc*64 + nh*32 + (j&1)*16 = wc*64 + j*16
@@ -400,14 +383,7 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
     rd_on = false;
 #endif
     bool credit = false;                            // previous drain was of an interior tile
-#ifdef KZV_STAMPS
-    // per-block stamps: [blockIdx][16]: start, then (K loop end, drain end) per tile
-    unsigned long long* stp = (EPI == KZV_EPI_BF16 && tid == 0) ? (unsigned long long*)p.aux + blockIdx.x * 16 : nullptr;
-    int stk = 0;
-#define KZV_STAMP() do { if (stp) stp[stk++] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define KZV_STAMP() do {} while (0)
-#endif
+    KZV_STAMPS_BEGIN(EPI, tid, p.aux, blockIdx.x);
     KZV_STAMP();
 #ifdef KZV_STAMPS
     const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
@@ -439,16 +415,7 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
 
 int nt256f_min_tiles() {
     static int v = -1;
-    if (v < 0) { const char* e = getenv("KZV_NT256P_MIN_TILES"); v = e ? atoi(e) : 384; }
-    return v;
-}
-int device_cus_f() {
-    static int v = -1;
-    if (v < 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        v = n;
-    }
+    if (v < 0) v = kzv_env_int("KZV_NT256P_MIN_TILES", 384);
     return v;
 }
 
@@ -458,15 +425,10 @@ int kzv_nt256f_launch(const NtParams& p, int epilogue, hipStream_t s) {
     const int tilesN = (p.N + 255) / 256;
     const int tiles = ((p.M + 255) / 256) * tilesN;
     if (p.K < 128 || p.K % 128 || tiles < nt256f_min_tiles()) return 0;   // even number of K-tiles (odd: gemm_nt256.hip)
-    if ((uint64_t)256 * (uint64_t)p.lda * 2 > 0xffffffffull || (uint64_t)p.n_valid * (uint64_t)p.ldb * 2 > 0xffffffffull) return 0;   // 32-bit DMA offsets
+    if (!nt_dma_offsets_fit(p, 2)) return 0;
     if (p.n_valid <= (tilesN - 1) * 256 || p.lda * 2 < 128 || p.ldb * 2 < 128) return 0;          // every tile starts on a valid column (the DMA clamp needs one)
-    const int grid = tiles < device_cus_f() ? tiles : device_cus_f();
-#define KZV_NT256F_CASE(E)                                                                                          \
-    case E: {                                                                                                       \
-        static bool attr_done = false;                                                                              \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_nt256f_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr_done = true; } \
-        hipLaunchKernelGGL((gemm_nt256f_kernel<E>), dim3(grid), dim3(512), LDS_BYTES, s, p, tiles, tilesN, kzv_nt_strip());         \
-    } break;
+    const int grid = tiles < kzv_device_cus() ? tiles : kzv_device_cus();
+#define KZV_NT256F_CASE(E) case E: kzv_launch_lds<gemm_nt256f_kernel<E>>(dim3(grid), dim3(512), NT256P_LDS_BYTES, s, p, tiles, tilesN, kzv_nt_strip()); break;
     switch (epilogue) {
         KZV_NT256F_CASE(KZV_EPI_BF16) KZV_NT256F_CASE(KZV_EPI_F32) KZV_NT256F_CASE(KZV_EPI_GELU)
         KZV_NT256F_CASE(KZV_EPI_RESID) KZV_NT256F_CASE(KZV_EPI_DGELU) KZV_NT256F_CASE(KZV_EPI_GELU_F32)

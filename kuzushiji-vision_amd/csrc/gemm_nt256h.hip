@@ -20,7 +20,7 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "gemm_nt.h"
-#include <cstdlib>
+#include "gemm256_common.h"
 #include <type_traits>
 
 namespace {
@@ -31,22 +31,7 @@ constexpr int B_BASE = 3 * A_HT;           // B slots behind the three A slots
 constexpr int RING_BYTES = 3 * (A_HT + B_HT);      // 72 KiB
 constexpr int LDS_BYTES = RING_BYTES + 4 * 2048;   // + one 2-KiB drain patch per wave = 80 KiB: two workgroups per CU
 
-__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 38) asm volatile("s_waitcnt vmcnt(38)" ::: "memory");
-    else if constexpr (N == 63) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
-}
-constexpr int cmin(int a, int b) { return a < b ? a : b; }
 #define KZV_SB() __builtin_amdgcn_sched_barrier(0)
-
-// VMEM operations one wave issues while draining an interior tile (32 four-column groups per lane)
-template <int EPI> constexpr int drain_ops() { return (EPI == KZV_EPI_BF16 || EPI == KZV_EPI_F32) ? 32 : 64; }
 
 struct TileSrc {            // where the next half-tile group of one half index comes from: wave-uniform (SGPRs) throughout
     const char* a; const char* b;      // tile row panel of A, tile column panel of B, both at the stream's current K-tile
@@ -142,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt256h_kernel(const NtParams p, c
     auto mm4 = [&](int mh, int nh, int i, const Frag (&fb)[2]) { mm2(mh, nh, i, 0, fb); mm2(mh, nh, i, 1, fb); };
 
     TileSrc s0, s1;                    // s0 feeds the h0 groups (stands at K-tile u + 2 when K-tile u starts), s1 the h1 groups (u + 1)
-    constexpr int D = drain_ops<EPI>();
+    constexpr int D = drain_ops<EPI, false>();
     constexpr int W6 = cmin(63, 6 + D);
 
     // One K-tile of the stream (header).  U = u % 3 fixes the slots; Bf: the B set holding B0(u) (p1, p4), Bs: the set B1(u) is
@@ -190,6 +175,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt256h_kernel(const NtParams p, c
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
 
     // ---- drain: this wave's 128x64 accumulators -> global, through its private 2-KiB LDS patch, half a row block at a time ----
+    // (the 2-KiB relative of the drain in gemm_nt256p_body.h / gemm_nt256f.hip, kept in step with them by hand)
     auto drain = [&](int tm, int tn, auto interiorc) {
         constexpr bool interior = decltype(interiorc)::value;
         int ln = lane;
@@ -299,19 +285,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt256h_kernel(const NtParams p, c
     };
     first_frags();
     bool credit = false;                            // previous drain was of an interior tile
+    KZV_STAMPS_BEGIN(EPI, tid, p.aux, blockIdx.x);
 #ifdef KZV_STAMPS
-    // per-block stamps (dev, tools/dev/r4_half_stamps.py): [blockIdx][16] u64 in p.aux: start, then (K loop end, drain end) per tile; [15] = HW_ID | XCC_ID << 32
-    unsigned long long* stp = (EPI == KZV_EPI_BF16 && tid == 0) ? (unsigned long long*)p.aux + blockIdx.x * 16 : nullptr;
-    int stk = 0;
-    if (stp) {
+    if (stp) {                                      // [15] = HW_ID | XCC_ID << 32
         unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         stp[15] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
     }
-#define KZV_STAMP() do { if (stp && stk < 15) stp[stk++] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define KZV_STAMP() do {} while (0)
 #endif
     KZV_STAMP();
     for (int seq = 0; ; ++seq) {
@@ -341,16 +322,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt256h_kernel(const NtParams p, c
 
 int nt256h_min_tiles() {
     static int v = -1;
-    if (v < 0) { const char* e = getenv("KZV_NT256H_MIN_TILES"); v = e ? atoi(e) : 768; }
-    return v;
-}
-int device_cus_h() {
-    static int v = -1;
-    if (v < 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        v = n;
-    }
+    if (v < 0) v = kzv_env_int("KZV_NT256H_MIN_TILES", 768);
     return v;
 }
 int g_stagger = -1;
@@ -363,17 +335,12 @@ int kzv_nt256h_launch(const NtParams& p, int epilogue, hipStream_t s) {
     const int tilesN = (p.N + 127) / 128;
     const int tiles = ((p.M + 255) / 256) * tilesN;
     if (p.K < 384 || p.K % 384 || tiles < nt256h_min_tiles()) return 0;   // six K-tile bodies per round of the slot / fragment-set pattern
-    if ((uint64_t)256 * (uint64_t)p.lda * 2 > 0xffffffffull || (uint64_t)p.n_valid * (uint64_t)p.ldb * 2 > 0xffffffffull) return 0;   // 32-bit DMA offsets
+    if (!nt_dma_offsets_fit(p, 2)) return 0;
     if (p.n_valid <= (tilesN - 1) * 128 || p.lda * 2 < 128 || p.ldb * 2 < 128) return 0;          // every tile starts on a valid column (the DMA clamp needs one)
-    if (g_stagger < 0) { const char* e = getenv("KZV_NTH_STAGGER"); g_stagger = e ? atoi(e) : 8; }
-    const int grid = tiles < 2 * device_cus_h() ? tiles : 2 * device_cus_h();
+    if (g_stagger < 0) g_stagger = kzv_env_int("KZV_NTH_STAGGER", 8);
+    const int grid = tiles < 2 * kzv_device_cus() ? tiles : 2 * kzv_device_cus();
     const int strip = (kzv_nt_strip() & 0xff) * 2;
-#define KZV_NT256H_CASE(E)                                                                                          \
-    case E: {                                                                                                       \
-        static bool attr_done = false;                                                                              \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_nt256h_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr_done = true; } \
-        hipLaunchKernelGGL((gemm_nt256h_kernel<E>), dim3(grid), dim3(256), LDS_BYTES, s, p, tiles, tilesN, strip, g_stagger);         \
-    } break;
+#define KZV_NT256H_CASE(E) case E: kzv_launch_lds<gemm_nt256h_kernel<E>>(dim3(grid), dim3(256), LDS_BYTES, s, p, tiles, tilesN, strip, g_stagger); break;
     switch (epilogue) {
         KZV_NT256H_CASE(KZV_EPI_BF16) KZV_NT256H_CASE(KZV_EPI_F32) KZV_NT256H_CASE(KZV_EPI_GELU)
         KZV_NT256H_CASE(KZV_EPI_RESID) KZV_NT256H_CASE(KZV_EPI_DGELU) KZV_NT256H_CASE(KZV_EPI_GELU_F32)

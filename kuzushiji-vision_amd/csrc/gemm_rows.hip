@@ -254,7 +254,7 @@ extern "C" int kzv_set_rows_max_m(int n) {
 
 // returns 1 when it took the launch
 int kzv_rows_launch(const NtParams& p, int epilogue, hipStream_t s) {
-    if (g_rows_max_m < 0) { const char* e = getenv("KZV_ROWS_MAX_M"); g_rows_max_m = e ? atoi(e) : 0; }
+    if (g_rows_max_m < 0) g_rows_max_m = kzv_env_int("KZV_ROWS_MAX_M", 0);
     if (p.M > (g_rows_scope > 0 ? 4096 : g_rows_max_m)) return 0;      // the generation step (KzvRowsScope) or an explicit threshold
     if (p.K > 4096) return 0;
     const dim3 grid((p.N + 63) / 64, (p.M + 15) / 16);

@@ -1,4 +1,5 @@
-// Shared between the two gemm_tn kernels (gemm.hip: 128x128 two-stage; gemm_tn256.hip: 256x256 eight-phase).
+// Shared by the gemm_tn kernels -- gemm.hip (128x128 two-stage, single and grouped, and the dispatch) and gemm_tn256.hip (256x256:
+// eight-phase, free-running, and the dgrad + wgrad pair kernel): launch parameters and the launchers' contracts.
 #pragma once
 #include "kzv_common.h"
 
@@ -8,6 +9,11 @@ struct TnParams {
     int Mtok, N, K, n_store, splits, chunk;   // chunk = tokens per split (multiple of 64)
     float* dbias;                              // optional: dbias[n] += sum_t P[t][n]  (the nn.Linear bias gradient)
 };
+
+// gemm_tn256.hip's twin of nt_dma_offsets_fit (gemm_nt.h): a 64-token stage of P and of Q within the 32-bit per-lane LDS-DMA offsets
+inline bool tn_dma_offsets_fit(const TnParams& p) {
+    return (uint64_t)64 * (uint64_t)p.ldp * 2 + (uint64_t)p.N * 2 <= 0xffffffffull && (uint64_t)64 * (uint64_t)p.ldq * 2 + (uint64_t)p.K * 2 <= 0xffffffffull;
+}
 
 // gemm_tn256.hip: returns 1 when it took the launch (p.splits / p.chunk are chosen inside), 0 when the shape is left
 // to the 128x128 kernel.

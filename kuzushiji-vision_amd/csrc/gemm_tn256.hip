@@ -31,17 +31,10 @@
 #include "kzv_host.h"
 #include "gemm_tn.h"
 #include "gemm_nt.h"
+#include "gemm256_common.h"
+#include "gemm_nt256p_body.h"      // the persistent gemm_nt kernel's body: first phase of the dgrad + wgrad pair kernel below
 #include <vector>
-#include <cstdlib>
 #include <type_traits>
-
-// the persistent gemm_nt kernel's body, for the dgrad + wgrad pair kernel below (kernels of a translation unit cannot call into
-// another one's: the source is compiled here a second time, device functions only)
-namespace kzv_pair_nt {
-#define KZV_NT256P_BODY_ONLY
-#include "gemm_nt256p.hip"
-#undef KZV_NT256P_BODY_ONLY
-}  // namespace kzv_pair_nt
 
 namespace {
 
@@ -55,18 +48,6 @@ constexpr size_t PART_FLOATS = 32768;
 #else
 constexpr size_t PART_FLOATS = 65536;
 #endif
-
-__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
-}
 
 __global__ __launch_bounds__(512) void gemm_tn256_kernel(const TnParams p, float* part_ws) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -514,7 +495,7 @@ template <int EPI>
 __global__ __launch_bounds__(512) void gemm_pair_kernel(const NtParams pn, const int tiles, const int tilesN, const int strip_in, const TnParams pt,
                                                         float* part_ws, const int per, const PairPlan plan) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    kzv_pair_nt::nt256p_body<EPI, false>(pn, tiles, tilesN, strip_in, (int)blockIdx.x, (int)gridDim.x, smem);
+    nt256p_body<EPI, false>(pn, tiles, tilesN, strip_in, (int)blockIdx.x, (int)gridDim.x, smem);
     const int cnt = plan.cnt[blockIdx.x];
     if (cnt == 0) return;
     __syncthreads();                               // every wave is done with the gemm_nt ring and drain patches
@@ -531,7 +512,6 @@ __global__ __launch_bounds__(256) void gemm_tn256_fold_kernel(const float* part_
     const int tnb = tile / tilesK, tkb = tile - tnb * tilesK;
     const int gn = tnb * 256 + row, gk = tkb * 256 + k4;
     if (gn >= n_store || gk >= K) return;                             // K % 4 == 0 (launcher): a 4-column group is all in or all out
-    const float* src = part_ws + ((size_t)tile * 256 + row) * 256 + k4;
     f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
 #ifndef KZV_TN_F32_PARTIALS
     typedef __attribute__((ext_vector_type(2))) unsigned u32x2p;
@@ -541,6 +521,7 @@ __global__ __launch_bounds__(256) void gemm_tn256_fold_kernel(const float* part_
         s[0] += bf2f((bf16_t)(u[0] & 0xffffu)); s[1] += bf2f((bf16_t)(u[0] >> 16)); s[2] += bf2f((bf16_t)(u[1] & 0xffffu)); s[3] += bf2f((bf16_t)(u[1] >> 16));
     }
 #else
+    const float* src = part_ws + ((size_t)tile * 256 + row) * 256 + k4;
 #pragma unroll 4
     for (int sp = 0; sp < splits; ++sp) s += __builtin_nontemporal_load((const f32x4*)(src + (size_t)sp * per * PART_FLOATS));
 #endif
@@ -613,23 +594,14 @@ int tn_flush(hipStream_t s) {
 // stage schedule: 0 = eight-phase ping-pong (gemm_tn256_kernel), 1 = free-running (gemm_tn256f_kernel); kzv_set_tn_schedule / KZV_TN_FREE
 int g_tn_schedule = -1;
 int tn_schedule() {
-    if (g_tn_schedule < 0) { const char* e = getenv("KZV_TN_FREE"); g_tn_schedule = e ? (atoi(e) != 0) : 1; }      // default: free-running (+10..13 % per launch, same-box A/B, bit-identical partial tiles)
+    if (g_tn_schedule < 0) g_tn_schedule = kzv_env_int("KZV_TN_FREE", 1) != 0;      // default: free-running (+10..13 % per launch, same-box A/B, bit-identical partial tiles)
     return g_tn_schedule;
 }
 int tn256_min_tiles() {
     static int v = -1;
     // 9: the 768 x 768 outputs (attention output projection, patch embedding) take this kernel too -- 28 token splits each,
     // 83 -> ~70 us against the 128 x 128 kernel (-0.13 ms per step, same-box A/B; round 2's threshold was 24)
-    if (v < 0) { const char* e = getenv("KZV_TN256_MIN_TILES"); v = e ? atoi(e) : 9; }
-    return v;
-}
-int device_cus() {
-    static int v = -1;
-    if (v < 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        v = n;
-    }
+    if (v < 0) v = kzv_env_int("KZV_TN256_MIN_TILES", 9);
     return v;
 }
 
@@ -639,11 +611,11 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     const int tiles = ((p0.N + 255) / 256) * ((p0.K + 255) / 256);
     const int tok_tiles = p0.Mtok / 64;
     if (tiles < tn256_min_tiles() || p0.Mtok % 64 || tok_tiles < 2 || p0.N < 8 || p0.K < 8) return 0;
-    if ((uint64_t)64 * (uint64_t)p0.ldp * 2 + (uint64_t)p0.N * 2 > 0xffffffffull || (uint64_t)64 * (uint64_t)p0.ldq * 2 + (uint64_t)p0.K * 2 > 0xffffffffull) return 0;
+    if (!tn_dma_offsets_fit(p0)) return 0;
     TnParams p = p0;
     // one workgroup per CU in total; every split keeps >= 8 reduction stages (and at least 2: the prologue stages two)
-    int cus = device_cus() - kzv_cu_reserve();
-    { const char* e = getenv("KZV_TN_CUS"); const int g = e ? atoi(e) : 0; if (g > 0 && g < cus) cus = g; }   // dev: two-stream experiment
+    int cus = kzv_device_cus() - kzv_cu_reserve();
+    { const int g = kzv_env_int("KZV_TN_CUS", 0); if (g > 0 && g < cus) cus = g; }   // dev: two-stream experiment (read at every launch)
     int splits = cus / tiles;      // leave the reserved CUs to a concurrent collective
     if (splits > tok_tiles / 8) splits = tok_tiles / 8;
     if (splits < 1) splits = 1;
@@ -652,8 +624,6 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     splits = (tok_tiles + chunk_tiles - 1) / chunk_tiles;
     if (tok_tiles - (splits - 1) * chunk_tiles < 2) return 0;         // a one-stage last split: leave it to the 128x128 kernel
     p.splits = splits; p.chunk = chunk_tiles * 64;
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr_done = true; }
     if (p.K % 4 || p.ldo % 4 || ((uintptr_t)p.OUT & 15)) return 0;
     const size_t need = (size_t)tiles * splits * PART_FLOATS;
     const bool deferred = g_tn_defer > 0;
@@ -664,12 +634,8 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     }
     float* ws = tn_partials(need, deferred ? 1 + (int)g_tn_pending.size() : 0);
     if (!ws) return 0;
-    if (tn_schedule()) {
-        static bool attr_f = false;
-        if (!attr_f) { (void)hipFuncSetAttribute((const void*)gemm_tn256f_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr_f = true; }
-        hipLaunchKernelGGL(gemm_tn256f_kernel, dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
-    } else
-        hipLaunchKernelGGL(gemm_tn256_kernel, dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
+    if (tn_schedule()) kzv_launch_lds<gemm_tn256f_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
+    else kzv_launch_lds<gemm_tn256_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
     if (deferred) {
         g_tn_pending.push_back(TnFold{ws, p.OUT, p.ldo, p.n_store, p.K, (p.K + 255) / 256, tiles, splits, 0});
         return 1;
@@ -689,13 +655,13 @@ int pair_enabled() {
     // boundary per pair), +0.4 % img/s on the whole step -- and NO gain from sizing the token ranges to the gemm_nt tile counts (the
     // workgroups that leave the gemm_nt phase early then run their weight-gradient stages beside the others' gemm_nt tiles, and the
     // two loops slow each other as they do on two streams).  DESIGN.md section 8.
-    if (g_pair < 0) { const char* e = getenv("KZV_PAIR"); g_pair = e ? (atoi(e) != 0) : 0; }
+    if (g_pair < 0) g_pair = kzv_env_int("KZV_PAIR", 0) != 0;
     return g_pair;
 }
 // stages of the weight-gradient loop one gemm_nt tile is worth: (K-tiles x 1.45 us + drain) / 1.55 us per stage; KZV_PAIR_R overrides (x 0.01)
 double pair_ratio(int nk, int epilogue) {
     static int ov = -2;
-    if (ov == -2) { const char* e = getenv("KZV_PAIR_R"); ov = e ? atoi(e) : -1; }
+    if (ov == -2) ov = kzv_env_int("KZV_PAIR_R", -1);
     const double drain = (epilogue == KZV_EPI_DGELU || epilogue == KZV_EPI_RESID) ? 5.0 : 2.5;
     const double r = 0.6 * (nk * 1.45 + drain) / 1.55;          // 0.6: the best of a sweep over 0 / 0.6 / 1 / 1.4 / 2 (flat between 0 and 0.6)
     return ov >= 0 ? r * ov * 0.01 / 0.6 : r;
@@ -704,14 +670,14 @@ double pair_ratio(int nk, int epilogue) {
 
 // 1 = launched as one kernel; 0 = not taken (the caller issues the two GEMMs separately); < 0 = error
 int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gemm_tn_args* ta, hipStream_t s) {
-    if (!pair_enabled() || kzv_cu_reserve() != 0 || !tn_schedule() || device_cus() != 256) return 0;
+    if (!pair_enabled() || kzv_cu_reserve() != 0 || !tn_schedule() || kzv_device_cus() != 256) return 0;
     if (epilogue != KZV_EPI_BF16 && epilogue != KZV_EPI_F32 && epilogue != KZV_EPI_DGELU && epilogue != KZV_EPI_RESID) return 0;
     NtParams pn;
     if (kzv_nt_params(na, epilogue, &pn) != KZV_OK) return 0;
     // the conditions of kzv_nt256p_launch ...
     const int tilesN = (pn.N + 255) / 256, tiles = ((pn.M + 255) / 256) * tilesN;
     if (pn.K < 128 || pn.K % 128 || tiles < 256) return 0;
-    if ((uint64_t)256 * (uint64_t)pn.lda * 2 > 0xffffffffull || (uint64_t)pn.n_valid * (uint64_t)pn.ldb * 2 > 0xffffffffull) return 0;
+    if (!nt_dma_offsets_fit(pn, 2)) return 0;
     // ... and of kzv_tn256_launch
     TnParams pt{};
     pt.P = (const bf16_t*)ta->P; pt.Q = (const bf16_t*)ta->Q; pt.OUT = ta->OUT; pt.zero16 = kzv_zero_page();
@@ -721,7 +687,7 @@ int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gem
     const int tilesKw = (pt.K + 255) / 256, tilesNw = (pt.N + 255) / 256, per = tilesNw * tilesKw;
     const int stages = pt.Mtok / 64;
     if (per < tn256_min_tiles() || per > 128 || pt.Mtok % 64 || pt.N < 8 || pt.K < 8 || pt.N % 8 || pt.K % 8) return 0;
-    if ((uint64_t)64 * (uint64_t)pt.ldp * 2 + (uint64_t)pt.N * 2 > 0xffffffffull || (uint64_t)64 * (uint64_t)pt.ldq * 2 + (uint64_t)pt.K * 2 > 0xffffffffull) return 0;
+    if (!tn_dma_offsets_fit(pt)) return 0;
     if (pt.K % 4 || pt.ldo % 4 || ((uintptr_t)pt.OUT & 15) || ((uintptr_t)pt.P & 15) || ((uintptr_t)pt.Q & 15) || pt.ldp % 8 || pt.ldq % 8) return 0;
     const int G = 256, S = G / per;
     if (S < 1 || stages < 8 * S || stages > 65000) return 0;
@@ -776,13 +742,7 @@ int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gem
     float* ws = tn_partials(need, deferred ? 1 + (int)g_tn_pending.size() : 0);
     if (!ws) return 0;
     KzvProfScope prof(5, 2.0 * pn.M * pn.n_valid * pn.K + 2.0 * pt.Mtok * pt.N * pt.K, s);
-    constexpr int PAIR_LDS = 160 * 1024;
-#define KZV_PAIR_CASE(E)                                                                                            \
-    case E: {                                                                                                       \
-        static bool attr_done = false;                                                                              \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_pair_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS); attr_done = true; } \
-        hipLaunchKernelGGL((gemm_pair_kernel<E>), dim3(G), dim3(512), PAIR_LDS, s, pn, tiles, tilesN, kzv_nt_strip(), pt, ws, per, plan);   \
-    } break;
+#define KZV_PAIR_CASE(E) case E: kzv_launch_lds<gemm_pair_kernel<E>>(dim3(G), dim3(512), NT256P_LDS_BYTES, s, pn, tiles, tilesN, kzv_nt_strip(), pt, ws, per, plan); break;
     switch (epilogue) {
         KZV_PAIR_CASE(KZV_EPI_BF16) KZV_PAIR_CASE(KZV_EPI_F32) KZV_PAIR_CASE(KZV_EPI_DGELU) KZV_PAIR_CASE(KZV_EPI_RESID)
         default: return 0;

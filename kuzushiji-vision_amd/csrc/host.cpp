@@ -51,10 +51,25 @@ extern "C" uint32_t kzv_drop_key(uint64_t seed, uint32_t site) {
 
 extern "C" const char* kzv_last_error(void) { return g_err; }
 
+int kzv_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+int kzv_device_cus() {
+    static int v = -1;
+    if (v < 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        v = n;
+    }
+    return v;
+}
+
 // CUs the GEMM launchers leave to concurrently running collectives (see include/kzv.h)
 static int g_cu_reserve = -1;
 int kzv_cu_reserve() {
-    if (g_cu_reserve < 0) { const char* e = getenv("KZV_CU_RESERVE"); g_cu_reserve = (e && e[0]) ? atoi(e) : 0; }
+    if (g_cu_reserve < 0) g_cu_reserve = kzv_env_int("KZV_CU_RESERVE", 0);      // (an empty value counts as unset: atoi("") is the default)
     return g_cu_reserve;
 }
 extern "C" int kzv_set_cu_reserve(int n) {

@@ -4,11 +4,26 @@
 #include <stdint.h>
 
 int kzv_fail(int code, const char* fmt, ...);          // records message, returns code
-int kzv_check_launch(const char* what);
-int kzv_cu_reserve();                                  // CUs left to concurrent collectives (kzv_set_cu_reserve / KZV_CU_RESERVE)                // hipGetLastError -> KZV_E_HIP
+int kzv_check_launch(const char* what);                // hipGetLastError -> KZV_E_HIP
+int kzv_cu_reserve();                                  // CUs left to concurrent collectives (kzv_set_cu_reserve / KZV_CU_RESERVE)
+#define KZV_LOCAL __attribute__((visibility("hidden")))  // shared by the library's units, not part of its dynamic symbol table
+KZV_LOCAL int kzv_device_cus();                        // compute units of the current device (read once; 256 if the query fails)
+// An integer knob from the environment: atoi of the variable, `dflt` when it is unset.  One getenv per call: the caller keeps the
+// result in a static of its own (a launcher runs ~180 times per training step), and a kzv_set_* that puts its global back to -1
+// has the variable read again.
+KZV_LOCAL int kzv_env_int(const char* name, int dflt);
 const void* kzv_zero_page();                           // 4 KiB of device zeros (allocated once per process)
 void kzv_drop_params(float p, unsigned* thr16, float* inv_keep);
 extern "C" uint32_t kzv_drop_key(uint64_t seed, uint32_t site);
+
+// Launch of a kernel that takes more dynamic LDS than the 64 KiB a kernel gets by default: the limit is raised once per kernel (the
+// flag is a static of this template's instantiation, i.e. per kernel), then every call is a plain launch.  The caller checks the launch.
+template <auto Kernel, typename... Args>
+inline void kzv_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); attr_done = true; }
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+}
 
 // ---- optional per-launch HIP-event timing of the hot kernels (bench.py's roofline leg) -------------
 // kind: 0 gemm_nt, 1 gemm_tn, 2 attn_fwd, 3 attn_bwd.  Off by default: zero cost when disabled.

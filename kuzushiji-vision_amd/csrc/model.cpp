@@ -344,14 +344,14 @@ inline float dp(const kzv_model* m, float p) { return m->train ? p : 0.f; }
 // chains (+ the 256 x 256 input gradients on the row-panel kernel), 2 (default) = also the backward's row-local segments, one launch each
 int g_dec_chain = -1;
 int dec_chain_mode() {
-    if (g_dec_chain < 0) { const char* e = getenv("KZV_DEC_CHAIN"); g_dec_chain = e ? atoi(e) : 2; if (g_dec_chain < 0 || g_dec_chain > 2) g_dec_chain = 2; }
+    if (g_dec_chain < 0) { g_dec_chain = kzv_env_int("KZV_DEC_CHAIN", 2); if (g_dec_chain < 0 || g_dec_chain > 2) g_dec_chain = 2; }
     return g_dec_chain;
 }
 bool dec_pack_wanted(const kzv_model* m);
 int ensure_dec_pack(kzv_model* m, hipStream_t s);
 int g_head_ce = -1;
 bool head_ce_mode() {       // the one-launch LM head + CE (KZV_HEAD_CE / kzv_set_head_ce; default on)
-    if (g_head_ce < 0) { const char* e = getenv("KZV_HEAD_CE"); g_head_ce = e ? (atoi(e) != 0) : 1; }
+    if (g_head_ce < 0) g_head_ce = kzv_env_int("KZV_HEAD_CE", 1) != 0;
     return g_head_ce != 0;
 }
 
@@ -598,7 +598,7 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
     if (fused_head) {
         KzvHeadCE hc{m->hd_ln, m->dec_pack + m->head_pack_off, P + m->hbias, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
         static int fuse_dh = -1;     // the head's input gradient inside the same launch (KZV_HEAD_DGRAD=0: the separate GEMM)
-        if (fuse_dh < 0) { const char* e = getenv("KZV_HEAD_DGRAD"); fuse_dh = e ? atoi(e) : 1; }
+        if (fuse_dh < 0) fuse_dh = kzv_env_int("KZV_HEAD_DGRAD", 1);
         m->dhln_fused = m->train && fuse_dh && m->w_word.ldt % 8 == 0;
         if (m->dhln_fused) { hc.wpt = m->dec_pack + m->head_tpack_off; hc.dh = m->dhln; }
         KZV_TRY(kzv_head_ce(hc, s));
@@ -634,13 +634,13 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
     // the decoder's input-gradient GEMMs on the row-panel kernel (decoder_chain.hip kzv_dec_lin) where the forward's fragment-ordered
     // packs exist (the reference decoder's geometry, chains on): transposed packs, same layout as the forward's
     static int dgrad_rows = -1;          // dev A/B: KZV_DEC_DGRAD=0 keeps the 128 x 128 kernel for these
-    if (dgrad_rows < 0) { const char* e = getenv("KZV_DEC_DGRAD"); dgrad_rows = e ? atoi(e) : 1; }
+    if (dgrad_rows < 0) dgrad_rows = kzv_env_int("KZV_DEC_DGRAD", 1);
     const bool rows_dgrad = dgrad_rows && dec_chain_mode() && dec_pack_wanted(m) && kzv_dec_chain_supported(Hd, Fd) && m->dec_pack_ok && !m->use_side;
     const int64_t HHd = (int64_t)Hd * Hd, FHd = (int64_t)Fd * Hd, perd = 6 * HHd + 2 * FHd;
     // measured (profiles/r04): the 256 x 256 products take 7.8 / 12.6 us there against ~16 us on the 128 x 128 kernel; the 768-wide ones
     // (fc2's DGELU output, the K = 768 reductions of fc1 / qkv) are SLOWER on it (35 / 21 us against 22 / 16 - 22): they keep gemm_nt
     static int wide_rows = -1;
-    if (wide_rows < 0) { const char* e = getenv("KZV_DEC_DGRAD_WIDE"); wide_rows = e ? atoi(e) : 0; }
+    if (wide_rows < 0) wide_rows = kzv_env_int("KZV_DEC_DGRAD_WIDE", 0);
     auto tp = [&](int layer, int64_t off) { return (const bf16_t*)(m->dec_pack + m->tpack_off + perd * layer + off); };
     // ---- CE -> LM head ------------------------------------------------------------------------------
     KZV_TRY(wgrad_batch(m, CLS_MISC, s, m->dlogits, m->Vp, m->hd_ln, Hd, G + m->word, Md, m->Vp, Hd, m->V, G + m->hbias));
@@ -949,13 +949,12 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
             return kzv_fail(KZV_E_HIP, "model_bind: fp8 scale state");
     }
     if (!m->side) {
-        const char* e = getenv("KZV_SIDE_STREAM");
         // KZV_SIDE_STREAM: 0 (default) = one stream; 1 = weight gradients free-running on a side stream: +3 % img/s
         // (7,180 -> 7,410), but the co-running kernels stretch each other (gemm_nt family 920 -> 715 TFLOP/s per launch),
         // so the per-kernel roofline accounting is only meaningful with it off; 2 = encoder weight gradients only under
         // the LayerNorm / attention backward kernels, every input-gradient GEMM joining the side stream first: the 120
         // cross-stream waits per step cost more than the overlap returns (6,400 img/s) -- kept for the record.
-        m->side_mode = (e && e[0]) ? atoi(e) : 0;
+        m->side_mode = kzv_env_int("KZV_SIDE_STREAM", 0);
         m->use_side = m->side_mode != 0;
         if (m->use_side) {
             // (stream priorities make no measurable difference here: the range on this part is {0, -1})
@@ -1159,7 +1158,7 @@ static int decode_step_body_fused(kzv_model* m, const int64_t* d_tokens, const i
 
 static int g_decode_one_launch = -1;           // -1: KZV_DECODE_ONE_LAUNCH (default 1)
 static int decode_one_launch_mode() {
-    if (g_decode_one_launch < 0) { const char* e = getenv("KZV_DECODE_ONE_LAUNCH"); g_decode_one_launch = e ? (atoi(e) != 0) : 1; }
+    if (g_decode_one_launch < 0) g_decode_one_launch = kzv_env_int("KZV_DECODE_ONE_LAUNCH", 1) != 0;
     return g_decode_one_launch;
 }
 extern "C" int kzv_set_dec_chain(int on) {
@@ -1271,7 +1270,7 @@ static int decode_step_body(kzv_model* m, const int64_t* d_tokens, const int* d_
     float* P = m->P;
     const float eps = c.ln_eps;
     static int fuse_ln = -1;
-    if (fuse_ln < 0) { const char* e = getenv("KZV_DECODE_FUSE_LN"); fuse_ln = e ? atoi(e) : 1; }
+    if (fuse_ln < 0) fuse_ln = kzv_env_int("KZV_DECODE_FUSE_LN", 1);
     if (decode_one_launch(m)) return decode_step_body_one_launch(m, d_tokens, d_posids, t, tptr, d_valid, ld_valid, d_logits, s);
     if (fuse_ln && Hd == 256 && B <= 4096) return decode_step_body_fused(m, d_tokens, d_posids, t, tptr, d_valid, ld_valid, d_logits, s);
     KzvRowsScope rows_scope;                     // M = B rows: every GEMM of the step takes the few-rows kernel (gemm_rows.hip)

@@ -3,20 +3,27 @@ ADVICE r03): hipcc cannot be told about the clobber (m0 is a reserved register: 
 invariant "a kernel whose inline asm writes M0 contains no compiler-generated use of M0" is checked on the ISA instead (a kernel is
 either all-asm or all-builtin in its LDS-DMA: the builtin's M0 is the compiler's own business): every mention of m0 outside an inline-asm
 block (;;#ASMSTART .. ;;#ASMEND) in a kernel that also mentions m0 INSIDE one is reported.
-   python tools/check_m0.py [file.hip ...]      (default: every csrc/*.hip that contains a *_m0 / glds16_s helper call)
+   python tools/check_m0.py [file.hip ...]      (default: every csrc/*.hip that contains a *_m0 / glds16_s helper call, in its own text
+                                                 or in a csrc header it includes, directly or through another header)
 Exit code 1 if any compiler-generated M0 use is found."""
 import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kuzushiji-vision_amd", "csrc")
 
 
+def text_with_headers(path, seen):
+    """the unit's text followed by that of every csrc header it includes (each once)"""
+    if path in seen or not os.path.isfile(path):
+        return ""
+    seen.add(path)
+    s = open(path, encoding="utf-8").read()
+    return s + "".join(text_with_headers(os.path.join(CSRC, h), seen) for h in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', s, re.M))
+
+
 def users():
-    out = []
-    for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
-        s = open(f, encoding="utf-8").read()
-        if re.search(r"glds16_asm_m0\(|glds16_asm_soff_m0\(|glds16_s\(", s):
-            out.append(f)
-    return out
+    # a call, not a definition: the helpers' own definitions (kzv_common.h, gemm256_common.h) do not make every includer a subject
+    call = re.compile(r"(?<!void )(?:glds16_asm_m0|glds16_asm_soff_m0|glds16_s)\(")
+    return [f for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))) if call.search(text_with_headers(f, set()))]
 
 
 def check(src):

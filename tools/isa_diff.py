@@ -1,13 +1,14 @@
 """Proof that a source change left kernels alone: compiles the same .hip units of two trees with the Makefile's flags and compares
 the gfx950 assembly kernel by kernel.
-   python tools/isa_diff.py PARENT_CSRC [--new CSRC] [--units attention.hip ...] [--cache DIR] [--show]
-(default units: csrc/attention*.hip; --cache keeps the parent's assembly between runs; --show prints the diff of every kernel whose
-instruction stream differs).  Per kernel it reports
+   python tools/isa_diff.py PARENT_CSRC [--new CSRC] [--units attention.hip gemm_nt256p.hip ...] [--cache DIR] [--show] [--strict]
+(--units takes any .hip units of csrc, default: csrc/attention*.hip; --cache keeps the parent's assembly between runs; --show prints
+the diff of every kernel whose instruction stream differs).  Per kernel it reports
    (a) the resource counts (.vgpr_count, .agpr_count, .sgpr_count, LDS, scratch, spills: equal to the parent's; a count of
        scratch or spills that is not 0 is noted on the kernel's line) and the MULTISET of instructions, an
        instruction being its mnemonic plus its cache-policy modifiers (nt, sc0, sc1): registers, immediates, labels ignored;
    (b) whether the instruction STREAM is identical line for line (comments, directives and symbol names stripped).
-Exit code 1 if (a) fails for any kernel, or a kernel exists on one side only."""
+Exit code 1 if (a) fails for any kernel, or a kernel exists on one side only; with --strict also if (b) is not "identical" for any
+kernel (the proof a pure refactor owes: the code objects did not move at all)."""
 import argparse, collections, difflib, glob, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,10 +17,14 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-u
 META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count"]
 
 
+def asm_of(unit, out):      # "<stem>-hip-amdgcn-amd-amdhsa-gfx950.s": the whole stem, so that gemm.hip does not pick up gemm_rows.hip's
+    return glob.glob(os.path.join(out, os.path.splitext(unit)[0] + "-hip-*gfx950.s"))
+
+
 def compile_unit(csrc, unit, out):
     os.makedirs(out, exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "--save-temps=obj", "-c", unit, "-o", os.path.join(out, unit + ".o")], check=True, cwd=csrc)
-    return glob.glob(os.path.join(out, os.path.splitext(unit)[0] + "*gfx950.s"))[0]
+    return asm_of(unit, out)[0]
 
 
 def demangle(names):
@@ -73,13 +78,14 @@ def main():
     ap.add_argument("--units", nargs="*")
     ap.add_argument("--cache")
     ap.add_argument("--show", action="store_true")
+    ap.add_argument("--strict", action="store_true")
     a = ap.parse_args()
     units = a.units or sorted(os.path.basename(f) for f in glob.glob(os.path.join(a.new, "attention*.hip")))
     with tempfile.TemporaryDirectory() as tmp:
         pdir = a.cache or os.path.join(tmp, "parent")
 
         def parent_asm(u):
-            hit = glob.glob(os.path.join(pdir, os.path.splitext(u)[0] + "*gfx950.s"))
+            hit = asm_of(u, pdir)
             return hit[0] if hit else compile_unit(os.path.abspath(a.parent), u, pdir)
         with ThreadPoolExecutor(8) as ex:
             old = list(ex.map(parent_asm, units))
@@ -95,7 +101,7 @@ def main():
                 (mo, bo), (mn, bn) = ko[name], kn[name]
                 a_ok = mo == mn and collections.Counter(map(key, bo)) == collections.Counter(map(key, bn))
                 spills = [k for k in META[4:] if mn[k] != "0"]
-                bad += not a_ok
+                bad += not a_ok or (a.strict and bo != bn)
                 print(f"{u}: {name}: vgpr {mn['.vgpr_count']} agpr {mn['.agpr_count']} sgpr {mn['.sgpr_count']} lds {mn['.group_segment_fixed_size']} "
                       f"instructions {len(bn)}  (a) {'ok' if a_ok else 'FAIL'}  (b) {'identical' if bo == bn else 'DIFFERS'}"
                       + "".join(f"  NOTE {k} {mn[k]} (parent {mo[k]})" for k in spills))
@@ -106,6 +112,7 @@ def main():
                     print("   multiset (new - parent):", {k: v for k, v in d.items() if v})
                 if bo != bn and a.show:
                     print("\n".join("   " + x for x in difflib.unified_diff(bo, bn, "parent", "new", n=2, lineterm="")))
+        print(f"{len(units)} units: {bad} kernels failed" + (" (strict)" if a.strict else ""))
         sys.exit(1 if bad else 0)
 
 
