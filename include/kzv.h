@@ -174,12 +174,17 @@ int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const i
  * active image width / weights must not change between kzv_decode_begin and the last step. */
 int kzv_decode_begin(kzv_model* m, void* stream);
 /* How a step runs (both entry points).  1 (default; KZV_DECODE_ONE_LAUNCH): for the reference decoder's geometry -- hidden 256, 4
- * heads, FFN 768, <= 128 cached and <= 160 patch keys, 1 / 2 / 4 rows per image -- embeddings, all layers and the LM head's dense
+ * heads, FFN 768, <= 128 cached and <= 320 patch keys, 1 / 2 / 4 rows per image -- embeddings, all layers and the LM head's dense
  * layer are ONE launch (csrc/decode_fused.hip: a workgroup per image owns its beams through every layer), followed by the
- * vocabulary GEMM.  0, or any other geometry: one launch per operation (~50 per token).  Same results up to fp32 summation order.
+ * vocabulary GEMM; up to 160 patch keys go through the attention waves' registers in one pass, 161 .. 320 in chunks with an online
+ * softmax.  0, or any other geometry: one launch per operation (~50 per token).  Same results up to fp32 summation order.
  * -1 returns to the environment's default.  The fragment-ordered weight copies the one-launch step reads (9.6 MB) are refreshed by
  * the first step after kzv_model_sync_weights. */
 int kzv_set_decode_one_launch(int on);
+/* Which of the two the next kzv_decode_step / kzv_decode_step_graph on this handle runs: 1 = the one-launch kernel, 0 = one launch
+ * per operation.  Answers for the bound rows, the images of the last kzv_encode_images / forward, the active image width and the
+ * current kzv_set_decode_one_launch mode; launches nothing.  A negative error before kzv_model_bind. */
+int kzv_decode_step_impl(const kzv_model* m);
 /* Training / evaluation forward: the linear chains of a decoder layer -- [output projection + dropout + residual -> LayerNorm ->
  * cross query] and [output projection -> LayerNorm -> fc1 + GELU -> fc2 -> LayerNorm -> the next layer's QKV] -- as TWO launches
  * per layer (csrc/decoder_chain.hip; hidden 256, 4 heads, FFN 768) instead of nine.  0: one launch per operation; 1: the forward

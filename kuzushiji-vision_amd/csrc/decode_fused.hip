@@ -8,7 +8,8 @@
 // Every operation of a decoder step is local to a sequence -- the linears are row-wise, a sequence attends to its own cache and to
 // its own image's patch keys -- so ONE workgroup owns the G sequences of one image (G = beams) through all layers and never talks
 // to another workgroup: no grid barrier, no flags.  Hidden size 256, 4 heads of 64, FFN 768 (the reference decoder), <= 128 cached
-// keys, <= 160 patch keys; other geometries keep the launch-per-operation path (model.cpp).
+// keys, <= 320 patch keys (up to 160 in one pass through the attention waves' registers, 161 .. 320 in chunks with an online
+// softmax: see cross_chunk_*); other geometries keep the launch-per-operation path (model.cpp).
 //
 // What bounds it is ONE CU's load path (~60 GB/s from L2): per token a workgroup streams all 9.4 MB of decoder weights plus its
 // sequences' attention rows.  So the eight waves are split by what they LOAD, and each stream stays in flight across the barriers:
@@ -39,6 +40,10 @@ constexpr int PL1W = 2560, PL1B = 2816, PL2W = 3072, PL2B = 3328, PL3W = 3584, P
 constexpr int NR = 40;               // role registers: 40 fragments (160 VGPRs): the weight window, or key + value rows
 constexpr int WIN = 24;
 constexpr int NIS = TMAX / 8, NIC = NPMAX / 8;
+constexpr int NPWIDE = 320, NIW = NPWIDE / 8;      // the chunked instances: 161 .. 320 patch keys, NIW key iterations in all
+#ifndef KZV_DF_CHUNKS
+#define KZV_DF_CHUNKS 2                            // chunks of the 320 keys (2, 4 or 8): DESIGN.md section 7, N1 has the measurements
+#endif
 
 // the lane id, re-derived per phase: hipcc otherwise hoists every lane-derived offset of all phases out of the layer loop and spills them
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
@@ -305,6 +310,91 @@ __device__ __forceinline__ void cross_compute(bf16x8 (&R)[NR], Lds<G>& sm, const
         }
     }
 }
+// ---- 161 .. 320 patch keys: NC chunks of CI = NIW / NC key iterations (8 keys each) through NB = max(NC / 2, 1) buffers of the role
+// registers (2 CI fragments each: a chunk's keys, then its values).  Chunk S lives in buffer S % NB; the chunks of the first NB are
+// requested behind B2 like cross_load's rows, chunk S + NB right behind the last use of chunk S, so with NB > 1 a chunk's rows travel
+// while its neighbour is being used.  Per sequence the running maximum, the running sum and the lane's 8 unnormalised output sums are
+// carried from chunk to chunk in LDS (each lane re-reads what it wrote itself: no barrier) with the usual rescale
+//   m' = max(m, chunk maximum), l' = l e^(m - m') + sum e^(s - m'), o' = o e^(m - m') + sum e^(s - m') v
+// and the last chunk reduces over the key rows, normalises and packs to bf16 once, as cross_compute does.  Chunk 0 holds key 0, so m
+// is finite from the first chunk on and a chunk that lies wholly past npa (its loads clamped to the last row) adds exact zeros.
+template <int G> struct CrossState { float v[G][NH][10][64]; };      // [8 output sums, m, l][lane]
+template <int NC, int S>
+__device__ __forceinline__ void cross_chunk_load(bf16x8 (&R)[NR], const FusedP& p, int li, int img, int h, int lane) {
+    constexpr int CI = NIW / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
+    static_assert(NIW % NC == 0 && 2 * CI * NB <= NR, "cross_chunk_load: buffers");
+    const int r = lane >> 3, c = lane & 7;
+    const char* Kc = (const char*)(p.ckv + (int64_t)(2 * li) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
+    const char* Vc = (const char*)(p.ckv + (int64_t)(2 * li + 1) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
+#pragma unroll
+    for (int i = 0; i < CI; ++i) {
+        const unsigned off = ((unsigned)min(8 * (S * CI + i) + r, p.npa - 1) * 64u + (unsigned)c * 8u) * 2u;  // past the last key: a real row, probability 0
+        R[BASE + i] = *(const bf16x8*)(Kc + off);
+        R[BASE + CI + i] = *(const bf16x8*)(Vc + off);
+    }
+}
+template <int G, int NC, int S>
+__device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>& st, const FusedP& p, int h, int lane) {
+    constexpr int CI = NIW / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
+    const int r = lane >> 3, c = lane & 7;
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+        // the rows are the same for every sequence: without this hipcc hoists their bf16 -> fp32 conversions out of the loop (and spills them)
+#pragma unroll
+        for (int i = 0; i < 2 * CI; ++i) asm volatile("" : "+v"(R[BASE + i]));
+        const u32x4_t qp = scaled_query(&sm.wide[g][h * 64 + c * 8]);
+        float* sv = &st.v[g][h][0][lane];
+        float sc[CI];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < CI; ++i) {
+            const float a = sum8(dot8(R[BASE + i], qp));
+            sc[i] = (8 * (S * CI + i) + r < p.npa) ? a : -INFINITY;
+            mx = fmaxf(mx, sc[i]);
+        }
+        mx = wave_max_d(mx);
+        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float l = 0.f;
+        if (S > 0) {
+            const float m0 = sv[8 * 64];
+            mx = fmaxf(mx, m0);
+            const float f = __expf(m0 - mx);
+            l = sv[9 * 64] * f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = sv[e * 64] * f;
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < CI; ++i) { sc[i] = __expf(sc[i] - mx); sum += sc[i]; }
+        l += wave_sum_d(sum) * 0.125f;                   // every key is counted by the 8 lanes of its row
+#pragma unroll
+        for (int i = 0; i < CI; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] += sc[i] * bf2f((bf16_t)R[BASE + CI + i][e]);
+        if (S + 1 < NC) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sv[e * 64] = o[e];
+            sv[8 * 64] = mx; sv[9 * 64] = l;
+        } else {
+            const float inv = 1.f / l;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = sum_rows(o[e]);
+            if (r == 0) {
+                typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+                *(u32x4*)(&sm.ctx[g][h * 64 + c * 8]) = (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv), pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
+            }
+        }
+    }
+}
+// chunks S .. NC - 1 in turn: use chunk S, then request chunk S + NB into the buffer it leaves
+template <int G, int NC, int S>
+__device__ __forceinline__ void cross_chunks(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>& st, const FusedP& p, int li, int img, int h, int lane0) {
+    constexpr int NB = NC > 1 ? NC / 2 : 1;
+    cross_chunk_compute<G, NC, S>(R, sm, st, p, h, opaque(lane0));
+    DF_STAMP_A(8 + S);
+    if constexpr (S + NB < NC) cross_chunk_load<NC, S + NB>(R, p, li, img, h, opaque(lane0));
+    if constexpr (S + 1 < NC) cross_chunks<G, NC, S + 1>(R, sm, st, p, li, img, h, lane0);
+}
 // biases + LayerNorm weights of one layer -> LDS (256 threads; the loads go out together, one wait, then the writes)
 __device__ __forceinline__ void params_load(float* par, const FusedLayer& L, int t256_) {
     const int t256 = opaque(t256_);
@@ -487,7 +577,7 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
     DF_STAMP(41);
 }
 
-template <int G>
+template <int G, int NC>
 __device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int h, int lane0, int t256, int img, int b0, int tdev) {
     bf16x8 R[NR];                                     // key + value rows
     {   // layer 0's biases / LayerNorm weights, the sequences' row table and usable-key flags -> LDS
@@ -518,15 +608,24 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int 
             DF_STAMP_A(2);
         }
         wg_barrier();            // B2: the attention output is in LDS; the image's patch keys / values are requested behind it
-        cross_load(R, p, li, img, h, opaque(lane0));
+        if constexpr (NC == 1) cross_load(R, p, li, img, h, opaque(lane0));
+        else {
+            cross_chunk_load<NC, 0>(R, p, li, img, h, opaque(lane0));
+            if constexpr (NC >= 4) cross_chunk_load<NC, 1>(R, p, li, img, h, opaque(lane0));
+            if constexpr (NC >= 8) { cross_chunk_load<NC, 2>(R, p, li, img, h, opaque(lane0)); cross_chunk_load<NC, 3>(R, p, li, img, h, opaque(lane0)); }
+        }
         DF_STAMP_A(3);
         wg_barrier();            // B3
         wg_barrier();            // B4
         wg_barrier();            // B5: the cross query is in LDS
         DF_STAMP_A(4);
-        {   // cross-attention of head h for every sequence; then the next layer's parameters and its first cached rows
+        if constexpr (NC == 1) {   // cross-attention of head h for every sequence; then the next layer's parameters and its first cached rows
             const int lane = opaque(lane0);
             cross_compute<G>(R, sm, p, h, lane);
+            DF_STAMP_A(5);
+        } else {
+            __shared__ CrossState<G> st;              // the chunked instances only
+            cross_chunks<G, NC, 0>(R, sm, st, p, li, img, h, lane0);
             DF_STAMP_A(5);
         }
         wg_barrier();            // B6: the cross-attention output is in LDS; behind it, the next layer's parameters and first cached rows
@@ -546,7 +645,7 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int 
     }
 }
 
-template <int G>
+template <int G, int NC>      // NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks
 __global__ __launch_bounds__(512) void decode_fused_kernel(const FusedP p) {
     __shared__ Lds<G> sm;
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -555,7 +654,7 @@ __global__ __launch_bounds__(512) void decode_fused_kernel(const FusedP p) {
     static_assert((12 * 8 + 3 * 32 + 2 * 96) % WIN == 0, "a layer's fragments must fill the window a whole number of times");
     DF_STAMP(0);
     if (w < 4) linear_role<G>(sm, p, w, lane0, b0);
-    else attention_role<G>(sm, p, w - 4, lane0, tid - 256, img, b0, tdev);
+    else attention_role<G, NC>(sm, p, w - 4, lane0, tid - 256, img, b0, tdev);
 }
 
 }  // namespace
@@ -568,7 +667,7 @@ extern "C" int kzv_debug_decode_stamps(long long* host, int n) {
 
 int kzv_decode_fused_supported(int Hd, int heads, int Fd, int layers, int group, int T, int npa) {
     return Hd == HD && heads == NH && Fd == FD && layers >= 1 && layers <= KZV_DECODE_FUSED_MAX_LAYERS && (group == 1 || group == 2 || group == 4) &&
-           T >= 1 && T <= TMAX && npa >= 1 && npa <= NPMAX;
+           T >= 1 && T <= TMAX && npa >= 1 && npa <= NPWIDE;
 }
 
 int kzv_pack_frag(const bf16_t* W, bf16_t* out, int N, int K, hipStream_t s) {
@@ -591,8 +690,10 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     p.whd = a.whd; p.bhd = a.bhd; p.hd_out = a.hd_out; p.cache = a.cache; p.plane = a.plane; p.ckv = a.ckv; p.plane2 = a.plane2;
     p.valid = a.valid; p.ldvalid = a.ldvalid; p.tptr = a.tptr; p.t = a.t; p.T = a.T; p.npa = a.npa; p.B = a.B; p.rows = a.rows; p.eps = a.eps;
     const int images = a.B / a.group;
-    if (a.group == 1) hipLaunchKernelGGL(decode_fused_kernel<1>, dim3(images), dim3(512), 0, s, p);
-    else if (a.group == 2) hipLaunchKernelGGL(decode_fused_kernel<2>, dim3(images), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL(decode_fused_kernel<4>, dim3(images), dim3(512), 0, s, p);
+    // up to NPMAX keys: the one-pass instances (a chunk that held no key at all would be all -inf); beyond: the chunked ones
+    void (*kern)(const FusedP) = nullptr;
+    if (a.npa <= NPMAX) kern = a.group == 1 ? decode_fused_kernel<1, 1> : a.group == 2 ? decode_fused_kernel<2, 1> : decode_fused_kernel<4, 1>;
+    else kern = a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS> : decode_fused_kernel<4, KZV_DF_CHUNKS>;
+    hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, p);
     return kzv_check_launch("decode_fused");
 }

@@ -1179,6 +1179,10 @@ extern "C" int kzv_set_decode_one_launch(int on) {
 static bool decode_one_launch(const kzv_model* m) {
     return decode_one_launch_mode() && m->Be >= 1 && m->B % m->Be == 0 && kzv_decode_fused_supported(m->Hd, m->c.dec_heads, m->Fd, m->Ld, m->B / m->Be, m->T, m->npa);
 }
+extern "C" int kzv_decode_step_impl(const kzv_model* m) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "decode_step_impl: model not bound");
+    return decode_one_launch(m) ? 1 : 0;
+}
 
 // fragment-ordered copies of the decoder's weights (9.6 MB) for the one-launch generation step and the training forward's linear
 // chains: ONE table-driven launch after every weight change (outside any capture)

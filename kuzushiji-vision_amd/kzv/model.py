@@ -207,6 +207,16 @@ class TrOCRModel:
         widest crop)."""
         return encoder_attention_impl(self.cfg, self.long_sequences)
 
+    @property
+    def decode_step_impl(self) -> str:
+        """"one-launch" | "per-operation": how the next KV-cached generation step of this model runs (kzv_decode_step_impl: the
+        bound rows, the images and crop width of the last generate, the kzv_set_decode_one_launch mode).  Valid once a generate
+        (or _bind) has bound the model; before the first encoder pass it answers "per-operation"."""
+        rc = L.load().kzv_decode_step_impl(self._h)
+        if rc < 0:
+            L.check(rc, "kzv_decode_step_impl")
+        return "one-launch" if rc == 1 else "per-operation"
+
     def train(self, mode: bool = True):
         self.training = mode
         return self

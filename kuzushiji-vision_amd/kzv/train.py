@@ -229,6 +229,14 @@ def main(argv=None):
     if rank == 0:
         c = model.cfg
         print(f"encoder attention: {model.encoder_attention_impl} (head_dim {c.enc_hidden // c.enc_heads}, {c.enc_seq} tokens)")
+        generate = model.generate
+
+        def generate_and_report(*a, **kw):      # the first validation decode binds the model: say once which step it took
+            out = generate(*a, **kw)
+            print(f"decode step: {model.decode_step_impl}")
+            del model.generate
+            return out
+        model.generate = generate_and_report
     if args.synthetic:
         n_val = max(args.batch_size, args.synthetic // 10)
         train_ds = SyntheticLineDataset(model.cfg, args.synthetic, args.max_length, seed=args.seed)

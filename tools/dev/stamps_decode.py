@@ -1,15 +1,19 @@
-"""dev: phase timeline of the one-launch decoder step (variant library built with -DKZV_STAMPS; KZV_LIB points at it)."""
-import ctypes, os, sys, tempfile
+"""dev: phase timeline of the one-launch decoder step (variant library built with -DKZV_STAMPS; KZV_LIB points at it).
+DEC_PATCHES=256 (or 161 / 320) times the chunked instances at the reference CLI's encoder instead of the 160-key benchmark geometry."""
+import ctypes, dataclasses, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "kuzushiji-vision_amd")]
 import torch
-from kzv.config import vit_b_config
+from kzv.config import reference_cli_config, vit_b_config
 from kzv.data import build_decoder_dir, synthetic_batch
 from kzv.model import TrOCRModel
 from kzv import _lib
 cfg = vit_b_config(dec_layers=6)
+WIDE = {161: dict(image_h=16, image_w=2576), 256: dict(image_h=1024, image_w=64), 320: dict(image_h=64, image_w=1280, enc_heads=12)}
+if os.environ.get("DEC_PATCHES"):
+    cfg = dataclasses.replace(reference_cli_config(), dec_layers=6, **WIDE[int(os.environ["DEC_PATCHES"])])
 with tempfile.TemporaryDirectory() as tmp:
-    m = TrOCRModel(cfg.encoder_config_dict(), build_decoder_dir(os.path.join(tmp, "d"), cfg), load_tokenizer=False)
+    m = TrOCRModel(cfg.encoder_config_dict(), build_decoder_dir(os.path.join(tmp, "d"), cfg), load_tokenizer=False, long_sequences=cfg.enc_seq > 288)
 px = torch.from_numpy(synthetic_batch(cfg, 256, 128, seed=1)[0]).cuda()
 m.eval()
 names = ["qkv", "self", "o", "ln1", "cq", "cross", "co", "ln2", "fc1", "fc2", "ln3"]
@@ -27,3 +31,7 @@ for beams in (1, 4):
     a = st[44:52]
     print("  attention wave, layer 1: B1->self done", a[1] - a[0], "rest of sequences", a[2] - a[1], "cross issue", a[3] - a[2], "| B5->cross done", a[5] - a[4],
           "params", a[6] - a[5], "self issue", a[7] - a[6], "| B1 -> B5", a[4] - a[0])
+    if cfg.num_patches > 160:      # the two-chunk instances: stamp 8 behind chunk 0's use (chunk 1's request follows it), stamp 5 behind chunk 1's
+        nc = int(os.environ.get("DEC_CHUNKS", "2"))      # a development build with more chunks stamps 8 + S behind chunk S: exactly nc slots
+        ends = st[52:52 + nc - 1] + [a[5]]
+        print("  cross chunks, B5 -> end of chunk S:", " ".join(str(v - a[4]) for v in ends))

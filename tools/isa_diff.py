@@ -1,7 +1,9 @@
 """Proof that a source change left kernels alone: compiles the same .hip units of two trees with the Makefile's flags and compares
 the gfx950 assembly kernel by kernel.
    python tools/isa_diff.py PARENT_CSRC [--new CSRC] [--units attention.hip gemm_nt256p.hip ...] [--cache DIR] [--show] [--strict]
-(--units takes any .hip units of csrc, default: csrc/attention*.hip; --cache keeps the parent's assembly between runs; --show prints
+                            [--rename REGEX REPLACEMENT]
+(--rename rewrites the parent's demangled kernel names before they are matched, for a kernel template that gained a parameter:
+--rename 'decode_fused_kernel<(\d)>' 'decode_fused_kernel<\1, 1>'; --units takes any .hip units of csrc, default: csrc/attention*.hip; --cache keeps the parent's assembly between runs; --show prints
 the diff of every kernel whose instruction stream differs).  Per kernel it reports
    (a) the resource counts (.vgpr_count, .agpr_count, .sgpr_count, LDS, scratch, spills: equal to the parent's; a count of
        scratch or spills that is not 0 is noted on the kernel's line) and the MULTISET of instructions, an
@@ -79,6 +81,7 @@ def main():
     ap.add_argument("--cache")
     ap.add_argument("--show", action="store_true")
     ap.add_argument("--strict", action="store_true")
+    ap.add_argument("--rename", nargs=2, metavar=("REGEX", "REPLACEMENT"))
     a = ap.parse_args()
     units = a.units or sorted(os.path.basename(f) for f in glob.glob(os.path.join(a.new, "attention*.hip")))
     with tempfile.TemporaryDirectory() as tmp:
@@ -93,6 +96,8 @@ def main():
         bad = 0
         for u, fo, fn in zip(units, old, new):
             ko, kn = parse(fo), parse(fn)
+            if a.rename:
+                ko = {re.sub(a.rename[0], a.rename[1], k): v for k, v in ko.items()}
             for name in sorted(set(ko) | set(kn)):
                 if name not in ko or name not in kn:
                     print(f"{u}: {name}: only in {'parent' if name in ko else 'new'}")
