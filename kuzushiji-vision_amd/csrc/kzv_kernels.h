@@ -1,4 +1,4 @@
-// Internal launcher API (C++ linkage) used by model.cpp; the per-op C ABI in include/kzv.h wraps a subset.
+// Internal launcher API (C++ linkage) used by the model handle's units (model.cpp, model_train.cpp, model_decode.cpp); the per-op C ABI in include/kzv.h wraps a subset.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

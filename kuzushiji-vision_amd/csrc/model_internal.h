@@ -1,0 +1,237 @@
+// The model handle and what its three units share (model.cpp: table, plan, bind; model_train.cpp: forward / backward schedules;
+// model_decode.cpp: generation steps): the handle itself, one descriptor per Linear (Lin), the fragment-pack layout (DecPack),
+// and the call helpers that take their shapes, weight copies and gradient destinations from a Lin instead of positional arguments.
+// Nothing declared here is part of the library's dynamic symbol table.
+#pragma once
+#include "kzv_host.h"
+#include "kzv_kernels.h"
+#include "../../include/kzv.h"
+#include "gemm_nt.h"
+#include "gemm_tn.h"
+#include "attention_common.h"
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+#pragma clang diagnostic ignored "-Wc++20-designator"      // the units initialise the option aggregates below by field name
+
+#define KZV_TRY(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)
+
+struct PEntry { std::string name; int64_t off, rows, cols; };
+
+inline int64_t align_up(int64_t n, int64_t a) { return (n + a - 1) / a * a; }
+
+struct W16 { bf16_t* w; bf16_t* wt; int64_t ldt; };   // bf16 copy [N,K] and transposed copy [K, ldt]
+struct W8 { unsigned char* w; float* scale; };         // fp8 path: e4m3 copy [N,K] quantised per output row, scale [N]
+// One Linear: fp32 offsets of weight [N,K] and bias [N] into P and G, its bf16 copies, and (fp8 path, some encoder linears) the e4m3
+// copy q and the e4m3 copy qt of the transposed weight
+struct Lin { int64_t w = 0, b = 0; int N = 0, K = 0; W16 h{}; W8 q{}, qt{}; };
+
+struct EncLayerP { int64_t ln1w, ln1b, ln2w, ln2b; Lin qkv, o, fc1, fc2; };
+struct DecLayerP { int64_t ln1w, ln1b, ln2w, ln2b, ln3w, ln3b; Lin qkv, o, cq, co, fc1, fc2; };
+
+struct EncAct {
+    float *x_in, *x_mid, *st1, *st2, *lse;
+    bf16_t *ln1, *qkv, *ctx, *ln2, *pre, *act;
+};
+struct DecAct {
+    float *s1, *x1, *s2, *x2, *s3, *x3, *st1, *st2, *st3, *lse_sa, *lse_ca;
+    bf16_t *qkv, *ctx, *x1h, *cq, *cctx, *x2h, *pre, *act, *x3h;
+    // backward (segment path): this layer's six "dY" operands stay alive until ONE grouped weight-gradient launch behind the last layer
+    bf16_t *g_dy = nullptr, *g_dbig = nullptr, *g_dy2 = nullptr, *g_dq = nullptr, *g_dy3 = nullptr, *g_dqkv = nullptr;
+};
+
+// The decoder's bf16 weights in MFMA fragment order (decode_fused.hip, decoder_chain.hip), element offsets into kzv_model::dec_pack:
+//   [layer 0..Ld-1: qkv | o | cq | co | fc1 | fc2] [head dense] [tied LM head, vq rows] then the same again TRANSPOSED ([in, out]
+//   row-major, the B operands of the input-gradient GEMMs).  vq = the vocabulary in 256-row chunks (zeros beyond it).
+struct DecPack {
+    enum Which { QKV, O, CQ, CO, FC1, FC2 };
+    int64_t HH = 0, FH = 0, per = 0, half = 0; int Ld = 0, vq = 0;
+    DecPack() = default;
+    DecPack(int Hd, int Fd, int layers, int V) : HH((int64_t)Hd * Hd), FH((int64_t)Fd * Hd), per(6 * HH + 2 * FH), Ld(layers), vq((V + 255) / 256 * 256) {
+        half = per * Ld + HH + (int64_t)vq * Hd;
+    }
+    int64_t in_layer(Which w) const { return w == QKV ? 0 : w <= CO ? (2 + (int)w) * HH : w == FC1 ? 6 * HH : 6 * HH + FH; }
+    int64_t fwd(int layer, Which w) const { return per * layer + in_layer(w); }
+    int64_t head_dense() const { return per * Ld; }
+    int64_t head() const { return per * Ld + HH; }
+    int64_t tr(int layer, Which w) const { return half + fwd(layer, w); }
+    int64_t head_dense_t() const { return half + head_dense(); }
+    int64_t head_t() const { return half + head(); }
+    int64_t total() const { return 2 * half; }
+};
+
+#pragma GCC visibility pop       // the handle's type is the C ABI's (include/kzv.h): default visibility, as ever
+struct kzv_model {
+    kzv_config c;
+    int np, Se, PD, He, Fe, Hd, Fd, V, Vp, Le, Ld;
+    int npa = 0, Sa = 0, img_w = 0;   // ACTIVE geometry (kzv_set_image_width): img_w <= c.image_w, npa patches, Sa = npa + 1 tokens
+    bool has_proj;
+    bool long_seq = false;            // KZV_MODEL_LONG_SEQ: launches beyond 288 tokens take the streaming attention kernels
+    std::vector<PEntry> table;
+    int64_t total = 0;
+    // parameters: the model-level linears (word: the tied LM head, its bias the head bias; ckv: cross-attention K/V of all decoder layers;
+    // hd: the head's dense layer), the other offsets, the layers
+    Lin patch, proj, word, ckv, hd;
+    int64_t cls, pos, lnf_w, lnf_b, dpos, dtype, eln_w, eln_b, hln_w, hln_b;
+    std::vector<EncLayerP> ep;
+    std::vector<DecLayerP> dp;
+    // bound state
+    float* P = nullptr; float* G = nullptr; char* ws = nullptr; int64_t ws_bytes = 0;
+    int B = 0, L = 0, T = 0, Ta = 0;
+    int Be = 0;              // images the encoder states / cross-attention K/V currently hold (B after kzv_forward_loss; fewer after kzv_encode_images)
+    bool bound = false, have_fwd = false, have_enc = false, train = false;
+    uint64_t seed = 0;
+    const int64_t* labels = nullptr;
+    // workspace pointers
+    KzvCastDesc* d_desc = nullptr; int ndesc = 0, cast_tiles = 0;
+    std::vector<KzvCastDesc> h_desc;
+    bf16_t *patches, *enc_out, *proj_out, *crosskv, *xd0h, *hd_pre, *hd_ln, *dlogits;
+    float *pe32, *x_last, *stf, *emb_sum, *emb_st, *xd0, *hd_gelu, *hd_st, *logits, *count, *loss_acc;
+    int *posids, *err;
+    std::vector<EncAct> ea;
+    std::vector<DecAct> da;
+    // backward scratch
+    float *dx_e, *dx_d, *dsum_d;
+    bf16_t *dy_e2;           // second dy_e (overlap mode 2: the fc2 weight gradient still reads dy_e while LayerNorm-2 backward writes its output)
+    bf16_t *dy_e, *dbig_e, *dh_e, *dqkv_e, *dctx_e, *dpatch, *denc_out, *denc, *dckv, *dy_d, *dbig_d, *dqkv_d, *dctx_d, *dq_d, *dhln;
+    bf16_t *dy_d2, *dy_d3;   // the decoder's three "dropout(linear)" gradients of a layer stay alive until its grouped weight-gradient launch
+    std::vector<kzv_gemm_tn_args> wbatch;
+    // weight-gradient GEMMs run on an internal side stream so they overlap the input-gradient chain on the
+    // caller's stream (their tails and epilogues fill each other's idle workgroup slots)
+    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr; hipEvent_t ev_done[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool pending[4] = {false, false, false, false}; bool use_side = false, join_each_segment = true;
+    // KV cache of the generation path (kzv_decode_step): two copies [2*Ld][B][T][Hd] (beam re-ordering gathers from one into the other)
+    bf16_t* kvc[2] = {nullptr, nullptr}; int kv_cur = 0, kvB = 0, kvT = 0;
+    // beam re-parenting by indirection: rowtab[x][b][j] = cache row holding key j of sequence b; rt_cur = -1: identity (no table)
+    int* rowtab[2] = {nullptr, nullptr}; int rt_cur = -1;
+    // cross-attention K/V re-laid out for the generation steps ([layer][K|V][image][head][key][64]); rebuilt when the encoder ran
+    bf16_t* ckv_dec = nullptr; size_t ckv_dec_bytes = 0; bool ckv_dec_ok = false;
+    // the decoder's bf16 weights in MFMA fragment order, refreshed after every weight change; pk: where each matrix sits in it
+    bf16_t* dec_pack = nullptr; bool dec_pack_ok = false; DecPack pk;
+    bool dhln_fused = false;     // the last training forward's head_ce launch already wrote dhln (the LM head's input gradient)
+    // graph-replayed decode step (kzv_decode_step_graph): device-side step index + one instantiated graph per cache copy
+    int* d_t = nullptr;
+    hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
+    const void* dg_key[3][6] = {};
+    int64_t dg_ld[3] = {0, 0, 0};
+    // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
+    // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
+    // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU
+    // epilogue writes an e4m3 copy of the activation with a per-tensor multiplier (f8_q[layer]) derived from the largest |value|
+    // the previous forward saw (f8_amax[layer]; "delayed scaling").  Backward and the output projection stay bf16.
+    int fp8 = 0;
+    KzvQuantDesc* d_qdesc = nullptr; int nqdesc = 0, qrows = 0;
+    std::vector<KzvQuantDesc> h_qdesc;
+    unsigned char *x8 = nullptr, *act8 = nullptr;
+    float *x8_scale = nullptr, *f8_q = nullptr, *f8_amax = nullptr, *f8_rows = nullptr;
+    int64_t f8_stride = 0;
+    // mode 2: also the MLP's two INPUT-GRADIENT GEMMs (d fc2 with the DGELU epilogue, d fc1).  Transposed e4m3 weight copies
+    // (Lin::qt, quantised per row from the bf16 transposed copies); the masked gradient rows arriving at fc2 come from the LayerNorm
+    // backward above them as e4m3 with their own amax (dy8, dy8_scale); the gradient of the GELU input is quantised per row
+    // in the DGELU epilogue with a multiplier from the bound ||dy row|| * max ||W2 column|| (rq / rqinv; f8_wnorm[layer]).
+    unsigned char *dy8 = nullptr, *dbig8 = nullptr;
+    float *dy8_scale = nullptr, *dy8_rq = nullptr, *dy8_rqinv = nullptr, *f8_wnorm = nullptr;
+    bool side_ok = false;    // mode 2: set only inside the encoder-layer schedule (everything else stays on the caller's stream)
+    int side_mode = 0;       // 0 off, 1 free-running wgrads, 2 wgrads only under the HBM-bound kernels (LayerNorm / attention backward)
+};
+
+#pragma GCC visibility push(hidden)
+
+// ---- what crosses the units --------------------------------------------------------------------------------------------
+// model_train.cpp
+KZV_LOCAL int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss, float* d_logits, hipStream_t s,
+                      bool run_encoder = true, int logits_pos = -1, int enc_batch = 0, bool run_decoder = true);
+KZV_LOCAL int backward_decoder(kzv_model* m, hipStream_t s);
+KZV_LOCAL int backward_enc_layer(kzv_model* m, int i, hipStream_t s);
+KZV_LOCAL int backward_embed(kzv_model* m, hipStream_t s);
+KZV_LOCAL int dec_chain_mode();         // KZV_DEC_CHAIN / kzv_set_dec_chain: 0, 1 or 2 (default)
+KZV_LOCAL bool head_ce_mode();          // KZV_HEAD_CE / kzv_set_head_ce (default on)
+// model_decode.cpp
+KZV_LOCAL bool dec_pack_wanted(const kzv_model* m);
+KZV_LOCAL int ensure_dec_pack(kzv_model* m, hipStream_t s);
+KZV_LOCAL int decode_one_launch_mode(); // KZV_DECODE_ONE_LAUNCH / kzv_set_decode_one_launch (default on)
+
+// a captured decode step holds pointers into the workspace, the caches and the pack: dropped whenever one of them moves
+static inline void drop_decode_graphs(kzv_model* m) {
+    for (int i = 0; i < 3; ++i) if (m->dgraph[i]) { (void)hipGraphExecDestroy(m->dgraph[i]); m->dgraph[i] = nullptr; }
+}
+
+// dropout site ids (distinct hash keys per call site and layer)
+enum { SITE_ENC_EMB = KZV_SITE_ENC_EMB, SITE_ENC_L = KZV_SITE_ENC_LAYER(0, 0), SITE_DEC_EMB = KZV_SITE_DEC_EMB, SITE_DEC_L = KZV_SITE_DEC_LAYER(0, 0) };
+static inline uint32_t key(const kzv_model* m, uint32_t site) { return kzv_drop_key(m->seed, site); }
+static inline float dp(const kzv_model* m, float p) { return m->train ? p : 0.f; }
+
+// ---- Linear forward and input gradient ------------------------------------------------------------------------------------
+// What a call adds to "C = A . W^T + bias" (forward) or "dX = dY . W" (input gradient); every field is optional.
+struct LinOpts {
+    const float* resid = nullptr;       // KZV_EPI_RESID: C += resid (row stride = ldc)
+    void* aux = nullptr; int64_t ldaux = 0;   // GELU: the pre-activation written beside C; DGELU: read
+    float drop_p = 0.f; uint32_t drop_key = 0;
+    int n = 0;                          // the tied LM head only: the vocabulary padded to n columns (zeros / no store beyond lin.N)
+    // fp8 path: A as e4m3 with one scale per row (the Lin's q copy multiplies it, qt in the input gradient) ...
+    const unsigned char* a8 = nullptr; const float* a8_scale = nullptr;
+    // ... and an e4m3 copy of C for the next GEMM: per-tensor multiplier + amax, or one multiplier per row
+    unsigned char* c8 = nullptr; const float* c8_qscale = nullptr; float* c8_amax = nullptr; const float* c8_rowq = nullptr;
+};
+
+static inline int gemm_nt_call(const bf16_t* A, int64_t lda, const bf16_t* Bw, int64_t ldb, int M, int N, int K, int n_valid, const float* bias,
+                               void* C, int64_t ldc, int epi, hipStream_t s, const LinOpts& o) {
+    kzv_gemm_nt_args a;
+    memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.B = Bw; a.ldb = ldb;
+    a.C = C; a.ldc = ldc; a.bias = bias; a.resid = o.resid; a.ldr = ldc; a.aux = o.aux; a.ldaux = o.ldaux;
+    a.M = M; a.N = N; a.K = K; a.n_valid = n_valid; a.drop_p = o.drop_p; a.drop_key = o.drop_key;
+    return kzv_gemm_nt(&a, epi, s);
+}
+// fp8 GEMM of the encoder: A e4m3 with one scale per row, W e4m3 with one scale per output row
+static inline int gemm_fp8_call(const W8& w, int M, int N, int K, const float* bias, void* C, int64_t ldc, int epi, hipStream_t s, const LinOpts& o) {
+    kzv_gemm_nt_fp8_args a;
+    memset(&a, 0, sizeof(a));
+    a.A = o.a8; a.lda = K; a.a_scale = o.a8_scale; a.B = w.w; a.ldb = K; a.b_scale = w.scale;
+    a.C = C; a.ldc = ldc; a.bias = bias; a.resid = o.resid; a.ldr = ldc; a.aux = o.aux; a.ldaux = o.ldaux;
+    a.c8 = o.c8; a.ldc8 = N; a.c8_qscale = o.c8_qscale; a.c8_amax = o.c8_amax; a.c8_rowq = o.c8_rowq;
+    a.M = M; a.N = N; a.K = K; a.n_valid = N; a.drop_p = o.drop_p; a.drop_key = o.drop_key;
+    return kzv_gemm_nt_fp8(&a, epi, s);
+}
+
+// C[M, N] = epi(A[M, K] . W^T + bias); with o.a8 the e4m3 operands (A is then unused)
+static inline int lin_fwd(const kzv_model* m, const Lin& l, const bf16_t* A, int64_t lda, int M, void* C, int64_t ldc, int epi, hipStream_t s,
+                          const LinOpts& o = {}) {
+    if (o.a8) return gemm_fp8_call(l.q, M, l.N, l.K, m->P + l.b, C, ldc, epi, s, o);
+    return gemm_nt_call(A, lda, l.h.w, l.K, M, o.n ? o.n : l.N, l.K, l.N, m->P + l.b, C, ldc, epi, s, o);
+}
+// dX[M, K] = epi(dY[M, N] . W)  (B operand = the transposed copy [K, ldt])
+static inline int lin_dgrad(const kzv_model* m, const Lin& l, const bf16_t* dY, int64_t ldy, int M, void* dX, int64_t ldx, int epi, hipStream_t s,
+                            const LinOpts& o = {}) {
+    if (o.a8) return gemm_fp8_call(l.qt, M, l.K, l.N, nullptr, dX, ldx, epi, s, o);
+    return gemm_nt_call(dY, ldy, l.h.wt, l.h.ldt, M, l.K, o.n ? o.n : l.N, l.K, nullptr, dX, ldx, epi, s, o);
+}
+
+// ---- LayerNorm ---------------------------------------------------------------------------------------------------------------
+// gw / gb: the offsets of gamma and beta.  The defaults are the common case: every row normalised alike, no dropout.
+struct LnFwdOpts {
+    int seq = 1, drop_first = 0;        // rows per sequence; 1: the first row of each sequence (CLS) is left out of the output
+    float drop_p = 0.f; uint32_t drop_key = 0;
+    void* y8 = nullptr; float* y8_scale = nullptr;      // fp8 path: e4m3 copy of the output, one scale per row
+};
+static inline int ln_fwd(const kzv_model* m, const float* x, int64_t gw, int64_t gb, void* y16, float* y32, float* stats, int rows, int H, hipStream_t s,
+                         const LnFwdOpts& o = {}) {
+    return kzv_ln_fwd_ex(x, m->P + gw, m->P + gb, y16, y32, stats, rows, H, m->c.ln_eps, o.seq, o.drop_first, o.drop_p, o.drop_key, s, o.y8, o.y8_scale);
+}
+struct LnBwdOpts {
+    int seq = 1, drop_first = 0;
+    float drop_p = 0.f; uint32_t drop_key = 0;          // the dropout the forward applied to the LayerNorm's output
+    bf16_t* out16 = nullptr; float out_drop_p = 0.f; uint32_t out_drop_key = 0;    // bf16 copy of dx under the mask of the Linear below
+    const KzvLnBwdF8* f8 = nullptr;
+};
+// dx (+)= LayerNorm backward of dy (bf16, or fp32 with dy_is_f32); gamma / beta gradients go to G at the same offsets
+static inline int ln_bwd(const kzv_model* m, const void* dy, int dy_is_f32, const float* x, const float* stats, int64_t gw, int64_t gb, float* dx,
+                         int accumulate_dx, int rows, int H, hipStream_t s, const LnBwdOpts& o = {}) {
+    return kzv_ln_bwd_ex(dy, dy_is_f32, x, stats, m->P + gw, dx, accumulate_dx, m->G + gw, m->G + gb, rows, H, o.seq, o.drop_first, o.drop_p, o.drop_key, s,
+                         o.out16, o.out_drop_p, o.out_drop_key, o.f8);
+}
+
+#pragma GCC visibility pop
