@@ -113,6 +113,22 @@ int kzv_set_active_length(kzv_model* m, int t_active);
  * pos only depends on ids[:, :pos+1].  Invalidates the saved activations (no backward afterwards). */
 int kzv_decode_logits(kzv_model* m, const int64_t* d_labels, int pos, float* d_logits, void* stream);
 
+/* What the last kzv_forward_loss knows about each label position beyond the loss, read back from its saved decoder activations.
+ * Both need the decoder activations of a FULL kzv_forward_loss (train 0 or 1) in the workspace: a rebind, a change of the image
+ * width or the active length, kzv_encode_images, kzv_decode_logits and the kzv_decode_step calls invalidate them (KZV_E_STATE).
+ * Both only read saved activations (kzv_score_tokens also rewrites the workspace's logits region, which nothing else reads later):
+ * kzv_backward after them still works.
+ *
+ * Cross-attention weights of decoder layer `layer` (0..Ld-1; -1 = last) of the last kzv_forward_loss,
+ * averaged over heads: rows are the PACKED decoder rows [B, t_active]; keys are the active patches,
+ * grid_w = active image width / patch_w.  HF: output_attentions=True -> cross_attentions[layer].mean(1).
+ * d_map fp32 [B, t_active, ld_map] or NULL, d_pos fp32 [B, t_active, 4], d_peak int32 [B, t_active]: kzv_attn_probs' outputs.  In
+ * training mode they are the probabilities before attention dropout. */
+int kzv_cross_attention(kzv_model* m, int layer, float* d_map, int64_t ld_map, float* d_pos, int32_t* d_peak, void* stream);
+/* Per-position log-probabilities of the labels of the last kzv_forward_loss, [B, t_active] each: kzv_token_scores' outputs on the
+ * vocabulary GEMM re-run from the saved LM-head input (valid after the one-launch head + CE path too, which never wrote logits). */
+int kzv_score_tokens(kzv_model* m, float* d_logprob, int64_t* d_top1, float* d_top1_logprob, void* stream);
+
 /* Encoder only (ViTEncoder.forward + encoder_decoder_proj + the cross-attention K/V of every decoder layer) for n_images
  * crops [n_images, C, H, W], n_images dividing the bound batch: the bound batch counts DECODER rows, and beam search runs
  * batch / n_images beams per image that all attend to that image's K/V (HF expands encoder_hidden_states per beam,
@@ -407,6 +423,31 @@ int kzv_attn_stream_bwd(const kzv_attn_args* a, void* stream);
 #define KZV_ATTN_STREAM64 4
 #define KZV_ATTN_STREAM96 5
 int kzv_attn_impl_ex(const kzv_attn_args* a, int bwd, unsigned flags);
+
+/* Head-averaged attention probabilities, recomputed from what a forward leaves behind (csrc/attention_probs.hip; HF:
+ * output_attentions=True -> attentions.mean(1) in eval mode, i.e. BEFORE dropout).  Q [B*Sq, ldq] and K [B*Sk, ldk] bf16 with head h at
+ * column h * 64 and LSE fp32 [B, heads, Sq] in natural log are kzv_attn_args' -- exactly what kzv_attn_fwd / kzv_attn_stream_fwd read and
+ * write.  Mode 0 and head_dim 64 only, Sq in 1..288, Sk in 1..4,097; anything else is KZV_E_ARG.
+ *   map  fp32 [B, Sq, ld_map] or NULL: map[b,q,k] = (1/heads) * sum_h exp(q_h . k_h * 64^-0.5 - LSE[b,h,q]); with NULL nothing of size Sk is written
+ *   pos  fp32 [B, Sq, 4] = (sum_k P (k / grid_w), sum_k P (k % grid_w), max_k P, sum_k P): centroid in patch rows / columns of a grid
+ *        grid_w patches wide, the peak weight, and the row sum (~ 1 when LSE belongs to Q and K)
+ *   peak int32 [B, Sq] = the first arg-max key
+ * No atomics, fixed summation order: bit-reproducible. */
+typedef struct kzv_attn_probs_args {
+    const void* Q; const void* K; int64_t ldq, ldk;
+    const float* LSE;
+    float* map; int64_t ld_map;      /* NULL: no map */
+    float* pos; int32_t* peak;       /* [B,Sq,4], [B,Sq]; either may be NULL */
+    int32_t B, heads, Sq, Sk, grid_w, head_dim;   /* head_dim 0 = 64 */
+    int32_t mode;                    /* kzv_attn_args' mode: 0 (no mask) is the only one served */
+} kzv_attn_probs_args;
+int kzv_attn_probs(const kzv_attn_probs_args* a, void* stream);
+/* Per-token scores from fp32 logits rows [rows_b * T, ld], one wave per row: the row's log-sum-exp over `vocab` columns (maximum
+ * subtracted first); logprob[b,t] = log-softmax at targets[b, t + 1] (kzv_ce_fwd_bwd's indexing: row b * T + t against column t + 1
+ * of int64 targets [rows_b, ld_targets]), 0 where that target is pad_id; top1 = the first arg-max column and top1_logprob its
+ * log-probability.  Each output [rows_b, T], any of them NULL. */
+int kzv_token_scores(const float* logits, int64_t ld, const int64_t* targets, int64_t ld_targets, int rows_b, int T, int vocab, int pad_id,
+                     float* logprob, int64_t* top1, float* top1_logprob, void* stream);
 
 /* ------------------------------------------------------------- the ResNet / BiLSTM / CTC model of ocr_lightning/model.py
  * (SURVEY.md section 8(f), row N3).  Per-op entry points; the host mirror kzv/ocr_model.py strings them together the way

@@ -342,7 +342,7 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
     // a captured decode step holds pointers INTO the workspace and the parameter buffer: none survives a rebind
     drop_decode_graphs(m);
     m->ckv_dec_ok = false; m->dec_pack_ok = false;
-    m->bound = true; m->have_fwd = false; m->have_enc = false;
+    m->bound = true; m->have_fwd = false; m->have_enc = false; m->have_dec = false;
     return KZV_OK;
 }
 
@@ -383,7 +383,7 @@ extern "C" int kzv_set_image_width(kzv_model* m, int width) {
     const kzv_config& c = m->c;
     if (width < c.patch_w || width > c.image_w || width % c.patch_w)
         return kzv_fail(KZV_E_ARG, "set_image_width: %d is not a multiple of the patch width %d within %d..%d", width, c.patch_w, c.patch_w, c.image_w);
-    if (width != m->img_w) { m->have_fwd = false; m->have_enc = false; }    // saved activations belong to the old geometry
+    if (width != m->img_w) { m->have_fwd = false; m->have_enc = false; m->have_dec = false; }    // saved activations belong to the old geometry
     m->img_w = width;
     m->npa = (c.image_h / c.patch_h) * (width / c.patch_w);
     m->Sa = m->npa + 1;
@@ -393,7 +393,7 @@ extern "C" int kzv_set_image_width(kzv_model* m, int width) {
 extern "C" int kzv_set_active_length(kzv_model* m, int t_active) {
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "set_active_length: model not bound");
     if (t_active < 1 || t_active > m->T) return kzv_fail(KZV_E_ARG, "set_active_length: must be in 1..%d", m->T);
-    if (m->have_fwd && t_active != m->Ta) m->have_fwd = false;   // saved activations belong to the old length
+    if (t_active != m->Ta) { m->have_fwd = false; m->have_dec = false; }   // saved activations belong to the old length
     m->Ta = t_active;
     return KZV_OK;
 }

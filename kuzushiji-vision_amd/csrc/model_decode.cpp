@@ -247,7 +247,7 @@ extern "C" int kzv_decode_step(kzv_model* m, const int64_t* d_tokens, const int*
     if (t == 0) m->rt_cur = -1;                 // a new generation: no beam has been re-parented yet
     KZV_TRY(ensure_cross_layout(m, (hipStream_t)stream));
     KZV_TRY(ensure_dec_pack(m, (hipStream_t)stream));
-    m->train = false; m->have_fwd = false;      // decoder activations are overwritten: no backward after this
+    m->train = false; m->have_fwd = false; m->have_dec = false;      // decoder activations are overwritten: no backward after this
     return decode_step_body(m, StepArgs{d_tokens, d_posids, t, nullptr, d_valid, ld_valid, d_logits}, (hipStream_t)stream);
 }
 
@@ -268,7 +268,7 @@ extern "C" int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, cons
     KZV_TRY(ensure_kv_cache(m));
     KZV_TRY(ensure_cross_layout(m, (hipStream_t)stream));          // before any capture: a plain launch, once per generation
     KZV_TRY(ensure_dec_pack(m, (hipStream_t)stream));
-    m->train = false; m->have_fwd = false;
+    m->train = false; m->have_fwd = false; m->have_dec = false;
     hipStream_t s = (hipStream_t)stream;
     const int g = m->rt_cur + 1;
     const void* key[6] = {d_tokens, d_posids, d_valid, d_logits, m->kvc[0], (const void*)((intptr_t)m->ckv_dec ^ (intptr_t)(m->npa * 4096 + m->Be) ^ ((intptr_t)decode_one_launch_mode() << 40))};

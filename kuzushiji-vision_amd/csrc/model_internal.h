@@ -83,6 +83,8 @@ struct kzv_model {
     int B = 0, L = 0, T = 0, Ta = 0;
     int Be = 0;              // images the encoder states / cross-attention K/V currently hold (B after kzv_forward_loss; fewer after kzv_encode_images)
     bool bound = false, have_fwd = false, have_enc = false, train = false;
+    // the decoder activations of a full kzv_forward_loss (train or not) are in the workspace: what kzv_cross_attention / kzv_score_tokens read
+    bool have_dec = false;
     uint64_t seed = 0;
     const int64_t* labels = nullptr;
     // workspace pointers

@@ -514,6 +514,7 @@ extern "C" int kzv_forward_loss(kzv_model* m, const float* d_pixel_values, const
     m->train = train != 0; m->seed = seed;
     const int rc = forward(m, d_pixel_values, d_labels, d_loss, d_logits, (hipStream_t)stream);
     m->have_fwd = rc == KZV_OK && m->train;
+    m->have_dec = rc == KZV_OK;
     return rc;
 }
 
@@ -531,7 +532,7 @@ extern "C" int kzv_encode_images(kzv_model* m, const float* d_pixel_values, int 
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "encode_images: model not bound");
     if (!d_pixel_values || n_images < 1 || n_images > m->B || m->B % n_images)
         return kzv_fail(KZV_E_ARG, "encode_images: 1 <= n_images <= bound batch %d, which must be a multiple of it", m->B);
-    m->train = false; m->seed = 0; m->have_fwd = false;
+    m->train = false; m->seed = 0; m->have_fwd = false; m->have_dec = false;
     return forward(m, d_pixel_values, nullptr, nullptr, nullptr, (hipStream_t)stream, true, -1, n_images, false);
 }
 
@@ -540,8 +541,32 @@ extern "C" int kzv_decode_logits(kzv_model* m, const int64_t* d_labels, int pos,
     if (!m->have_enc) return kzv_fail(KZV_E_STATE, "decode_logits: call kzv_forward_loss on the images first");
     if (!d_labels || !d_logits || pos < 0 || pos >= m->Ta) return kzv_fail(KZV_E_ARG, "decode_logits: position outside the active decoder length");
     m->train = false;
-    m->have_fwd = false;     // decoder activations are overwritten: no backward after this
+    m->have_fwd = false; m->have_dec = false;     // decoder activations are overwritten: no backward after this
     return forward(m, nullptr, d_labels, nullptr, d_logits, (hipStream_t)stream, false, pos);
+}
+
+// ---- read-backs of the last forward's decoder activations (have_dec) -----------------------------------------------------------------
+extern "C" int kzv_cross_attention(kzv_model* m, int layer, float* d_map, int64_t ld_map, float* d_pos, int32_t* d_peak, void* stream) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "cross_attention: model not bound");
+    if (!m->have_dec) return kzv_fail(KZV_E_STATE, "cross_attention: call kzv_forward_loss first (its decoder activations are gone or were never computed)");
+    if (layer < -1 || layer >= m->Ld) return kzv_fail(KZV_E_ARG, "cross_attention: layer must be in -1..%d", m->Ld - 1);
+    const AttnSite t = dec_cross(m, layer < 0 ? m->Ld - 1 : layer);
+    kzv_attn_probs_args a;
+    memset(&a, 0, sizeof(a));
+    a.Q = t.Q; a.K = t.K; a.ldq = t.ldq; a.ldk = t.ldkv; a.LSE = t.LSE;
+    a.map = d_map; a.ld_map = ld_map; a.pos = d_pos; a.peak = d_peak;
+    a.B = t.batch; a.heads = t.heads; a.Sq = t.Sq; a.Sk = t.Sk; a.grid_w = m->img_w / m->c.patch_w; a.head_dim = t.head_dim; a.mode = t.mode;
+    return kzv_attn_probs(&a, stream);
+}
+
+extern "C" int kzv_score_tokens(kzv_model* m, float* d_logprob, int64_t* d_top1, float* d_top1_logprob, void* stream) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "score_tokens: model not bound");
+    if (!m->have_dec) return kzv_fail(KZV_E_STATE, "score_tokens: call kzv_forward_loss first (its decoder activations are gone or were never computed)");
+    hipStream_t s = (hipStream_t)stream;
+    // the vocabulary GEMM of forward()'s non-fused branch, from the saved LM-head input into the logits region (the fused head + CE path
+    // never wrote it; the backward reads dlogits and hd_ln, not logits)
+    KZV_TRY(lin_fwd(m, m->word, m->hd_ln, m->Hd, m->B * m->Ta, m->logits, m->Vp, KZV_EPI_F32, s, {.n = m->Vp}));
+    return kzv_token_scores(m->logits, m->Vp, m->labels, m->L, m->B, m->Ta, m->V, m->c.pad_id, d_logprob, d_top1, d_top1_logprob, stream);
 }
 
 extern "C" int kzv_backward_segments(const kzv_model* m) { return m ? m->Le + 2 : 0; }

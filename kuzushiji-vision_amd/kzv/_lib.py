@@ -77,6 +77,13 @@ class kzv_attn_args(C.Structure):
                 ("drop_p", C.c_float), ("drop_key", C.c_uint32), ("head_dim", C.c_int32)]
 
 
+class kzv_attn_probs_args(C.Structure):
+    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("ldq", C.c_int64), ("ldk", C.c_int64), ("LSE", C.c_void_p),
+                ("map", C.c_void_p), ("ld_map", C.c_int64), ("pos", C.c_void_p), ("peak", C.c_void_p),
+                ("B", C.c_int32), ("heads", C.c_int32), ("Sq", C.c_int32), ("Sk", C.c_int32), ("grid_w", C.c_int32),
+                ("head_dim", C.c_int32), ("mode", C.c_int32)]
+
+
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU = range(5)
 ATTN_MFMA64, ATTN_MFMA96, ATTN_VALU = 1, 2, 3          # kzv_attn_impl
 ATTN_STREAM64, ATTN_STREAM96 = 4, 5                    # kzv_attn_impl_ex with MODEL_LONG_SEQ
@@ -141,6 +148,10 @@ SYMBOLS = {
     "kzv_attn_stream_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_stream_bwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_impl_ex": (C.c_int, [C.POINTER(kzv_attn_args), C.c_int, C.c_uint]),
+    "kzv_attn_probs": (C.c_int, [C.POINTER(kzv_attn_probs_args), _P]),
+    "kzv_token_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "kzv_cross_attention": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, _P, _P]),
+    "kzv_score_tokens": (C.c_int, [_P, _P, _P, _P, _P]),
     "kzv_drop_key": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "kzv_debug_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "kzv_debug_attn_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int32, C.c_int32, _P, _P]),

@@ -66,6 +66,8 @@ class TrOCRModel:
         self._step_seed = 0
         self.trim_padding = True
         self._len_cache = (None, 0)
+        self._keep = None                  # inputs of the last engine call (kept alive; align_last reads the labels)
+        self.last_active_length = 0
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
         # image_size is the WIDEST crop; batches whose width is one of `width_buckets` (multiples of the patch width, <= it)
         # run with fewer patch tokens and the position rows of the same (h, w) cells (include/kzv.h: kzv_set_image_width).
@@ -315,6 +317,100 @@ class TrOCRModel:
         st = L.stream_handle()
         L.check(lib.kzv_zero_grads(self._h, st), "zero_grads")
         L.check(lib.kzv_backward(self._h, st), "kzv_backward")
+
+    # ------------------------------------------------------------------ per-character confidence and position
+    def align_last(self, layer=-1, want_map: bool = False):
+        """Scores and cross-attention of the LAST ``forward_loss`` / ``forward(pixel_values, labels)`` on this model, read back from
+        its saved activations (kzv_score_tokens, kzv_cross_attention); see ``align`` for the result.  Raises KzvError when a
+        generate, a rebind or a change of geometry has replaced those activations.  A pending ``backward`` still works."""
+        import torch
+        from . import align as A
+        c = self.cfg
+        lib = L.load()
+        st = L.stream_handle()
+        if self._keep is None:
+            raise L.KzvError("align_last: no forward_loss has run on this model")
+        px, lab = self._keep
+        B, Lh = lab.shape
+        Ta = self.last_active_length
+        grid_w = px.shape[3] // c.patch_w
+        n_patches = (c.image_h // c.patch_h) * grid_w
+        layers = [layer] if isinstance(layer, int) else [int(x) for x in layer]
+        if not layers:
+            raise ValueError("layer: an int or a non-empty sequence of ints")
+        for x in layers:
+            if not -c.dec_layers <= x < c.dec_layers:
+                raise ValueError(f"layer {x} outside -{c.dec_layers}..{c.dec_layers - 1}")
+        layers = [x % c.dec_layers for x in layers]
+        dev = self.device
+        logprob = torch.empty(B, Ta, dtype=torch.float32, device=dev)
+        top1 = torch.empty(B, Ta, dtype=torch.int64, device=dev)
+        top1_lp = torch.empty(B, Ta, dtype=torch.float32, device=dev)
+        L.check(lib.kzv_score_tokens(self._h, logprob.data_ptr(), top1.data_ptr(), top1_lp.data_ptr(), st), "kzv_score_tokens")
+        pos = torch.empty(B, Ta, 4, dtype=torch.float32, device=dev)
+        peak = torch.empty(B, Ta, dtype=torch.int32, device=dev)
+        amap = None
+        need_map = want_map or len(layers) > 1
+        for i, x in enumerate(layers):
+            m_i = torch.empty(B, Ta, n_patches, dtype=torch.float32, device=dev) if need_map else None
+            L.check(lib.kzv_cross_attention(self._h, x, L.ptr(m_i), n_patches, pos.data_ptr(), peak.data_ptr(), st), "kzv_cross_attention")
+            if need_map:
+                amap = m_i if amap is None else amap.add_(m_i)
+        if len(layers) > 1:                                   # the mean map of several layers: centroid / peak restated in torch
+            amap = amap / len(layers)
+            pos, peak = A.stats_from_map(amap, grid_w)
+        T = Lh - 1
+        out = {
+            "logprob": A.pad_rows(logprob, T), "top1": A.pad_rows(top1, T, c.pad_id), "top1_logprob": A.pad_rows(top1_lp, T),
+            "centroid": A.pad_rows(A.patch_to_pixel(pos[..., :2], c.patch_h, c.patch_w), T),
+            "peak_patch": A.pad_rows(peak, T), "peak_weight": A.pad_rows(pos[..., 2].contiguous(), T),
+            "row_sum": A.pad_rows(pos[..., 3].contiguous(), T),
+            "live": A.live_mask(lab, c.pad_id),
+        }
+        if want_map:
+            out["map"] = A.pad_rows(amap, T)
+        return out
+
+    def align(self, pixel_values, labels, layer=-1, want_map: bool = False):
+        """Per-position confidence and position of ``labels`` [B, L] on the crops: one eval-mode teacher-forced pass (no logits
+        are materialised for the caller; trailing padding is trimmed as in training), then the two read-backs.  Returns device
+        tensors padded back to [B, L - 1]; row t belongs to the token labels[:, t + 1]:
+
+          logprob, top1, top1_logprob   log-softmax at the label, the arg-max token and its log-probability
+          centroid [B, L - 1, 2]        attention centroid (y, x) in pixels: ((row + 0.5) * patch_h, (col + 0.5) * patch_w)
+          peak_patch, peak_weight       the arg-max patch of the head-averaged cross-attention and its weight
+          row_sum                       the sum of the weights (1 up to rounding: a health value)
+          map [B, L - 1, n_patches]     the weights themselves, when ``want_map``
+          live                          decoder input and target both non-pad (other rows are padding or zeros)
+
+        ``layer``: a decoder layer (negative from the end) or a sequence of them, whose maps are averaged (HF:
+        ``cross_attentions[layer].mean(1)``)."""
+        was = self.training
+        self.training = False
+        try:
+            self.forward_loss(pixel_values, labels, want_logits=False, seed=0)
+        finally:
+            self.training = was
+        return self.align_last(layer, want_map)
+
+    def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1) -> list[dict]:
+        """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
+        ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
+        ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
+        pixels) and ``peak_patches`` (kzv/align.py: build_records)."""
+        import torch
+        from . import align as A
+        c = self.cfg
+        gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True)
+        if gen.shape[1] < 2:                                  # labels need a target column
+            gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
+        out = self.align(pixel_values, gen, layer=layer)
+        ids = gen.cpu().numpy()
+        tok = self.tokenizer
+        return A.build_records(ids, out["logprob"].cpu().numpy(), out["centroid"].cpu().numpy(), out["peak_patch"].cpu().numpy(),
+                               pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
+                               texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens)
 
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True):
