@@ -383,6 +383,75 @@ int kzv_layernorm_fwd(const float* x, const float* gamma, const float* beta, voi
 /* dx(+)= LN backward; dy bf16 or fp32; dgamma/dbeta accumulated (atomics). */
 int kzv_layernorm_bwd(const void* dy, int dy_is_f32, const float* x, const float* stats, const float* gamma,
                       float* dx, int accumulate_dx, float* dgamma, float* dbeta, int rows, int H, void* stream);
+/* The same two kernels with everything the model's call sites fuse into them (csrc/layernorm.hip; the fp8 copies keep their own
+ * entry, kzv_layernorm_fwd_fp8).  seq / drop_first: the encoder's final LayerNorm drops the CLS token (trocr_model.py:200): rows
+ * with row % seq == 0 write no output (their statistics are still written) and row r lands in output row r - r / seq - 1; the
+ * backward reads dy at that row and treats the CLS rows' dy as zero.  drop_p / drop_key: hidden-state dropout on the forward's
+ * OUTPUT (element index = output row * H + col), and in the backward on dy (same index) before anything else.  out16: optional
+ * bf16 copy of the dx row the call stored (the total when accumulate_dx), masked with out_drop_p / out_drop_key at row * H + col. */
+typedef struct kzv_ln_fwd_args {
+    const float* x; const float* gamma; const float* beta;
+    void* y_bf16; float* y_f32;       /* either may be NULL */
+    float* stats;                     /* [rows, 2] mean, rstd, or NULL */
+    int32_t rows, H, seq, drop_first;
+    float eps, drop_p; uint32_t drop_key;
+} kzv_ln_fwd_args;
+int kzv_ln_fwd_ex(const kzv_ln_fwd_args* a, void* stream);
+typedef struct kzv_ln_bwd_args {
+    const void* dy; const float* x; const float* stats; const float* gamma;
+    float* dx; float* dgamma; float* dbeta;
+    void* out16;                      /* bf16 [rows, H] or NULL */
+    int32_t dy_is_f32, accumulate_dx, rows, H, seq, drop_first;
+    float drop_p; uint32_t drop_key;
+    float out_drop_p; uint32_t out_drop_key;
+} kzv_ln_bwd_args;
+int kzv_ln_bwd_ex(const kzv_ln_bwd_args* a, void* stream);
+
+/* The HBM-bound glue kernels of the training step (csrc/elementwise.hip), as the model handle launches them.
+ * kzv_im2row: the data movement of nn.Conv2d(kernel = stride = patch) (trocr_model.py:77,89-90): px fp32 [B, C, H, W] -> bf16
+ *   [B * (H / ph) * (W / pw), C * ph * pw], column (c * ph + i) * pw + j; pw % 8 == 0. */
+int kzv_im2row(const float* px, void* out_bf16, int B, int C, int H, int W, int ph, int pw, void* stream);
+/* kzv_embed_assemble: x0 [B, np + 1, He] = dropout(cat(cls, patch_emb [B, np, He]) + pos) (trocr_model.py:183-190), element index
+ *   row * He + col.  gw / gw_max: patches per grid row of this batch / of the position table: patch p takes position row
+ *   1 + (p / gw) * gw_max + p % gw (width buckets); <= 0 means the table is the batch's own.
+ * kzv_embed_assemble_bwd: dpatch bf16 [B, np, He] = the masked dx0 rows of the patches; dcls [He], dpos [table rows, He] and
+ *   dpatch_bias [He] are accumulated into (+=) in a fixed summation order (bit-reproducible). */
+int kzv_embed_assemble(const float* patch_emb, const float* cls, const float* pos, float* x0, int B, int np, int He,
+                       float drop_p, uint32_t drop_key, int gw, int gw_max, void* stream);
+int kzv_embed_assemble_bwd(const float* dx0, void* dpatch_bf16, float* dcls, float* dpos, float* dpatch_bias, int B, int np, int He,
+                           float drop_p, uint32_t drop_key, int gw, int gw_max, void* stream);
+/* Backward of "dropout(linear(x))": out bf16 [M, N] = g fp32 [M, N] * mask (index row * N + col) [* gelu_pre bf16 [M, N], the GELU
+ *   derivative a forward epilogue saved; NULL = none]; dbias [N] += column sums of the ROUNDED out (float atomics).  N % 4 == 0.
+ * kzv_colsum_bf16: dbias [N] += column sums of g bf16 [M, N] with row stride ld (N, ld % 4 == 0). */
+int kzv_cast_drop_colsum(const float* g, void* out_bf16, float* dbias, int M, int N, float drop_p, uint32_t drop_key,
+                         const void* gelu_pre_bf16, void* stream);
+int kzv_colsum_bf16(const void* g_bf16, int64_t ld, float* dbias, int M, int N, void* stream);
+/* RobertaEmbeddings (HF modeling_roberta.py:75-155) over labels int64 [B, L], decoder inputs = columns 0 .. T - 1 (T < L):
+ *   kzv_dec_prepare: posids int32 [B, T] = cumsum(id != pad) * (id != pad) + pad; *count += targets labels[:, 1 : T + 1] != pad;
+ *     ids >= max_pos are clamped to max_pos - 1 and *err is set to 1 (never cleared here).
+ *   kzv_embed_gather: out fp32 [B * T, Hd] = (word[id] + type0) + postab[posid].
+ *   kzv_embed_scatter_bwd: dword[id] += dsum row, dpostab[posid] += dsum row (not for the pad row of either table), dtype0 += every
+ *     row (float atomics). */
+int kzv_dec_prepare(const int64_t* labels, int B, int L, int T, int pad, int max_pos, int32_t* posids, float* count, int32_t* err, void* stream);
+int kzv_embed_gather(const int64_t* labels, int L, const int32_t* posids, const float* word, const float* type0, const float* postab,
+                     float* out, int B, int T, int Hd, void* stream);
+int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int32_t* posids, float* dword, float* dtype0,
+                          float* dpostab, int B, int T, int Hd, int pad, void* stream);
+/* nn.CrossEntropyLoss(ignore_index = pad) (trocr_model.py:256,292) on fp32 logits [B * T, ldl] (ldl % 4 == 0, V <= ldl): row b * T + t
+ *   scores labels[b][t + 1]; *loss += mean over the *count scored rows; dlogits bf16 [B * T, ldl] or NULL = (softmax - onehot) /
+ *   count, zero in pad-target rows and in columns [V, ldl).  Rows up to 5,120 columns stay in registers; wider ones take three passes.
+ * kzv_copy_logits: out fp32 [rows, V] = logits[row * ldl + col] (drops the padding columns; ldl may also skip rows). */
+int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
+                   const float* count, float* loss, void* dlogits_bf16, void* stream);
+int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream);
+/* fp32 masters -> bf16 compute copies, n matrices in one launch (what kzv_model_sync_weights does for the whole table): dst bf16
+ *   [rows, cols], dstT bf16 [cols, ldT] = the transpose, or NULL.  `descs` is a HOST array of device pointers; cols % 4 == 0, and
+ *   with dstT rows % 4 == 0, ldT % 4 == 0, ldT >= rows.  Uploads the table, launches and waits for `stream`. */
+typedef struct kzv_cast_desc {
+    const float* src; void* dst; void* dstT;
+    int32_t rows, cols; int64_t ldT;
+} kzv_cast_desc;
+int kzv_cast_weights(const kzv_cast_desc* descs, int n, void* stream);
 
 /* Multi-head attention, one workgroup per (batch, head) on bf16 MFMA kernels for head_dim 64 (the benchmark geometry and the
  * decoder; attention.hip) and for head_dim 96 in mode 0 with Sq, Sk <= 288 (the reference's CLI default ViT, 768 / 8 heads on

@@ -10,6 +10,7 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "kzv_kernels.h"
+#include <vector>
 
 namespace {
 
@@ -600,4 +601,75 @@ extern "C" int kzv_debug_dropout_mask(uint32_t key, float p, int64_t rows, int64
     unsigned thr; float ik; kzv_drop_params(p, &thr, &ik);
     hipLaunchKernelGGL(dropout_mask_kernel, dim3(nblk(rows * cols, 256)), dim3(256), 0, (hipStream_t)stream, d_out, rows, cols, ld_index, thr, ik, key);
     return kzv_check_launch("debug_dropout_mask");
+}
+
+// ------------------------------------------------------------------- per-op C ABI (include/kzv.h, unit parity tests)
+// Each forwards to the launcher of the same name above (C++ linkage, hipStream_t), which does the validation.
+extern "C" int kzv_im2row(const float* px, void* out_bf16, int B, int C, int H, int W, int ph, int pw, void* stream) {
+    return kzv_im2row(px, (bf16_t*)out_bf16, B, C, H, W, ph, pw, (hipStream_t)stream);
+}
+
+extern "C" int kzv_embed_assemble(const float* patch_emb, const float* cls, const float* pos, float* x0, int B, int np, int He,
+                                  float drop_p, uint32_t drop_key, int gw, int gw_max, void* stream) {
+    return kzv_embed_assemble(patch_emb, cls, pos, x0, B, np, He, drop_p, drop_key, (hipStream_t)stream, gw, gw_max);
+}
+
+extern "C" int kzv_embed_assemble_bwd(const float* dx0, void* dpatch_bf16, float* dcls, float* dpos, float* dpatch_bias, int B, int np, int He,
+                                      float drop_p, uint32_t drop_key, int gw, int gw_max, void* stream) {
+    return kzv_embed_assemble_bwd(dx0, (bf16_t*)dpatch_bf16, dcls, dpos, dpatch_bias, B, np, He, drop_p, drop_key, (hipStream_t)stream, gw, gw_max);
+}
+
+extern "C" int kzv_cast_drop_colsum(const float* g, void* out_bf16, float* dbias, int M, int N, float drop_p, uint32_t drop_key,
+                                    const void* gelu_pre_bf16, void* stream) {
+    return kzv_cast_drop_colsum(g, (bf16_t*)out_bf16, dbias, M, N, drop_p, drop_key, (hipStream_t)stream, (const bf16_t*)gelu_pre_bf16);
+}
+
+extern "C" int kzv_colsum_bf16(const void* g_bf16, int64_t ld, float* dbias, int M, int N, void* stream) {
+    return kzv_colsum_bf16((const bf16_t*)g_bf16, ld, dbias, M, N, (hipStream_t)stream);
+}
+
+extern "C" int kzv_dec_prepare(const int64_t* labels, int B, int L, int T, int pad, int max_pos, int32_t* posids, float* count, int32_t* err,
+                               void* stream) {
+    return kzv_dec_prepare(labels, B, L, T, pad, max_pos, posids, count, err, (hipStream_t)stream);
+}
+
+extern "C" int kzv_embed_gather(const int64_t* labels, int L, const int32_t* posids, const float* word, const float* type0, const float* postab,
+                                float* out, int B, int T, int Hd, void* stream) {
+    return kzv_embed_gather(labels, L, posids, word, type0, postab, out, B, T, Hd, (hipStream_t)stream);
+}
+
+extern "C" int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int32_t* posids, float* dword, float* dtype0,
+                                     float* dpostab, int B, int T, int Hd, int pad, void* stream) {
+    return kzv_embed_scatter_bwd(dsum, labels, L, posids, dword, dtype0, dpostab, B, T, Hd, pad, (hipStream_t)stream);
+}
+
+extern "C" int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
+                              const float* count, float* loss, void* dlogits_bf16, void* stream) {
+    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, (hipStream_t)stream);
+}
+
+extern "C" int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream) {
+    return kzv_copy_logits(logits, ldl, out, rows, V, (hipStream_t)stream);
+}
+
+// n HOST descriptors -> the tile-indexed device table of kzv_model_sync_weights (model.cpp take_w16), one launch
+extern "C" int kzv_cast_weights(const kzv_cast_desc* descs, int n, void* stream) {
+    if (!descs || n <= 0) return kzv_fail(KZV_E_ARG, "cast_weights: empty table");
+    std::vector<KzvCastDesc> h((size_t)n);
+    int tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const kzv_cast_desc& d = descs[i];
+        if (!d.src || !d.dst || d.rows <= 0 || d.cols <= 0 || d.cols % 4) return kzv_fail(KZV_E_ARG, "cast_weights: matrix %d: null/empty or cols %% 4", i);
+        if (d.dstT && (d.rows % 4 || d.ldT % 4 || d.ldT < d.rows)) return kzv_fail(KZV_E_ARG, "cast_weights: matrix %d: the transposed copy needs rows %% 4 == 0 and ldT %% 4 == 0, ldT >= rows", i);
+        h[i] = KzvCastDesc{d.src, (bf16_t*)d.dst, (bf16_t*)d.dstT, d.rows, d.cols, d.ldT, tiles, (d.cols + 63) / 64};
+        tiles += ((d.rows + 63) / 64) * h[i].tiles_c;
+    }
+    KzvCastDesc* d_desc = nullptr;
+    const size_t bytes = h.size() * sizeof(KzvCastDesc);
+    if (hipMalloc((void**)&d_desc, bytes) != hipSuccess) return kzv_fail(KZV_E_HIP, "cast_weights: table (%zu bytes)", bytes);
+    int rc = hipMemcpy(d_desc, h.data(), bytes, hipMemcpyHostToDevice) == hipSuccess ? KZV_OK : kzv_fail(KZV_E_HIP, "cast_weights: table upload");
+    if (rc == KZV_OK) rc = kzv_cast_weights(d_desc, n, tiles, (hipStream_t)stream);
+    if (rc == KZV_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = kzv_fail(KZV_E_HIP, "cast_weights: synchronize");
+    (void)hipFree(d_desc);
+    return rc;
 }

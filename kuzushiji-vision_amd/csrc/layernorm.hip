@@ -506,3 +506,16 @@ extern "C" int kzv_layernorm_bwd(const void* dy, int dy_is_f32, const float* x, 
                                  float* dx, int accumulate_dx, float* dgamma, float* dbeta, int rows, int H, void* stream) {
     return kzv_ln_bwd_ex(dy, dy_is_f32, x, stats, gamma, dx, accumulate_dx, dgamma, dbeta, rows, H, 1, 0, 0.f, 0, (hipStream_t)stream);
 }
+
+extern "C" int kzv_ln_fwd_ex(const kzv_ln_fwd_args* a, void* stream) {
+    if (!a) return kzv_fail(KZV_E_ARG, "ln_fwd_ex: null arguments");
+    return kzv_ln_fwd_ex(a->x, a->gamma, a->beta, a->y_bf16, a->y_f32, a->stats, a->rows, a->H, a->eps, a->seq, a->drop_first,
+                         a->drop_p, a->drop_key, (hipStream_t)stream);
+}
+
+extern "C" int kzv_ln_bwd_ex(const kzv_ln_bwd_args* a, void* stream) {
+    if (!a) return kzv_fail(KZV_E_ARG, "ln_bwd_ex: null arguments");
+    return kzv_ln_bwd_ex(a->dy, a->dy_is_f32, a->x, a->stats, a->gamma, a->dx, a->accumulate_dx, a->dgamma, a->dbeta, a->rows, a->H,
+                         a->seq, a->drop_first, a->drop_p, a->drop_key, (hipStream_t)stream, (bf16_t*)a->out16, a->out_drop_p,
+                         a->out_drop_key);
+}

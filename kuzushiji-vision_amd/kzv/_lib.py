@@ -84,6 +84,25 @@ class kzv_attn_probs_args(C.Structure):
                 ("head_dim", C.c_int32), ("mode", C.c_int32)]
 
 
+class kzv_ln_fwd_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y_bf16", C.c_void_p), ("y_f32", C.c_void_p),
+                ("stats", C.c_void_p), ("rows", C.c_int32), ("H", C.c_int32), ("seq", C.c_int32), ("drop_first", C.c_int32),
+                ("eps", C.c_float), ("drop_p", C.c_float), ("drop_key", C.c_uint32)]
+
+
+class kzv_ln_bwd_args(C.Structure):
+    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("stats", C.c_void_p), ("gamma", C.c_void_p),
+                ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("out16", C.c_void_p),
+                ("dy_is_f32", C.c_int32), ("accumulate_dx", C.c_int32), ("rows", C.c_int32), ("H", C.c_int32),
+                ("seq", C.c_int32), ("drop_first", C.c_int32),
+                ("drop_p", C.c_float), ("drop_key", C.c_uint32), ("out_drop_p", C.c_float), ("out_drop_key", C.c_uint32)]
+
+
+class kzv_cast_desc(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("dstT", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("ldT", C.c_int64)]
+
+
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU = range(5)
 ATTN_MFMA64, ATTN_MFMA96, ATTN_VALU = 1, 2, 3          # kzv_attn_impl
 ATTN_STREAM64, ATTN_STREAM96 = 4, 5                    # kzv_attn_impl_ex with MODEL_LONG_SEQ
@@ -142,6 +161,19 @@ SYMBOLS = {
     "kzv_gemm_tn": (C.c_int, [C.POINTER(kzv_gemm_tn_args), _P]),
     "kzv_layernorm_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "kzv_layernorm_bwd": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "kzv_ln_fwd_ex": (C.c_int, [C.POINTER(kzv_ln_fwd_args), _P]),
+    "kzv_ln_bwd_ex": (C.c_int, [C.POINTER(kzv_ln_bwd_args), _P]),
+    "kzv_im2row": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "kzv_embed_assemble": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_int, C.c_int, _P]),
+    "kzv_embed_assemble_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_int, C.c_int, _P]),
+    "kzv_cast_drop_colsum": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_uint32, _P, _P]),
+    "kzv_colsum_bf16": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P]),
+    "kzv_dec_prepare": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P, _P]),
+    "kzv_embed_gather": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "kzv_embed_scatter_bwd": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "kzv_ce_fwd_bwd": (C.c_int, [_P, C.c_int64, _P] + [C.c_int] * 5 + [_P, _P, _P, _P]),
+    "kzv_copy_logits": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P]),
+    "kzv_cast_weights": (C.c_int, [C.POINTER(kzv_cast_desc), C.c_int, _P]),
     "kzv_attn_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_bwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
     "kzv_attn_impl": (C.c_int, [C.POINTER(kzv_attn_args), C.c_int]),

@@ -3,8 +3,9 @@
   (a) the clip + RAdamScheduleFree kernels (csrc/optim.hip) against the oracle's fp64 restatement
       (scripts/train_trocr.py:175, src/models/trocr_model.py:412-451);
   (b) dropout ON: the masks every fused epilogue draws are fetched from the library (kzv_debug_dropout_mask) and replayed
-      through the oracle -- logits, loss and EVERY gradient must agree, which is the only thing that verifies the masks
-      regenerated in backward (LayerNorm backward, column sums, embedding backward, attention backward);
+      through the oracle -- logits, loss and EVERY gradient must agree: the whole-step check that the masks regenerated in
+      backward (LayerNorm backward, column sums, embedding backward, attention backward) are the forward's.  Each of those kernels
+      is pinned on its own, element by element, in tests/test_glue_ops_gpu.py (and tests/test_ops_gpu.py for attention);
   (c) a 10-step trajectory of the whole step (forward, backward, clip 1.0, optimizer) against the oracle.
 """
 import dataclasses
