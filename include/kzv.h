@@ -201,6 +201,28 @@ int kzv_set_decode_one_launch(int on);
  * per operation.  Answers for the bound rows, the images of the last kzv_encode_images / forward, the active image width and the
  * current kzv_set_decode_one_launch mode; launches nothing.  A negative error before kzv_model_bind. */
 int kzv_decode_step_impl(const kzv_model* m);
+/* Generation from e4m3 decoder weights (opt-in; the default is bf16).  With KZV_DECODE_WEIGHTS_E4M3 the one-launch step reads the
+ * eight linears it streams per decoder layer (self query | key | value, self output, cross query, cross output, fc1, fc2) and the LM
+ * head's dense layer as OCP e4m3 with one POWER-OF-TWO scale per output row -- s = the smallest 2^e with amax(row) / s <= 448,
+ * q = e4m3(w / s) rounded to nearest even from the bf16 weight -- widens them to bf16 in registers and runs the same bf16 MFMAs in
+ * the same order; activations, attention, LayerNorm, the KV cache, the cross key / value projection, the vocabulary GEMM, every
+ * bias and all of training are untouched.  q * s is a bf16 number and the scale commutes with every fp32 rounding, so the step's
+ * logits EQUAL, bit for bit, those of the bf16 one-launch step on a model whose nine weights were replaced by q * s
+ * (kzv/quant.py: dequantised_decoder_weights); how far that is from the original model is a property of the checkpoint.  Only the
+ * one-launch step has this path: wherever kzv_decode_step_impl answers 0 the step keeps reading bf16, silently.  The e4m3 copies
+ * (4.7 MB at 12 layers) are made by the first step after the format is chosen and after every kzv_model_sync_weights, in one
+ * launch.  Any time after kzv_model_create; a format other than the two is KZV_E_ARG. */
+#define KZV_DECODE_WEIGHTS_BF16 0
+#define KZV_DECODE_WEIGHTS_E4M3 1
+int kzv_set_decode_weights(kzv_model* m, int format);
+int kzv_get_decode_weights(const kzv_model* m);      /* the format asked for; a negative error for a null handle */
+/* What the next kzv_decode_step / kzv_decode_step_graph on this handle will actually read: KZV_DECODE_WEIGHTS_E4M3 only where the
+ * format was asked for AND kzv_decode_step_impl answers 1.  Launches nothing; a negative error before kzv_model_bind. */
+int kzv_decode_weights_impl(const kzv_model* m);
+/* The quantiser by itself (per-op tests): w_bf16 [N, K] row-major bf16 on the device (N % 16 == 0, K % 64 == 0) -> q_out [N, K]
+ * row-major e4m3 bytes and scale_out [N] fp32, by the recipe above; an all-zero row keeps scale 1, a row whose amax lies below
+ * 2^-118 scale 2^-126.  (The generation step keeps its own copy in the order its waves consume it; that layout is internal.) */
+int kzv_quant_pack_e4m3(const void* w_bf16, int N, int K, void* q_out, float* scale_out, void* stream);
 /* Training / evaluation forward: the linear chains of a decoder layer -- [output projection + dropout + residual -> LayerNorm ->
  * cross query] and [output projection -> LayerNorm -> fc1 + GELU -> fc2 -> LayerNorm -> the next layer's QKV] -- as TWO launches
  * per layer (csrc/decoder_chain.hip; hidden 256, 4 heads, FFN 768) instead of nine.  0: one launch per operation; 1: the forward

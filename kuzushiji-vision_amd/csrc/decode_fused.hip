@@ -153,6 +153,66 @@ __device__ __forceinline__ void rows_gemm(bf16x8 (&R)[NR], const char* wb, const
     }
 }
 
+// ---- the same stream as OCP e4m3 (kzv_set_decode_weights) -------------------------------------------------------------------------
+// Half the bytes per weight, the same 96 KiB in flight: a window slot is a 64-DEEP fragment -- the lane's 8 bytes of k-step 2 j, then
+// its 8 bytes of k-step 2 j + 1 -- and wave w's fragments of ALL linears lie in the order it consumes them, as one contiguous stream
+// (quant_pack8_kernel): per layer QKV half 0 | half 1 | O | CQ | CO | FC1 half 0 | half 1 | FC2 (S8_LAYER fragments), then the head's
+// dense layer, then WIN8 fragments of zeros.  So a refill is `slot = stream[position + WIN8]`, whatever GEMM that position belongs to:
+// no pointer to a next GEMM, no condition, and no load past the allocation.  Widened to bf16 in registers (both conversions exact),
+// a fragment feeds the same two MFMAs in the same order as rows_gemm's, so with W = q * 2^e per output row the accumulators are
+// 2^-e times the bf16 step's, bit for bit, and the epilogue's acc * 2^e + bias restores them.
+#ifndef KZV_DF_WIN8
+#define KZV_DF_WIN8 24                             // e4m3 fragments (1 KiB per wave each) in flight per linear wave; 32 also builds spill-free: DESIGN.md section 7, N1 has both timed
+#endif
+constexpr int WIN8 = KZV_DF_WIN8;                  // the e4m3 stream's window only: the bf16 stream keeps WIN
+constexpr int S8_QKV = 0, S8_O = 48, S8_CQ = 64, S8_CO = 80, S8_FC1 = 96, S8_FC2 = 144, S8_LAYER = 192, S8_HEAD = 16;
+constexpr int SCL = 2560;            // a layer's row scales in LDS, in the order of its biases (PB_*); the head's take [0, 256)
+static_assert(S8_LAYER % WIN8 == 0, "a layer's e4m3 fragments must fill the window a whole number of times");
+__device__ __forceinline__ bf16x8 widen8(unsigned lo, unsigned hi) {
+    // v_cvt_pk_f32_fp8 (the low, then the high byte pair of a dword), v_cvt_pk_bf16_f32: 8 conversions per 8 weights
+    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+    const f2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+    const u32x4_t r = {pack_bf2(a[0], a[1]), pack_bf2(b[0], b[1]), pack_bf2(c[0], c[1]), pack_bf2(d[0], d[1])};
+    return __builtin_bit_cast(bf16x8, r);
+}
+__device__ __forceinline__ void fill_window8(bf16x8 (&R)[NR], const char* sb, int lane) {
+    const unsigned wo = (unsigned)lane * 16u;
+#pragma unroll
+    for (int i = 0; i < WIN8; ++i) R[i] = *(const bf16x8*)(sb + i * 1024 + wo);
+}
+// sb = the wave's stream at this layer's first fragment; POS = this GEMM's first fragment in the layer (and, mod WIN8, its window slot);
+// KS counts 32-deep k-steps as rows_gemm's does
+template <int CB, int KS, int POS, int G>
+__device__ __forceinline__ void rows_gemm8(bf16x8 (&R)[NR], const char* sb, const bf16_t* a_lds, int lda, int lane, f32x4 (&acc)[CB]) {
+    constexpr int F = CB * KS / 2;
+    static_assert(KS % 2 == 0 && WIN8 <= NR, "rows_gemm8: window");
+    const int l15 = lane & 15, g = lane >> 4;
+    const unsigned wo = (unsigned)lane * 16u;
+    const bf16_t* ap = a_lds + min(l15, G - 1) * lda + g * 8;
+#pragma unroll
+    for (int c = 0; c < CB; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bf16x8 fa0, fa1;
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        const int ks2 = i / CB, c = i % CB, slot = (POS + i) % WIN8;
+        if (c == 0) { fa0 = *(const bf16x8*)(ap + ks2 * 64); fa1 = *(const bf16x8*)(ap + ks2 * 64 + 32); }
+        const u32x4_t q = __builtin_bit_cast(u32x4_t, R[slot]);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(widen8(q[0], q[1]), fa0, acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(widen8(q[2], q[3]), fa1, acc[c], 0, 0, 0);
+        R[slot] = *(const bf16x8*)(sb + (POS + i + WIN8) * 1024 + wo);
+        __builtin_amdgcn_sched_barrier(0);      // the refill stays behind ITS MFMAs: left to itself hipcc gathers a GEMM's refills at its end and the window drains
+    }
+}
+// the epilogues' "accumulator + bias": with row scales, accumulator * scale + bias (a power of two: fused or not, the same bits)
+template <bool F8> __device__ __forceinline__ float4 scale4(const float* scl, int at) {
+    if constexpr (F8) return *(const float4*)(scl + at);
+    else return make_float4(1.f, 1.f, 1.f, 1.f);
+}
+template <bool F8> __device__ __forceinline__ float sb_add(float acc, float s, float b) {
+    if constexpr (F8) return fmaf(acc, s, b);
+    else return acc + b;
+}
+
 // W [N, K] row-major -> fragment order (see rows_gemm); one thread per 16-byte piece
 __global__ void pack_frag_kernel(const uint4* __restrict__ W, uint4* __restrict__ out, int N, int K) {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -160,6 +220,53 @@ __global__ void pack_frag_kernel(const uint4* __restrict__ W, uint4* __restrict_
     const int lane = t & 63, f = t >> 6, KS = K / 32;
     const int nb = f / KS, ks = f - nb * KS;
     out[t] = W[((int64_t)(nb * 16 + (lane & 15)) * K + ks * 32 + (lane >> 4) * 8) / 8];
+}
+
+// ---- quantise-and-pack: bf16 [N, K] -> OCP e4m3 with one power-of-two scale per output row, one launch over a table of matrices ------
+// Per row: s = 2^e, the smallest power of two with amax / s <= 448 (the exponent from amax's bits: 448 = 1.75 * 2^8, so e is amax's
+// exponent - 8, or - 7 where its fraction exceeds 1.75), clamped to the normal range; an all-zero row keeps s = 1; q = e4m3(w / s),
+// round-to-nearest-even (pack_fp8x4).  q * s is a bf16 number: 3 mantissa bits.  One wave per row, 4 weights per lane and pass.
+// cb == 0: the bytes stay row-major [N, K] (the per-op entry).  cb = 4 or 6: the decode stream of rows_gemm8 -- 16-row block nb belongs
+// to wave nb % 4 as its column block nb / 4 = half * cb + c, and its 64-deep fragment ks2 is fragment pos + half * F + ks2 * cb + c
+// of that wave's stream (F = cb * K / 64 fragments per half).
+struct Quant8Desc { const bf16_t* src; int N, K, row0, scale_at, cb, pos; };
+constexpr int Q8_MAX_JOBS = 8 * KZV_DECODE_FUSED_MAX_LAYERS + 1;       // 32-byte descriptors in the kernel argument block (4 KiB limit)
+struct Quant8Table { Quant8Desc d[Q8_MAX_JOBS]; int n, rows, pad_pos; unsigned char* dst; float* scales; int64_t wave_bytes; };
+__global__ __launch_bounds__(256) void quant_pack8_kernel(const Quant8Table tab) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= tab.rows) {       // the blocks behind the last row: the WIN8 zero fragments that end each wave's stream
+        const int t = (blockIdx.x - tab.rows / 4) * 256 + threadIdx.x;
+        if (tab.pad_pos >= 0 && t < 4 * WIN8 * 64)
+            *(uint4*)(tab.dst + (int64_t)(t / (WIN8 * 64)) * tab.wave_bytes + ((int64_t)tab.pad_pos * 64 + t % (WIN8 * 64)) * 16) = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    int lo = 0, hi = tab.n - 1;                  // the last job with row0 <= row
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab.d[mid].row0 <= row) lo = mid; else hi = mid - 1; }
+    const Quant8Desc& d = tab.d[lo];
+    const int n = row - d.row0, K = d.K;
+    const bf16_t* src = d.src + (int64_t)n * K;
+    float amax = 0.f;
+    for (int k = lane * 4; k < K; k += 256) {
+        const uint2 v = *(const uint2*)(src + k);
+        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(bf2f((bf16_t)(v.x & 0xffffu))), fabsf(bf2f((bf16_t)(v.x >> 16))))),
+                     fmaxf(fabsf(bf2f((bf16_t)(v.y & 0xffffu))), fabsf(bf2f((bf16_t)(v.y >> 16)))));
+    }
+    amax = wave_max(amax);
+    const unsigned ab = __builtin_bit_cast(unsigned, amax);
+    int e = (int)(ab >> 23) - 127 - ((ab & 0x7fffffu) > 0x600000u ? 7 : 8);
+    e = amax == 0.f ? 0 : min(max(e, -126), 126);
+    const float s = __builtin_bit_cast(float, (unsigned)(e + 127) << 23), inv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+    if (lane == 0) tab.scales[d.scale_at + n] = s;
+    const int nb = n >> 4, cbg = nb >> 2, cb = d.cb;
+    const int64_t frag0 = cb ? (int64_t)d.pos + (cbg / cb) * (cb * (K >> 6)) + cbg % cb : 0;
+    unsigned char* out = cb ? tab.dst + (int64_t)(nb & 3) * tab.wave_bytes + (n & 15) * 16 : tab.dst + (int64_t)d.pos + (int64_t)n * K;
+    for (int k = lane * 4; k < K; k += 256) {
+        const uint2 v = *(const uint2*)(src + k);
+        const unsigned q = pack_fp8x4(bf2f((bf16_t)(v.x & 0xffffu)) * inv, bf2f((bf16_t)(v.x >> 16)) * inv, bf2f((bf16_t)(v.y & 0xffffu)) * inv, bf2f((bf16_t)(v.y >> 16)) * inv);
+        // in a fragment: lane (n & 15) + 16 * ((k & 31) / 8), byte 8 * ((k & 63) / 32) + (k & 7)
+        if (cb) *(unsigned*)(out + (frag0 + (int64_t)(k >> 6) * cb) * 1024 + ((k & 31) >> 3) * 256 + ((k & 63) >> 5) * 8 + (k & 7)) = q;
+        else *(unsigned*)(out + k) = q;
+    }
 }
 
 // LayerNorm of one row (fp32, LDS) by one wave: the normalised row goes to xs (fp32) and ab (bf16); gamma / beta from LDS
@@ -192,6 +299,12 @@ struct FusedP {
     int* rows;                                                  // beam row table [B][T] or null
     float eps;
 };
+struct FusedP8 : FusedP {                                       // the e4m3 instances' arguments (the bf16 instances keep FusedP as it was)
+    const char* w8; int64_t wave8;                              // the four waves' fragment streams, wave8 bytes each
+    const float* sc8;                                           // row scales [layer][SCL], then the head's 256
+};
+template <bool F8> struct FusedArgs { typedef FusedP type; };
+template <> struct FusedArgs<true> { typedef FusedP8 type; };
 
 // ---- the attention streams (waves 4-7, head h each) ------------------------------------------------------------------------------
 // lane = (row r = lane >> 3 of an 8-key group, 16-byte piece c = lane & 7); iteration i holds key 8 i + r.
@@ -408,10 +521,22 @@ __device__ __forceinline__ void params_load(float* par, const FusedLayer& L, int
     for (int k = 0; k < 12; ++k) if (t256 < n4[k]) *(float4*)(par + dst[k] + t256 * 4) = v[k];
 }
 
+// a layer's row scales (e4m3 instances) -> LDS, likewise; n4 = SCL / 4, or 64 for the head's dense layer
+__device__ __forceinline__ void scales_load(float* scl, const float* src, int n4, int t256_) {
+    const int t256 = opaque(t256_);
+    float4 v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = ((const float4*)src)[min(t256 + 256 * k, n4 - 1)];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) if (t256 + 256 * k < n4) *(float4*)(scl + (t256 + 256 * k) * 4) = v[k];
+}
+
 // ---- the two roles: each runs its own layer loop; the barrier sequences match (1 + 11 per layer) -------------------------------
-template <int G>
-__device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, int lane0, int b0) {
+template <int G, bool F8>       // F8: the weights come from the e4m3 stream (rows_gemm8), scl = the row scales the attention waves put in LDS
+__device__ __forceinline__ void linear_role(Lds<G>& sm, float (*scl)[SCL], const typename FusedArgs<F8>::type& p, int w, int lane0, int b0) {
     bf16x8 R[NR];                                     // only R[0 .. WIN) is used here: the weight window
+    const char* sb = nullptr;                         // the wave's e4m3 stream at the current layer
+    if constexpr (F8) sb = p.w8 + (int64_t)w * p.wave8;
     {
         // embeddings: x0 = LN(word[token] + type[0] + position[posid]) (modeling_roberta.py:75-122); requested BEFORE the window
         const int lane = opaque(lane0);
@@ -423,7 +548,8 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
             pv = *(const float4*)(p.postab + (int64_t)pid * HD + lane * 4);
             ga = *(const float4*)(p.elnw + lane * 4); be = *(const float4*)(p.elnb + lane * 4);
         }
-        fill_window<6, 8>(R, wave_frags<6, 8>(p.L[0].wqkv, w), lane);
+        if constexpr (F8) fill_window8(R, sb, lane);
+        else fill_window<6, 8>(R, wave_frags<6, 8>(p.L[0].wqkv, w), lane);
         if (w < G) {
             const float4 v = make_float4(wv.x + ty.x + pv.x, wv.y + ty.y + pv.y, wv.z + ty.z + pv.z, wv.w + ty.w + pv.w);
             const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.f / HD);
@@ -439,20 +565,23 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
     for (int li = 0; li < p.nlayers; ++li) {
         const FusedLayer& L = p.L[li];
         const float* par = sm.par[li & 1];
+        const float* sc = F8 ? scl[li & 1] : nullptr;
         DF_STAMP_L(0);
         {   // q | k | v = x Wqkv^T + b, in two column halves (24 accumulator registers instead of 48: the window gets them)
             const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 f32x4 acc[6];
-                if (half == 0) rows_gemm<6, 8, 6, 8, 0, G>(R, wave_frags<6, 8>(L.wqkv, w), wave_frags<6, 8>(L.wqkv, w + 24), &sm.ab[0][0], LDH, lane, acc);
+                if constexpr (F8) { if (half == 0) rows_gemm8<6, 8, S8_QKV, G>(R, sb, &sm.ab[0][0], LDH, lane, acc); else rows_gemm8<6, 8, S8_QKV + 24, G>(R, sb, &sm.ab[0][0], LDH, lane, acc); }
+                else if (half == 0) rows_gemm<6, 8, 6, 8, 0, G>(R, wave_frags<6, 8>(L.wqkv, w), wave_frags<6, 8>(L.wqkv, w + 24), &sm.ab[0][0], LDH, lane, acc);
                 else rows_gemm<6, 8, 4, 8, 48 % WIN, G>(R, wave_frags<6, 8>(L.wqkv, w + 24), wave_frags<4, 8>(L.wo, w), &sm.ab[0][0], LDH, lane, acc);
                 if (l15 < G) {
 #pragma unroll
                     for (int cb = 0; cb < 6; ++cb) {
                         const int n = (w + 4 * (cb + 6 * half)) * 16 + 4 * g4;
-                        const float4 bb = *(const float4*)(par + PB_QKV + n);
-                        *(uint2*)(&sm.wide[l15][n]) = make_uint2(pack_bf2(acc[cb][0] + bb.x, acc[cb][1] + bb.y), pack_bf2(acc[cb][2] + bb.z, acc[cb][3] + bb.w));
+                        const float4 bb = *(const float4*)(par + PB_QKV + n), s4 = scale4<F8>(sc, PB_QKV + n);
+                        *(uint2*)(&sm.wide[l15][n]) = make_uint2(pack_bf2(sb_add<F8>(acc[cb][0], s4.x, bb.x), sb_add<F8>(acc[cb][1], s4.y, bb.y)),
+                                                                 pack_bf2(sb_add<F8>(acc[cb][2], s4.z, bb.z), sb_add<F8>(acc[cb][3], s4.w, bb.w)));
                     }
                 }
             }
@@ -464,13 +593,15 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
         {   // s1 = ctx Wo^T + b + x
             const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
             f32x4 acc[4];
-            rows_gemm<4, 8, 4, 8, (12 * 8) % WIN, G>(R, wave_frags<4, 8>(L.wo, w), wave_frags<4, 8>(L.wcq, w), &sm.ctx[0][0], LDH, lane, acc);
+            if constexpr (F8) rows_gemm8<4, 8, S8_O, G>(R, sb, &sm.ctx[0][0], LDH, lane, acc);
+            else rows_gemm<4, 8, 4, 8, (12 * 8) % WIN, G>(R, wave_frags<4, 8>(L.wo, w), wave_frags<4, 8>(L.wcq, w), &sm.ctx[0][0], LDH, lane, acc);
             if (l15 < G) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const int n = (w + 4 * cb) * 16 + 4 * g4;
-                    const float4 bb = *(const float4*)(par + PB_O + n), x4 = *(const float4*)(&sm.xs[l15][n]);
-                    *(float4*)(&sm.ss[l15][n]) = make_float4(acc[cb][0] + bb.x + x4.x, acc[cb][1] + bb.y + x4.y, acc[cb][2] + bb.z + x4.z, acc[cb][3] + bb.w + x4.w);
+                    const float4 bb = *(const float4*)(par + PB_O + n), x4 = *(const float4*)(&sm.xs[l15][n]), s4 = scale4<F8>(sc, PB_O + n);
+                    *(float4*)(&sm.ss[l15][n]) = make_float4(sb_add<F8>(acc[cb][0], s4.x, bb.x) + x4.x, sb_add<F8>(acc[cb][1], s4.y, bb.y) + x4.y,
+                                                             sb_add<F8>(acc[cb][2], s4.z, bb.z) + x4.z, sb_add<F8>(acc[cb][3], s4.w, bb.w) + x4.w);
                 }
             }
         }
@@ -482,13 +613,15 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
         {   // cross query
             const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
             f32x4 acc[4];
-            rows_gemm<4, 8, 4, 8, (12 * 8 + 32) % WIN, G>(R, wave_frags<4, 8>(L.wcq, w), wave_frags<4, 8>(L.wco, w), &sm.ab[0][0], LDH, lane, acc);
+            if constexpr (F8) rows_gemm8<4, 8, S8_CQ, G>(R, sb, &sm.ab[0][0], LDH, lane, acc);
+            else rows_gemm<4, 8, 4, 8, (12 * 8 + 32) % WIN, G>(R, wave_frags<4, 8>(L.wcq, w), wave_frags<4, 8>(L.wco, w), &sm.ab[0][0], LDH, lane, acc);
             if (l15 < G) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const int n = (w + 4 * cb) * 16 + 4 * g4;
-                    const float4 bb = *(const float4*)(par + PB_CQ + n);
-                    *(uint2*)(&sm.wide[l15][n]) = make_uint2(pack_bf2(acc[cb][0] + bb.x, acc[cb][1] + bb.y), pack_bf2(acc[cb][2] + bb.z, acc[cb][3] + bb.w));
+                    const float4 bb = *(const float4*)(par + PB_CQ + n), s4 = scale4<F8>(sc, PB_CQ + n);
+                    *(uint2*)(&sm.wide[l15][n]) = make_uint2(pack_bf2(sb_add<F8>(acc[cb][0], s4.x, bb.x), sb_add<F8>(acc[cb][1], s4.y, bb.y)),
+                                                             pack_bf2(sb_add<F8>(acc[cb][2], s4.z, bb.z), sb_add<F8>(acc[cb][3], s4.w, bb.w)));
                 }
             }
         }
@@ -499,13 +632,15 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
         {   // s2 = cctx Wco^T + b + x
             const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
             f32x4 acc[4];
-            rows_gemm<4, 8, 6, 8, (12 * 8 + 64) % WIN, G>(R, wave_frags<4, 8>(L.wco, w), wave_frags<6, 8>(L.wfc1, w), &sm.ctx[0][0], LDH, lane, acc);
+            if constexpr (F8) rows_gemm8<4, 8, S8_CO, G>(R, sb, &sm.ctx[0][0], LDH, lane, acc);
+            else rows_gemm<4, 8, 6, 8, (12 * 8 + 64) % WIN, G>(R, wave_frags<4, 8>(L.wco, w), wave_frags<6, 8>(L.wfc1, w), &sm.ctx[0][0], LDH, lane, acc);
             if (l15 < G) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const int n = (w + 4 * cb) * 16 + 4 * g4;
-                    const float4 bb = *(const float4*)(par + PB_CO + n), x4 = *(const float4*)(&sm.xs[l15][n]);
-                    *(float4*)(&sm.ss[l15][n]) = make_float4(acc[cb][0] + bb.x + x4.x, acc[cb][1] + bb.y + x4.y, acc[cb][2] + bb.z + x4.z, acc[cb][3] + bb.w + x4.w);
+                    const float4 bb = *(const float4*)(par + PB_CO + n), x4 = *(const float4*)(&sm.xs[l15][n]), s4 = scale4<F8>(sc, PB_CO + n);
+                    *(float4*)(&sm.ss[l15][n]) = make_float4(sb_add<F8>(acc[cb][0], s4.x, bb.x) + x4.x, sb_add<F8>(acc[cb][1], s4.y, bb.y) + x4.y,
+                                                             sb_add<F8>(acc[cb][2], s4.z, bb.z) + x4.z, sb_add<F8>(acc[cb][3], s4.w, bb.w) + x4.w);
                 }
             }
         }
@@ -519,16 +654,17 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 f32x4 acc[6];
-                if (half == 0) rows_gemm<6, 8, 6, 8, (96 + 96) % WIN, G>(R, wave_frags<6, 8>(L.wfc1, w), wave_frags<6, 8>(L.wfc1, w + 24), &sm.ab[0][0], LDH, lane, acc);
+                if constexpr (F8) { if (half == 0) rows_gemm8<6, 8, S8_FC1, G>(R, sb, &sm.ab[0][0], LDH, lane, acc); else rows_gemm8<6, 8, S8_FC1 + 24, G>(R, sb, &sm.ab[0][0], LDH, lane, acc); }
+                else if (half == 0) rows_gemm<6, 8, 6, 8, (96 + 96) % WIN, G>(R, wave_frags<6, 8>(L.wfc1, w), wave_frags<6, 8>(L.wfc1, w + 24), &sm.ab[0][0], LDH, lane, acc);
                 else rows_gemm<6, 8, 4, 24, (96 + 96 + 48) % WIN, G>(R, wave_frags<6, 8>(L.wfc1, w + 24), wave_frags<4, 24>(L.wfc2, w), &sm.ab[0][0], LDH, lane, acc);
                 if (l15 < G) {
 #pragma unroll
                     for (int cb = 0; cb < 6; ++cb) {
                         const int n = (w + 4 * (cb + 6 * half)) * 16 + 4 * g4;
-                        const float4 bb = *(const float4*)(par + PB_FC1 + n);
+                        const float4 bb = *(const float4*)(par + PB_FC1 + n), s4 = scale4<F8>(sc, PB_FC1 + n);
                         float y[4], d;
-                        gelu_erf_both(acc[cb][0] + bb.x, &y[0], &d); gelu_erf_both(acc[cb][1] + bb.y, &y[1], &d);
-                        gelu_erf_both(acc[cb][2] + bb.z, &y[2], &d); gelu_erf_both(acc[cb][3] + bb.w, &y[3], &d);
+                        gelu_erf_both(sb_add<F8>(acc[cb][0], s4.x, bb.x), &y[0], &d); gelu_erf_both(sb_add<F8>(acc[cb][1], s4.y, bb.y), &y[1], &d);
+                        gelu_erf_both(sb_add<F8>(acc[cb][2], s4.z, bb.z), &y[2], &d); gelu_erf_both(sb_add<F8>(acc[cb][3], s4.w, bb.w), &y[3], &d);
                         *(uint2*)(&sm.wide[l15][n]) = make_uint2(pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]));
                     }
                 }
@@ -539,14 +675,16 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
         {   // s3 = act Wfc2^T + b + x
             const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
             f32x4 acc[4];
-            if (li + 1 < p.nlayers) rows_gemm<4, 24, 6, 8, (12 * 8 + 96 + 96) % WIN, G>(R, wave_frags<4, 24>(L.wfc2, w), wave_frags<6, 8>(p.L[li + 1].wqkv, w), &sm.wide[0][0], LDW, lane, acc);
+            if constexpr (F8) { rows_gemm8<4, 24, S8_FC2, G>(R, sb, &sm.wide[0][0], LDW, lane, acc); sb += S8_LAYER * 1024; }
+            else if (li + 1 < p.nlayers) rows_gemm<4, 24, 6, 8, (12 * 8 + 96 + 96) % WIN, G>(R, wave_frags<4, 24>(L.wfc2, w), wave_frags<6, 8>(p.L[li + 1].wqkv, w), &sm.wide[0][0], LDW, lane, acc);
             else rows_gemm<4, 24, 4, 8, (12 * 8 + 96 + 96) % WIN, G>(R, wave_frags<4, 24>(L.wfc2, w), wave_frags<4, 8>(p.whd, w), &sm.wide[0][0], LDW, lane, acc);
             if (l15 < G) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const int n = (w + 4 * cb) * 16 + 4 * g4;
-                    const float4 bb = *(const float4*)(par + PB_FC2 + n), x4 = *(const float4*)(&sm.xs[l15][n]);
-                    *(float4*)(&sm.ss[l15][n]) = make_float4(acc[cb][0] + bb.x + x4.x, acc[cb][1] + bb.y + x4.y, acc[cb][2] + bb.z + x4.z, acc[cb][3] + bb.w + x4.w);
+                    const float4 bb = *(const float4*)(par + PB_FC2 + n), x4 = *(const float4*)(&sm.xs[l15][n]), s4 = scale4<F8>(sc, PB_FC2 + n);
+                    *(float4*)(&sm.ss[l15][n]) = make_float4(sb_add<F8>(acc[cb][0], s4.x, bb.x) + x4.x, sb_add<F8>(acc[cb][1], s4.y, bb.y) + x4.y,
+                                                             sb_add<F8>(acc[cb][2], s4.z, bb.z) + x4.z, sb_add<F8>(acc[cb][3], s4.w, bb.w) + x4.w);
                 }
             }
         }
@@ -560,16 +698,18 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
     {   // LM head, first half: gelu(x Wd^T + b) in fp32 (its LayerNorm and the vocabulary GEMM are the next launch)
         const int lane = opaque(lane0), l15 = lane & 15, g4 = lane >> 4;
         const float* par = sm.par[p.nlayers & 1];
+        const float* sc = F8 ? scl[p.nlayers & 1] : nullptr;
         f32x4 acc[4];
-        rows_gemm<4, 8, 4, 8, 0, G>(R, wave_frags<4, 8>(p.whd, w), nullptr, &sm.ab[0][0], LDH, lane, acc);
+        if constexpr (F8) rows_gemm8<4, 8, 0, G>(R, sb, &sm.ab[0][0], LDH, lane, acc);
+        else rows_gemm<4, 8, 4, 8, 0, G>(R, wave_frags<4, 8>(p.whd, w), nullptr, &sm.ab[0][0], LDH, lane, acc);
         if (l15 < G) {
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 const int n = (w + 4 * cb) * 16 + 4 * g4;
-                const float4 bb = *(const float4*)(par + n);
+                const float4 bb = *(const float4*)(par + n), s4 = scale4<F8>(sc, n);
                 float y[4], d;
-                gelu_erf_both(acc[cb][0] + bb.x, &y[0], &d); gelu_erf_both(acc[cb][1] + bb.y, &y[1], &d);
-                gelu_erf_both(acc[cb][2] + bb.z, &y[2], &d); gelu_erf_both(acc[cb][3] + bb.w, &y[3], &d);
+                gelu_erf_both(sb_add<F8>(acc[cb][0], s4.x, bb.x), &y[0], &d); gelu_erf_both(sb_add<F8>(acc[cb][1], s4.y, bb.y), &y[1], &d);
+                gelu_erf_both(sb_add<F8>(acc[cb][2], s4.z, bb.z), &y[2], &d); gelu_erf_both(sb_add<F8>(acc[cb][3], s4.w, bb.w), &y[3], &d);
                 *(float4*)(p.hd_out + (int64_t)(b0 + l15) * HD + n) = make_float4(y[0], y[1], y[2], y[3]);
             }
         }
@@ -577,12 +717,13 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, const FusedP& p, int w, 
     DF_STAMP(41);
 }
 
-template <int G, int NC>
-__device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int h, int lane0, int t256, int img, int b0, int tdev) {
+template <int G, int NC, bool F8>
+__device__ __forceinline__ void attention_role(Lds<G>& sm, float (*scl)[SCL], const typename FusedArgs<F8>::type& p, int h, int lane0, int t256, int img, int b0, int tdev) {
     bf16x8 R[NR];                                     // key + value rows
     {   // layer 0's biases / LayerNorm weights, the sequences' row table and usable-key flags -> LDS
         const int lane = opaque(lane0);
         params_load(sm.par[0], p.L[0], t256);
+        if constexpr (F8) scales_load(scl[0], p.sc8, SCL / 4, t256);
         for (int g = h; g < G; g += 4) {
             const int b = b0 + g;
 #pragma unroll
@@ -631,11 +772,13 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int 
         wg_barrier();            // B6: the cross-attention output is in LDS; behind it, the next layer's parameters and first cached rows
         if (li + 1 < p.nlayers) {
             params_load(sm.par[(li + 1) & 1], p.L[li + 1], t256);
+            if constexpr (F8) scales_load(scl[(li + 1) & 1], p.sc8 + (int64_t)(li + 1) * SCL, SCL / 4, t256);
             DF_STAMP_A(6);
             self_load<G, true, true>(R, sm, p, li + 1, 0, h, b0, tdev, opaque(lane0));
             DF_STAMP_A(7);
         } else if (opaque(t256) < 64) {
             *(float4*)(sm.par[(li + 1) & 1] + opaque(t256) * 4) = ((const float4*)p.bhd)[opaque(t256)];      // the LM head dense layer's bias
+            if constexpr (F8) *(float4*)(scl[(li + 1) & 1] + opaque(t256) * 4) = ((const float4*)(p.sc8 + (int64_t)(li + 1) * SCL))[opaque(t256)];      // ... and its row scales
         }
         wg_barrier();            // B7
         wg_barrier();            // B8
@@ -645,16 +788,18 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, const FusedP& p, int 
     }
 }
 
-template <int G, int NC>      // NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks
-__global__ __launch_bounds__(512) void decode_fused_kernel(const FusedP p) {
+template <int G, int NC, bool F8>      // NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks; F8: e4m3 weights
+__global__ __launch_bounds__(512) void decode_fused_kernel(const typename FusedArgs<F8>::type p) {
     __shared__ Lds<G> sm;
+    float (*scl)[SCL] = nullptr;                         // the layer's / the next layer's row scales: the e4m3 instances only
+    if constexpr (F8) { __shared__ float scl_s[2][SCL]; scl = scl_s; }
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int img = blockIdx.x, b0 = img * G;
     const int tdev = p.tptr ? min(*p.tptr, p.T - 1) : p.t;
     static_assert((12 * 8 + 3 * 32 + 2 * 96) % WIN == 0, "a layer's fragments must fill the window a whole number of times");
     DF_STAMP(0);
-    if (w < 4) linear_role<G>(sm, p, w, lane0, b0);
-    else attention_role<G, NC>(sm, p, w - 4, lane0, tid - 256, img, b0, tdev);
+    if (w < 4) linear_role<G, F8>(sm, scl, p, w, lane0, b0);
+    else attention_role<G, NC, F8>(sm, scl, p, w - 4, lane0, tid - 256, img, b0, tdev);
 }
 
 }  // namespace
@@ -689,11 +834,62 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     p.nlayers = a.nlayers; p.tokens = a.tokens; p.posids = a.posids; p.word = a.word; p.type0 = a.type0; p.postab = a.postab; p.elnw = a.elnw; p.elnb = a.elnb;
     p.whd = a.whd; p.bhd = a.bhd; p.hd_out = a.hd_out; p.cache = a.cache; p.plane = a.plane; p.ckv = a.ckv; p.plane2 = a.plane2;
     p.valid = a.valid; p.ldvalid = a.ldvalid; p.tptr = a.tptr; p.t = a.t; p.T = a.T; p.npa = a.npa; p.B = a.B; p.rows = a.rows; p.eps = a.eps;
+    if ((a.w8 == nullptr) != (a.scales8 == nullptr)) return kzv_fail(KZV_E_ARG, "decode_fused: the e4m3 stream and its row scales go together");
     const int images = a.B / a.group;
     // up to NPMAX keys: the one-pass instances (a chunk that held no key at all would be all -inf); beyond: the chunked ones
-    void (*kern)(const FusedP) = nullptr;
-    if (a.npa <= NPMAX) kern = a.group == 1 ? decode_fused_kernel<1, 1> : a.group == 2 ? decode_fused_kernel<2, 1> : decode_fused_kernel<4, 1>;
-    else kern = a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS> : decode_fused_kernel<4, KZV_DF_CHUNKS>;
-    hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, p);
+    const bool wide = a.npa > NPMAX;
+#define KZV_DF_PICK(F8_) (!wide ? (a.group == 1 ? decode_fused_kernel<1, 1, F8_> : a.group == 2 ? decode_fused_kernel<2, 1, F8_> : decode_fused_kernel<4, 1, F8_>) \
+                                : (a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS, F8_> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS, F8_> : decode_fused_kernel<4, KZV_DF_CHUNKS, F8_>))
+    if (a.w8) {
+        FusedP8 p8;
+        static_cast<FusedP&>(p8) = p;
+        p8.w8 = (const char*)a.w8; p8.wave8 = kzv_decode_fused_pack8_bytes(a.nlayers) / 4; p8.sc8 = a.scales8;
+        void (*kern)(const FusedP8) = KZV_DF_PICK(true);
+        hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, p8);
+    } else {
+        void (*kern)(const FusedP) = KZV_DF_PICK(false);
+        hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, p);
+    }
+#undef KZV_DF_PICK
     return kzv_check_launch("decode_fused");
+}
+
+// ---- the e4m3 copies ------------------------------------------------------------------------------------------------------------
+int64_t kzv_decode_fused_pack8_bytes(int layers) { return (int64_t)4 * (S8_LAYER * layers + S8_HEAD + WIN8) * 1024; }
+int64_t kzv_decode_fused_scales8(int layers) { return (int64_t)SCL * layers + HD; }
+
+static int quant8_launch(Quant8Table& tab, hipStream_t s) {
+    const int pad_blocks = tab.pad_pos >= 0 ? (4 * WIN8 * 64 + 255) / 256 : 0;
+    hipLaunchKernelGGL(quant_pack8_kernel, dim3(tab.rows / 4 + pad_blocks), dim3(256), 0, s, tab);
+    return kzv_check_launch("quant_pack8");
+}
+
+int kzv_decode_fused_pack8(const KzvDecodeFused8Src* layers, int nlayers, const bf16_t* whd, unsigned char* stream, float* scales, hipStream_t s) {
+    if (!layers || !whd || !stream || !scales || nlayers < 1 || nlayers > KZV_DECODE_FUSED_MAX_LAYERS) return kzv_fail(KZV_E_ARG, "decode_fused_pack8: bad argument");
+    Quant8Table tab;
+    tab.n = 0; tab.rows = 0;
+    const auto add = [&](const bf16_t* src, int N, int K, int scale_at, int cb, int pos) {
+        tab.d[tab.n++] = Quant8Desc{src, N, K, tab.rows, scale_at, cb, pos};
+        tab.rows += N;
+    };
+    for (int i = 0; i < nlayers; ++i) {
+        const KzvDecodeFused8Src& l = layers[i];
+        const int at = i * SCL, pos = i * S8_LAYER;
+        add(l.wqkv, 3 * HD, HD, at + PB_QKV, 6, pos + S8_QKV); add(l.wo, HD, HD, at + PB_O, 4, pos + S8_O);
+        add(l.wcq, HD, HD, at + PB_CQ, 4, pos + S8_CQ); add(l.wco, HD, HD, at + PB_CO, 4, pos + S8_CO);
+        add(l.wfc1, FD, HD, at + PB_FC1, 6, pos + S8_FC1); add(l.wfc2, HD, FD, at + PB_FC2, 4, pos + S8_FC2);
+    }
+    add(whd, HD, HD, nlayers * SCL, 4, nlayers * S8_LAYER);
+    tab.pad_pos = nlayers * S8_LAYER + S8_HEAD; tab.dst = stream; tab.scales = scales; tab.wave_bytes = kzv_decode_fused_pack8_bytes(nlayers) / 4;
+    return quant8_launch(tab, s);
+}
+
+extern "C" int kzv_quant_pack_e4m3(const void* w_bf16, int N, int K, void* q_out, float* scale_out, void* stream) {
+    if (!w_bf16 || !q_out || !scale_out) return kzv_fail(KZV_E_ARG, "quant_pack_e4m3: null operand");
+    if (N < 16 || K < 64 || N % 16 || K % 64) return kzv_fail(KZV_E_ARG, "quant_pack_e4m3: N %% 16, K %% 64");
+    if ((int64_t)N * K >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "quant_pack_e4m3: matrix too large");
+    Quant8Table tab;
+    tab.d[0] = Quant8Desc{(const bf16_t*)w_bf16, N, K, 0, 0, 0, 0};
+    tab.n = 1; tab.rows = N; tab.pad_pos = -1; tab.dst = (unsigned char*)q_out; tab.scales = scale_out; tab.wave_bytes = 0;
+    return quant8_launch(tab, (hipStream_t)stream);
 }

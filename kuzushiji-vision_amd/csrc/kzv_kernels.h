@@ -100,7 +100,14 @@ struct KzvDecodeFused {
     const unsigned char* valid; int64_t ldvalid;
     const int* tptr; int t, T, npa, B, group;
     int* rows; float eps;
+    // e4m3 weights (both or neither): the stream and the row scales kzv_decode_fused_pack8 wrote; the layers' w* and whd are then not read
+    const unsigned char* w8 = nullptr; const float* scales8 = nullptr;
 };
+// the e4m3 copies of the linears the step streams, in the order its linear waves consume them, + one power-of-two scale per output row
+struct KzvDecodeFused8Src { const bf16_t *wqkv, *wo, *wcq, *wco, *wfc1, *wfc2; };      // the row-major bf16 copies [N, K]
+int64_t kzv_decode_fused_pack8_bytes(int layers);       // bytes of the stream
+int64_t kzv_decode_fused_scales8(int layers);           // floats of the scales
+int kzv_decode_fused_pack8(const KzvDecodeFused8Src* layers, int nlayers, const bf16_t* whd, unsigned char* stream, float* scales, hipStream_t s);
 int kzv_decode_fused_supported(int Hd, int heads, int Fd, int layers, int group, int T, int npa);
 int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s);
 int kzv_pack_frag(const bf16_t* W, bf16_t* out, int N, int K, hipStream_t s);     // [N, K] row-major -> fragment order

@@ -261,6 +261,8 @@ extern "C" int kzv_model_destroy(kzv_model* m) {
         for (int i = 0; i < 2; ++i) if (m->rowtab[i]) (void)hipFree(m->rowtab[i]);
         if (m->ckv_dec) (void)hipFree(m->ckv_dec);
         if (m->dec_pack) (void)hipFree(m->dec_pack);
+        if (m->dec_pack8) (void)hipFree(m->dec_pack8);
+        if (m->dec_scale8) (void)hipFree(m->dec_scale8);
         drop_decode_graphs(m);
     }
     delete m;
@@ -341,7 +343,7 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
     }
     // a captured decode step holds pointers INTO the workspace and the parameter buffer: none survives a rebind
     drop_decode_graphs(m);
-    m->ckv_dec_ok = false; m->dec_pack_ok = false;
+    m->ckv_dec_ok = false; m->dec_pack_ok = false; m->dec_pack8_ok = false;
     m->bound = true; m->have_fwd = false; m->have_enc = false; m->have_dec = false;
     return KZV_OK;
 }
@@ -349,7 +351,7 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
 extern "C" int kzv_model_sync_weights(kzv_model* m, void* stream) {
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "sync_weights: model not bound");
     KZV_TRY(kzv_cast_weights(m->d_desc, m->ndesc, m->cast_tiles, (hipStream_t)stream));
-    m->dec_pack_ok = false;
+    m->dec_pack_ok = false; m->dec_pack8_ok = false;
     if (m->fp8) {
         if (m->fp8 >= 2 && hipMemsetAsync(m->f8_wnorm, 0, sizeof(float) * m->Le, (hipStream_t)stream) != hipSuccess)
             return kzv_fail(KZV_E_HIP, "sync_weights: memset");

@@ -20,6 +20,23 @@ extern "C" int kzv_decode_step_impl(const kzv_model* m) {
     return decode_one_launch(m) ? 1 : 0;
 }
 
+// e4m3 decoder weights: only the one-launch step reads them, so every case that step does not take keeps bf16 whatever was asked for
+extern "C" int kzv_set_decode_weights(kzv_model* m, int format) {
+    if (!m) return kzv_fail(KZV_E_ARG, "set_decode_weights: null model");
+    if (format != KZV_DECODE_WEIGHTS_BF16 && format != KZV_DECODE_WEIGHTS_E4M3) return kzv_fail(KZV_E_ARG, "set_decode_weights: format 0 (bf16) or 1 (e4m3), not %d", format);
+    m->dec_weights = format;
+    return KZV_OK;
+}
+extern "C" int kzv_get_decode_weights(const kzv_model* m) {
+    if (!m) return kzv_fail(KZV_E_ARG, "get_decode_weights: null model");
+    return m->dec_weights;
+}
+static bool decode_e4m3(const kzv_model* m) { return m->dec_weights == KZV_DECODE_WEIGHTS_E4M3 && decode_one_launch(m); }
+extern "C" int kzv_decode_weights_impl(const kzv_model* m) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "decode_weights_impl: model not bound");
+    return decode_e4m3(m) ? KZV_DECODE_WEIGHTS_E4M3 : KZV_DECODE_WEIGHTS_BF16;
+}
+
 static int ensure_kv_cache(kzv_model* m) {
     if (m->kvc[0] && m->kvB == m->B && m->kvT == m->T) return KZV_OK;
     for (int i = 0; i < 2; ++i) { if (m->kvc[i]) (void)hipFree(m->kvc[i]); m->kvc[i] = nullptr; }
@@ -86,6 +103,28 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
     jobs.push_back({m->word.h.wt, base + pk.head_t(), Hd, pk.vq, Hd, (int)m->word.h.ldt, (int)m->Vp});
     KZV_TRY(kzv_pack_frag_multi(jobs.data(), (int)jobs.size(), s));
     m->dec_pack_ok = true;
+    return KZV_OK;
+}
+
+// the e4m3 stream and row scales of the same linears (4.7 MB), quantised from their bf16 copies in ONE launch (outside any capture)
+int ensure_dec_pack8(kzv_model* m, hipStream_t s) {
+    if (m->dec_pack8_ok || !decode_e4m3(m)) return KZV_OK;
+    if (!m->dec_pack8) {
+        if (hipMalloc((void**)&m->dec_pack8, (size_t)kzv_decode_fused_pack8_bytes(m->Ld)) != hipSuccess ||
+            hipMalloc((void**)&m->dec_scale8, sizeof(float) * (size_t)kzv_decode_fused_scales8(m->Ld)) != hipSuccess) {
+            if (m->dec_pack8) (void)hipFree(m->dec_pack8);
+            m->dec_pack8 = nullptr; m->dec_scale8 = nullptr;
+            return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
+        }
+        drop_decode_graphs(m);
+    }
+    KzvDecodeFused8Src src[KZV_DECODE_FUSED_MAX_LAYERS];
+    for (int i = 0; i < m->Ld; ++i) {
+        const DecLayerP& d = m->dp[i];
+        src[i] = KzvDecodeFused8Src{d.qkv.h.w, d.o.h.w, d.cq.h.w, d.co.h.w, d.fc1.h.w, d.fc2.h.w};
+    }
+    KZV_TRY(kzv_decode_fused_pack8(src, m->Ld, m->hd.h.w, m->dec_pack8, m->dec_scale8, s));
+    m->dec_pack8_ok = true;
     return KZV_OK;
 }
 
@@ -188,6 +227,10 @@ static int decode_step_body_one_launch(kzv_model* m, const StepArgs& st, hipStre
     a.ckv = m->ckv_dec; a.plane2 = (int64_t)m->Be * m->npa * Hd;
     a.valid = st.valid; a.ldvalid = st.ld_valid; a.tptr = st.tptr; a.t = st.t; a.T = T; a.npa = m->npa; a.B = B; a.group = B / m->Be;
     a.rows = m->rt_cur >= 0 ? m->rowtab[m->rt_cur] : nullptr; a.eps = m->c.ln_eps;
+    if (decode_e4m3(m)) {
+        if (!m->dec_pack8_ok) return kzv_fail(KZV_E_STATE, "decode_step: the e4m3 decoder weights are stale");
+        a.w8 = m->dec_pack8; a.scales8 = m->dec_scale8;
+    }
     KZV_TRY(kzv_decode_fused_launch(a, s));
     return vocab_logits(m, true, st.logits, s);
 }
@@ -247,6 +290,7 @@ extern "C" int kzv_decode_step(kzv_model* m, const int64_t* d_tokens, const int*
     if (t == 0) m->rt_cur = -1;                 // a new generation: no beam has been re-parented yet
     KZV_TRY(ensure_cross_layout(m, (hipStream_t)stream));
     KZV_TRY(ensure_dec_pack(m, (hipStream_t)stream));
+    KZV_TRY(ensure_dec_pack8(m, (hipStream_t)stream));
     m->train = false; m->have_fwd = false; m->have_dec = false;      // decoder activations are overwritten: no backward after this
     return decode_step_body(m, StepArgs{d_tokens, d_posids, t, nullptr, d_valid, ld_valid, d_logits}, (hipStream_t)stream);
 }
@@ -256,6 +300,7 @@ extern "C" int kzv_decode_begin(kzv_model* m, void* stream) {
     KZV_TRY(ensure_kv_cache(m));
     if (m->have_enc) KZV_TRY(ensure_cross_layout(m, (hipStream_t)stream));
     KZV_TRY(ensure_dec_pack(m, (hipStream_t)stream));
+    KZV_TRY(ensure_dec_pack8(m, (hipStream_t)stream));
     m->rt_cur = -1;                              // a new generation: every sequence reads its own cache row
     if (hipMemsetAsync(m->d_t, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode_begin: memset");
     return KZV_OK;
@@ -268,10 +313,11 @@ extern "C" int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, cons
     KZV_TRY(ensure_kv_cache(m));
     KZV_TRY(ensure_cross_layout(m, (hipStream_t)stream));          // before any capture: a plain launch, once per generation
     KZV_TRY(ensure_dec_pack(m, (hipStream_t)stream));
+    KZV_TRY(ensure_dec_pack8(m, (hipStream_t)stream));
     m->train = false; m->have_fwd = false; m->have_dec = false;
     hipStream_t s = (hipStream_t)stream;
     const int g = m->rt_cur + 1;
-    const void* key[6] = {d_tokens, d_posids, d_valid, d_logits, m->kvc[0], (const void*)((intptr_t)m->ckv_dec ^ (intptr_t)(m->npa * 4096 + m->Be) ^ ((intptr_t)decode_one_launch_mode() << 40))};
+    const void* key[6] = {d_tokens, d_posids, d_valid, d_logits, m->kvc[0], (const void*)((intptr_t)m->ckv_dec ^ (intptr_t)(m->npa * 4096 + m->Be) ^ ((intptr_t)decode_one_launch_mode() << 40) ^ ((intptr_t)decode_e4m3(m) << 41))};
     bool same = m->dgraph[g] != nullptr && m->dg_ld[g] == ld_valid;
     for (int i = 0; i < 6 && same; ++i) same = m->dg_key[g][i] == key[i];
     if (!same) {                               // (re)capture: the step with its index read from m->d_t, then t += 1

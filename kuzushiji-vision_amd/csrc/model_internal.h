@@ -113,6 +113,10 @@ struct kzv_model {
     bf16_t* ckv_dec = nullptr; size_t ckv_dec_bytes = 0; bool ckv_dec_ok = false;
     // the decoder's bf16 weights in MFMA fragment order, refreshed after every weight change; pk: where each matrix sits in it
     bf16_t* dec_pack = nullptr; bool dec_pack_ok = false; DecPack pk;
+    // generation from e4m3 decoder weights (kzv_set_decode_weights): the format asked for, and the e4m3 stream + row scales of the
+    // linears the one-launch step reads (decode_fused.hip), built lazily while the format is e4m3 and refreshed like dec_pack
+    int dec_weights = KZV_DECODE_WEIGHTS_BF16;
+    unsigned char* dec_pack8 = nullptr; float* dec_scale8 = nullptr; bool dec_pack8_ok = false;
     bool dhln_fused = false;     // the last training forward's head_ce launch already wrote dhln (the LM head's input gradient)
     // graph-replayed decode step (kzv_decode_step_graph): device-side step index + one instantiated graph per cache copy
     int* d_t = nullptr;
@@ -154,6 +158,7 @@ KZV_LOCAL bool head_ce_mode();          // KZV_HEAD_CE / kzv_set_head_ce (defaul
 // model_decode.cpp
 KZV_LOCAL bool dec_pack_wanted(const kzv_model* m);
 KZV_LOCAL int ensure_dec_pack(kzv_model* m, hipStream_t s);
+KZV_LOCAL int ensure_dec_pack8(kzv_model* m, hipStream_t s);      // the e4m3 stream, where the next cached step would read it
 KZV_LOCAL int decode_one_launch_mode(); // KZV_DECODE_ONE_LAUNCH / kzv_set_decode_one_launch (default on)
 
 // a captured decode step holds pointers into the workspace, the caches and the pack: dropped whenever one of them moves

@@ -226,6 +226,10 @@ SYMBOLS = {
     "kzv_decode_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kzv_set_decode_one_launch": (C.c_int, [C.c_int]),
     "kzv_decode_step_impl": (C.c_int, [C.c_void_p]),
+    "kzv_set_decode_weights": (C.c_int, [C.c_void_p, C.c_int]),
+    "kzv_get_decode_weights": (C.c_int, [C.c_void_p]),
+    "kzv_decode_weights_impl": (C.c_int, [C.c_void_p]),
+    "kzv_quant_pack_e4m3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kzv_set_dec_chain": (C.c_int, [C.c_int]),
     "kzv_set_head_ce": (C.c_int, [C.c_int]),
     "kzv_decode_step_graph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

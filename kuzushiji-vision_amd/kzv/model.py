@@ -41,7 +41,7 @@ class TrOCRModel:
     def __init__(self, encoder_config: dict[str, Any], decoder_path: str, learning_rate: float = 1e-4,
                  beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, weight_decay: float = 0,
                  *, device: str = "cuda", init_seed: int = 42, load_tokenizer: bool = True, width_buckets=None,
-                 fp8: bool = False, long_sequences: bool = False):
+                 fp8: bool = False, long_sequences: bool = False, decode_weights: str = "bf16"):
         import torch
         self.hparams = types.SimpleNamespace(encoder_config=encoder_config, decoder_path=decoder_path,
                                              learning_rate=learning_rate, beta1=beta1, beta2=beta2,
@@ -98,6 +98,9 @@ class TrOCRModel:
         self.fp8 = int(fp8)
         if self.fp8:
             L.check(lib.kzv_set_fp8(h, self.fp8), "kzv_set_fp8")
+        # generation from e4m3 decoder weights (an extension; include/kzv.h: kzv_set_decode_weights, kzv/quant.py): opt-in, and only
+        # where the one-launch step runs -- decode_weights_impl says what a generate actually read
+        self.set_decode_weights(decode_weights)
         self._offsets, total = P.param_offsets(c)
         if lib.kzv_param_total(h) != total:
             raise L.KzvError("parameter table mismatch between kzv/params.py and libkzv")
@@ -218,6 +221,24 @@ class TrOCRModel:
         if rc < 0:
             L.check(rc, "kzv_decode_step_impl")
         return "one-launch" if rc == 1 else "per-operation"
+
+    _DECODE_WEIGHTS = ("bf16", "e4m3")
+
+    def set_decode_weights(self, fmt: str) -> None:
+        """"bf16" (default) | "e4m3": what the KV-cached generation steps after this call read the decoder's streamed linears as."""
+        if fmt not in self._DECODE_WEIGHTS:
+            raise ValueError(f"decode_weights must be one of {self._DECODE_WEIGHTS}, not {fmt!r}")
+        L.check(L.load().kzv_set_decode_weights(self._h, self._DECODE_WEIGHTS.index(fmt)), "kzv_set_decode_weights")
+        self.decode_weights = fmt
+
+    @property
+    def decode_weights_impl(self) -> str:
+        """"bf16" | "e4m3": what the next KV-cached generation step of this model will actually read (kzv_decode_weights_impl): "e4m3"
+        only where it was asked for and decode_step_impl is "one-launch".  Valid when decode_step_impl is."""
+        rc = L.load().kzv_decode_weights_impl(self._h)
+        if rc < 0:
+            L.check(rc, "kzv_decode_weights_impl")
+        return self._DECODE_WEIGHTS[rc]
 
     def train(self, mode: bool = True):
         self.training = mode

@@ -59,6 +59,9 @@ def parse_args(argv=None):
                    help="bf16-mixed = the reference's setting and this engine's arithmetic; fp8-mixed (an extension, BASELINE configs[4]) "
                         "additionally runs the encoder's QKV / fc1 / fc2 forward GEMMs on e4m3 operands (hidden and ffn sizes must be multiples of 256)")
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--decode_weights", type=str, default="bf16", choices=["bf16", "e4m3"],
+                   help="e4m3 (an extension): validation / test decodes read the decoder's streamed linears as e4m3 with a power-of-two "
+                        "scale per output row where the one-launch generation step runs (kzv.quant states what that equals); training is untouched")
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize / pad / normalise the decoded crops on the GPU (kzv.preprocess; byte-exact with the PIL transform)")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
@@ -224,7 +227,7 @@ def main(argv=None):
                       "hidden_dropout_prob": 0.1, "attention_probs_dropout_prob": 0.1}   # :111-121
     model = TrOCRModel(encoder_config, decoder_path, learning_rate=args.learning_rate, beta1=args.beta1, beta2=args.beta2,
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
-                       fp8=args.precision == "fp8-mixed", long_sequences=True)
+                       fp8=args.precision == "fp8-mixed", long_sequences=True, decode_weights=args.decode_weights)
     model._step_seed = 1_000_003 * rank
     if rank == 0:
         c = model.cfg
@@ -233,7 +236,7 @@ def main(argv=None):
 
         def generate_and_report(*a, **kw):      # the first validation decode binds the model: say once which step it took
             out = generate(*a, **kw)
-            print(f"decode step: {model.decode_step_impl}")
+            print(f"decode step: {model.decode_step_impl}, decoder weights: {model.decode_weights_impl}")
             del model.generate
             return out
         model.generate = generate_and_report
