@@ -8,13 +8,14 @@
 // Every operation of a decoder step is local to a sequence -- the linears are row-wise, a sequence attends to its own cache and to
 // its own image's patch keys -- so ONE workgroup owns the G sequences of one image (G = beams) through all layers and never talks
 // to another workgroup: no grid barrier, no flags.  Hidden size 256, 4 heads of 64, FFN 768 (the reference decoder), <= 128 cached
-// keys, <= 320 patch keys (up to 160 in one pass through the attention waves' registers, 161 .. 320 in chunks with an online
-// softmax: see cross_chunk_*); other geometries keep the launch-per-operation path (model.cpp).
+// keys, <= 320 patch keys (one cross-attention path, cross_chunk_*: up to 160 keys are its NC = 1 instance, one pass through the
+// attention waves' registers; 161 .. 320 go through them in NC chunks with an online softmax); other geometries keep the
+// launch-per-operation path (model.cpp).
 //
 // What bounds it is ONE CU's load path (~60 GB/s from L2): per token a workgroup streams all 9.4 MB of decoder weights plus its
 // sequences' attention rows.  So the eight waves are split by what they LOAD, and each stream stays in flight across the barriers:
 //   * waves 0-3, the linears: the 16-row MFMA tile holds the G rows (lanes of rows >= G repeat row G - 1); wave w owns the
-//     16-column blocks w, w + 4, ... and reads its weight fragments in MFMA fragment order (pack_frag_kernel: a wave-instruction is one
+//     16-column blocks w, w + 4, ... and reads its weight fragments in MFMA fragment order (frag_stream.h: a wave-instruction is one
 //     contiguous KiB), a window of 16 fragments always in flight and refilled with the NEXT linear's first fragments as a linear ends.
 //   * waves 4-7, attention, one head each: key / value rows go to registers (a wave-instruction = 8 rows x 128 B) and are requested
 //     one phase early -- the cached rows of the first sequence while the QKV projection runs, the image's patch keys / values
@@ -26,6 +27,7 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "kzv_kernels.h"
+#include "frag_stream.h"
 #include <cmath>
 
 namespace {
@@ -38,19 +40,12 @@ constexpr int LDW = FD + 8;          // bf16 rows, 768 wide (qkv / FFN activatio
 constexpr int PB_QKV = 0, PB_O = 768, PB_CQ = 1024, PB_CO = 1280, PB_FC1 = 1536, PB_FC2 = 2304;
 constexpr int PL1W = 2560, PL1B = 2816, PL2W = 3072, PL2B = 3328, PL3W = 3584, PL3B = 3840, PAR = 4096;
 constexpr int NR = 40;               // role registers: 40 fragments (160 VGPRs): the weight window, or key + value rows
-constexpr int WIN = 24;
+constexpr int NLW = 4, WIN = 24;     // the linear waves, and the bf16 weight fragments each keeps in flight (frag_stream.h)
 constexpr int NIS = TMAX / 8, NIC = NPMAX / 8;
 constexpr int NPWIDE = 320, NIW = NPWIDE / 8;      // the chunked instances: 161 .. 320 patch keys, NIW key iterations in all
 #ifndef KZV_DF_CHUNKS
 #define KZV_DF_CHUNKS 2                            // chunks of the 320 keys (2, 4 or 8): DESIGN.md section 7, N1 has the measurements
 #endif
-
-// the lane id, re-derived per phase: hipcc otherwise hoists every lane-derived offset of all phases out of the layer loop and spills them
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// Workgroup barrier for LDS hand-offs that leaves global loads in flight: __syncthreads() is a workgroup-scope release, and on gfx9
-// that means s_waitcnt vmcnt(0) -- it would drain both streams at every phase boundary.  Nothing a phase writes to global memory
-// is read by another wave of the same launch.
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Sums / maxima over lane groups without the LDS crossbar (ds_bpermute, what __shfl_xor compiles to): DPP moves for the steps inside a
 // 16-lane row, the crossbar only for the two steps across rows.
@@ -114,25 +109,7 @@ struct Lds {
 
 // ---- the weight stream (waves 0-3) --------------------------------------------------------------------------------------------
 // acc[c][r] = sum_k W[n][k] * a[m][k] for m = lane & 15 (rows >= G repeat row G - 1), n = (w + 4 c) * 16 + 4 (lane >> 4) + r.
-// Wp = the weight in FRAGMENT ORDER: the 64 lanes' 16-byte pieces of (16-column block nb, 32-deep k-step ks) are 1 KiB of contiguous
-// memory at ((nb * KS + ks) * 64 + lane) * 16 bytes.  (Read from the row-major [N, K] copy, the 64 lanes of a fragment are 64
-// separate 16-byte requests -- 16 rows x 4 pieces -- and the address coalescer, at one request per cycle, held the stream at 30 GB/s
-// per CU: 13 us for the 393 KB of a QKV projection against 6.6.)  Fragment i of a CB x KS GEMM is (k-step i / CB, column block i % CB);
-// slot i % WIN of the window is refilled right behind the MFMA that consumed it, with this GEMM's fragment i + WIN or, past its end,
-// with the NEXT GEMM's first fragments.
-template <int CB, int KS>
-__device__ __forceinline__ const char* wave_frags(const bf16_t* Wp, int w) { return (const char*)(Wp + (int64_t)w * KS * 512); }
-template <int CB, int KS>
-__device__ __forceinline__ bf16x8 ld_frag(const char* wb, unsigned wo, int i) {
-    const int ks = i / CB, c = i % CB;
-    return *(const bf16x8*)(wb + ((int64_t)(4 * c) * KS + ks) * 1024 + wo);
-}
-template <int CB, int KS>
-__device__ __forceinline__ void fill_window(bf16x8 (&R)[NR], const char* wb, int lane) {
-    const unsigned wo = (unsigned)lane * 16u;
-#pragma unroll
-    for (int i = 0; i < WIN; ++i) R[i] = ld_frag<CB, KS>(wb, wo, i);
-}
+// The fragment order of Wp, the window and its refill rule: frag_stream.h.
 template <int CB, int KS, int NCB, int NKS, int OFF, int G>      // OFF: window slot of this GEMM's fragment 0 (the stream's fragments take the slots in turn)
 __device__ __forceinline__ void rows_gemm(bf16x8 (&R)[NR], const char* wb, const char* next, const bf16_t* a_lds, int lda, int lane, f32x4 (&acc)[CB]) {
     constexpr int F = CB * KS;
@@ -148,8 +125,8 @@ __device__ __forceinline__ void rows_gemm(bf16x8 (&R)[NR], const char* wb, const
         const int ks = i / CB, c = i % CB, slot = (OFF + i) % WIN;
         if (c == 0) fa = *(const bf16x8*)(ap + ks * 32);
         acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(R[slot], fa, acc[c], 0, 0, 0);
-        if (i + WIN < F) R[slot] = ld_frag<CB, KS>(wb, wo, i + WIN);
-        else if (next) R[slot] = ld_frag<NCB, NKS>(next, wo, i + WIN - F);
+        if (i + WIN < F) R[slot] = ld_frag<CB, KS, NLW>(wb, wo, i + WIN);
+        else if (next) R[slot] = ld_frag<NCB, NKS, NLW>(next, wo, i + WIN - F);
     }
 }
 
@@ -211,15 +188,6 @@ template <bool F8> __device__ __forceinline__ float4 scale4(const float* scl, in
 template <bool F8> __device__ __forceinline__ float sb_add(float acc, float s, float b) {
     if constexpr (F8) return fmaf(acc, s, b);
     else return acc + b;
-}
-
-// W [N, K] row-major -> fragment order (see rows_gemm); one thread per 16-byte piece
-__global__ void pack_frag_kernel(const uint4* __restrict__ W, uint4* __restrict__ out, int N, int K) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= N * K / 8) return;
-    const int lane = t & 63, f = t >> 6, KS = K / 32;
-    const int nb = f / KS, ks = f - nb * KS;
-    out[t] = W[((int64_t)(nb * 16 + (lane & 15)) * K + ks * 32 + (lane >> 4) * 8) / 8];
 }
 
 // ---- quantise-and-pack: bf16 [N, K] -> OCP e4m3 with one power-of-two scale per output row, one launch over a table of matrices ------
@@ -376,66 +344,22 @@ __device__ __forceinline__ void self_compute(bf16x8 (&R)[NR], Lds<G>& sm, const 
         *(u32x4*)(&sm.ctx[g][h * 64 + c * 8]) = (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv), pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
     }
 }
-// the image's patch keys of head h -> R[0 .. NIC), values -> R[NIC .. 2 NIC) (shared by the G sequences)
-__device__ __forceinline__ void cross_load(bf16x8 (&R)[NR], const FusedP& p, int li, int img, int h, int lane) {
-    const int r = lane >> 3, c = lane & 7;
-    const char* Kc = (const char*)(p.ckv + (int64_t)(2 * li) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
-    const char* Vc = (const char*)(p.ckv + (int64_t)(2 * li + 1) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
-#pragma unroll
-    for (int i = 0; i < NIC; ++i) {
-        const unsigned off = ((unsigned)min(8 * i + r, p.npa - 1) * 64u + (unsigned)c * 8u) * 2u;       // past the last key: a real row, probability 0
-        R[i] = *(const bf16x8*)(Kc + off);
-        R[NIC + i] = *(const bf16x8*)(Vc + off);
-    }
-}
-template <int G>
-__device__ __forceinline__ void cross_compute(bf16x8 (&R)[NR], Lds<G>& sm, const FusedP& p, int h, int lane) {
-    const int r = lane >> 3, c = lane & 7;
-#pragma unroll 1
-    for (int g = 0; g < G; ++g) {
-        // the rows are the same for every sequence: without this hipcc hoists their 320 bf16 -> fp32 conversions out of the loop (and spills them)
-#pragma unroll
-        for (int i = 0; i < 2 * NIC; ++i) asm volatile("" : "+v"(R[i]));
-        const u32x4_t qp = scaled_query(&sm.wide[g][h * 64 + c * 8]);
-        float sc[NIC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NIC; ++i) {
-            const float a = sum8(dot8(R[i], qp));
-            sc[i] = (8 * i + r < p.npa) ? a : -INFINITY;
-            mx = fmaxf(mx, sc[i]);
-        }
-        mx = wave_max_d(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < NIC; ++i) { sc[i] = __expf(sc[i] - mx); sum += sc[i]; }
-        const float inv = 1.f / (wave_sum_d(sum) * 0.125f);
-        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < NIC; ++i)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] += sc[i] * bf2f((bf16_t)R[NIC + i][e]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = sum_rows(o[e]);
-        if (r == 0) {
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-            *(u32x4*)(&sm.ctx[g][h * 64 + c * 8]) = (u32x4){pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv), pack_bf2(o[4] * inv, o[5] * inv), pack_bf2(o[6] * inv, o[7] * inv)};
-        }
-    }
-}
-// ---- 161 .. 320 patch keys: NC chunks of CI = NIW / NC key iterations (8 keys each) through NB = max(NC / 2, 1) buffers of the role
-// registers (2 CI fragments each: a chunk's keys, then its values).  Chunk S lives in buffer S % NB; the chunks of the first NB are
-// requested behind B2 like cross_load's rows, chunk S + NB right behind the last use of chunk S, so with NB > 1 a chunk's rows travel
-// while its neighbour is being used.  Per sequence the running maximum, the running sum and the lane's 8 unnormalised output sums are
-// carried from chunk to chunk in LDS (each lane re-reads what it wrote itself: no barrier) with the usual rescale
+// ---- cross-attention over the image's patch keys of head h (shared by the G sequences): NC chunks of CI key iterations (8 keys each)
+// through NB = max(NC / 2, 1) buffers of the role registers (2 CI fragments each: a chunk's keys, then its values).  NC = 1 is the
+// instance for up to NPMAX keys: all NIC iterations in one pass, no carried state.  NC > 1 takes 161 .. NPWIDE keys, NIW iterations in
+// all: chunk S lives in buffer S % NB; the chunks of the first NB are requested behind B2, chunk S + NB right behind the last use of
+// chunk S, so with NB > 1 a chunk's rows travel while its neighbour is being used.  Per sequence the running maximum, the running sum
+// and the lane's 8 unnormalised output sums are carried from chunk to chunk in LDS (each lane re-reads what it wrote itself: no
+// barrier) with the usual rescale
 //   m' = max(m, chunk maximum), l' = l e^(m - m') + sum e^(s - m'), o' = o e^(m - m') + sum e^(s - m') v
-// and the last chunk reduces over the key rows, normalises and packs to bf16 once, as cross_compute does.  Chunk 0 holds key 0, so m
-// is finite from the first chunk on and a chunk that lies wholly past npa (its loads clamped to the last row) adds exact zeros.
-template <int G> struct CrossState { float v[G][NH][10][64]; };      // [8 output sums, m, l][lane]
+// and the last chunk reduces over the key rows, normalises and packs to bf16 once.  Chunk 0 holds key 0, so m is finite from the
+// first chunk on and a chunk that lies wholly past npa (its loads clamped to the last row) adds exact zeros.
+template <int G> struct CrossState { float v[G][NH][10][64]; };      // [8 output sums, m, l][lane]; NC > 1 only
+constexpr int cross_iters(int NC) { return NC == 1 ? NIC : NIW; }      // key iterations of all NC chunks together
 template <int NC, int S>
 __device__ __forceinline__ void cross_chunk_load(bf16x8 (&R)[NR], const FusedP& p, int li, int img, int h, int lane) {
-    constexpr int CI = NIW / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
-    static_assert(NIW % NC == 0 && 2 * CI * NB <= NR, "cross_chunk_load: buffers");
+    constexpr int CI = cross_iters(NC) / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
+    static_assert(cross_iters(NC) % NC == 0 && 2 * CI * NB <= NR, "cross_chunk_load: buffers");
     const int r = lane >> 3, c = lane & 7;
     const char* Kc = (const char*)(p.ckv + (int64_t)(2 * li) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
     const char* Vc = (const char*)(p.ckv + (int64_t)(2 * li + 1) * p.plane2 + ((int64_t)img * NH + h) * p.npa * 64);
@@ -446,9 +370,9 @@ __device__ __forceinline__ void cross_chunk_load(bf16x8 (&R)[NR], const FusedP& 
         R[BASE + CI + i] = *(const bf16x8*)(Vc + off);
     }
 }
-template <int G, int NC, int S>
-__device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>& st, const FusedP& p, int h, int lane) {
-    constexpr int CI = NIW / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
+template <int G, int NC, int S>      // st: null for NC = 1
+__device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>* st, const FusedP& p, int h, int lane) {
+    constexpr int CI = cross_iters(NC) / NC, NB = NC > 1 ? NC / 2 : 1, BASE = (S % NB) * 2 * CI;
     const int r = lane >> 3, c = lane & 7;
 #pragma unroll 1
     for (int g = 0; g < G; ++g) {
@@ -456,7 +380,7 @@ __device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm,
 #pragma unroll
         for (int i = 0; i < 2 * CI; ++i) asm volatile("" : "+v"(R[BASE + i]));
         const u32x4_t qp = scaled_query(&sm.wide[g][h * 64 + c * 8]);
-        float* sv = &st.v[g][h][0][lane];
+        float* sv = NC > 1 ? &st->v[g][h][0][lane] : nullptr;
         float sc[CI];
         float mx = -INFINITY;
 #pragma unroll
@@ -468,7 +392,7 @@ __device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm,
         mx = wave_max_d(mx);
         float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float l = 0.f;
-        if (S > 0) {
+        if constexpr (S > 0) {
             const float m0 = sv[8 * 64];
             mx = fmaxf(mx, m0);
             const float f = __expf(m0 - mx);
@@ -479,12 +403,15 @@ __device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm,
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < CI; ++i) { sc[i] = __expf(sc[i] - mx); sum += sc[i]; }
-        l += wave_sum_d(sum) * 0.125f;                   // every key is counted by the 8 lanes of its row
+        // every key is counted by the 8 lanes of its row.  Two forms, so that neither family's code moves: `l +=` contracts to an FMA
+        // (with l = 0 in chunk 0 too), which the one-pass instances never had
+        if constexpr (NC == 1) l = wave_sum_d(sum) * 0.125f;
+        else l += wave_sum_d(sum) * 0.125f;
 #pragma unroll
         for (int i = 0; i < CI; ++i)
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] += sc[i] * bf2f((bf16_t)R[BASE + CI + i][e]);
-        if (S + 1 < NC) {
+        if constexpr (S + 1 < NC) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) sv[e * 64] = o[e];
             sv[8 * 64] = mx; sv[9 * 64] = l;
@@ -501,10 +428,10 @@ __device__ __forceinline__ void cross_chunk_compute(bf16x8 (&R)[NR], Lds<G>& sm,
 }
 // chunks S .. NC - 1 in turn: use chunk S, then request chunk S + NB into the buffer it leaves
 template <int G, int NC, int S>
-__device__ __forceinline__ void cross_chunks(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>& st, const FusedP& p, int li, int img, int h, int lane0) {
+__device__ __forceinline__ void cross_chunks(bf16x8 (&R)[NR], Lds<G>& sm, CrossState<G>* st, const FusedP& p, int li, int img, int h, int lane0) {
     constexpr int NB = NC > 1 ? NC / 2 : 1;
     cross_chunk_compute<G, NC, S>(R, sm, st, p, h, opaque(lane0));
-    DF_STAMP_A(8 + S);
+    if constexpr (NC > 1) { DF_STAMP_A(8 + S); }
     if constexpr (S + NB < NC) cross_chunk_load<NC, S + NB>(R, p, li, img, h, opaque(lane0));
     if constexpr (S + 1 < NC) cross_chunks<G, NC, S + 1>(R, sm, st, p, li, img, h, lane0);
 }
@@ -549,7 +476,7 @@ __device__ __forceinline__ void linear_role(Lds<G>& sm, float (*scl)[SCL], const
             ga = *(const float4*)(p.elnw + lane * 4); be = *(const float4*)(p.elnb + lane * 4);
         }
         if constexpr (F8) fill_window8(R, sb, lane);
-        else fill_window<6, 8>(R, wave_frags<6, 8>(p.L[0].wqkv, w), lane);
+        else fill_window<6, 8, NLW, WIN>(R, wave_frags<6, 8>(p.L[0].wqkv, w), lane);
         if (w < G) {
             const float4 v = make_float4(wv.x + ty.x + pv.x, wv.y + ty.y + pv.y, wv.z + ty.z + pv.z, wv.w + ty.w + pv.w);
             const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.f / HD);
@@ -749,23 +676,17 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, float (*scl)[SCL], co
             DF_STAMP_A(2);
         }
         wg_barrier();            // B2: the attention output is in LDS; the image's patch keys / values are requested behind it
-        if constexpr (NC == 1) cross_load(R, p, li, img, h, opaque(lane0));
-        else {
-            cross_chunk_load<NC, 0>(R, p, li, img, h, opaque(lane0));
-            if constexpr (NC >= 4) cross_chunk_load<NC, 1>(R, p, li, img, h, opaque(lane0));
-            if constexpr (NC >= 8) { cross_chunk_load<NC, 2>(R, p, li, img, h, opaque(lane0)); cross_chunk_load<NC, 3>(R, p, li, img, h, opaque(lane0)); }
-        }
+        cross_chunk_load<NC, 0>(R, p, li, img, h, opaque(lane0));                      // the chunks of the first NB buffers
+        if constexpr (NC >= 4) cross_chunk_load<NC, 1>(R, p, li, img, h, opaque(lane0));
+        if constexpr (NC >= 8) { cross_chunk_load<NC, 2>(R, p, li, img, h, opaque(lane0)); cross_chunk_load<NC, 3>(R, p, li, img, h, opaque(lane0)); }
         DF_STAMP_A(3);
         wg_barrier();            // B3
         wg_barrier();            // B4
         wg_barrier();            // B5: the cross query is in LDS
         DF_STAMP_A(4);
-        if constexpr (NC == 1) {   // cross-attention of head h for every sequence; then the next layer's parameters and its first cached rows
-            const int lane = opaque(lane0);
-            cross_compute<G>(R, sm, p, h, lane);
-            DF_STAMP_A(5);
-        } else {
-            __shared__ CrossState<G> st;              // the chunked instances only
+        {   // cross-attention of head h for every sequence; then the next layer's parameters and its first cached rows
+            CrossState<G>* st = nullptr;
+            if constexpr (NC > 1) { __shared__ CrossState<G> st_s; st = &st_s; }      // the chunked instances only
             cross_chunks<G, NC, 0>(R, sm, st, p, li, img, h, lane0);
             DF_STAMP_A(5);
         }
@@ -813,12 +734,6 @@ extern "C" int kzv_debug_decode_stamps(long long* host, int n) {
 int kzv_decode_fused_supported(int Hd, int heads, int Fd, int layers, int group, int T, int npa) {
     return Hd == HD && heads == NH && Fd == FD && layers >= 1 && layers <= KZV_DECODE_FUSED_MAX_LAYERS && (group == 1 || group == 2 || group == 4) &&
            T >= 1 && T <= TMAX && npa >= 1 && npa <= NPWIDE;
-}
-
-int kzv_pack_frag(const bf16_t* W, bf16_t* out, int N, int K, hipStream_t s) {
-    if (N % 16 || K % 32) return kzv_fail(KZV_E_ARG, "pack_frag: N %% 16, K %% 32");
-    hipLaunchKernelGGL(pack_frag_kernel, dim3((N * K / 8 + 255) / 256), dim3(256), 0, s, (const uint4*)W, (uint4*)out, N, K);
-    return kzv_check_launch("pack_frag");
 }
 
 int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {

@@ -6,7 +6,7 @@
 // At the decoder's size (hidden 256, FFN 768, ~15k rows) every one of these is a 15 - 21 us launch for 2 GFLOP: 240 tiles of
 // 128 x 128 leave the chip under one wave per SIMD and the chain is launch- and latency-bound.  The chains are ROW-LOCAL, so one
 // workgroup takes 64 rows through a whole chain: the activations stay in LDS (bf16 A operands, fp32 pre-LayerNorm sums), the
-// weights arrive in MFMA fragment order (decode_fused.hip's pack: a wave-instruction = one contiguous KiB) as one stream per wave
+// weights arrive in MFMA fragment order (frag_stream.h, shared with decode_fused.hip: a wave-instruction = one contiguous KiB) as one stream per wave
 // with a window of 16 fragments in flight across the GEMM boundaries, and every tensor the backward reads is written on the way
 // (same tensors, same rounding points as the launch-per-operation path: bf16 GEMM operands, fp32 sums / statistics / residuals;
 // the dropout bits of the two residual epilogues are the engine's own -- key, element index m * 256 + n -- so the backward's
@@ -15,6 +15,7 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "kzv_kernels.h"
+#include "frag_stream.h"
 
 namespace {
 
@@ -22,27 +23,10 @@ constexpr int HD = 256, FD = 768, RM = 64, RT = RM / 16;
 constexpr int LDH = HD + 8;          // bf16 rows, 256 wide
 constexpr int LDW = FD + 8;          // bf16 rows, 768 wide
 constexpr int LDS_ = HD + 4;         // fp32 rows of a pre-LayerNorm sum
-constexpr int WIN = 16;
+constexpr int NW = 8, WIN = 16;      // waves on the weight stream, fragments in flight per wave (frag_stream.h has the layout and the primitives)
 constexpr int LDS_A1 = RM * LDH * 2;                                   // bytes of the 256-wide operand tile
 constexpr int LDS_A = LDS_A1 + RM * LDS_ * 4, LDS_B = LDS_A1 + RM * LDW * 2;
 
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// LDS hand-offs only: global loads stay in flight (see decode_fused.hip)
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int CB, int KS>
-__device__ __forceinline__ const char* wave_frags(const bf16_t* Wp, int w) { return (const char*)(Wp + (int64_t)w * KS * 512); }
-template <int CB, int KS>
-__device__ __forceinline__ bf16x8 ld_frag(const char* wb, unsigned wo, int i) {       // fragment i = (k-step i / CB, column block w + 8 (i % CB))
-    const int ks = i / CB, c = i % CB;
-    return *(const bf16x8*)(wb + ((int64_t)(8 * c) * KS + ks) * 1024 + wo);
-}
-template <int CB, int KS>
-__device__ __forceinline__ void fill_window(bf16x8 (&R)[WIN], const char* wb, int lane) {
-    const unsigned wo = (unsigned)lane * 16u;
-#pragma unroll
-    for (int i = 0; i < WIN; ++i) R[i] = ld_frag<CB, KS>(wb, wo, i);
-}
 // acc[c][rt][r] = sum_k W[n][k] * a[m][k],  m = 16 rt + (lane & 15),  n = (w + 8 c) * 16 + 4 (lane >> 4) + r
 // NEXT (compile time): refill the window from `next` behind the last fragments -- no run-time branch around a load (see pin)
 template <int CB, int KS, int NCB, int NKS, bool NEXT>
@@ -66,8 +50,8 @@ __device__ __forceinline__ void chain_gemm(bf16x8 (&R)[WIN], const char* wb, con
         }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[c][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(R[i % WIN], fa[rt], acc[c][rt], 0, 0, 0);
-        if (i + WIN < F) R[i % WIN] = ld_frag<CB, KS>(wb, wo, i + WIN);
-        else if constexpr (NEXT) R[i % WIN] = ld_frag<NCB, NKS>(next, wo, i + WIN - F);
+        if (i + WIN < F) R[i % WIN] = ld_frag<CB, KS, NW>(wb, wo, i + WIN);
+        else if constexpr (NEXT) R[i % WIN] = ld_frag<NCB, NKS, NW>(next, wo, i + WIN - F);
     }
 }
 
@@ -269,7 +253,7 @@ __global__ __launch_bounds__(512) void dec_chain_a_kernel(const SegA p) {
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
-    fill_window<2, 8>(R, wave_frags<2, 8>(p.wo, w), opaque(lane0));
+    fill_window<2, 8, NW, WIN>(R, wave_frags<2, 8>(p.wo, w), opaque(lane0));
     load_rows(p.ctx, a1, m0, p.M, opaque(tid));
     ResidRegs rr;
     resid_prefetch(p.xres, rr, m0, p.M, w, opaque(lane0));
@@ -303,7 +287,7 @@ __global__ __launch_bounds__(512) void dec_chain_b_kernel(const SegB p) {
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
     CH_STAMP(0);
-    fill_window<2, 8>(R, wave_frags<2, 8>(p.wco, w), opaque(lane0));
+    fill_window<2, 8, NW, WIN>(R, wave_frags<2, 8>(p.wco, w), opaque(lane0));
     load_rows(p.cctx, a1, m0, p.M, opaque(tid));
     ResidRegs rr;
     resid_prefetch(p.x1, rr, m0, p.M, w, opaque(lane0));
@@ -412,7 +396,7 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
-    fill_window<2, 8>(R, wave_frags<2, 8>(p.wp, w), opaque(lane0));
+    fill_window<2, 8, NW, WIN>(R, wave_frags<2, 8>(p.wp, w), opaque(lane0));
     load_rows(p.x, a1, m0, p.M, opaque(tid));
     if (tid < RM) {
         const int m = m0 + tid;
@@ -562,7 +546,7 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
             }
             const int jn = j + 1 < p.nch ? j + 1 : 0;     // (the last refill is unused: no branch around the loads)
 #pragma unroll
-            for (int i = 0; i < WIN; ++i) R[i] = ld_frag<2, 8>(wave_frags<2, 8>(p.wp + (int64_t)jn * 65536, w), wo, i);
+            for (int i = 0; i < WIN; ++i) R[i] = ld_frag<2, 8, NW>(wave_frags<2, 8>(p.wp + (int64_t)jn * 65536, w), wo, i);
         }
         wg_barrier();
     }
@@ -596,7 +580,7 @@ __global__ __launch_bounds__(512) void dec_lin_kernel(const DecLin p) {
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
-    fill_window<CB, KS>(R, wave_frags<CB, KS>(p.wp, w), opaque(lane0));
+    fill_window<CB, KS, NW, WIN>(R, wave_frags<CB, KS>(p.wp, w), opaque(lane0));
     {
         const int t2 = opaque(tid);
 #pragma unroll
@@ -686,7 +670,7 @@ __global__ __launch_bounds__(512) void dec_bwd_seg_kernel(const SegBwd p) {
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
     SEG_STAMP(16);
-    fill_window<2, KS1>(R, wave_frags<2, KS1>(p.wp1, w), opaque(lane0));
+    fill_window<2, KS1, NW, WIN>(R, wave_frags<2, KS1>(p.wp1, w), opaque(lane0));
     {
         const int t2 = opaque(tid);
 #pragma unroll

@@ -87,7 +87,7 @@ int kzv_cross_relayout(const bf16_t* src, bf16_t* dst, int images, int keys, int
 // decode_fused.hip: the whole KV-cached decoder step (embeddings .. LM-head dense) of a generation token in one launch
 #define KZV_DECODE_FUSED_MAX_LAYERS 12
 struct KzvDecodeFusedLayer {
-    const bf16_t *wqkv, *wo, *wcq, *wco, *wfc1, *wfc2;          // bf16 copies in MFMA fragment order (kzv_pack_frag)
+    const bf16_t *wqkv, *wo, *wcq, *wco, *wfc1, *wfc2;          // bf16 copies in MFMA fragment order (kzv_pack_frag_multi)
     const float *bqkv, *bo, *bcq, *bco, *bfc1, *bfc2;
     const float *ln1w, *ln1b, *ln2w, *ln2b, *ln3w, *ln3b;
 };
@@ -110,7 +110,6 @@ int64_t kzv_decode_fused_scales8(int layers);           // floats of the scales
 int kzv_decode_fused_pack8(const KzvDecodeFused8Src* layers, int nlayers, const bf16_t* whd, unsigned char* stream, float* scales, hipStream_t s);
 int kzv_decode_fused_supported(int Hd, int heads, int Fd, int layers, int group, int T, int npa);
 int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s);
-int kzv_pack_frag(const bf16_t* W, bf16_t* out, int N, int K, hipStream_t s);     // [N, K] row-major -> fragment order
 
 // decoder_chain.hip: the linear chains of a decoder layer in the training forward, one launch each (weights in fragment order)
 struct KzvDecChainA {          // s1 = drop(ctx Wo^T + b) + xres;  x1 = LN1(s1);  cq = x1 Wcq^T + b
