@@ -240,6 +240,57 @@ int kzv_set_head_ce(int on);
 int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, const int32_t* d_posids, const uint8_t* d_valid, int64_t ld_valid,
                           float* d_logits, void* stream);
 
+/* ---- Slot-refill greedy decoding of many images (opt-in; kzv/stream.py states the bookkeeping in torch ops) ------------------------
+ * A fixed set of decoder SLOTS (the bound batch: one workgroup of the one-launch step each) works through a WAVE of n_images images
+ * whose cross-attention K/V sit in a pool in decode layout: a slot whose line has ended takes the next unseated image and restarts at
+ * BOS in the very next step, so no step is spent on an ended line while images wait.  Selection and seating run on the device; the
+ * host only polls a counter.  Greedy only; per image the tokens are those of the lockstep greedy generation.
+ *
+ * The bookkeeping by itself (per-op tests): the state arrays live in caller memory.  kzv_stream_seat_first gives the first
+ * min(slots, n_images) images the slots in order (step 0, token bos_id, position id pad_id + 1), marks the rest idle (slot_image = -1)
+ * and sets counters = {next unseated image, lines ended = 0, steps = 0}.  kzv_stream_update takes one step's logits [slots, ld]:
+ *   per live slot (image i at step t): token = the first arg-max column; out_ids[i][t + 1] = token; out_logprob[i][t + 1] = max - lse
+ *   (if given); the line has ended when token == eos_id, t + 2 >= limit[i] (if given) or t + 2 >= max_len;
+ *   then, over all slots: the ended ones take images counters[0], counters[0] + 1, ... in ASCENDING SLOT ORDER (a prefix sum, no
+ *   atomic ticket: the same assignment in every run) and restart at step 0, or go idle when no image is left; the others advance
+ *   (slot_t + 1, their token, position id t + 2 + pad_id); counters += {images seated, lines ended, 1 while a line was open}.
+ * limit [n_images] int32: the most tokens, BOS included, an image may get (values beyond max_len count as max_len, values below 2 as 2).
+ * KZV_E_ARG: a null array other than out_logprob / limit, max_len < 2, rows shorter than max_len, ld < vocab. */
+typedef struct kzv_stream_state {
+    int32_t slots, n_images, max_len, vocab, bos_id, eos_id, pad_id, reserved;
+    int32_t* slot_image; int32_t* slot_t;                /* [slots] */
+    int64_t* tokens; int32_t* posids;                    /* [slots]: the next step's inputs */
+    int32_t* counters;                                   /* [3]: next unseated image, lines ended, steps taken */
+    int32_t* scratch;                                    /* [2 * slots]: selection -> seating */
+    int64_t* out_ids; int64_t ld_ids;                    /* [n_images, ld_ids >= max_len]; the caller fills BOS / padding */
+    float* out_logprob; int64_t ld_logprob;              /* optional [n_images, ld_logprob >= max_len] */
+    const int32_t* limit;                                /* optional [n_images] */
+} kzv_stream_state;
+int kzv_stream_seat_first(const kzv_stream_state* st, void* stream);
+int kzv_stream_update(const kzv_stream_state* st, const float* d_logits, int64_t ld, void* stream);
+/* On the model handle (the bound batch = the slot count; the bound label length >= max_len).
+ * kzv_stream_decode_impl: 1 where the bound geometry gets slot-refill decoding -- exactly where the one-launch step serves one row per
+ * image (hidden 256, 4 heads, FFN 768, <= 12 layers, <= 128 cached and <= 320 patch keys) and kzv_set_decode_one_launch is on -- else 0;
+ * launches nothing; KZV_E_STATE before kzv_model_bind.
+ * kzv_stream_begin: a wave of n_images images over a pool of pool_images >= n_images entries (>= the slot count): checks, (re)allocates
+ * the pool (the library's own, grow-only: Ld * 2 * pool_images * patches * hidden bf16), refreshes the weight packs after a weight
+ * change, zeroes the head's input so that a never-used slot's vocabulary row stays finite.  d_out_ids [n_images, ld_ids] int64 must hold
+ * BOS in column 0 and padding elsewhere.  KZV_E_ARG for a pool smaller than the slot count or the wave, null d_out_ids, max_len < 2 or
+ * beyond the bound length, rows shorter than max_len -- nothing is launched then; KZV_E_STATE where kzv_stream_decode_impl says 0.
+ * kzv_stream_encode: the encoder + cross K/V projection of n images (n divides the bound batch, as kzv_encode_images) into pool entries
+ * first .. first + n - 1.
+ * kzv_stream_start: seats the first images.  kzv_stream_step: one token for every live slot -- the one-launch step (slot instances:
+ * csrc/decode_fused.hip), the vocabulary GEMM, selection and seating; with graph != 0 replayed from a hipGraph captured at the wave's
+ * first step (a single chain of kernel nodes; `stream` must then not be the default stream).
+ * kzv_stream_poll: lines ended and steps taken so far (one stream synchronise); the wave is done when *finished == n_images. */
+int kzv_stream_decode_impl(const kzv_model* m);
+int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids,
+                     float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit, void* stream);
+int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream);
+int kzv_stream_start(kzv_model* m, void* stream);
+int kzv_stream_step(kzv_model* m, int graph, void* stream);
+int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream);
+
 /* loss.backward() for the step above: fills the bound fp32 grad buffer (which must be zero on entry;
  * kzv_zero_grads does that).  Backward is split in `kzv_backward_segments()` segments so the host can
  * launch an RCCL all-reduce for a segment's finished gradients while later segments still run

@@ -11,6 +11,8 @@
 #include <cmath>
 #include <cstdlib>
 
+#define KZV_TRY_RC(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)
+
 namespace {
 
 struct DecAttnP {
@@ -203,6 +205,137 @@ __global__ __launch_bounds__(256) void cross_relayout_kernel(const uint4* __rest
     const int img = r % images; r /= images;
     const int l2 = (int)r;
     dst[t] = src[(((int64_t)img * keys + key) * layers2 + l2) * heads * 8 + h * 8 + c];
+}
+
+// the same copy into a POOL of dst_images images ([layer][K|V][pool image][head][key][64]) at entries first .. first + images - 1:
+// slot-refill decoding keeps the cross-attention K/V of a whole wave of images resident (kzv_stream_encode)
+__global__ __launch_bounds__(256) void cross_relayout_pool_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int images, int keys, int heads,
+                                                                  int layers2, int64_t total16, int dst_images, int first) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total16) return;
+    int64_t r = t;                                  // source-side order: [l2][img][h][key][8 chunks]
+    const int c = r & 7; r >>= 3;
+    const int key = r % keys; r /= keys;
+    const int h = r % heads; r /= heads;
+    const int img = r % images; r /= images;
+    const int l2 = (int)r;
+    dst[((((int64_t)l2 * dst_images + first + img) * heads + h) * keys + key) * 8 + c] = src[(((int64_t)img * keys + key) * layers2 + l2) * heads * 8 + h * 8 + c];
+}
+
+// ---- slot-refill greedy decoding: selection and seating (kzv/stream.py::select_seat is the readable statement these are pinned against) ----
+// A fixed set of decoder SLOTS (one workgroup of the one-launch step each) works through n_images images: slot b holds image
+// slot_image[b] (< 0: idle) at step slot_t[b].  Per step, (1) stream_select_kernel, one workgroup per slot over its logits row: the first
+// arg-max column (greedy_update_kernel's rule) and the row's log-sum-exp; the token goes to out_ids[image][t + 1], the line has ended on
+// EOS or at its limit; (2) stream_seat_kernel, ONE workgroup over all slots: the slots whose lines ended take the next unseated images
+// in ascending slot order (a prefix sum over the ended flags, no atomic ticket: the assignment is the same in every run), the others
+// advance.  Nothing waits on another workgroup; the hand-off between the two is stream order.
+struct StreamP {
+    const float* logits; int64_t ld; int V;
+    int slots, n_images, max_len, bos, eos, pad;
+    int* slot_image; int* slot_t; int64_t* tokens; int* posids;     // [slots]
+    int* counters;                                                  // next unseated image, lines ended, steps taken
+    int* sel;                                                       // [slots][2]: ended, token (select -> seat)
+    int64_t* out_ids; int64_t ld_ids; float* out_lp; int64_t ld_lp; const int* limit;
+};
+
+__global__ __launch_bounds__(256) void stream_select_kernel(const StreamP p) {
+    __shared__ float s_v[4], s_s[4]; __shared__ int s_i[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int img = p.slot_image[b];
+    if (img < 0) {                               // idle (workgroup-uniform, before any barrier)
+        if (tid == 0) p.sel[2 * b] = 0;
+        return;
+    }
+    const float* row = p.logits + (int64_t)b * p.ld;
+    const int V = p.V;
+    constexpr int E = 8;
+    float bv = -INFINITY; int bi = 0x7fffffff;
+    for (int v0 = tid; v0 < V; v0 += 256 * E) {
+        float x[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
+#pragma unroll
+        for (int e = 0; e < E; ++e) { const int v = v0 + e * 256; if (v < V && x[e] > bv) { bv = x[e]; bi = v; } }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { s_v[w] = bv; s_i[w] = bi; }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (s_v[q] > bv || (s_v[q] == bv && s_i[q] < bi)) { bv = s_v[q]; bi = s_i[q]; }
+    // log-sum-exp against the row maximum (the row is in cache): log p(token) = max - lse = -log(sum)
+    float sum = 0.f;
+    for (int v0 = tid; v0 < V; v0 += 256 * E) {
+        float x[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
+#pragma unroll
+        for (int e = 0; e < E; ++e) sum += (v0 + e * 256 < V) ? expf(x[e] - bv) : 0.f;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) s_s[w] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        sum = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
+        const int t = p.slot_t[b];
+        int lim = p.limit ? min(p.limit[img], p.max_len) : p.max_len;
+        if (t + 1 < p.max_len && img < p.n_images) {
+            p.out_ids[(int64_t)img * p.ld_ids + t + 1] = bi;
+            if (p.out_lp) p.out_lp[(int64_t)img * p.ld_lp + t + 1] = -logf(sum);
+        }
+        p.sel[2 * b] = (bi == p.eos || t + 2 >= lim) ? 1 : 0;
+        p.sel[2 * b + 1] = bi;
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_seat_kernel(const StreamP p) {
+    __shared__ int s_w[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int next = p.counters[0];
+    int carry = 0;                               // lines ended in the slots below this pass
+    for (int base = 0; base < p.slots; base += 256) {
+        const int s = base + tid;
+        const bool in = s < p.slots;
+        const int e = in ? p.sel[2 * s] : 0;
+        const unsigned long long mask = __ballot(e != 0);
+        if (lane == 0) s_w[w] = __popcll(mask);
+        __syncthreads();
+        int below = 0, total = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { below += q < w ? s_w[q] : 0; total += s_w[q]; }
+        const int rank = carry + below + __popcll(mask & ((1ull << lane) - 1ull));      // ended slots below slot s
+        if (in) {
+            if (e) {
+                const int ni = next + rank;
+                p.slot_image[s] = ni < p.n_images ? ni : -1;
+                p.slot_t[s] = 0; p.tokens[s] = p.bos; p.posids[s] = p.pad + 1;
+            } else if (p.slot_image[s] >= 0) {
+                const int t = p.slot_t[s];
+                p.slot_t[s] = t + 1; p.tokens[s] = p.sel[2 * s + 1]; p.posids[s] = t + 2 + p.pad;
+            }
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        p.counters[0] = min(next + carry, p.n_images);
+        const int ended = p.counters[1];
+        p.counters[1] = ended + carry;
+        if (ended < p.n_images) p.counters[2] += 1;      // steps issued past the end (the host looks only every few steps) do not count
+    }
+}
+
+// the first min(slots, n_images) images take the slots in order; the other slots are idle
+__global__ void stream_start_kernel(const StreamP p) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s < p.slots) {
+        p.slot_image[s] = s < p.n_images ? s : -1;
+        p.slot_t[s] = 0; p.tokens[s] = p.bos; p.posids[s] = p.pad + 1;
+    }
+    if (s == 0) { p.counters[0] = min(p.slots, p.n_images); p.counters[1] = 0; p.counters[2] = 0; }
 }
 
 // beam re-parenting without moving the cache: dst[b][j] = src[parent[b]][j] for the keys written before this step, and the key
@@ -628,6 +761,41 @@ int kzv_cross_relayout(const bf16_t* src, bf16_t* dst, int images, int keys, int
     hipLaunchKernelGGL(cross_relayout_kernel, dim3((unsigned)((total16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, images, keys, heads,
                        layers2, total16);
     return kzv_check_launch("cross_relayout");
+}
+
+int kzv_cross_relayout_pool(const bf16_t* src, bf16_t* dst, int images, int keys, int heads, int layers2, int dst_images, int first, hipStream_t s) {
+    if (images < 1 || first < 0 || first + images > dst_images) return kzv_fail(KZV_E_ARG, "cross_relayout_pool: entries %d .. %d outside a pool of %d images", first, first + images - 1, dst_images);
+    const int64_t total16 = (int64_t)layers2 * images * heads * keys * 8;
+    hipLaunchKernelGGL(cross_relayout_pool_kernel, dim3((unsigned)((total16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, images, keys, heads,
+                       layers2, total16, dst_images, first);
+    return kzv_check_launch("cross_relayout_pool");
+}
+
+static int stream_params(const kzv_stream_state* st, const float* d_logits, int64_t ld, StreamP* p, const char* who) {
+    if (!st) return kzv_fail(KZV_E_ARG, "%s: null state", who);
+    if (!st->slot_image || !st->slot_t || !st->tokens || !st->posids || !st->counters || !st->scratch) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
+    if (!st->out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
+    if (st->slots < 1 || st->n_images < 1 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "%s: slots, images and vocabulary must be positive", who);
+    if (st->max_len < 2 || st->ld_ids < st->max_len || (st->out_logprob && st->ld_logprob < st->max_len)) return kzv_fail(KZV_E_ARG, "%s: max_len >= 2 columns within the output rows", who);
+    *p = StreamP{d_logits, ld, st->vocab, st->slots, st->n_images, st->max_len, st->bos_id, st->eos_id, st->pad_id, st->slot_image, st->slot_t, st->tokens,
+                 st->posids, st->counters, st->scratch, st->out_ids, st->ld_ids, st->out_logprob, st->ld_logprob, st->limit};
+    return KZV_OK;
+}
+
+extern "C" int kzv_stream_seat_first(const kzv_stream_state* st, void* stream) {
+    StreamP p;
+    KZV_TRY_RC(stream_params(st, nullptr, 0, &p, "stream_seat_first"));
+    hipLaunchKernelGGL(stream_start_kernel, dim3((st->slots + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
+    return kzv_check_launch("stream_seat_first");
+}
+
+extern "C" int kzv_stream_update(const kzv_stream_state* st, const float* d_logits, int64_t ld, void* stream) {
+    StreamP p;
+    KZV_TRY_RC(stream_params(st, d_logits, ld, &p, "stream_update"));
+    if (!d_logits || ld < st->vocab) return kzv_fail(KZV_E_ARG, "stream_update: logits [slots, ld >= vocab]");
+    hipLaunchKernelGGL(stream_select_kernel, dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(stream_seat_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    return kzv_check_launch("stream_update");
 }
 
 extern "C" int kzv_beam_topk(const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,

@@ -271,8 +271,14 @@ struct FusedP8 : FusedP {                                       // the e4m3 inst
     const char* w8; int64_t wave8;                              // the four waves' fragment streams, wave8 bytes each
     const float* sc8;                                           // row scales [layer][SCL], then the head's 256
 };
-template <bool F8> struct FusedArgs { typedef FusedP type; };
-template <> struct FusedArgs<true> { typedef FusedP8 type; };
+// the slot instances' arguments (slot-refill decoding, kzv_stream_*): workgroup b serves image slot_image[b] (< 0: idle) at ITS step
+// slot_t[b]; both derive, so every other instance keeps its argument layout
+struct FusedPS : FusedP { const int* slot_image; const int* slot_t; };
+struct FusedPS8 : FusedP8 { const int* slot_image; const int* slot_t; };
+template <bool F8, bool SL = false> struct FusedArgs { typedef FusedP type; };
+template <> struct FusedArgs<true, false> { typedef FusedP8 type; };
+template <> struct FusedArgs<false, true> { typedef FusedPS type; };
+template <> struct FusedArgs<true, true> { typedef FusedPS8 type; };
 
 // ---- the attention streams (waves 4-7, head h each) ------------------------------------------------------------------------------
 // lane = (row r = lane >> 3 of an 8-key group, 16-byte piece c = lane & 7); iteration i holds key 8 i + r.
@@ -709,14 +715,23 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, float (*scl)[SCL], co
     }
 }
 
-template <int G, int NC, bool F8>      // NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks; F8: e4m3 weights
-__global__ __launch_bounds__(512) void decode_fused_kernel(const typename FusedArgs<F8>::type p) {
+// NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks; F8: e4m3 weights; SL (G = 1): the workgroup is a decoder
+// SLOT -- its image and its step index are two scalar loads at the top (an idle slot leaves before the first barrier: the test is
+// workgroup-uniform), tokens / position ids / head output / self-attention cache stay indexed by the slot.  Every step costs the
+// same at every t and cache rows past t are never used (self_load, self_compute), so a slot restarts at t = 0 without any clean-up.
+template <int G, int NC, bool F8, bool SL = false>
+__global__ __launch_bounds__(512) void decode_fused_kernel(const typename FusedArgs<F8, SL>::type p) {
     __shared__ Lds<G> sm;
     float (*scl)[SCL] = nullptr;                         // the layer's / the next layer's row scales: the e4m3 instances only
     if constexpr (F8) { __shared__ float scl_s[2][SCL]; scl = scl_s; }
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int img = blockIdx.x, b0 = img * G;
-    const int tdev = p.tptr ? min(*p.tptr, p.T - 1) : p.t;
+    static_assert(!SL || G == 1, "a slot holds one sequence");
+    const int b0 = blockIdx.x * G;
+    int img = blockIdx.x, tdev;
+    if constexpr (SL) {
+        img = p.slot_image[blockIdx.x]; tdev = min(p.slot_t[blockIdx.x], p.T - 1);
+        if (img < 0) return;
+    } else tdev = p.tptr ? min(*p.tptr, p.T - 1) : p.t;
     static_assert((12 * 8 + 3 * 32 + 2 * 96) % WIN == 0, "a layer's fragments must fill the window a whole number of times");
     DF_STAMP(0);
     if (w < 4) linear_role<G, F8>(sm, scl, p, w, lane0, b0);
@@ -739,7 +754,9 @@ int kzv_decode_fused_supported(int Hd, int heads, int Fd, int layers, int group,
 int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     if (!kzv_decode_fused_supported(HD, NH, FD, a.nlayers, a.group, a.T, a.npa)) return kzv_fail(KZV_E_ARG, "decode_fused: geometry not instantiated");
     if (a.B % a.group) return kzv_fail(KZV_E_ARG, "decode_fused: rows must be a multiple of the group");
-    if (a.rows && (int64_t)a.B * a.T * HD >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "decode_fused: cache too large");
+    if ((a.rows || a.slot_image) && (int64_t)a.B * a.T * HD >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "decode_fused: cache too large");
+    if ((a.slot_image == nullptr) != (a.slot_t == nullptr)) return kzv_fail(KZV_E_ARG, "decode_fused: a slot's image and step tables go together");
+    if (a.slot_image && (a.group != 1 || a.rows || a.valid || a.tptr)) return kzv_fail(KZV_E_ARG, "decode_fused: slots are single greedy sequences (group 1, no row table, no key flags, no launch-wide step)");
     FusedP p;
     for (int i = 0; i < a.nlayers; ++i) {
         const KzvDecodeFusedLayer& l = a.layers[i];
@@ -755,7 +772,22 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     const bool wide = a.npa > NPMAX;
 #define KZV_DF_PICK(F8_) (!wide ? (a.group == 1 ? decode_fused_kernel<1, 1, F8_> : a.group == 2 ? decode_fused_kernel<2, 1, F8_> : decode_fused_kernel<4, 1, F8_>) \
                                 : (a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS, F8_> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS, F8_> : decode_fused_kernel<4, KZV_DF_CHUNKS, F8_>))
-    if (a.w8) {
+    if (a.slot_image) {
+        if (a.w8) {
+            FusedPS8 ps;
+            static_cast<FusedP&>(ps) = p;
+            ps.w8 = (const char*)a.w8; ps.wave8 = kzv_decode_fused_pack8_bytes(a.nlayers) / 4; ps.sc8 = a.scales8;
+            ps.slot_image = a.slot_image; ps.slot_t = a.slot_t;
+            void (*kern)(const FusedPS8) = wide ? decode_fused_kernel<1, KZV_DF_CHUNKS, true, true> : decode_fused_kernel<1, 1, true, true>;
+            hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, ps);
+        } else {
+            FusedPS ps;
+            static_cast<FusedP&>(ps) = p;
+            ps.slot_image = a.slot_image; ps.slot_t = a.slot_t;
+            void (*kern)(const FusedPS) = wide ? decode_fused_kernel<1, KZV_DF_CHUNKS, false, true> : decode_fused_kernel<1, 1, false, true>;
+            hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, ps);
+        }
+    } else if (a.w8) {
         FusedP8 p8;
         static_cast<FusedP&>(p8) = p;
         p8.w8 = (const char*)a.w8; p8.wave8 = kzv_decode_fused_pack8_bytes(a.nlayers) / 4; p8.sc8 = a.scales8;

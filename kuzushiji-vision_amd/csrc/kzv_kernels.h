@@ -83,6 +83,8 @@ int kzv_attn_decode(const bf16_t* q, int64_t ldq, const bf16_t* knew, const bf16
 int kzv_kv_rows(const int* src, int* dst, const int64_t* parent, int B, int ld, int len, hipStream_t s);
 int kzv_step_inc(int* d_t, hipStream_t s);
 int kzv_cross_relayout(const bf16_t* src, bf16_t* dst, int images, int keys, int heads, int layers2, hipStream_t s);
+// ... into entries first .. first + images - 1 of a pool whose planes hold dst_images images
+int kzv_cross_relayout_pool(const bf16_t* src, bf16_t* dst, int images, int keys, int heads, int layers2, int dst_images, int first, hipStream_t s);
 
 // decode_fused.hip: the whole KV-cached decoder step (embeddings .. LM-head dense) of a generation token in one launch
 #define KZV_DECODE_FUSED_MAX_LAYERS 12
@@ -102,6 +104,9 @@ struct KzvDecodeFused {
     int* rows; float eps;
     // e4m3 weights (both or neither): the stream and the row scales kzv_decode_fused_pack8 wrote; the layers' w* and whd are then not read
     const unsigned char* w8 = nullptr; const float* scales8 = nullptr;
+    // slot-refill decoding (both or neither; group 1, rows / valid / tptr null): workgroup b serves image slot_image[b] (< 0: idle) at
+    // step slot_t[b]; plane2 is then the POOL's image count * npa * Hd
+    const int* slot_image = nullptr; const int* slot_t = nullptr;
 };
 // the e4m3 copies of the linears the step streams, in the order its linear waves consume them, + one power-of-two scale per output row
 struct KzvDecodeFused8Src { const bf16_t *wqkv, *wo, *wcq, *wco, *wfc1, *wfc2; };      // the row-major bf16 copies [N, K]

@@ -263,6 +263,8 @@ extern "C" int kzv_model_destroy(kzv_model* m) {
         if (m->dec_pack) (void)hipFree(m->dec_pack);
         if (m->dec_pack8) (void)hipFree(m->dec_pack8);
         if (m->dec_scale8) (void)hipFree(m->dec_scale8);
+        if (m->spool) (void)hipFree(m->spool);
+        if (m->sstate) (void)hipFree(m->sstate);
         drop_decode_graphs(m);
     }
     delete m;
@@ -343,7 +345,7 @@ extern "C" int kzv_model_bind(kzv_model* m, float* d_params, float* d_grads, voi
     }
     // a captured decode step holds pointers INTO the workspace and the parameter buffer: none survives a rebind
     drop_decode_graphs(m);
-    m->ckv_dec_ok = false; m->dec_pack_ok = false; m->dec_pack8_ok = false;
+    m->ckv_dec_ok = false; m->dec_pack_ok = false; m->dec_pack8_ok = false; m->swave = false;
     m->bound = true; m->have_fwd = false; m->have_enc = false; m->have_dec = false;
     return KZV_OK;
 }

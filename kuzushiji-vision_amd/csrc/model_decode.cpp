@@ -107,8 +107,8 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
 }
 
 // the e4m3 stream and row scales of the same linears (4.7 MB), quantised from their bf16 copies in ONE launch (outside any capture)
-int ensure_dec_pack8(kzv_model* m, hipStream_t s) {
-    if (m->dec_pack8_ok || !decode_e4m3(m)) return KZV_OK;
+static int build_dec_pack8(kzv_model* m, hipStream_t s) {
+    if (m->dec_pack8_ok) return KZV_OK;
     if (!m->dec_pack8) {
         if (hipMalloc((void**)&m->dec_pack8, (size_t)kzv_decode_fused_pack8_bytes(m->Ld)) != hipSuccess ||
             hipMalloc((void**)&m->dec_scale8, sizeof(float) * (size_t)kzv_decode_fused_scales8(m->Ld)) != hipSuccess) {
@@ -127,6 +127,7 @@ int ensure_dec_pack8(kzv_model* m, hipStream_t s) {
     m->dec_pack8_ok = true;
     return KZV_OK;
 }
+int ensure_dec_pack8(kzv_model* m, hipStream_t s) { return decode_e4m3(m) ? build_dec_pack8(m, s) : KZV_OK; }
 
 // ---- one decoder step for the newest token of every sequence ------------------------------------------------------------------
 // What every body gets: the step's operands; tptr != nullptr: the step index is read from device memory (graph replay), `t` is then
@@ -205,12 +206,12 @@ static int decode_step_body_fused(kzv_model* m, const StepArgs& st, hipStream_t 
 
 // The whole step up to the LM head's dense layer in ONE launch (decode_fused.hip: a workgroup per image owns its beams through all
 // layers), then the vocabulary GEMM with the head's LayerNorm folded into its A operand as before.
-static int decode_step_body_one_launch(kzv_model* m, const StepArgs& st, hipStream_t s) {
+// what every one-launch step reads whatever it serves: the weights in fragment order (or the e4m3 stream), embeddings, head, cache
+static int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* who) {
     const int B = m->B, Hd = m->Hd, T = m->T;
     float* P = m->P;
-    KzvDecodeFused a;
     memset(&a, 0, sizeof(a));
-    if (!m->dec_pack_ok) return kzv_fail(KZV_E_STATE, "decode_step: the fragment-ordered decoder weights are stale");
+    if (!m->dec_pack_ok) return kzv_fail(KZV_E_STATE, "%s: the fragment-ordered decoder weights are stale", who);
     const DecPack& pk = m->pk;
     const bf16_t* wp = m->dec_pack;
     for (int i = 0; i < m->Ld; ++i) {
@@ -220,17 +221,25 @@ static int decode_step_body_one_launch(kzv_model* m, const StepArgs& st, hipStre
                                           P + d.qkv.b, P + d.o.b, P + d.cq.b, P + d.co.b, P + d.fc1.b, P + d.fc2.b,
                                           P + d.ln1w, P + d.ln1b, P + d.ln2w, P + d.ln2b, P + d.ln3w, P + d.ln3b};
     }
-    a.nlayers = m->Ld; a.tokens = st.tokens; a.posids = st.posids;
+    a.nlayers = m->Ld;
     a.word = P + m->word.w; a.type0 = P + m->dtype; a.postab = P + m->dpos; a.elnw = P + m->eln_w; a.elnb = P + m->eln_b;
     a.whd = wp + pk.head_dense(); a.bhd = P + m->hd.b; a.hd_out = m->hd_gelu;
     a.cache = m->kvc[m->kv_cur]; a.plane = (int64_t)B * T * Hd;
-    a.ckv = m->ckv_dec; a.plane2 = (int64_t)m->Be * m->npa * Hd;
-    a.valid = st.valid; a.ldvalid = st.ld_valid; a.tptr = st.tptr; a.t = st.t; a.T = T; a.npa = m->npa; a.B = B; a.group = B / m->Be;
-    a.rows = m->rt_cur >= 0 ? m->rowtab[m->rt_cur] : nullptr; a.eps = m->c.ln_eps;
-    if (decode_e4m3(m)) {
-        if (!m->dec_pack8_ok) return kzv_fail(KZV_E_STATE, "decode_step: the e4m3 decoder weights are stale");
+    a.T = T; a.npa = m->npa; a.B = B; a.eps = m->c.ln_eps;
+    if (e4m3) {
+        if (!m->dec_pack8_ok) return kzv_fail(KZV_E_STATE, "%s: the e4m3 decoder weights are stale", who);
         a.w8 = m->dec_pack8; a.scales8 = m->dec_scale8;
     }
+    return KZV_OK;
+}
+
+static int decode_step_body_one_launch(kzv_model* m, const StepArgs& st, hipStream_t s) {
+    KzvDecodeFused a;
+    KZV_TRY(fused_common(m, a, decode_e4m3(m), "decode_step"));
+    a.tokens = st.tokens; a.posids = st.posids;
+    a.ckv = m->ckv_dec; a.plane2 = (int64_t)m->Be * m->npa * m->Hd;
+    a.valid = st.valid; a.ldvalid = st.ld_valid; a.tptr = st.tptr; a.t = st.t; a.group = m->B / m->Be;
+    a.rows = m->rt_cur >= 0 ? m->rowtab[m->rt_cur] : nullptr;
     KZV_TRY(kzv_decode_fused_launch(a, s));
     return vocab_logits(m, true, st.logits, s);
 }
@@ -346,5 +355,128 @@ extern "C" int kzv_decode_reorder(kzv_model* m, const int64_t* d_rows, int len, 
     const int nxt = m->rt_cur < 0 ? 0 : m->rt_cur ^ 1;
     KZV_TRY(kzv_kv_rows(m->rt_cur < 0 ? nullptr : m->rowtab[m->rt_cur], m->rowtab[nxt], d_rows, m->B, m->T, len, (hipStream_t)stream));
     m->rt_cur = nxt;
+    return KZV_OK;
+}
+
+// ---- slot-refill greedy decoding (include/kzv.h: kzv_stream_*) -------------------------------------------------------------------
+static bool stream_supported(const kzv_model* m) {
+    return decode_one_launch_mode() && kzv_decode_fused_supported(m->Hd, m->c.dec_heads, m->Fd, m->Ld, 1, m->T, m->npa);
+}
+extern "C" int kzv_stream_decode_impl(const kzv_model* m) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_decode_impl: model not bound");
+    return stream_supported(m) ? 1 : 0;
+}
+static bool stream_e4m3(const kzv_model* m) { return m->dec_weights == KZV_DECODE_WEIGHTS_E4M3; }
+
+extern "C" int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids,
+                                float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit, void* stream) {
+    // what needs no bound state first: these are argument errors on any handle
+    if (!m) return kzv_fail(KZV_E_ARG, "stream_begin: null model");
+    if (!d_out_ids) return kzv_fail(KZV_E_ARG, "stream_begin: null out_ids");
+    if (max_len < 2) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d: a line is BOS and at least one token", max_len);
+    if (n_images < 1 || n_images > pool_images) return kzv_fail(KZV_E_ARG, "stream_begin: a wave of %d images for a pool of %d", n_images, pool_images);
+    if (ld_ids < max_len || (d_out_logprob && ld_logprob < max_len)) return kzv_fail(KZV_E_ARG, "stream_begin: output rows shorter than max_len");
+    if (!m->bound) return kzv_fail(KZV_E_STATE, "stream_begin: model not bound");
+    m->swave = false;
+    if (pool_images < m->B) return kzv_fail(KZV_E_ARG, "stream_begin: a pool of %d images is smaller than the %d slots", pool_images, m->B);
+    if (bos_id < 0 || bos_id >= m->V || eos_id < 0 || eos_id >= m->V) return kzv_fail(KZV_E_ARG, "stream_begin: BOS / EOS outside the vocabulary");
+    if (max_len > m->L) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d outside 2..%d (the bound length)", max_len, m->L);
+    if (max_len - 1 + m->c.pad_id >= m->c.max_pos) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d needs position id %d, the table has %d rows", max_len, max_len - 1 + m->c.pad_id, m->c.max_pos);
+    if (!stream_supported(m)) return kzv_fail(KZV_E_STATE, "stream_begin: this geometry has no slot-refill decoding (kzv_stream_decode_impl)");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = m->B, V = m->V;
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // it holds the last wave's outputs and counts
+    const size_t bytes = (size_t)m->Ld * 2 * pool_images * m->npa * m->Hd * sizeof(bf16_t);
+    if (bytes > m->spool_bytes) {
+        if (m->spool) (void)hipFree(m->spool);
+        m->spool = nullptr; m->spool_bytes = 0;
+        if (hipMalloc((void**)&m->spool, bytes) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: pool allocation (%zu bytes)", bytes);
+        m->spool_bytes = bytes;
+        drop_decode_graphs(m);
+    }
+    m->spool_images = pool_images;
+    if (!m->sstate || m->sstate_slots < B || m->sstate_V < V) {
+        if (m->sstate) (void)hipFree(m->sstate);
+        m->sstate = nullptr;
+        // logits [B, V] | tokens [B] int64 | slot_image, slot_t, posids [B] | scratch [2 B] | counters [4]
+        const size_t sb = align_up((size_t)B * V * sizeof(float), 256) + (size_t)B * 8 + (size_t)B * 5 * 4 + 16;
+        if (hipMalloc((void**)&m->sstate, sb) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: slot state allocation (%zu bytes)", sb);
+        m->sstate_slots = B; m->sstate_V = V;
+    }
+    char* q = m->sstate;
+    m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
+    kzv_stream_state& st = m->sst;
+    st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
+    st.tokens = (int64_t*)q; q += (size_t)B * 8;
+    st.slot_image = (int32_t*)q; q += (size_t)B * 4;
+    st.slot_t = (int32_t*)q; q += (size_t)B * 4;
+    st.posids = (int32_t*)q; q += (size_t)B * 4;
+    st.scratch = (int32_t*)q; q += (size_t)B * 8;
+    st.counters = (int32_t*)q;
+    st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_logprob = d_out_logprob; st.ld_logprob = ld_logprob; st.limit = d_limit;
+    KZV_TRY(ensure_kv_cache(m));
+    KZV_TRY(ensure_dec_pack(m, s));
+    if (stream_e4m3(m)) KZV_TRY(build_dec_pack8(m, s));
+    m->rt_cur = -1;
+    if (hipMemsetAsync(m->hd_gelu, 0, sizeof(float) * (size_t)B * m->Hd, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: memset");
+    m->train = false; m->have_fwd = false; m->have_dec = false;
+    m->swave = true;
+    return KZV_OK;
+}
+
+extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_encode: model not bound");
+    if (!m->swave) return kzv_fail(KZV_E_STATE, "stream_encode: call kzv_stream_begin first");
+    if (first < 0 || n < 1 || first + n > m->spool_images) return kzv_fail(KZV_E_ARG, "stream_encode: entries %d .. %d outside the pool of %d images", first, first + n - 1, m->spool_images);
+    if ((size_t)m->Ld * 2 * m->spool_images * m->npa * m->Hd * sizeof(bf16_t) > m->spool_bytes) return kzv_fail(KZV_E_STATE, "stream_encode: the image width changed since kzv_stream_begin");
+    KZV_TRY(kzv_encode_images(m, d_pixel_values, n, stream));
+    return kzv_cross_relayout_pool(m->crosskv, m->spool, n, m->npa, m->c.dec_heads, 2 * m->Ld, m->spool_images, first, (hipStream_t)stream);
+}
+
+extern "C" int kzv_stream_start(kzv_model* m, void* stream) {
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_start: call kzv_stream_begin first");
+    return kzv_stream_seat_first(&m->sst, stream);
+}
+
+static int stream_step_body(kzv_model* m, hipStream_t s) {
+    KzvDecodeFused a;
+    KZV_TRY(fused_common(m, a, stream_e4m3(m), "stream_step"));
+    a.tokens = m->sst.tokens; a.posids = m->sst.posids;
+    a.ckv = m->spool; a.plane2 = (int64_t)m->spool_images * m->npa * m->Hd;
+    a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t;
+    KZV_TRY(kzv_decode_fused_launch(a, s));
+    KZV_TRY(vocab_logits(m, true, m->slogits, s));
+    return kzv_stream_update(&m->sst, m->slogits, m->V, s);
+}
+
+extern "C" int kzv_stream_step(kzv_model* m, int graph, void* stream) {
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_step: call kzv_stream_begin first");
+    if (!stream_supported(m)) return kzv_fail(KZV_E_STATE, "stream_step: the geometry or the step mode changed since kzv_stream_begin");
+    hipStream_t s = (hipStream_t)stream;
+    if (!graph) return stream_step_body(m, s);
+    if (!stream) return kzv_fail(KZV_E_ARG, "stream_step: graph replay needs a non-default stream (stream capture)");
+    if (!m->sgraph) {                            // kzv_stream_begin dropped the last wave's: captured at the wave's first step
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_step: begin capture");
+        const int rc = stream_step_body(m, s);
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(s, &g);
+        if (rc != KZV_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
+        if (e != hipSuccess || !g) return kzv_fail(KZV_E_HIP, "stream_step: end capture (%s)", hipGetErrorString(e));
+        const hipError_t ei = hipGraphInstantiate(&m->sgraph, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (ei != hipSuccess) { m->sgraph = nullptr; return kzv_fail(KZV_E_HIP, "stream_step: instantiate (%s)", hipGetErrorString(ei)); }
+    }
+    if (hipGraphLaunch(m->sgraph, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_step: launch");
+    return KZV_OK;
+}
+
+extern "C" int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream) {
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_poll: call kzv_stream_begin first");
+    if (!finished || !steps) return kzv_fail(KZV_E_ARG, "stream_poll: null result");
+    int32_t c[3] = {0, 0, 0};
+    if (hipMemcpyAsync(c, m->sst.counters, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        return kzv_fail(KZV_E_HIP, "stream_poll: copy");
+    *finished = c[1]; *steps = c[2];
     return KZV_OK;
 }

@@ -123,6 +123,12 @@ struct kzv_model {
     hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
     const void* dg_key[3][6] = {};
     int64_t dg_ld[3] = {0, 0, 0};
+    // slot-refill decoding (kzv_stream_*): the pool of cross-attention K/V in decode layout ([layer][K|V][pool image][head][key][64]; the
+    // library's own, grow-only), the slots' state and logits (one allocation, sized by the bound batch), the wave in progress, its graph
+    bf16_t* spool = nullptr; size_t spool_bytes = 0; int spool_images = 0;
+    char* sstate = nullptr; int sstate_slots = 0, sstate_V = 0;
+    kzv_stream_state sst = {}; float* slogits = nullptr; bool swave = false;
+    hipGraphExec_t sgraph = nullptr;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU
@@ -164,6 +170,7 @@ KZV_LOCAL int decode_one_launch_mode(); // KZV_DECODE_ONE_LAUNCH / kzv_set_decod
 // a captured decode step holds pointers into the workspace, the caches and the pack: dropped whenever one of them moves
 static inline void drop_decode_graphs(kzv_model* m) {
     for (int i = 0; i < 3; ++i) if (m->dgraph[i]) { (void)hipGraphExecDestroy(m->dgraph[i]); m->dgraph[i] = nullptr; }
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }
 }
 
 // dropout site ids (distinct hash keys per call site and layer)

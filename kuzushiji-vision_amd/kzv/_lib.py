@@ -61,6 +61,13 @@ class kzv_beam_state(C.Structure):
                 ("unsatisfied", C.c_void_p)]
 
 
+class kzv_stream_state(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("slots", "n_images", "max_len", "vocab", "bos_id", "eos_id", "pad_id", "reserved")] + [
+        ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("tokens", C.c_void_p), ("posids", C.c_void_p), ("counters", C.c_void_p),
+        ("scratch", C.c_void_p), ("out_ids", C.c_void_p), ("ld_ids", C.c_int64), ("out_logprob", C.c_void_p), ("ld_logprob", C.c_int64),
+        ("limit", C.c_void_p)]
+
+
 class kzv_gemm_tn_args(C.Structure):
     _fields_ = [("P", C.c_void_p), ("ldp", C.c_int64), ("Q", C.c_void_p), ("ldq", C.c_int64),
                 ("OUT", C.c_void_p), ("ldo", C.c_int64),
@@ -239,6 +246,14 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "kzv_beam_update": (C.c_int, [C.POINTER(kzv_beam_state), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kzv_beam_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_stream_seat_first": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p]),
+    "kzv_stream_update": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_void_p]),
+    "kzv_stream_decode_impl": (C.c_int, [C.c_void_p]),
+    "kzv_stream_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "kzv_stream_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "kzv_stream_start": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kzv_stream_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "kzv_stream_poll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "kzv_lanczos_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "kzv_preprocess_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -8,6 +8,7 @@ autograd and no fallback path.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 import types
 from typing import Any
@@ -68,6 +69,7 @@ class TrOCRModel:
         self._len_cache = (None, 0)
         self._keep = None                  # inputs of the last engine call (kept alive; align_last reads the labels)
         self.last_active_length = 0
+        self.last_stream_steps = 0
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
         # image_size is the WIDEST crop; batches whose width is one of `width_buckets` (multiples of the patch width, <= it)
         # run with fewer patch tokens and the position rows of the same (h, w) cells (include/kzv.h: kzv_set_image_width).
@@ -531,6 +533,174 @@ class TrOCRModel:
             return out
         finally:
             self.training = was
+
+    # ------------------------------------------------------------------ greedy decoding of many images (slot refill)
+    @property
+    def stream_decode_impl(self) -> str:
+        """"slot-refill" | "static": what ``generate_stream`` on this model runs (kzv_stream_decode_impl: the bound decoder geometry,
+        the crop width of the last call, the kzv_set_decode_one_launch mode).  "static" is lockstep ``generate(num_beams=1)`` over
+        batches of ``slots``: the same results without the saving.  Valid once a generate / generate_stream (or _bind) has bound the
+        model."""
+        rc = L.load().kzv_stream_decode_impl(self._h)
+        if rc < 0:
+            L.check(rc, "kzv_stream_decode_impl")
+        return "slot-refill" if rc == 1 else "static"
+
+    @staticmethod
+    def _waves(pixel_values, wave: int):
+        """[N, C, H, W] or an iterable of such batches -> tensors of exactly ``wave`` images (the last one shorter)."""
+        import torch
+        if torch.is_tensor(pixel_values):
+            pixel_values = (pixel_values,)
+        held, n = [], 0
+        for b in pixel_values:
+            held.append(b); n += b.shape[0]
+            while n >= wave:
+                allb = torch.cat(held) if len(held) > 1 else held[0]
+                yield allb[:wave]
+                held, n = ([allb[wave:]], allb.shape[0] - wave) if allb.shape[0] > wave else ([], 0)
+        if n:
+            yield torch.cat(held) if len(held) > 1 else held[0]
+
+    def generate_stream(self, pixel_values, max_length: int = 128, slots: int | None = None, limits=None, return_logprobs: bool = False,
+                        pool_bytes: int = 4 << 30):
+        """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
+        full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
+        the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
+
+        ``pixel_values``: [N, C, H, W] on host or device, or an iterable of such batches (one crop width).  ``slots`` defaults to the
+        device's compute-unit count (one workgroup of the one-launch step fills a CU).  ``limits``: optional [N] ints, the most tokens,
+        BOS included, each image may get (a bound for junk crops that would otherwise run to max_length).  The images are taken in
+        WAVES as large as ``pool_bytes`` allows (dec_layers * 2 * patches * dec_hidden * 2 bytes of cross-attention K/V per image):
+        a wave is encoded first, then decoded.  Returns int64 [N, <= max_length] in input order -- BOS, the tokens, EOS if emitted,
+        padding -- and with ``return_logprobs`` also fp32 of the same shape, the log-probability of every emitted token at its column.
+        Without ``limits`` each row equals the matching row of ``generate(num_beams=1)``; with them, that row cut at the limit.
+        Where ``stream_decode_impl`` says "static" this IS ``generate(num_beams=1)`` over batches of ``slots`` (log-probabilities then
+        from ``align``)."""
+        import torch
+        c = self.cfg
+        Lh = min(max_length, c.max_pos - c.pad_id - 1)
+        if Lh < 2:
+            raise ValueError("max_length must be at least 2")
+        if slots is None:
+            slots = torch.cuda.get_device_properties(self.device).multi_processor_count
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError("slots must be positive")
+        lim_all = None if limits is None else torch.as_tensor(limits, dtype=torch.int32).reshape(-1).clamp(min=2)
+        ids_out, lp_out, done = [], [], 0
+        self.last_stream_steps = 0               # decoder steps the last call took (every wave; the static path leaves 0)
+        src = iter((pixel_values,) if torch.is_tensor(pixel_values) else pixel_values)
+        first_batch = next(src)
+        src = itertools.chain((first_batch,), src)
+        per_image = c.dec_layers * 2 * (c.image_h // c.patch_h) * (first_batch.shape[3] // c.patch_w) * c.dec_hidden * 2
+        wave = max(slots, int(pool_bytes) // per_image // slots * slots)
+        for px in self._waves(src, wave):
+            n = px.shape[0]
+            lim = None if lim_all is None else lim_all[done:done + n]
+            if lim is not None and lim.numel() != n:
+                raise ValueError("limits must hold one entry per image")
+            ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs)
+            ids_out.append(ids); lp_out.append(lp); done += n
+        ids = torch.cat(ids_out)
+        width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
+        if return_logprobs:
+            return ids[:, :width], torch.cat(lp_out)[:, :width]
+        return ids[:, :width]
+
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool):
+        """One wave of generate_stream: ids [n, Lh] (and log-probabilities [n, Lh] or None)."""
+        import torch
+        from . import stream as ST
+        c = self.cfg
+        lib = L.load()
+        n = px.shape[0]
+        dev = self.device
+        self._check_inputs(px[:1])                                # geometry checks + the active crop width
+        self._bind(slots, Lh)
+        if self.stream_decode_impl == "static":
+            ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
+            lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
+            for a in range(0, n, slots):
+                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1)
+                ids[a:a + g.shape[0], :g.shape[1]] = g
+            if lim is not None:
+                ids = torch.where(torch.arange(Lh, device=dev).view(1, Lh) >= lim.to(dev).view(n, 1), torch.full_like(ids, c.pad_id), ids)
+            if want_lp:
+                for a in range(0, n, slots):
+                    sc = self.align(px[a:a + slots], ids[a:a + slots])
+                    lp[a:a + slots, 1:] = torch.where(sc["live"], sc["logprob"], torch.zeros_like(sc["logprob"]))
+            return ids, lp
+        was = self.training
+        self.training = False
+        ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
+        ids[:, 0] = c.bos_id
+        lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
+        limd = None if lim is None else lim.to(dev).contiguous()
+        pool = -(-n // slots) * slots
+        divisors = [d for d in range(1, slots + 1) if slots % d == 0]
+        graph = os.environ.get("KZV_DECODE_GRAPH", "1") != "0"
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev) if graph else cur
+        if graph:
+            side.wait_stream(cur)
+        keep = []
+        try:
+            with torch.cuda.stream(side):
+                st = L.stream_handle()
+                L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
+                a = 0
+                while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
+                    k = min(slots, n - a)                         # is filled by repeating its last image
+                    d = next(x for x in divisors if x >= k)
+                    chunk = px[a:a + k].to(dev, dtype=torch.float32)
+                    if d > k:
+                        chunk = torch.cat((chunk, chunk[-1:].expand(d - k, -1, -1, -1)))
+                    chunk = chunk.contiguous()
+                    keep.append(chunk)
+                    L.check(lib.kzv_stream_encode(self._h, chunk.data_ptr(), d, a, st), "stream_encode")
+                    a += k
+                L.check(lib.kzv_stream_start(self._h, st), "stream_start")
+                bound = ST.step_bound(n, slots, Lh)
+                fin, took = C.c_int32(0), C.c_int32(0)
+                steps = 0
+                while True:
+                    L.check(lib.kzv_stream_step(self._h, 1 if graph else 0, st), "stream_step")
+                    steps += 1
+                    if steps % 8 == 0 or steps >= bound:          # the host only looks: selection and seating are the device's
+                        L.check(lib.kzv_stream_poll(self._h, C.byref(fin), C.byref(took), st), "stream_poll")
+                        if fin.value >= n:
+                            break
+                        if steps >= bound:
+                            raise L.KzvError(f"generate_stream: {fin.value} of {n} lines ended after {steps} steps; {slots} slots bound them by {bound}")
+                self.last_stream_steps += took.value
+            if graph:
+                cur.wait_stream(side)
+                for t_ in [ids] + keep + [x for x in (lp, limd) if x is not None]:
+                    t_.record_stream(cur)
+            return ids, lp
+        finally:
+            self.training = was
+
+    def recognize_many(self, pixel_values, **kw) -> list[dict]:
+        """``generate_stream`` with its own log-probabilities: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD),
+        ``token_strings``, ``logprobs`` and ``confidence`` = exp(mean log-probability over the tokens, EOS included) -- ``recognize``'s
+        definitions, for greedy decoding, with no teacher-forced second pass.  It returns NO centroids or peak patches: those come
+        from the cross-attention maps of a teacher-forced pass, which ``recognize`` runs.  ``kw``: generate_stream's arguments."""
+        import numpy as np
+        from . import align as A
+        c = self.cfg
+        gen, lp = self.generate_stream(pixel_values, return_logprobs=True, **kw)
+        ids = gen.cpu().numpy()
+        B, W = ids.shape
+        tok = self.tokenizer
+        recs = A.build_records(ids, lp[:, 1:].cpu().numpy(), np.zeros((B, W - 1, 2)), np.zeros((B, W - 1), dtype=np.int64),
+                               pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
+                               texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens)
+        for r in recs:
+            del r["centroids"], r["peak_patches"]
+        return recs
 
     # ------------------------------------------------------------------ Lightning-shaped steps (:323-398)
     def training_step(self, batch, batch_idx):

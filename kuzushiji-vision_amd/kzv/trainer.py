@@ -225,10 +225,11 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     return ck
 
 
-def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0):
+def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0, stream_decode: bool = False):
     """``trainer.test(model, test_loader, ckpt_path="best")`` (scripts/train_trocr.py:193-195): load the best checkpoint,
     switch the optimizer to its eval parameters (on_test_epoch_start, trocr_model.py:441-445), run test_step over the
-    loader, report the epoch means of test_loss / test_cer."""
+    loader, report the epoch means of test_loss / test_cer.  ``stream_decode`` (an extension): also ``test_cer_greedy``, the mean CER
+    of ONE slot-refill greedy decode over the whole loader (``generate_stream``); test_step itself is untouched."""
     if ckpt_path:
         load_checkpoint(model, model.optimizers(), ckpt_path)
     model.eval()
@@ -236,9 +237,19 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
     model.logged.pop("test_loss", None); model.logged.pop("test_cer", None)
     for j, b in enumerate(test_loader):
         model.test_step(b, j)
+    keys = ("test_loss", "test_cer")
+    if stream_decode and model.tokenizer is not None:
+        import torch
+        model.logged.pop("test_cer_greedy", None)
+        gen = model.generate_stream(b["pixel_values"] for b in test_loader)
+        preds = model.tokenizer.batch_decode(gen, skip_special_tokens=True)
+        tgts = model.tokenizer.batch_decode(torch.cat([b["labels"] for b in test_loader]), skip_special_tokens=True)
+        for p, t in zip(preds, tgts):
+            model.log("test_cer_greedy", model.calculate_cer(p, t))
+        keys += ("test_cer_greedy",)
     if model.optimizers() is not None:
         model.optimizers().train()
-    out = {k: (sum(model.logged[k]) / len(model.logged[k]) if model.logged.get(k) else float("nan")) for k in ("test_loss", "test_cer")}
+    out = {k: (sum(model.logged[k]) / len(model.logged[k]) if model.logged.get(k) else float("nan")) for k in keys}
     if rank == 0:
-        log(f"test_loss {out['test_loss']:.4f} test_cer {out['test_cer']:.4f}")
+        log(" ".join(f"{k} {out[k]:.4f}" for k in keys))
     return out

@@ -1,0 +1,79 @@
+"""dev: slot-refill greedy decoding (TrOCRModel.generate_stream) against lockstep generate(num_beams=1) over batches, on a dataset-sized
+decode (the table of profiles/decode_stream.md and DESIGN.md section 7, N1).  The benchmark's geometry: ViT-B encoder, 64 x 640 crops
+(160 patch keys), the reference decoder at 6 and 12 layers; N resident crops; limits = 2 + U{8..60} (seeded) -- an untrained model emits
+no EOS, so the limits ARE the stop times, which is bench.py's label distribution -- and, for the case with nothing to gain, limits = Lh.
+Baseline: generate(num_beams=1, max_length=Lh) over batches of --batch with the same truncation (that code is what the parent commit
+ships).  The two are alternated, each timing includes the encoder and ends on a synchronise; per cell the median of --reps and the
+spread (max - min).  Steps: the stream's own counter; lockstep = sum over batches of (longest limit - 1).
+   python tools/dev/decode_stream_bench.py [--images 4096] [--layers 6 12] [--reps 3] [--slots N] [--batch 256] [--weights bf16 e4m3]"""
+import argparse, dataclasses, os, statistics, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.environ.get("KZV_PKG") or os.path.join(ROOT, "kuzushiji-vision_amd"))
+import torch
+from kzv import _lib as L
+from kzv.config import vit_b_config
+from kzv.data import build_decoder_dir, synthetic_batch
+from kzv.model import TrOCRModel
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--images", type=int, default=4096)
+ap.add_argument("--layers", type=int, nargs="*", default=[6, 12])
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--slots", type=int, default=0, help="0 = the device's compute-unit count (generate_stream's default)")
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--weights", nargs="*", default=["bf16"])
+ap.add_argument("--max_length", type=int, default=128)
+a = ap.parse_args()
+lib = L.load()
+print(f"library {L.LIB_PATH}; {a.images} crops; lockstep batches of {a.batch}")
+print("| layers | weights | limits | lockstep steps | stream steps | step ratio | lockstep ms (spread) | stream ms (spread) | time ratio |")
+print("|---|---|---|---|---|---|---|---|---|")
+
+
+def lockstep(m, x, limits, Lh):
+    out = torch.full((x.shape[0], Lh), m.cfg.pad_id, dtype=torch.int64, device=x.device)
+    steps = 0
+    for s in range(0, x.shape[0], a.batch):
+        # the batch stops where its longest limit does: generate() has no per-row limit, so the baseline is GIVEN that bound
+        top = int(limits[s:s + a.batch].max())
+        g = m.generate(x[s:s + a.batch], max_length=top, num_beams=1)
+        out[s:s + g.shape[0], :g.shape[1]] = g
+        steps += g.shape[1] - 1
+    cols = torch.arange(Lh, device=x.device).view(1, Lh)
+    return torch.where(cols >= limits.to(x.device).view(-1, 1), torch.full_like(out, m.cfg.pad_id), out), steps
+
+
+for layers in a.layers:
+    cfg = vit_b_config(dec_layers=layers)
+    assert cfg.num_patches == 160, cfg.num_patches
+    Lh = min(a.max_length, cfg.max_pos - cfg.pad_id - 1)
+    x = torch.from_numpy(synthetic_batch(cfg, a.batch, 16, seed=3)[0]).cuda()
+    x = x.repeat(-(-a.images // a.batch), 1, 1, 1)[:a.images].contiguous()        # resident crops; their content does not change the step count
+    g = torch.Generator().manual_seed(5)
+    cases = {"2 + U{8..60}": (2 + torch.randint(8, 61, (a.images,), generator=g)).clamp(max=Lh).to(torch.int32),
+             f"all {Lh}": torch.full((a.images,), Lh, dtype=torch.int32)}
+    for fmt in a.weights:
+        with tempfile.TemporaryDirectory() as tmp:
+            m = TrOCRModel(cfg.encoder_config_dict(), build_decoder_dir(os.path.join(tmp, "d"), cfg), init_seed=1, load_tokenizer=False, decode_weights=fmt)
+        m.eval()
+        slots = a.slots or None
+        for name, limits in cases.items():
+            want, lock_steps = lockstep(m, x, limits, Lh)                         # warm both: binds, packs, graphs
+            got = m.generate_stream(x, max_length=Lh, slots=slots, limits=limits)
+            assert m.stream_decode_impl == "slot-refill"
+            same = bool(torch.equal(torch.nn.functional.pad(got, (0, Lh - got.shape[1]), value=cfg.pad_id), want))
+            ts = {"lock": [], "stream": []}
+            for _ in range(a.reps):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                lockstep(m, x, limits, Lh)
+                torch.cuda.synchronize(); ts["lock"].append((time.perf_counter() - t0) * 1e3)
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                m.generate_stream(x, max_length=Lh, slots=slots, limits=limits)
+                torch.cuda.synchronize(); ts["stream"].append((time.perf_counter() - t0) * 1e3)
+            med = {k: statistics.median(v) for k, v in ts.items()}
+            spr = {k: max(v) - min(v) for k, v in ts.items()}
+            print(f"| {layers} | {fmt} | {name} | {lock_steps} | {m.last_stream_steps} | {m.last_stream_steps / lock_steps:.3f} | {med['lock']:.1f} ({spr['lock']:.1f}) | "
+                  f"{med['stream']:.1f} ({spr['stream']:.1f}) | {med['stream'] / med['lock']:.3f} |" + ("" if same else " TOKENS DIFFER"), flush=True)
+        del m
+        torch.cuda.empty_cache()
+    del x
