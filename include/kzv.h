@@ -714,6 +714,12 @@ int kzv_debug_attn_dropout_mask(uint32_t key, float p, int64_t pairs, int32_t Sq
 int kzv_set_cu_reserve(int n);
 int kzv_get_cu_reserve(void);
 
+/* Diagnostic: how often one of the library's process-wide scratch workspaces (split-K partial tiles of the GEMMs, the generic
+ * attention backward, the patch-embedding backward) has moved to a larger block since the library was loaded.  A workspace that
+ * grows keeps its old block allocated for the rest of the process, so a captured graph or a kernel in flight never reads freed
+ * memory; each doubles at least, from 1 MiB, so the count stays small. */
+int64_t kzv_scratch_growths(void);
+
 /* ------------------------------------------------------------------ N2: input pipeline on the device
  * Replaces ResizeWithPadding + ToTensor + Normalize(0.5, 0.5) (src/data/trocr_dataset.py:24-53, 97-104) for a batch of
  * decoded uint8 RGB crops of different sizes: Pillow's two-pass LANCZOS resample (bit-exact: fixed-point coefficients,

@@ -491,16 +491,12 @@ extern "C" int kzv_debug_bwd_stamps(unsigned long long* host128) {
 template <int MODE, int NKT, bool EXACT>
 static void launch_fwd(const AttnP& p, int blocks, hipStream_t s) {
     constexpr int lds = (NKT * 16 + (NKT + 1) / 2 * 32) * 128 + NKT * 16 * 4;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<MODE, NKT, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-    hipLaunchKernelGGL((attn_fwd_kernel<MODE, NKT, EXACT>), dim3(blocks), dim3(256), lds, s, p);
+    kzv_launch_lds<attn_fwd_kernel<MODE, NKT, EXACT>>(dim3(blocks), dim3(256), lds, s, p);
 }
 template <int MODE, int NKT, int NW, bool EXACT>
 static void launch_bwd(const AttnP& p, int blocks, hipStream_t s) {
     constexpr int lds = bwd_lds_bytes(NKT, MODE, bwd_ds(MODE, NKT, NW, EXACT));
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<MODE, NKT, NW, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-    hipLaunchKernelGGL((attn_bwd_kernel<MODE, NKT, NW, EXACT>), dim3(blocks), dim3(NW * 64), lds, s, p);
+    kzv_launch_lds<attn_bwd_kernel<MODE, NKT, NW, EXACT>>(dim3(blocks), dim3(NW * 64), lds, s, p);
 }
 
 // The launch: kzv_attn_launch (attention_api.cpp) sends here what kzv_attn_impl answered KZV_ATTN_MFMA64 for.

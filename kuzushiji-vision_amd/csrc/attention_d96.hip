@@ -358,13 +358,9 @@ int kzv_attn_d96(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     if (int rc = kzv_attn_fill_zero(p, "attn")) return rc;
     const int blocks = a->B * a->heads;
     if (!bwd) {
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)attn96_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FWD_LDS); attr = true; }
-        hipLaunchKernelGGL(attn96_fwd_kernel, dim3(blocks), dim3(NT), FWD_LDS, s, p);
+        kzv_launch_lds<attn96_fwd_kernel>(dim3(blocks), dim3(NT), FWD_LDS, s, p);
         return kzv_check_launch("attn_fwd (head_dim 96)");
     }
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)attn96_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS); attr = true; }
-    hipLaunchKernelGGL(attn96_bwd_kernel, dim3(blocks), dim3(NT), BWD_LDS, s, p);
+    kzv_launch_lds<attn96_bwd_kernel>(dim3(blocks), dim3(NT), BWD_LDS, s, p);
     return kzv_check_launch("attn_bwd (head_dim 96)");
 }

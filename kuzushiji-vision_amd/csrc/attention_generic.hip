@@ -14,7 +14,6 @@
 //             writes dQ and parks dS * scale and P * keep (bf16) in a scratch matrix [pair][Sq][Sk_even];
 //             kernel B, one workgroup per (batch, head, 16 keys): dK = dS^T.Q, dV = (P keep)^T.dO, lane = dimension.
 #include "attention_common.h"
-#include <mutex>
 
 namespace {
 
@@ -181,20 +180,7 @@ __global__ __launch_bounds__(256) void attn_gen_dkv_kernel(const GenP p) {
     }
 }
 
-bf16_t* g_scratch = nullptr;
-size_t g_scratch_elems = 0;
-std::mutex g_mu;
-
-bf16_t* scratch(size_t elems) {          // grow-only, process-global (one device per process; calls are stream-ordered)
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (elems > g_scratch_elems) {
-        if (g_scratch) { (void)hipDeviceSynchronize(); (void)hipFree(g_scratch); g_scratch = nullptr; g_scratch_elems = 0; }
-        void* q = nullptr;
-        if (hipMalloc(&q, elems * sizeof(bf16_t)) != hipSuccess) return nullptr;
-        g_scratch = (bf16_t*)q; g_scratch_elems = elems;
-    }
-    return g_scratch;
-}
+KzvScratch g_scratch;                    // process-global (one device per process; calls are stream-ordered)
 
 }  // namespace
 
@@ -223,7 +209,7 @@ int kzv_attn_generic(const kzv_attn_args* a, int D, bool bwd, hipStream_t s) {
         return kzv_check_launch("attn_fwd (generic head_dim)");
     }
     const size_t per = (size_t)p.B * p.heads * p.Sq * ((p.Sk + 1) & ~1);
-    bf16_t* sc = scratch(2 * per);
+    bf16_t* sc = (bf16_t*)g_scratch.get(2 * per * sizeof(bf16_t));
     if (!sc) return kzv_fail(KZV_E_HIP, "attn_bwd (generic head_dim): %zu bytes of scratch", 2 * per * sizeof(bf16_t));
     p.dSs = sc; p.Pd = sc + per;
     hipLaunchKernelGGL(attn_gen_kernel<true>, grid, dim3(256), lds, s, p);

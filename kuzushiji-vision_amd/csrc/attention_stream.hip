@@ -429,13 +429,6 @@ __global__ __launch_bounds__(256, 2) void stream_bwd_q_kernel(const StreamP p) {
     }
 }
 
-// the dynamic-LDS limit is raised once per kernel, to the most any launch of it asks for (the dK / dV kernel: 4,097 queries)
-template <typename K>
-void launch(K kernel, bool& attr, int max_lds, int blocks, int lds, hipStream_t s, const StreamP& p) {
-    if (!attr) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds); attr = true; }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, s, p);
-}
-
 template <int D>
 int run(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     StreamP p;
@@ -444,17 +437,17 @@ int run(const kzv_attn_args* a, bool bwd, hipStream_t s) {
     const int bh = a->B * a->heads;
     constexpr int IMG2 = 2 * 2 * KB * 2 * D;                  // two buffers of a K and a V block
     constexpr int KV_MAX = kv_ring_bytes<D>() + 2 * ((KZV_ATTN_STREAM_MAX_S + 31) / 32 * 32) * 4;
-    static bool attr_fwd = false, attr_kv = false, attr_q = false;
     if (!bwd) {
         p.nblk = (a->Sq + 127) / 128;
-        launch(stream_fwd_kernel<D>, attr_fwd, IMG2, bh * p.nblk, IMG2, s, p);
+        kzv_launch_lds<stream_fwd_kernel<D>>(dim3(bh * p.nblk), dim3(256), IMG2, s, p);
         return kzv_check_launch(D == 64 ? "attn_stream_fwd (head_dim 64)" : "attn_stream_fwd (head_dim 96)");
     }
     p.nblk = (a->Sk + 64 * kv_tiles<D>() - 1) / (64 * kv_tiles<D>());
-    launch(stream_bwd_kv_kernel<D>, attr_kv, KV_MAX, bh * p.nblk, kv_ring_bytes<D>() + 2 * ((a->Sq + 31) / 32 * 32) * 4, s, p);
+    // the limit is raised to the most any launch of this kernel asks for (4,097 queries)
+    kzv_launch_lds_max<stream_bwd_kv_kernel<D>>(dim3(bh * p.nblk), dim3(256), KV_MAX, kv_ring_bytes<D>() + 2 * ((a->Sq + 31) / 32 * 32) * 4, s, p);
     if (int rc = kzv_check_launch(D == 64 ? "attn_stream_bwd dK/dV (head_dim 64)" : "attn_stream_bwd dK/dV (head_dim 96)")) return rc;
     p.nblk = (a->Sq + 63) / 64;
-    launch(stream_bwd_q_kernel<D>, attr_q, IMG2, bh * p.nblk, IMG2, s, p);
+    kzv_launch_lds<stream_bwd_q_kernel<D>>(dim3(bh * p.nblk), dim3(256), IMG2, s, p);
     return kzv_check_launch(D == 64 ? "attn_stream_bwd dQ (head_dim 64)" : "attn_stream_bwd dQ (head_dim 96)");
 }
 

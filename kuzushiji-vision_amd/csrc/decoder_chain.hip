@@ -844,16 +844,12 @@ int kzv_dec_chain_a(const KzvDecChainA& a, hipStream_t s) {
     p.ctx = a.ctx; p.xres = Resid{a.xres, a.xres_s, a.xres_st, a.xres_g, a.xres_b}; p.wo = a.wo; p.bo = a.bo; p.g1 = a.g1; p.b1 = a.b1; p.wcq = a.wcq; p.bcq = a.bcq;
     p.s1 = a.s1; p.st1 = a.st1; p.x1 = a.x1; p.x1h = a.x1h; p.cq = a.cq; p.M = a.M; p.eps = a.eps;
     p.drop.key = a.drop_key; kzv_drop_params(a.drop_p, &p.drop.thr16, &p.drop.inv_keep);
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)dec_chain_a_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_A); attr_done = true; }
-    hipLaunchKernelGGL(dec_chain_a_kernel, dim3((a.M + RM - 1) / RM), dim3(512), LDS_A, s, p);
+    kzv_launch_lds<dec_chain_a_kernel>(dim3((a.M + RM - 1) / RM), dim3(512), LDS_A, s, p);
     return kzv_check_launch("dec_chain_a");
 }
 
 int kzv_dec_chain_b(const KzvDecChainB& a, hipStream_t s) {
     if (a.M < 1) return kzv_fail(KZV_E_ARG, "dec_chain_b: rows");
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)dec_chain_b_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B); attr_done = true; }
     SegB p;
     p.cctx = a.cctx; p.x1 = Resid{a.x1, a.s1, a.st1, a.g1, a.b1}; p.wco = a.wco; p.bco = a.bco; p.g2 = a.g2; p.b2 = a.b2; p.wfc1 = a.wfc1; p.bfc1 = a.bfc1; p.wfc2 = a.wfc2; p.bfc2 = a.bfc2;
     p.g3 = a.g3; p.b3 = a.b3; p.wqkv = a.wqkv; p.bqkv = a.bqkv;
@@ -861,7 +857,7 @@ int kzv_dec_chain_b(const KzvDecChainB& a, hipStream_t s) {
     p.M = a.M; p.eps = a.eps;
     p.drop3.key = a.drop3_key; kzv_drop_params(a.drop_p, &p.drop3.thr16, &p.drop3.inv_keep);
     p.drop4.key = a.drop4_key; kzv_drop_params(a.drop_p, &p.drop4.thr16, &p.drop4.inv_keep);
-    hipLaunchKernelGGL(dec_chain_b_kernel, dim3((a.M + RM - 1) / RM), dim3(512), LDS_B, s, p);
+    kzv_launch_lds<dec_chain_b_kernel>(dim3((a.M + RM - 1) / RM), dim3(512), LDS_B, s, p);
     return kzv_check_launch("dec_chain_b");
 }
 
@@ -873,9 +869,7 @@ int kzv_dec_lin(const bf16_t* a, const bf16_t* wp, void* out, const float* resid
 #define KZV_DL(CB_, KS_, E_)                                                                                         \
     do {                                                                                                             \
         constexpr int lds = RM * ((KS_ * 32 + 8) * 2 > (E_ == DL_RESID ? (CB_ * 128 + 4) * 4 : (CB_ * 128 + 8) * 2) ? (KS_ * 32 + 8) * 2 : (E_ == DL_RESID ? (CB_ * 128 + 4) * 4 : (CB_ * 128 + 8) * 2)); \
-        static bool attr_done = false;                                                                               \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)dec_lin_kernel<CB_, KS_, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; } \
-        hipLaunchKernelGGL((dec_lin_kernel<CB_, KS_, E_>), grid, dim3(512), lds, s, p);                              \
+        kzv_launch_lds<dec_lin_kernel<CB_, KS_, E_>>(grid, dim3(512), lds, s, p);                                    \
         return kzv_check_launch("dec_lin");                                                                          \
     } while (0)
     if (N == 256 && K == 256 && epi == DL_BF16) KZV_DL(2, 8, DL_BF16);
@@ -899,9 +893,7 @@ int kzv_dec_bwd_seg(const KzvDecBwdSeg& a, hipStream_t s) {
     do {                                                                                                             \
         constexpr int xa = RM * (KS1_ * 32 + 8) * 2, xo = RM * (NP2_ * 256 + 8) * 2, xt = RM * LDS_ * 4;             \
         constexpr int lds = LDS_A1 + (xa > xo ? (xa > xt ? xa : xt) : (xo > xt ? xo : xt));                          \
-        static bool attr_done = false;                                                                               \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)dec_bwd_seg_kernel<KS1_, NP2_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; } \
-        hipLaunchKernelGGL((dec_bwd_seg_kernel<KS1_, NP2_>), grid, dim3(512), lds, s, p);                            \
+        kzv_launch_lds<dec_bwd_seg_kernel<KS1_, NP2_>>(grid, dim3(512), lds, s, p);                                  \
     } while (0)
     if (a.K1 == 256 && !a.aux) KZV_SEG(8, 1);
     else if (a.K1 == 768 && !a.aux) KZV_SEG(24, 1);

@@ -500,13 +500,10 @@ int kzv_embed_assemble_bwd(const float* dx0, bf16_t* dpatch, float* dcls, float*
     const int S = np + 1, total = S * (He / 4), nchunk = (B + EAB_CHUNK - 1) / EAB_CHUNK;
     if (gw <= 0 || gw_max <= 0) gw = gw_max = 1;
     // partial sums [nchunk + 1][S][He] fp32: a process-global scratch grown on demand (calls are stream-ordered)
-    static float* scratch = nullptr; static size_t scratch_floats = 0;
+    static KzvScratch ws;
     const size_t need = (size_t)(nchunk + 1) * S * He;
-    if (need > scratch_floats) {
-        if (scratch) { (void)hipDeviceSynchronize(); (void)hipFree(scratch); scratch = nullptr; scratch_floats = 0; }
-        if (hipMalloc((void**)&scratch, need * sizeof(float)) != hipSuccess) return kzv_fail(KZV_E_HIP, "embed_assemble_bwd: scratch (%zu bytes)", need * sizeof(float));
-        scratch_floats = need;
-    }
+    float* scratch = (float*)ws.get(need * sizeof(float));
+    if (!scratch) return kzv_fail(KZV_E_HIP, "embed_assemble_bwd: scratch (%zu bytes)", need * sizeof(float));
     float* tok = scratch + (size_t)nchunk * S * He;
     hipLaunchKernelGGL(embed_assemble_bwd_part_kernel, dim3(nblk(total, 64), nchunk), dim3(64), 0, s, dx0, dpatch, scratch, B, np, He, thr, ik, key);
     hipLaunchKernelGGL(embed_assemble_bwd_tok_kernel, dim3(nblk(total, 64)), dim3(64), 0, s, scratch, tok, dcls, dpos, nchunk, np, He, gw, gw_max);

@@ -23,18 +23,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int TB = 64;          // tile edge
 constexpr int KB = 32;          // reduction step
 
-// partial-tile workspace (grow-only; calls are stream-ordered)
-float* g_ws = nullptr;
-size_t g_ws_floats = 0;
-float* f32_ws(size_t floats) {
-    if (floats > g_ws_floats) {
-        if (g_ws) { (void)hipDeviceSynchronize(); (void)hipFree(g_ws); g_ws = nullptr; g_ws_floats = 0; }
-        void* q = nullptr;
-        if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return nullptr;
-        g_ws = (float*)q; g_ws_floats = floats;
-    }
-    return g_ws;
-}
+// partial-tile workspace (calls are stream-ordered; a captured training step keeps the block it was given: dev_buf.h)
+KzvScratch g_ws;
 
 struct NtF32 {
     const float* A; const float* B; float* C; const float* bias; const float* resid; float* part;
@@ -231,7 +221,7 @@ extern "C" int kzv_gemm_nt_f32(const kzv_gemm_nt_args* a, int epilogue, void* st
     p.splits = splits;
     hipStream_t s = (hipStream_t)stream;
     if (splits > 1) {
-        p.part = f32_ws((size_t)splits * p.M * p.N);
+        p.part = (float*)g_ws.get(sizeof(float) * splits * p.M * p.N);
         if (!p.part) return kzv_fail(KZV_E_HIP, "gemm_nt_f32: workspace");
     }
     hipLaunchKernelGGL(gemm_nt_f32_kernel, dim3(tiles, splits), dim3(256), 0, s, p);
@@ -257,7 +247,7 @@ extern "C" int kzv_gemm_tn_f32(const kzv_gemm_tn_args* a, void* stream) {
     p.splits = splits;
     hipStream_t s = (hipStream_t)stream;
     if (splits > 1) {
-        p.part = f32_ws((size_t)splits * p.n_store * p.K);
+        p.part = (float*)g_ws.get(sizeof(float) * splits * p.n_store * p.K);
         if (!p.part) return kzv_fail(KZV_E_HIP, "gemm_tn_f32: workspace");
     }
     hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3(tiles, splits), dim3(256), 0, s, p);

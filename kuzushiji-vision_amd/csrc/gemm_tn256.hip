@@ -532,20 +532,18 @@ __global__ __launch_bounds__(256) void gemm_tn256_fold_kernel(const float* part_
 // Invariant of the deferred folds (KzvTnFoldScope, and KzvLnDeferScope in layernorm.hip): the pending lists are process-global and
 // unsynchronised -- ONE host thread issues the launches of a scope, on ONE stream (model.cpp's backward); a scope held open defers
 // every kzv_gemm_tn of the process.  Outputs inside a scope must be distinct (a repeated one is folded first, below).
-// Partial-tile workspace: TN_REGIONS regions of the largest size asked for so far (grow-only; calls are stream-ordered).  Region 0
+// Partial-tile workspace: TN_REGIONS regions of the largest size asked for so far (calls are stream-ordered; dev_buf.h).  Region 0
 // serves a launch whose fold follows at once; regions 1.. the launches of a KzvTnFoldScope (the four weight gradients of an encoder
 // layer), whose folds are ONE launch when the scope closes: a fold is ~5 us of launch latency + ~5 us of data, 49 times per step.
 constexpr int TN_REGIONS = 6;
-float* g_tn_buf = nullptr;
+KzvScratch g_tn_buf;
 size_t g_tn_region = 0;                  // floats per region
 float* tn_partials(size_t floats, int region) {
-    if (floats > g_tn_region) {
-        if (g_tn_buf) { (void)hipDeviceSynchronize(); (void)hipFree(g_tn_buf); g_tn_buf = nullptr; g_tn_region = 0; }
-        void* q = nullptr;
-        if (hipMalloc(&q, (size_t)TN_REGIONS * floats * sizeof(float)) != hipSuccess) return nullptr;
-        g_tn_buf = (float*)q; g_tn_region = floats;
-    }
-    return g_tn_buf + (size_t)region * g_tn_region;
+    const size_t stride = floats > g_tn_region ? floats : g_tn_region;
+    float* base = (float*)g_tn_buf.get((size_t)TN_REGIONS * stride * sizeof(float));
+    if (!base) return nullptr;
+    g_tn_region = stride;
+    return base + (size_t)region * stride;
 }
 
 struct TnFold { const float* ws; float* OUT; int64_t ldo; int n_store, K, tilesK, per, splits, block0; };
@@ -579,7 +577,6 @@ __global__ __launch_bounds__(256) void gemm_tn256_fold_multi_kernel(const TnFold
 }
 int g_tn_defer = 0;
 std::vector<TnFold> g_tn_pending;
-std::vector<size_t> g_tn_pending_floats;
 int tn_flush(hipStream_t s) {
     if (g_tn_pending.empty()) return KZV_OK;
     TnFoldTable t;

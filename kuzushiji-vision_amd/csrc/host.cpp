@@ -24,6 +24,11 @@ int kzv_check_launch(const char* what) {
     return KZV_OK;
 }
 
+// the default allocator pair of KzvDevBuf / KzvScratch (dev_buf.h)
+int kzv_dev_alloc(void** out, size_t bytes) { return hipMalloc(out, bytes) == hipSuccess ? 0 : 1; }
+void kzv_dev_free(void* p) { (void)hipFree(p); }
+extern "C" int64_t kzv_scratch_growths(void) { return g_kzv_scratch_growths.load(); }
+
 const void* kzv_zero_page() {
     static void* page = nullptr;
     static std::once_flag once;

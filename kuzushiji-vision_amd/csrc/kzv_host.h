@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_buf.h"                                   // KzvDevBuf, KzvScratch: how device memory is owned
 
 int kzv_fail(int code, const char* fmt, ...);          // records message, returns code
 int kzv_check_launch(const char* what);                // hipGetLastError -> KZV_E_HIP
@@ -18,11 +19,16 @@ extern "C" uint32_t kzv_drop_key(uint64_t seed, uint32_t site);
 
 // Launch of a kernel that takes more dynamic LDS than the 64 KiB a kernel gets by default: the limit is raised once per kernel (the
 // flag is a static of this template's instantiation, i.e. per kernel), then every call is a plain launch.  The caller checks the launch.
+// kzv_launch_lds_max: a kernel whose launches ask for different amounts; the limit is the most any of them asks for.
+template <auto Kernel, typename... Args>
+inline void kzv_launch_lds_max(dim3 grid, dim3 block, int max_lds_bytes, int lds_bytes, hipStream_t s, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_bytes); attr_done = true; }
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+}
 template <auto Kernel, typename... Args>
 inline void kzv_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); attr_done = true; }
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    kzv_launch_lds_max<Kernel>(grid, block, lds_bytes, lds_bytes, s, args...);
 }
 
 // ---- optional per-launch HIP-event timing of the hot kernels (bench.py's roofline leg) -------------

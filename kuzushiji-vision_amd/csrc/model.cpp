@@ -80,7 +80,7 @@ struct Bump {
 };
 
 // the bf16 copy of a Linear's weight (and its transposed copy) + the cast job that refreshes them
-void take_w(kzv_model* m, Bump& b, Lin& l, bool need_t = true) {
+void take_w(kzv_model_plain* m, Bump& b, Lin& l, bool need_t = true) {
     const int64_t N = l.N, K = l.K;
     W16& w = l.h;
     w.w = b.take<bf16_t>(N * K);
@@ -95,7 +95,7 @@ void take_w(kzv_model* m, Bump& b, Lin& l, bool need_t = true) {
 }
 
 // the e4m3 copy of the TRANSPOSED weight ([K, N], quantised per row from the bf16 transposed copy) + its quantisation job
-void take_w8t(kzv_model* m, Bump& b, Lin& l, float* normmax) {
+void take_w8t(kzv_model_plain* m, Bump& b, Lin& l, float* normmax) {
     const int64_t rows = l.K, cols = l.N;
     l.qt.w = b.take<unsigned char>(rows * cols);
     l.qt.scale = b.take<float>(rows);
@@ -105,7 +105,7 @@ void take_w8t(kzv_model* m, Bump& b, Lin& l, float* normmax) {
 }
 
 // the e4m3 copy of the weight, quantised per output row from the fp32 master
-void take_w8(kzv_model* m, Bump& b, Lin& l) {
+void take_w8(kzv_model_plain* m, Bump& b, Lin& l) {
     const int64_t N = l.N, K = l.K;
     l.q.w = b.take<unsigned char>(N * K);
     l.q.scale = b.take<float>(N);
@@ -114,7 +114,7 @@ void take_w8(kzv_model* m, Bump& b, Lin& l) {
 }
 
 // The ORDER of the take calls is the workspace layout (and the order of the cast / quantisation jobs): every offset depends on it.
-int64_t plan(kzv_model* m, char* base, int B, int L) {
+int64_t plan(kzv_model_plain* m, char* base, int B, int L) {
     Bump b{base};
     const int T = L - 1;
     const int64_t Me = (int64_t)B * m->Se, Mp = (int64_t)B * m->np, Md = (int64_t)B * T;
@@ -257,15 +257,7 @@ extern "C" int kzv_model_destroy(kzv_model* m) {
         if (m->side) (void)hipStreamDestroy(m->side);
         if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
         for (int i = 0; i < 4; ++i) if (m->ev_done[i]) (void)hipEventDestroy(m->ev_done[i]);
-        for (int i = 0; i < 2; ++i) if (m->kvc[i]) (void)hipFree(m->kvc[i]);
-        for (int i = 0; i < 2; ++i) if (m->rowtab[i]) (void)hipFree(m->rowtab[i]);
-        if (m->ckv_dec) (void)hipFree(m->ckv_dec);
-        if (m->dec_pack) (void)hipFree(m->dec_pack);
-        if (m->dec_pack8) (void)hipFree(m->dec_pack8);
-        if (m->dec_scale8) (void)hipFree(m->dec_scale8);
-        if (m->spool) (void)hipFree(m->spool);
-        if (m->sstate) (void)hipFree(m->sstate);
-        drop_decode_graphs(m);
+        drop_decode_graphs(m);       // graphs die before the buffers they point into, which `delete` frees
     }
     delete m;
     return KZV_OK;
@@ -293,7 +285,7 @@ static int check_batch(const kzv_model* m, int batch, int label_len) {
 
 extern "C" int64_t kzv_workspace_bytes(const kzv_model* m, int batch, int label_len) {
     if (!m || check_batch(m, batch, label_len)) return -1;
-    kzv_model tmp = *m;   // plan() only writes pointer fields
+    kzv_model_plain tmp = *m;   // plan() only writes pointer fields
     tmp.P = nullptr;
     return plan(&tmp, nullptr, batch, label_len);
 }

@@ -37,17 +37,21 @@ extern "C" int kzv_decode_weights_impl(const kzv_model* m) {
     return decode_e4m3(m) ? KZV_DECODE_WEIGHTS_E4M3 : KZV_DECODE_WEIGHTS_BF16;
 }
 
+// `bytes` in one of the handle's buffers (false: the allocation failed); a buffer that moved drops the graphs that hold its old pointer
+static bool reserve(kzv_model* m, KzvDevBuf& buf, size_t bytes) {
+    const KzvDevBuf::Result r = buf.reserve(bytes);
+    if (r == KzvDevBuf::MOVED) drop_decode_graphs(m);
+    return r != KzvDevBuf::FAILED;
+}
+
 static int ensure_kv_cache(kzv_model* m) {
-    if (m->kvc[0] && m->kvB == m->B && m->kvT == m->T) return KZV_OK;
-    for (int i = 0; i < 2; ++i) { if (m->kvc[i]) (void)hipFree(m->kvc[i]); m->kvc[i] = nullptr; }
-    for (int i = 0; i < 2; ++i) { if (m->rowtab[i]) (void)hipFree(m->rowtab[i]); m->rowtab[i] = nullptr; }
+    if (m->kvc && m->kvB == m->B && m->kvT == m->T) return KZV_OK;
     // ONE cache [2*Ld][B][T][Hd]: beam steps re-parent rows through the row tables instead of copying into a second cache
     const size_t bytes = (size_t)2 * m->Ld * m->B * m->T * m->Hd * sizeof(bf16_t);
-    if (hipMalloc((void**)&m->kvc[0], bytes) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode_step: KV cache allocation (%zu bytes)", bytes);
-    for (int i = 0; i < 2; ++i)
-        if (hipMalloc((void**)&m->rowtab[i], (size_t)m->B * m->T * sizeof(int)) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode_step: row table allocation");
-    m->kvB = m->B; m->kvT = m->T; m->kv_cur = 0; m->rt_cur = -1;
-    drop_decode_graphs(m);
+    if (!reserve(m, m->kvc, bytes)) return kzv_fail(KZV_E_HIP, "decode_step: KV cache allocation (%zu bytes)", bytes);
+    for (int i = 0; i < 2; ++i) if (!reserve(m, m->rowtab[i], (size_t)m->B * m->T * sizeof(int))) return kzv_fail(KZV_E_HIP, "decode_step: row table allocation");
+    m->kvB = m->B; m->kvT = m->T; m->rt_cur = -1;
+    drop_decode_graphs(m);           // a captured step holds B and T as well: dropped even where every block was large enough
     return KZV_OK;
 }
 
@@ -55,14 +59,8 @@ static int ensure_kv_cache(kzv_model* m) {
 static int ensure_cross_layout(kzv_model* m, hipStream_t s) {
     if (m->ckv_dec_ok) return KZV_OK;
     const size_t bytes = (size_t)m->Ld * 2 * m->Be * m->npa * m->Hd * sizeof(bf16_t);
-    if (bytes > m->ckv_dec_bytes) {
-        if (m->ckv_dec) (void)hipFree(m->ckv_dec);
-        m->ckv_dec = nullptr; m->ckv_dec_bytes = 0;
-        if (hipMalloc((void**)&m->ckv_dec, bytes) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode: cross K/V copy allocation (%zu bytes)", bytes);
-        m->ckv_dec_bytes = bytes;
-        drop_decode_graphs(m);
-    }
-    KZV_TRY(kzv_cross_relayout(m->crosskv, m->ckv_dec, m->Be, m->npa, m->c.dec_heads, 2 * m->Ld, s));
+    if (!reserve(m, m->ckv_dec, bytes)) return kzv_fail(KZV_E_HIP, "decode: cross K/V copy allocation (%zu bytes)", bytes);
+    KZV_TRY(kzv_cross_relayout(m->crosskv, m->ckv_dec.as<bf16_t>(), m->Be, m->npa, m->c.dec_heads, 2 * m->Ld, s));
     m->ckv_dec_ok = true;
     return KZV_OK;
 }
@@ -76,11 +74,8 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
     if (m->dec_pack_ok || !dec_pack_wanted(m)) return KZV_OK;
     const DecPack& pk = m->pk;
     const int Hd = m->Hd;
-    if (!m->dec_pack) {
-        if (hipMalloc((void**)&m->dec_pack, sizeof(bf16_t) * (size_t)pk.total()) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode: weight pack allocation");
-        drop_decode_graphs(m);
-    }
-    bf16_t* const base = m->dec_pack;
+    if (!reserve(m, m->dec_pack, sizeof(bf16_t) * (size_t)pk.total())) return kzv_fail(KZV_E_HIP, "decode: weight pack allocation");
+    bf16_t* const base = m->dec_pack.as<bf16_t>();
     static const DecPack::Which six[6] = {DecPack::QKV, DecPack::O, DecPack::CQ, DecPack::CO, DecPack::FC1, DecPack::FC2};
     std::vector<KzvPackJob> jobs;
     for (int i = 0; i < m->Ld; ++i) {
@@ -109,21 +104,14 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
 // the e4m3 stream and row scales of the same linears (4.7 MB), quantised from their bf16 copies in ONE launch (outside any capture)
 static int build_dec_pack8(kzv_model* m, hipStream_t s) {
     if (m->dec_pack8_ok) return KZV_OK;
-    if (!m->dec_pack8) {
-        if (hipMalloc((void**)&m->dec_pack8, (size_t)kzv_decode_fused_pack8_bytes(m->Ld)) != hipSuccess ||
-            hipMalloc((void**)&m->dec_scale8, sizeof(float) * (size_t)kzv_decode_fused_scales8(m->Ld)) != hipSuccess) {
-            if (m->dec_pack8) (void)hipFree(m->dec_pack8);
-            m->dec_pack8 = nullptr; m->dec_scale8 = nullptr;
-            return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
-        }
-        drop_decode_graphs(m);
-    }
+    if (!reserve(m, m->dec_pack8, (size_t)kzv_decode_fused_pack8_bytes(m->Ld))) return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
+    if (!reserve(m, m->dec_scale8, sizeof(float) * (size_t)kzv_decode_fused_scales8(m->Ld))) return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
     KzvDecodeFused8Src src[KZV_DECODE_FUSED_MAX_LAYERS];
     for (int i = 0; i < m->Ld; ++i) {
         const DecLayerP& d = m->dp[i];
         src[i] = KzvDecodeFused8Src{d.qkv.h.w, d.o.h.w, d.cq.h.w, d.co.h.w, d.fc1.h.w, d.fc2.h.w};
     }
-    KZV_TRY(kzv_decode_fused_pack8(src, m->Ld, m->hd.h.w, m->dec_pack8, m->dec_scale8, s));
+    KZV_TRY(kzv_decode_fused_pack8(src, m->Ld, m->hd.h.w, m->dec_pack8.as<unsigned char>(), m->dec_scale8.as<float>(), s));
     m->dec_pack8_ok = true;
     return KZV_OK;
 }
@@ -165,17 +153,17 @@ static int vocab_logits(kzv_model* m, bool fold_ln, float* d_logits, hipStream_t
 static int self_attn_step(kzv_model* m, int i, const StepArgs& st, hipStream_t s) {
     const DecAct& a = m->da[i];
     const int B = m->B, Hd = m->Hd, T = m->T;
-    bf16_t* cache = m->kvc[m->kv_cur];
+    bf16_t* cache = m->kvc.as<bf16_t>();
     const int64_t plane = (int64_t)B * T * Hd;  // one layer's K (or V) cache
     return kzv_attn_decode(a.qkv, 3 * Hd, a.qkv + Hd, a.qkv + 2 * Hd, 3 * Hd, cache + (int64_t)(2 * i) * plane, cache + (int64_t)(2 * i + 1) * plane,
                            (int64_t)T * Hd, 64, st.valid, st.ld_valid, a.ctx, Hd, B, m->c.dec_heads, st.tptr ? T : st.t + 1, st.t, s, st.tptr, 1,
-                           m->rt_cur >= 0 ? m->rowtab[m->rt_cur] : nullptr, T, (int64_t)T * 64);
+                           m->rt_cur >= 0 ? m->rowtab[m->rt_cur].as<int>() : nullptr, T, (int64_t)T * 64);
 }
 // ... and cross-attention over the image's keys ([layer][K|V][image][head][key][64]; B / Be sequences share an image)
 static int cross_attn_step(kzv_model* m, int i, hipStream_t s) {
     const DecAct& a = m->da[i];
     const int64_t img = (int64_t)m->npa * m->Hd, plane2 = (int64_t)m->Be * img;
-    return kzv_attn_decode(a.cq, m->Hd, nullptr, nullptr, 0, m->ckv_dec + (int64_t)(2 * i) * plane2, m->ckv_dec + (int64_t)(2 * i + 1) * plane2,
+    return kzv_attn_decode(a.cq, m->Hd, nullptr, nullptr, 0, m->ckv_dec.as<bf16_t>() + (int64_t)(2 * i) * plane2, m->ckv_dec.as<bf16_t>() + (int64_t)(2 * i + 1) * plane2,
                            img, 64, nullptr, 0, a.cctx, m->Hd, m->B, m->c.dec_heads, m->npa, -1, s, nullptr, m->B / m->Be, nullptr, 0, (int64_t)m->npa * 64);
 }
 
@@ -213,7 +201,7 @@ static int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* 
     memset(&a, 0, sizeof(a));
     if (!m->dec_pack_ok) return kzv_fail(KZV_E_STATE, "%s: the fragment-ordered decoder weights are stale", who);
     const DecPack& pk = m->pk;
-    const bf16_t* wp = m->dec_pack;
+    const bf16_t* wp = m->dec_pack.as<bf16_t>();
     for (int i = 0; i < m->Ld; ++i) {
         const DecLayerP& d = m->dp[i];
         a.layers[i] = KzvDecodeFusedLayer{wp + pk.fwd(i, DecPack::QKV), wp + pk.fwd(i, DecPack::O), wp + pk.fwd(i, DecPack::CQ), wp + pk.fwd(i, DecPack::CO),
@@ -224,11 +212,11 @@ static int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* 
     a.nlayers = m->Ld;
     a.word = P + m->word.w; a.type0 = P + m->dtype; a.postab = P + m->dpos; a.elnw = P + m->eln_w; a.elnb = P + m->eln_b;
     a.whd = wp + pk.head_dense(); a.bhd = P + m->hd.b; a.hd_out = m->hd_gelu;
-    a.cache = m->kvc[m->kv_cur]; a.plane = (int64_t)B * T * Hd;
+    a.cache = m->kvc.as<bf16_t>(); a.plane = (int64_t)B * T * Hd;
     a.T = T; a.npa = m->npa; a.B = B; a.eps = m->c.ln_eps;
     if (e4m3) {
         if (!m->dec_pack8_ok) return kzv_fail(KZV_E_STATE, "%s: the e4m3 decoder weights are stale", who);
-        a.w8 = m->dec_pack8; a.scales8 = m->dec_scale8;
+        a.w8 = m->dec_pack8.as<unsigned char>(); a.scales8 = m->dec_scale8.as<float>();
     }
     return KZV_OK;
 }
@@ -237,9 +225,9 @@ static int decode_step_body_one_launch(kzv_model* m, const StepArgs& st, hipStre
     KzvDecodeFused a;
     KZV_TRY(fused_common(m, a, decode_e4m3(m), "decode_step"));
     a.tokens = st.tokens; a.posids = st.posids;
-    a.ckv = m->ckv_dec; a.plane2 = (int64_t)m->Be * m->npa * m->Hd;
+    a.ckv = m->ckv_dec.as<bf16_t>(); a.plane2 = (int64_t)m->Be * m->npa * m->Hd;
     a.valid = st.valid; a.ldvalid = st.ld_valid; a.tptr = st.tptr; a.t = st.t; a.group = m->B / m->Be;
-    a.rows = m->rt_cur >= 0 ? m->rowtab[m->rt_cur] : nullptr;
+    a.rows = m->rt_cur >= 0 ? m->rowtab[m->rt_cur].as<int>() : nullptr;
     KZV_TRY(kzv_decode_fused_launch(a, s));
     return vocab_logits(m, true, st.logits, s);
 }
@@ -291,6 +279,22 @@ static int decode_step_check(kzv_model* m, const void* a, const void* b, const v
     return KZV_OK;
 }
 
+// Captures what `body` launches on `s` into an instantiated graph: the capture is ended and the graph destroyed on every path; the
+// body's error comes back as it is, a failure of the capture itself as KZV_E_HIP
+template <typename Body>
+static int capture_into(hipGraphExec_t* out, hipStream_t s, const char* what, Body&& body) {
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: begin capture", what);
+    const int rc = body();
+    hipGraph_t graph = nullptr;
+    const hipError_t e = hipStreamEndCapture(s, &graph);
+    if (rc != KZV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess || !graph) return kzv_fail(KZV_E_HIP, "%s: end capture (%s)", what, hipGetErrorString(e));
+    const hipError_t ei = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ei != hipSuccess) { *out = nullptr; return kzv_fail(KZV_E_HIP, "%s: instantiate (%s)", what, hipGetErrorString(ei)); }
+    return KZV_OK;
+}
+
 extern "C" int kzv_decode_step(kzv_model* m, const int64_t* d_tokens, const int* d_posids, int t, const unsigned char* d_valid,
                                int64_t ld_valid, float* d_logits, void* stream) {
     KZV_TRY(decode_step_check(m, d_tokens, d_posids, d_valid, d_logits, "decode_step"));
@@ -326,21 +330,15 @@ extern "C" int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, cons
     m->train = false; m->have_fwd = false; m->have_dec = false;
     hipStream_t s = (hipStream_t)stream;
     const int g = m->rt_cur + 1;
-    const void* key[6] = {d_tokens, d_posids, d_valid, d_logits, m->kvc[0], (const void*)((intptr_t)m->ckv_dec ^ (intptr_t)(m->npa * 4096 + m->Be) ^ ((intptr_t)decode_one_launch_mode() << 40) ^ ((intptr_t)decode_e4m3(m) << 41))};
+    const void* key[6] = {d_tokens, d_posids, d_valid, d_logits, m->kvc.as<void>(), (const void*)((intptr_t)m->ckv_dec.as<void>() ^ (intptr_t)(m->npa * 4096 + m->Be) ^ ((intptr_t)decode_one_launch_mode() << 40) ^ ((intptr_t)decode_e4m3(m) << 41))};
     bool same = m->dgraph[g] != nullptr && m->dg_ld[g] == ld_valid;
     for (int i = 0; i < 6 && same; ++i) same = m->dg_key[g][i] == key[i];
     if (!same) {                               // (re)capture: the step with its index read from m->d_t, then t += 1
         if (m->dgraph[g]) { (void)hipGraphExecDestroy(m->dgraph[g]); m->dgraph[g] = nullptr; }
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "decode_step_graph: begin capture");
-        int rc = decode_step_body(m, StepArgs{d_tokens, d_posids, 0, m->d_t, d_valid, ld_valid, d_logits}, s);
-        if (rc == KZV_OK) rc = kzv_step_inc(m->d_t, s);
-        hipGraph_t graph = nullptr;
-        const hipError_t e = hipStreamEndCapture(s, &graph);
-        if (rc != KZV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph) return kzv_fail(KZV_E_HIP, "decode_step_graph: end capture (%s)", hipGetErrorString(e));
-        const hipError_t ei = hipGraphInstantiate(&m->dgraph[g], graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) { m->dgraph[g] = nullptr; return kzv_fail(KZV_E_HIP, "decode_step_graph: instantiate (%s)", hipGetErrorString(ei)); }
+        KZV_TRY(capture_into(&m->dgraph[g], s, "decode_step_graph", [&] {
+            KZV_TRY(decode_step_body(m, StepArgs{d_tokens, d_posids, 0, m->d_t, d_valid, ld_valid, d_logits}, s));
+            return kzv_step_inc(m->d_t, s);
+        }));
         for (int i = 0; i < 6; ++i) m->dg_key[g][i] = key[i];
         m->dg_ld[g] = ld_valid;
     }
@@ -349,11 +347,11 @@ extern "C" int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, cons
 }
 
 extern "C" int kzv_decode_reorder(kzv_model* m, const int64_t* d_rows, int len, void* stream) {
-    if (!m || !m->bound || !m->kvc[0]) return kzv_fail(KZV_E_STATE, "decode_reorder: no KV cache (call kzv_decode_step first)");
+    if (!m || !m->bound || !m->kvc) return kzv_fail(KZV_E_STATE, "decode_reorder: no KV cache (call kzv_decode_step first)");
     if (!d_rows || len < 1 || len > m->T) return kzv_fail(KZV_E_ARG, "decode_reorder: rows / length");
     // no cache row moves: the next step's attention reads key j of sequence b from the row of the ancestor that wrote it
     const int nxt = m->rt_cur < 0 ? 0 : m->rt_cur ^ 1;
-    KZV_TRY(kzv_kv_rows(m->rt_cur < 0 ? nullptr : m->rowtab[m->rt_cur], m->rowtab[nxt], d_rows, m->B, m->T, len, (hipStream_t)stream));
+    KZV_TRY(kzv_kv_rows(m->rt_cur < 0 ? nullptr : m->rowtab[m->rt_cur].as<int>(), m->rowtab[nxt].as<int>(), d_rows, m->B, m->T, len, (hipStream_t)stream));
     m->rt_cur = nxt;
     return KZV_OK;
 }
@@ -387,23 +385,15 @@ extern "C" int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int
     const int B = m->B, V = m->V;
     if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // it holds the last wave's outputs and counts
     const size_t bytes = (size_t)m->Ld * 2 * pool_images * m->npa * m->Hd * sizeof(bf16_t);
-    if (bytes > m->spool_bytes) {
-        if (m->spool) (void)hipFree(m->spool);
-        m->spool = nullptr; m->spool_bytes = 0;
-        if (hipMalloc((void**)&m->spool, bytes) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: pool allocation (%zu bytes)", bytes);
-        m->spool_bytes = bytes;
-        drop_decode_graphs(m);
-    }
+    if (!reserve(m, m->spool, bytes)) return kzv_fail(KZV_E_HIP, "stream_begin: pool allocation (%zu bytes)", bytes);
     m->spool_images = pool_images;
     if (!m->sstate || m->sstate_slots < B || m->sstate_V < V) {
-        if (m->sstate) (void)hipFree(m->sstate);
-        m->sstate = nullptr;
         // logits [B, V] | tokens [B] int64 | slot_image, slot_t, posids [B] | scratch [2 B] | counters [4]
         const size_t sb = align_up((size_t)B * V * sizeof(float), 256) + (size_t)B * 8 + (size_t)B * 5 * 4 + 16;
-        if (hipMalloc((void**)&m->sstate, sb) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: slot state allocation (%zu bytes)", sb);
+        if (!reserve(m, m->sstate, sb)) return kzv_fail(KZV_E_HIP, "stream_begin: slot state allocation (%zu bytes)", sb);
         m->sstate_slots = B; m->sstate_V = V;
     }
-    char* q = m->sstate;
+    char* q = m->sstate.as<char>();
     m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
     kzv_stream_state& st = m->sst;
     st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
@@ -428,9 +418,9 @@ extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int 
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_encode: model not bound");
     if (!m->swave) return kzv_fail(KZV_E_STATE, "stream_encode: call kzv_stream_begin first");
     if (first < 0 || n < 1 || first + n > m->spool_images) return kzv_fail(KZV_E_ARG, "stream_encode: entries %d .. %d outside the pool of %d images", first, first + n - 1, m->spool_images);
-    if ((size_t)m->Ld * 2 * m->spool_images * m->npa * m->Hd * sizeof(bf16_t) > m->spool_bytes) return kzv_fail(KZV_E_STATE, "stream_encode: the image width changed since kzv_stream_begin");
+    if ((size_t)m->Ld * 2 * m->spool_images * m->npa * m->Hd * sizeof(bf16_t) > m->spool.capacity()) return kzv_fail(KZV_E_STATE, "stream_encode: the image width changed since kzv_stream_begin");
     KZV_TRY(kzv_encode_images(m, d_pixel_values, n, stream));
-    return kzv_cross_relayout_pool(m->crosskv, m->spool, n, m->npa, m->c.dec_heads, 2 * m->Ld, m->spool_images, first, (hipStream_t)stream);
+    return kzv_cross_relayout_pool(m->crosskv, m->spool.as<bf16_t>(), n, m->npa, m->c.dec_heads, 2 * m->Ld, m->spool_images, first, (hipStream_t)stream);
 }
 
 extern "C" int kzv_stream_start(kzv_model* m, void* stream) {
@@ -442,7 +432,7 @@ static int stream_step_body(kzv_model* m, hipStream_t s) {
     KzvDecodeFused a;
     KZV_TRY(fused_common(m, a, stream_e4m3(m), "stream_step"));
     a.tokens = m->sst.tokens; a.posids = m->sst.posids;
-    a.ckv = m->spool; a.plane2 = (int64_t)m->spool_images * m->npa * m->Hd;
+    a.ckv = m->spool.as<bf16_t>(); a.plane2 = (int64_t)m->spool_images * m->npa * m->Hd;
     a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t;
     KZV_TRY(kzv_decode_fused_launch(a, s));
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
@@ -456,15 +446,7 @@ extern "C" int kzv_stream_step(kzv_model* m, int graph, void* stream) {
     if (!graph) return stream_step_body(m, s);
     if (!stream) return kzv_fail(KZV_E_ARG, "stream_step: graph replay needs a non-default stream (stream capture)");
     if (!m->sgraph) {                            // kzv_stream_begin dropped the last wave's: captured at the wave's first step
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_step: begin capture");
-        const int rc = stream_step_body(m, s);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc != KZV_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess || !g) return kzv_fail(KZV_E_HIP, "stream_step: end capture (%s)", hipGetErrorString(e));
-        const hipError_t ei = hipGraphInstantiate(&m->sgraph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ei != hipSuccess) { m->sgraph = nullptr; return kzv_fail(KZV_E_HIP, "stream_step: instantiate (%s)", hipGetErrorString(ei)); }
+        KZV_TRY(capture_into(&m->sgraph, s, "stream_step", [&] { return stream_step_body(m, s); }));
     }
     if (hipGraphLaunch(m->sgraph, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_step: launch");
     return KZV_OK;

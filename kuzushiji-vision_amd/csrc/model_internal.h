@@ -64,7 +64,8 @@ struct DecPack {
 };
 
 #pragma GCC visibility pop       // the handle's type is the C ABI's (include/kzv.h): default visibility, as ever
-struct kzv_model {
+// What of the handle is plain data (kzv_workspace_bytes plans on a copy of it); the device memory and graphs it owns follow in kzv_model
+struct kzv_model_plain {
     kzv_config c;
     int np, Se, PD, He, Fe, Hd, Fd, V, Vp, Le, Ld;
     int npa = 0, Sa = 0, img_w = 0;   // ACTIVE geometry (kzv_set_image_width): img_w <= c.image_w, npa patches, Sa = npa + 1 tokens
@@ -105,30 +106,19 @@ struct kzv_model {
     // caller's stream (their tails and epilogues fill each other's idle workgroup slots)
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr; hipEvent_t ev_done[4] = {nullptr, nullptr, nullptr, nullptr};
     bool pending[4] = {false, false, false, false}; bool use_side = false, join_each_segment = true;
-    // KV cache of the generation path (kzv_decode_step): two copies [2*Ld][B][T][Hd] (beam re-ordering gathers from one into the other)
-    bf16_t* kvc[2] = {nullptr, nullptr}; int kv_cur = 0, kvB = 0, kvT = 0;
-    // beam re-parenting by indirection: rowtab[x][b][j] = cache row holding key j of sequence b; rt_cur = -1: identity (no table)
-    int* rowtab[2] = {nullptr, nullptr}; int rt_cur = -1;
-    // cross-attention K/V re-laid out for the generation steps ([layer][K|V][image][head][key][64]); rebuilt when the encoder ran
-    bf16_t* ckv_dec = nullptr; size_t ckv_dec_bytes = 0; bool ckv_dec_ok = false;
-    // the decoder's bf16 weights in MFMA fragment order, refreshed after every weight change; pk: where each matrix sits in it
-    bf16_t* dec_pack = nullptr; bool dec_pack_ok = false; DecPack pk;
-    // generation from e4m3 decoder weights (kzv_set_decode_weights): the format asked for, and the e4m3 stream + row scales of the
-    // linears the one-launch step reads (decode_fused.hip), built lazily while the format is e4m3 and refreshed like dec_pack
+    // generation path (kzv_decode_step): the geometry of the KV cache (kzv_model::kvc) and the row table in use (rt_cur = -1: identity)
+    int kvB = 0, kvT = 0, rt_cur = -1;
+    bool ckv_dec_ok = false;     // kzv_model::ckv_dec holds the images encoded last
+    bool dec_pack_ok = false; DecPack pk;      // kzv_model::dec_pack is fresh; pk: where each matrix sits in it
+    // generation from e4m3 decoder weights (kzv_set_decode_weights): the format asked for; kzv_model::dec_pack8 / dec_scale8 are fresh
     int dec_weights = KZV_DECODE_WEIGHTS_BF16;
-    unsigned char* dec_pack8 = nullptr; float* dec_scale8 = nullptr; bool dec_pack8_ok = false;
+    bool dec_pack8_ok = false;
     bool dhln_fused = false;     // the last training forward's head_ce launch already wrote dhln (the LM head's input gradient)
-    // graph-replayed decode step (kzv_decode_step_graph): device-side step index + one instantiated graph per cache copy
-    int* d_t = nullptr;
-    hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
-    const void* dg_key[3][6] = {};
-    int64_t dg_ld[3] = {0, 0, 0};
-    // slot-refill decoding (kzv_stream_*): the pool of cross-attention K/V in decode layout ([layer][K|V][pool image][head][key][64]; the
-    // library's own, grow-only), the slots' state and logits (one allocation, sized by the bound batch), the wave in progress, its graph
-    bf16_t* spool = nullptr; size_t spool_bytes = 0; int spool_images = 0;
-    char* sstate = nullptr; int sstate_slots = 0, sstate_V = 0;
+    int* d_t = nullptr;          // graph-replayed decode step (kzv_decode_step_graph): device-side step index
+    // slot-refill decoding (kzv_stream_*): the images kzv_model::spool holds, the geometry kzv_model::sstate was laid out for, the slots'
+    // state and logits inside it, the wave in progress
+    int spool_images = 0, sstate_slots = 0, sstate_V = 0;
     kzv_stream_state sst = {}; float* slogits = nullptr; bool swave = false;
-    hipGraphExec_t sgraph = nullptr;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU
@@ -148,6 +138,27 @@ struct kzv_model {
     float *dy8_scale = nullptr, *dy8_rq = nullptr, *dy8_rqinv = nullptr, *f8_wnorm = nullptr;
     bool side_ok = false;    // mode 2: set only inside the encoder-layer schedule (everything else stays on the caller's stream)
     int side_mode = 0;       // 0 off, 1 free-running wgrads, 2 wgrads only under the HBM-bound kernels (LayerNorm / attention backward)
+};
+
+// The handle: the plain part plus the device memory of the generation paths, which it owns (dev_buf.h: freed with the handle) and the
+// captured graphs that hold pointers into it.  Graphs die before buffers: a graph handle has no destructor, so kzv_model_destroy calls
+// drop_decode_graphs first and the buffers' destructors run after it; every reserve() that moves a buffer is followed by the same call.
+struct kzv_model : kzv_model_plain {
+    // KV cache of the generation path [2*Ld][B][T][Hd]; beam steps re-parent rows through the two row tables instead of copying it:
+    // rowtab[x][b][j] = cache row holding key j of sequence b
+    KzvDevBuf kvc, rowtab[2];
+    // cross-attention K/V re-laid out for the generation steps ([layer][K|V][image][head][key][64]); rebuilt when the encoder ran
+    KzvDevBuf ckv_dec;
+    // the decoder's bf16 weights in MFMA fragment order (layout: DecPack), refreshed after every weight change; the e4m3 stream + row
+    // scales of the linears the one-launch step reads (decode_fused.hip), built lazily while the format is e4m3 and refreshed alike
+    KzvDevBuf dec_pack, dec_pack8, dec_scale8;
+    // slot-refill decoding: the pool of cross-attention K/V in decode layout ([layer][K|V][pool image][head][key][64]), the slots' state
+    // and logits (one allocation, sized by the bound batch)
+    KzvDevBuf spool, sstate;
+    hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
+    const void* dg_key[3][6] = {};
+    int64_t dg_ld[3] = {0, 0, 0};
+    hipGraphExec_t sgraph = nullptr;                                 // the wave's step
 };
 
 #pragma GCC visibility push(hidden)

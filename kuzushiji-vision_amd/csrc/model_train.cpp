@@ -241,7 +241,7 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
         if (!chain || i == 0) KZV_TRY(lin_fwd(m, d.qkv, xh, Hd, Md, a.qkv, 3 * Hd, KZV_EPI_BF16, s));
         KZV_TRY(attn_fwd(m, dec_self(m, i), s));
         if (chain) {
-            const bf16_t* wp = m->dec_pack;
+            const bf16_t* wp = m->dec_pack.as<bf16_t>();
             // the fp32 LayerNorm outputs x1 / x2 / x3 feed nothing but the next residual add: the chains recompute them from the sums and
             // row statistics the backward needs anyway instead of writing and re-reading them (layer 0 adds the embedding output xd0)
             KzvDecChainA ca{a.ctx, i == 0 ? x : nullptr, wp + pk.fwd(i, DecPack::O), P + d.o.b, hp, key(m, site + 1), P + d.ln1w, P + d.ln1b,
@@ -255,7 +255,7 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
         }
         KZV_TRY(attn_fwd(m, dec_cross(m, i), s));
         if (chain) {
-            const bf16_t* wp = m->dec_pack;
+            const bf16_t* wp = m->dec_pack.as<bf16_t>();
             const bool more = i + 1 < m->Ld;
             KzvDecChainB cb{a.cctx, nullptr, wp + pk.fwd(i, DecPack::CO), P + d.co.b, hp, key(m, site + 3), key(m, site + 4), P + d.ln2w, P + d.ln2b,
                             wp + pk.fwd(i, DecPack::FC1), P + d.fc1.b, wp + pk.fwd(i, DecPack::FC2), P + d.fc2.b, P + d.ln3w, P + d.ln3b,
@@ -278,11 +278,11 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
     // no logits asked for (the training / validation step): head GEMM + log-softmax + NLL + dlogits in ONE launch, the [B*T, Vp] fp32
     // logits never written (decoder_chain.hip head_ce_kernel).  Otherwise the GEMM materialises them and ce_kernel follows.
     if (fused_head) {
-        KzvHeadCE hc{m->hd_ln, m->dec_pack + pk.head(), P + m->word.b, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
+        KzvHeadCE hc{m->hd_ln, m->dec_pack.as<bf16_t>() + pk.head(), P + m->word.b, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
         static int fuse_dh = -1;     // the head's input gradient inside the same launch (KZV_HEAD_DGRAD=0: the separate GEMM)
         if (fuse_dh < 0) fuse_dh = kzv_env_int("KZV_HEAD_DGRAD", 1);
         m->dhln_fused = m->train && fuse_dh && m->word.h.ldt % 8 == 0;
-        if (m->dhln_fused) { hc.wpt = m->dec_pack + pk.head_t(); hc.dh = m->dhln; }
+        if (m->dhln_fused) { hc.wpt = m->dec_pack.as<bf16_t>() + pk.head_t(); hc.dh = m->dhln; }
         KZV_TRY(kzv_head_ce(hc, s));
     } else {
         m->dhln_fused = false;
@@ -319,7 +319,7 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
     if (wide_rows < 0) wide_rows = kzv_env_int("KZV_DEC_DGRAD_WIDE", 0);
     const bool rows_wide = rows_dgrad && wide_rows;
     const DecPack& pk = m->pk;
-    auto tp = [&](int layer, DecPack::Which w) { return (const bf16_t*)(m->dec_pack + pk.tr(layer, w)); };
+    auto tp = [&](int layer, DecPack::Which w) { return (const bf16_t*)(m->dec_pack.as<bf16_t>() + pk.tr(layer, w)); };
     const float hp = dp(m, c.dec_hidden_dropout);
     // ---- CE -> LM head ------------------------------------------------------------------------------
     KZV_TRY(lin_wgrad_batch(m, m->word, CLS_MISC, s, m->dlogits, m->Vp, m->hd_ln, Hd, Md, {.n = m->Vp}));
@@ -332,7 +332,7 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
     // gradient becomes the first GEMM of the top layer's first segment
     const bool segs = rows_dgrad && dec_chain_mode() >= 2 && m->Ld > 0;
     if (!segs) {
-        if (rows_dgrad) KZV_TRY(kzv_dec_lin(m->dy_d, m->dec_pack + pk.head_dense_t(), m->dx_d, nullptr, nullptr, Md, Hd, Hd, 1, s));
+        if (rows_dgrad) KZV_TRY(kzv_dec_lin(m->dy_d, m->dec_pack.as<bf16_t>() + pk.head_dense_t(), m->dx_d, nullptr, nullptr, Md, Hd, Hd, 1, s));
         else KZV_TRY(lin_dgrad(m, m->hd, m->dy_d, Hd, Md, m->dx_d, Hd, KZV_EPI_F32, s));
     }
     KZV_TRY(wgrad_flush(m, s));          // LM head (tied word embedding) + head dense: before dy_d is rewritten
@@ -350,7 +350,7 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
             // (36 problems, 288 tiles of 128 x 128 over all tokens instead of six part-filled grids of ten token splits and their atomics)
             // [head dense | the layer above's qkv] -> LN3 -> fc2 (gelu')
             KZV_TRY(kzv_dec_bwd_seg(KzvDecBwdSeg{top ? m->dy_d : m->da[i + 1].g_dqkv, top ? Hd : 3 * Hd,
-                                                 top ? m->dec_pack + pk.head_dense_t() : tp(i + 1, DecPack::QKV), top ? nullptr : m->dsum_d,
+                                                 top ? m->dec_pack.as<bf16_t>() + pk.head_dense_t() : tp(i + 1, DecPack::QKV), top ? nullptr : m->dsum_d,
                                                  a.s3, a.st3, P + d.ln3w, G + d.ln3w, G + d.ln3b, m->dsum_d, a.g_dy, hp, key(m, site + 4),
                                                  tp(i, DecPack::FC2), a.pre, a.g_dbig, Md}, s));
             KZV_TRY(lin_wgrad_batch(m, d.fc2, CLS_DY, s, a.g_dy, Hd, a.act, Fd, Md));

@@ -229,6 +229,7 @@ SYMBOLS = {
     "kzv_prof_seen": (C.c_int64, [C.c_int]),
     "kzv_set_cu_reserve": (C.c_int, [C.c_int]),
     "kzv_get_cu_reserve": (C.c_int, []),
+    "kzv_scratch_growths": (C.c_int64, []),
     "kzv_decode_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "kzv_decode_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kzv_set_decode_one_launch": (C.c_int, [C.c_int]),

@@ -600,6 +600,32 @@ def test_graph_replayed_fit_steps_equal_eager_ones():
     assert ms[0]._optimizer.step_count == ms[1]._optimizer.step_count == 7
 
 
+def test_a_captured_step_survives_a_workspace_that_grows_under_it():
+    """a captured fit step bakes in the pointer of the fp32 GEMMs' split-K workspace, a later batch geometry with a larger
+    request moves that workspace, and the earlier graph is replayed afterwards.  The workspace retires its old block instead of freeing
+    it (csrc/dev_buf.h), so the replays compute what the launch-by-launch replica computes.  Geometry A (batch 6: split-K launches
+    within the 1 MiB the workspace starts with) is captured, B (batch 12: on an MI355X a fresh process grows at batch 8, 16 and 32)
+    must move a workspace -- kzv_scratch_growths() rises, or this test has not tested anything -- and A runs again from its old graph.  The workspaces are
+    process-wide, so the scenario runs in a process of its own (tests/_ocr_growth_worker.py).  Tolerances: those of
+    test_graph_replayed_fit_steps_equal_eager_ones (the same arithmetic on both sides; the box loss sums with float atomics)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _ocr_growth_worker as W
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_ocr_growth_worker.py"), "6", "12"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][len("RESULT "):])
+    g, e = out["graph"], out["eager"]
+    a_end, b_end = W.A_FIRST - 1, W.A_FIRST + W.B_STEPS - 1
+    print("growths", g["growths"], "captured", g["captured"], "param_err", out["param_err"])
+    assert g["captured"][a_end] == 1, g["captured"]                          # A's step is a graph before B starts
+    assert g["growths"][b_end] > g["growths"][a_end], g["growths"]           # B moved a workspace that A's graph points into
+    assert g["captured"][b_end:] == [2] * (1 + W.A_AGAIN), g["captured"]     # A again: replayed, nothing captured anew
+    assert e["captured"] == [0] * len(out["plan"])
+    assert np.allclose(g["losses"], e["losses"], rtol=1e-5, atol=1e-6), (g["losses"], e["losses"])
+    assert out["param_err"] <= 1e-6, out["param_err"]
+    assert out["buffers_close"]
+    assert out["steps"] == [len(out["plan"])] * 2
+
+
 def test_optimizer_state_round_trips_in_adams_own_layout_and_a_resumed_run_continues_exactly():
     """the OCR checkpoints carry optim.Adam's state (Lightning's ``optimizer_states[0]``).  (1) The state_dict loads into a
     torch.optim.Adam over the oracle's parameters (same registration order) and equals what torch computes from the same gradients;
