@@ -291,6 +291,62 @@ int kzv_stream_start(kzv_model* m, void* stream);
 int kzv_stream_step(kzv_model* m, int graph, void* stream);
 int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream);
 
+/* ---- Beam search on the same slots (opt-in; kzv/stream.py: beam_select_seat / beam_stream state the bookkeeping in torch ops) ------------
+ * Serves decoder.generate(num_beams = 4, early_stopping = True, max_length = 128) as the reference asks for it on every validation and
+ * test image (src/models/trocr_model.py:306-316), over a whole dataset: a slot holds an image's whole beam GROUP (decoder rows slot *
+ * num_beams .. + num_beams - 1) at its own step index and takes the next unseated image the step after its search has ended.  Beam
+ * search is independent per image, so per image the result is that of the lockstep search (kzv_beam_update), in fewer steps.
+ *
+ * The bookkeeping by itself (per-op tests): the state lives in caller memory.  kzv_stream_beam_seat_first seats the first
+ * min(slots, n_images) images, puts every slot's beam state at the start (running scores 0, -1e9, ...; finished scores -1e9, lengths 1,
+ * unsatisfied; tokens bos_id at position id pad_id + 1; token rows BOS + padding) and sets counters = {next unseated image, 0, 0, 0}.
+ * kzv_stream_beam_update takes one step's ranking (kzv_beam_topk over the slots: d_top_scores / d_top_index [slots, 2 * num_beams]):
+ *   per live slot (image i at cur = slot_t + 1): kzv_beam_update's step for that image alone with max_len = min(limit[i], max_len) and
+ *   the divisor divisors[cur]; token rows, scores and the beam row table (rows, optional: new[b][j] = old[parent of b][j] for j <= slot_t)
+ *   are updated in place.  The search has ended when the image is no longer unsatisfied, or its finished list is full and
+ *   early_stopping, or every continuation stopped: then out_ids[i][:fin_len[0]] = fin_seq[0] and out_score[i] = fin_scores[0];
+ *   then, over all slots: seating as kzv_stream_update does it, a reseated slot's beam state back at the start;
+ *   counters += {images seated, searches ended, 1 while a search was open, running continuations that took pad_id}.
+ * A running continuation that takes pad_id breaks what the slots assume (position id = step + 1 + pad_id, every cached key usable): it is
+ * counted, and the caller decodes such a wave again with the lockstep search.
+ * divisors: device fp32 [max_len + 1], entry n = (float)pow((double)n, (double)length_penalty) -- the value kzv_beam_update divides by.
+ * KZV_E_ARG: a null array other than out_score / limit / rows, num_beams other than 2 or 4, max_len outside 2..128, output rows shorter
+ * than max_len, row table rows shorter than max_len - 1. */
+typedef struct kzv_stream_beam_state {
+    int32_t slots, n_images, num_beams, max_len, vocab, bos_id, eos_id, pad_id, early_stopping, reserved;
+    int32_t* slot_image; int32_t* slot_t;                /* [slots] */
+    int64_t* tokens; int32_t* posids;                    /* [slots * num_beams]: the next step's inputs */
+    int64_t* run_seq; int64_t* fin_seq;                  /* [slots, num_beams, max_len] */
+    float* run_scores; float* fin_scores;                /* [slots, num_beams] */
+    uint8_t* fin_done; int64_t* fin_len;                 /* [slots, num_beams] */
+    uint8_t* unsatisfied;                                /* [slots] */
+    int32_t* counters;                                   /* [4] */
+    int32_t* scratch;                                    /* [2 * slots]: update -> seating */
+    int64_t* out_ids; int64_t ld_ids;                    /* [n_images, ld_ids >= max_len]; the caller fills BOS / padding */
+    float* out_score;                                    /* optional [n_images]: HF sequences_scores */
+    const int32_t* limit;                                /* optional [n_images] */
+    const float* divisors;                               /* [max_len + 1] */
+    int32_t* rows; int64_t ld_rows;                      /* optional beam row table [slots * num_beams, ld_rows >= max_len - 1] */
+} kzv_stream_beam_state;
+int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void* stream);
+int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream);
+/* On the model handle: the bound batch = slots * num_beams decoder rows.
+ * kzv_stream_beam_impl: 1 where the bound geometry gets beam search on slots -- where kzv_stream_decode_impl's conditions hold for
+ * num_beams (2 or 4) rows per image, the bound batch is a multiple of num_beams and the vocabulary is within kzv_beam_topk's 16,384 --
+ * else 0; launches nothing; KZV_E_STATE before kzv_model_bind.
+ * kzv_stream_begin_beams: kzv_stream_begin for a wave of beam searches (generate's num_beams, early_stopping, length_penalty): lays the
+ * beam state out in the handle's slot state, builds the divisor table, uses the handle's first beam row table.  d_out_scores: optional
+ * fp32 [n_images].  d_out_logprob must be null (per-token log-probabilities of a beam winner are not produced).  Argument errors as
+ * kzv_stream_begin's, before any launch; the pool must hold at least bound batch / num_beams images.
+ * kzv_stream_encode / kzv_stream_start / kzv_stream_step / kzv_stream_poll then serve the wave as they serve a greedy one; a step is the
+ * one-launch step (slot instances with 2 / 4 rows and the row table), the vocabulary GEMM, kzv_beam_topk and kzv_stream_beam_update, in
+ * one captured graph.  kzv_stream_poll_beams: kzv_stream_poll plus the padding count (counters[3]). */
+int kzv_stream_beam_impl(const kzv_model* m, int num_beams);
+int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_stopping, float length_penalty, float* d_out_scores, int pool_images, int n_images,
+                           int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob, int64_t ld_logprob,
+                           const int32_t* d_limit, void* stream);
+int kzv_stream_poll_beams(kzv_model* m, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream);
+
 /* loss.backward() for the step above: fills the bound fp32 grad buffer (which must be zero on entry;
  * kzv_zero_grads does that).  Backward is split in `kzv_backward_segments()` segments so the host can
  * launch an RCCL all-reduce for a segment's finished gradients while later segments still run

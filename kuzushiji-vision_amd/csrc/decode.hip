@@ -470,102 +470,253 @@ struct BeamUpd {
     float div_fin, div_open;                                      // (cur + 1 - prompt) ** length_penalty, (cur + 1 + 1 - prompt - 1) ** length_penalty as fp32
 };
 
-__global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
+// One image's step, ranked: what one lane works out between the loads and the row copies.  The inputs are filled by the lanes together
+// (read by one lane alone they were as many serial round trips); the outputs are read by all of them.  Shared by beam_update_kernel
+// (every image at the launch's cur) and stream_beam_update_kernel (every slot at its own).
+struct BeamRank {
+    float lp[16]; int64_t ix[16];                                // in: the K ranked continuations
+    float fsc[8]; int64_t flen[8]; unsigned char fdone[8]; unsigned char unsat;      // in: the finished list, the image's unsatisfied flag
+    int src[16], tok[16]; unsigned char hit[16];                 // out: per continuation
+    int nxt[8], mix[8];                                          // out: continuation of running beam i; merged-list entry of finished row i (< nb: an old row)
+};
+struct BeamRankOut {                                             // the ranking lane's own copy of what it stores afterwards
+    float run_new[8], fsc_new[8]; int64_t fl_new[8]; unsigned char fd_new[8];
+    bool un, done_new, all_hits;                                 // still unsatisfied, finished list full, every continuation stopped
+};
+
+// `lim`: the length at which a continuation stops whatever its token (max_len, or the image's own limit)
+__device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, int K, int V, int eos, int cur, int lim, int early, float div_fin, float div_open) {
     constexpr float NEG = -1.0e9f;
-    __shared__ int s_src[16], s_tok[16], s_nxt[8], s_mix[8];
-    __shared__ unsigned char s_hit[16];
+    float s2[16], msc[24];
+    unsigned char mdone[24];
+    bool all_hits = true, all_done = true;
+    for (int i = 0; i < nb; ++i) all_done = all_done && r.fdone[i];
+    const float full_neg = (all_done && early) ? NEG : 0.f;
+    const float unsat_neg = r.unsat ? 0.f : NEG;
+    for (int k = 0; k < K; ++k) {
+        const int64_t ix = r.ix[k];
+        const float lp = r.lp[k];
+        const int src = min((int)(ix / V), nb - 1), tok = (int)min(ix - (int64_t)src * V, (int64_t)V - 1);     // in range whatever a row of NaN logits ranked
+        const bool hit = tok == eos || cur + 1 >= lim;
+        r.src[k] = src; r.tok[k] = tok; r.hit[k] = hit;
+        all_hits = all_hits && hit;
+        s2[k] = lp + (hit ? NEG : 0.f);
+        const bool just = hit && k < nb;
+        float f = lp / div_fin;
+        f = f + full_neg; f = f + unsat_neg; f = f + (just ? 0.f : NEG);
+        msc[nb + k] = f; mdone[nb + k] = just;
+    }
+    // running beams of the next step: the best nb continuations that did not stop (equal scores: the smaller rank first)
+    unsigned used = 0;
+    for (int i = 0; i < nb; ++i) {
+        int best = -1;
+        for (int k = 0; k < K; ++k) if (!((used >> k) & 1u) && (best < 0 || s2[k] > s2[best])) best = k;
+        used |= 1u << best;
+        r.nxt[i] = best; o.run_new[i] = s2[best];
+    }
+    // finished list: best nb of (old finished, stopped continuations of rank < nb)
+    int64_t mlen[24];
+    for (int i = 0; i < nb; ++i) { msc[i] = r.fsc[i]; mdone[i] = r.fdone[i]; mlen[i] = r.flen[i]; }
+    for (int k = 0; k < K; ++k) mlen[nb + k] = cur + 1;
+    used = 0;
+    for (int i = 0; i < nb; ++i) {
+        int best = -1;
+        for (int k = 0; k < nb + K; ++k) if (!((used >> k) & 1u) && (best < 0 || msc[k] > msc[best])) best = k;
+        used |= 1u << best;
+        r.mix[i] = best; o.fsc_new[i] = msc[best]; o.fd_new[i] = mdone[best]; o.fl_new[i] = mlen[best];
+    }
+    float fmin = o.fsc_new[0];
+    bool done_new = true;
+    for (int i = 0; i < nb; ++i) { fmin = fminf(fmin, o.fsc_new[i]); done_new = done_new && o.fd_new[i]; }
+    // can the best open beam still beat the worst finished one?
+    const float best_open = o.run_new[0] / div_open;
+    bool any = false;
+    for (int i = 0; i < nb; ++i) any = any || best_open > (o.fd_new[i] ? fmin : NEG);
+    o.un = r.unsat && any; o.done_new = done_new; o.all_hits = all_hits;
+}
+
+__global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
+    __shared__ BeamRank r;
     const int img = blockIdx.x, lane = threadIdx.x;
     const int nb = p.nb, K = p.K, L = p.L;
     if (p.flags[3]) return;                      // the search has ended (beam_stop_kernel): steps issued before the host noticed change nothing
-    // the ~40 state words of this image: one load per lane, together (read by lane 0 alone they were as many serial round trips)
-    __shared__ float s_lp[16], s_fsc[8];
-    __shared__ int64_t s_ix[16], s_flen[8];
-    __shared__ unsigned char s_fdone[8];
-    __shared__ unsigned char s_unsat;
-    if (lane < K) { s_lp[lane] = p.top_lp[(int64_t)img * K + lane]; s_ix[lane] = p.top_ix[(int64_t)img * K + lane]; }
+    // the ~40 state words of this image: one load per lane, together
+    if (lane < K) { r.lp[lane] = p.top_lp[(int64_t)img * K + lane]; r.ix[lane] = p.top_ix[(int64_t)img * K + lane]; }
     if (lane >= 16 && lane < 16 + nb) {
         const int i = lane - 16;
-        s_fsc[i] = p.fin_sc[img * nb + i]; s_fdone[i] = p.fin_done[img * nb + i]; s_flen[i] = p.fin_len[img * nb + i];
+        r.fsc[i] = p.fin_sc[img * nb + i]; r.fdone[i] = p.fin_done[img * nb + i]; r.flen[i] = p.fin_len[img * nb + i];
     }
-    if (lane == 32) s_unsat = p.unsat[img];
+    if (lane == 32) r.unsat = p.unsat[img];
     __syncthreads();
     if (lane == 0) {
-        float s2[16], msc[24];
-        unsigned char mdone[24];
-        bool all_hits = true, all_done = true;
-        for (int i = 0; i < nb; ++i) all_done = all_done && s_fdone[i];
-        const float full_neg = (all_done && p.early) ? NEG : 0.f;
-        const float unsat_neg = s_unsat ? 0.f : NEG;
-        for (int k = 0; k < K; ++k) {
-            const int64_t ix = s_ix[k];
-            const float lp = s_lp[k];
-            const int src = (int)(ix / p.V), tok = (int)(ix - (int64_t)src * p.V);
-            const bool hit = tok == p.eos || p.cur + 1 >= L;
-            s_src[k] = src; s_tok[k] = tok; s_hit[k] = hit;
-            all_hits = all_hits && hit;
-            s2[k] = lp + (hit ? NEG : 0.f);
-            const bool just = hit && k < nb;
-            float f = lp / p.div_fin;
-            f = f + full_neg; f = f + unsat_neg; f = f + (just ? 0.f : NEG);
-            msc[nb + k] = f; mdone[nb + k] = just;
-        }
-        // running beams of the next step: the best nb continuations that did not stop (equal scores: the smaller rank first)
-        unsigned used = 0;
-        float run_new[8];
+        BeamRankOut o;
+        beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, p.div_fin, p.div_open);
         for (int i = 0; i < nb; ++i) {
-            int best = -1;
-            for (int k = 0; k < K; ++k) if (!((used >> k) & 1u) && (best < 0 || s2[k] > s2[best])) best = k;
-            used |= 1u << best;
-            s_nxt[i] = best; run_new[i] = s2[best];
-            p.rows[img * nb + i] = (int64_t)img * nb + s_src[best];
+            p.rows[img * nb + i] = (int64_t)img * nb + r.src[r.nxt[i]];
+            p.run_sc[img * nb + i] = o.run_new[i];
+            p.fin_sc[img * nb + i] = o.fsc_new[i]; p.fin_done[img * nb + i] = o.fd_new[i]; p.fin_len[img * nb + i] = o.fl_new[i];
         }
-        for (int i = 0; i < nb; ++i) p.run_sc[img * nb + i] = run_new[i];
-        // finished list: best nb of (old finished, stopped continuations of rank < nb)
-        int64_t mlen[24];
-        for (int i = 0; i < nb; ++i) { msc[i] = s_fsc[i]; mdone[i] = s_fdone[i]; mlen[i] = s_flen[i]; }
-        for (int k = 0; k < K; ++k) mlen[nb + k] = p.cur + 1;
-        used = 0;
-        float fsc_new[8]; unsigned char fd_new[8]; int64_t fl_new[8];
-        for (int i = 0; i < nb; ++i) {
-            int best = -1;
-            for (int k = 0; k < nb + K; ++k) if (!((used >> k) & 1u) && (best < 0 || msc[k] > msc[best])) best = k;
-            used |= 1u << best;
-            s_mix[i] = best; fsc_new[i] = msc[best]; fd_new[i] = mdone[best]; fl_new[i] = mlen[best];
-        }
-        float fmin = fsc_new[0];
-        bool done_new = true;
-        for (int i = 0; i < nb; ++i) {
-            p.fin_sc[img * nb + i] = fsc_new[i]; p.fin_done[img * nb + i] = fd_new[i]; p.fin_len[img * nb + i] = fl_new[i];
-            fmin = fminf(fmin, fsc_new[i]); done_new = done_new && fd_new[i];
-        }
-        // can the best open beam still beat the worst finished one?
-        const float best_open = run_new[0] / p.div_open;
-        bool any = false;
-        for (int i = 0; i < nb; ++i) any = any || best_open > (fd_new[i] ? fmin : NEG);
-        const bool un = s_unsat && any;
-        p.unsat[img] = un;
-        if (un) atomicAdd(p.flags + 0, 1);
-        if (!done_new) atomicAdd(p.flags + 1, 1);
-        if (!all_hits) atomicAdd(p.flags + 2, 1);
+        p.unsat[img] = o.un;
+        if (o.un) atomicAdd(p.flags + 0, 1);
+        if (!o.done_new) atomicAdd(p.flags + 1, 1);
+        if (!o.all_hits) atomicAdd(p.flags + 2, 1);
     }
     __syncthreads();
-    // token rows: next running beams = continuation s_nxt[i]; finished rows = old finished row or a continuation
+    // token rows: next running beams = continuation nxt[i]; finished rows = old finished row or a continuation
     for (int i = 0; i < nb; ++i) {
-        const int k = s_nxt[i];
-        const int64_t* src = p.run_seq_in + ((int64_t)img * nb + s_src[k]) * L;
+        const int k = r.nxt[i];
+        const int64_t* src = p.run_seq_in + ((int64_t)img * nb + r.src[k]) * L;
         int64_t* dst = p.run_seq_out + ((int64_t)img * nb + i) * L;
-        for (int j = lane; j < L; j += 64) dst[j] = j == p.cur ? (int64_t)s_tok[k] : src[j];
-        const int mi = s_mix[i];
+        for (int j = lane; j < L; j += 64) dst[j] = j == p.cur ? (int64_t)r.tok[k] : src[j];
+        const int mi = r.mix[i];
         int64_t* fdst = p.fin_seq_out + ((int64_t)img * nb + i) * L;
         if (mi < nb) {
             const int64_t* fsrc = p.fin_seq_in + ((int64_t)img * nb + mi) * L;
             for (int j = lane; j < L; j += 64) fdst[j] = fsrc[j];
         } else {
             const int kk = mi - nb;
-            const int64_t* csrc = p.run_seq_in + ((int64_t)img * nb + s_src[kk]) * L;
-            for (int j = lane; j < L; j += 64) fdst[j] = j == p.cur ? (int64_t)s_tok[kk] : csrc[j];
+            const int64_t* csrc = p.run_seq_in + ((int64_t)img * nb + r.src[kk]) * L;
+            for (int j = lane; j < L; j += 64) fdst[j] = j == p.cur ? (int64_t)r.tok[kk] : csrc[j];
         }
     }
+}
+
+// ---- beam search on device-refilled slots (kzv/stream.py::beam_select_seat is the readable statement these are pinned against) ----
+// A slot holds an image's whole beam group: decoder rows slot * nb .. slot * nb + nb - 1 at the slot's own step index.  Per step, after
+// beam_topk_kernel has ranked every slot's 2 nb continuations: (1) stream_beam_update_kernel, one workgroup per slot: beam_rank at
+// cur = slot_t + 1 with the slot's own divisor, then the token rows, the beam row table and the scores in place -- the slot's old rows
+// are staged in LDS first, since ONE captured graph serves every step and there is no even / odd buffer to alternate; when the image's
+// search has ended, its best finished row and score go to the outputs; (2) stream_beam_seat_kernel, ONE workgroup over all slots:
+// stream_seat_kernel's prefix sum, the reset of every reseated slot's beam state, the counters.
+struct StreamBeamP {
+    const float* top_lp; const int64_t* top_ix;                     // [slots, 2 nb]
+    int slots, n_images, nb, L, V, bos, eos, pad, early;
+    int* slot_image; int* slot_t; int64_t* tokens; int* posids;     // [slots], [slots * nb]
+    int64_t* run_seq; int64_t* fin_seq;                             // [slots, nb, L]
+    float* run_sc; float* fin_sc; unsigned char* fin_done; int64_t* fin_len; unsigned char* unsat;
+    int* counters;                                                  // next unseated image, searches ended, steps taken, running continuations that took padding
+    int* sel;                                                       // [slots][2]: ended, continuations that took padding (update -> seat)
+    int64_t* out_ids; int64_t ld_ids; float* out_score; const int* limit;
+    const float* div;                                               // [L + 1]: fp32 of n ** length_penalty
+    int* rows; int64_t ld_rows;                                     // beam row table [slots * nb, ld_rows] or null
+};
+constexpr int SB_NB = 4, SB_L = 128;                                // what the staging holds: 2 x 4 x 128 token rows (8 KB) + 4 x 128 table entries
+
+__global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBeamP p) {
+    __shared__ BeamRank r;
+    __shared__ BeamRankOut o;                    // the ranking lane's results, for every thread
+    __shared__ int64_t s_run[SB_NB * SB_L], s_fin[SB_NB * SB_L];
+    __shared__ int s_rt[SB_NB * SB_L];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int nb = p.nb, K = 2 * nb, L = p.L;
+    const int img = p.slot_image[s];
+    if (img < 0) {                               // idle (workgroup-uniform, before any barrier)
+        if (tid == 0) { p.sel[2 * s] = 0; p.sel[2 * s + 1] = 0; }
+        return;
+    }
+    const int t = min(p.slot_t[s], L - 2), cur = t + 1;
+    const int lim = p.limit ? min(p.limit[img], L) : L;
+    const float div = p.div[cur];
+    if (tid < K) { r.lp[tid] = p.top_lp[(int64_t)s * K + tid]; r.ix[tid] = p.top_ix[(int64_t)s * K + tid]; }
+    if (tid >= 16 && tid < 16 + nb) {
+        const int i = tid - 16;
+        r.fsc[i] = p.fin_sc[s * nb + i]; r.fdone[i] = p.fin_done[s * nb + i]; r.flen[i] = p.fin_len[s * nb + i];
+    }
+    if (tid == 32) r.unsat = p.unsat[s];
+    // the slot's old rows: whole rows, as the statement moves them (what lies behind cur may be an earlier image's and is never read)
+    for (int e = tid; e < nb * L; e += 256) { s_run[e] = p.run_seq[(int64_t)s * nb * L + e]; s_fin[e] = p.fin_seq[(int64_t)s * nb * L + e]; }
+    if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; s_rt[i * L + j] = p.rows[((int64_t)s * nb + i) * p.ld_rows + j]; }
+    __syncthreads();
+    if (tid == 0) { BeamRankOut mine; beam_rank(r, mine, nb, K, p.V, p.eos, cur, lim, p.early, div, div); o = mine; }
+    __syncthreads();
+    const bool go_on = o.un && !(o.done_new && p.early) && !o.all_hits;      // beam_search's go_on, for this image
+    if (!go_on) {
+        // the best finished hypothesis: only its fl_new[0] tokens (the caller filled BOS / padding; the row behind them may be stale)
+        const int mi = r.mix[0], n = (int)o.fl_new[0];
+        if (img < p.n_images)
+            for (int j = tid; j < min(n, L); j += 256)
+                p.out_ids[(int64_t)img * p.ld_ids + j] = mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
+        if (tid == 0) {
+            if (p.out_score && img < p.n_images) p.out_score[img] = o.fsc_new[0];
+            p.sel[2 * s] = 1; p.sel[2 * s + 1] = 0;
+        }
+        return;                                  // the seat kernel puts the slot's beam state back at the start
+    }
+    for (int e = tid; e < nb * L; e += 256) {
+        const int i = e / L, j = e - i * L;
+        const int k = r.nxt[i], mi = r.mix[i];
+        p.run_seq[(int64_t)s * nb * L + e] = j == cur ? (int64_t)r.tok[k] : s_run[r.src[k] * L + j];
+        p.fin_seq[(int64_t)s * nb * L + e] = mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
+    }
+    // the row table, kv_rows_kernel's rule with len = slot_t + 1: the step kernel has just written old[b][slot_t] = b; nothing of the cache moves
+    if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; p.rows[((int64_t)s * nb + i) * p.ld_rows + j] = s_rt[r.src[r.nxt[i]] * L + j]; }
+    if (tid < nb) {
+        const int i = tid, k = r.nxt[i];
+        p.run_sc[s * nb + i] = o.run_new[i]; p.fin_sc[s * nb + i] = o.fsc_new[i]; p.fin_done[s * nb + i] = o.fd_new[i]; p.fin_len[s * nb + i] = o.fl_new[i];
+        p.tokens[s * nb + i] = r.tok[k]; p.posids[s * nb + i] = cur + 1 + p.pad;
+    }
+    if (tid == 0) {
+        int npad = 0;                            // a running prefix with padding breaks "position = step + 1 + pad, every cached key usable"
+        for (int i = 0; i < nb; ++i) npad += (r.tok[r.nxt[i]] == p.pad && !r.hit[r.nxt[i]]) ? 1 : 0;
+        p.unsat[s] = o.un;
+        p.sel[2 * s] = 0; p.sel[2 * s + 1] = npad;
+    }
+}
+
+// a slot's beam state at the start of a search (new_beam_state); the token rows keep what they hold: column 0 is BOS from the first seating on
+__device__ __forceinline__ void stream_beam_reset(const StreamBeamP& p, int s) {
+    for (int i = 0; i < p.nb; ++i) {
+        p.run_sc[s * p.nb + i] = i == 0 ? 0.f : -1.0e9f; p.fin_sc[s * p.nb + i] = -1.0e9f; p.fin_done[s * p.nb + i] = 0; p.fin_len[s * p.nb + i] = 1;
+        p.tokens[s * p.nb + i] = p.bos; p.posids[s * p.nb + i] = p.pad + 1;
+    }
+    p.unsat[s] = 1; p.slot_t[s] = 0;
+}
+
+__global__ __launch_bounds__(256) void stream_beam_seat_kernel(const StreamBeamP p) {
+    __shared__ int s_w[4], s_pad;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int next = p.counters[0];
+    if (tid == 0) s_pad = 0;
+    int carry = 0;                               // searches ended in the slots below this pass
+    for (int base = 0; base < p.slots; base += 256) {
+        const int s = base + tid;
+        const bool in = s < p.slots;
+        const int e = in ? p.sel[2 * s] : 0;
+        const unsigned long long mask = __ballot(e != 0);
+        if (lane == 0) s_w[w] = __popcll(mask);
+        __syncthreads();
+        int below = 0, total = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { below += q < w ? s_w[q] : 0; total += s_w[q]; }
+        const int rank = carry + below + __popcll(mask & ((1ull << lane) - 1ull));      // ended slots below slot s
+        if (in) {
+            if (e) {
+                const int ni = next + rank;
+                p.slot_image[s] = ni < p.n_images ? ni : -1;
+                stream_beam_reset(p, s);
+            } else if (p.slot_image[s] >= 0) {
+                p.slot_t[s] += 1;
+                if (p.sel[2 * s + 1]) atomicAdd(&s_pad, p.sel[2 * s + 1]);
+            }
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        p.counters[0] = min(next + carry, p.n_images);
+        const int ended = p.counters[1];
+        p.counters[1] = ended + carry;
+        if (ended < p.n_images) p.counters[2] += 1;      // steps issued past the end (the host looks only every few steps) do not count
+        p.counters[3] += s_pad;
+    }
+}
+
+// the first min(slots, n_images) images take the slots in order, every slot's beam state at the start, the token rows BOS + padding
+__global__ void stream_beam_start_kernel(const StreamBeamP p) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < p.slots * p.nb * p.L) { const int64_t v = e % p.L == 0 ? p.bos : p.pad; p.run_seq[e] = v; p.fin_seq[e] = v; }
+    if (e < p.slots) { p.slot_image[e] = e < p.n_images ? e : -1; stream_beam_reset(p, e); }
+    if (e == 0) { p.counters[0] = min(p.slots, p.n_images); p.counters[1] = 0; p.counters[2] = 0; p.counters[3] = 0; }
 }
 
 // More than 320 keys (cross-attention over long encoder sequences; no cache append, no row table): the lane layout of
@@ -796,6 +947,39 @@ extern "C" int kzv_stream_update(const kzv_stream_state* st, const float* d_logi
     hipLaunchKernelGGL(stream_select_kernel, dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(stream_seat_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
     return kzv_check_launch("stream_update");
+}
+
+static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_lp, const int64_t* top_ix, StreamBeamP* p, const char* who) {
+    if (!st) return kzv_fail(KZV_E_ARG, "%s: null state", who);
+    if (!st->slot_image || !st->slot_t || !st->tokens || !st->posids || !st->run_seq || !st->fin_seq || !st->run_scores || !st->fin_scores ||
+        !st->fin_done || !st->fin_len || !st->unsatisfied || !st->counters || !st->scratch) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
+    if (!st->out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
+    if (!st->divisors) return kzv_fail(KZV_E_ARG, "%s: null divisors (fp32 [max_len + 1] of n ** length_penalty)", who);
+    if (st->num_beams != 2 && st->num_beams != 4) return kzv_fail(KZV_E_ARG, "%s: num_beams %d: a slot holds 2 or 4 beams", who, st->num_beams);
+    if (st->slots < 1 || st->n_images < 1 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "%s: slots, images and vocabulary must be positive", who);
+    if (st->max_len < 2 || st->max_len > SB_L || st->ld_ids < st->max_len) return kzv_fail(KZV_E_ARG, "%s: max_len 2..%d columns within the output rows", who, SB_L);
+    if ((int64_t)st->slots * st->num_beams * st->max_len >= (1ll << 31) || (int64_t)st->num_beams * st->vocab >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "%s: state beyond 32-bit indices", who);
+    if (st->rows && st->ld_rows < st->max_len - 1) return kzv_fail(KZV_E_ARG, "%s: row table rows shorter than the max_len - 1 steps", who);
+    *p = StreamBeamP{top_lp, top_ix, st->slots, st->n_images, st->num_beams, st->max_len, st->vocab, st->bos_id, st->eos_id, st->pad_id, st->early_stopping ? 1 : 0,
+                     st->slot_image, st->slot_t, st->tokens, st->posids, st->run_seq, st->fin_seq, st->run_scores, st->fin_scores, st->fin_done, st->fin_len,
+                     st->unsatisfied, st->counters, st->scratch, st->out_ids, st->ld_ids, st->out_score, st->limit, st->divisors, st->rows, st->ld_rows};
+    return KZV_OK;
+}
+
+extern "C" int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void* stream) {
+    StreamBeamP p;
+    KZV_TRY_RC(stream_beam_params(st, nullptr, nullptr, &p, "stream_beam_seat_first"));
+    hipLaunchKernelGGL(stream_beam_start_kernel, dim3((st->slots * st->num_beams * st->max_len + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
+    return kzv_check_launch("stream_beam_seat_first");
+}
+
+extern "C" int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream) {
+    StreamBeamP p;
+    KZV_TRY_RC(stream_beam_params(st, d_top_scores, d_top_index, &p, "stream_beam_update"));
+    if (!d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "stream_beam_update: null ranking [slots, 2 * num_beams]");
+    hipLaunchKernelGGL(stream_beam_update_kernel, dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(stream_beam_seat_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
+    return kzv_check_launch("stream_beam_update");
 }
 
 extern "C" int kzv_beam_topk(const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,

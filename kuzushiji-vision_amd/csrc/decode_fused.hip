@@ -715,17 +715,20 @@ __device__ __forceinline__ void attention_role(Lds<G>& sm, float (*scl)[SCL], co
     }
 }
 
-// NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks; F8: e4m3 weights; SL (G = 1): the workgroup is a decoder
+// NC = 1: up to NPMAX patch keys in one pass; NC > 1: up to NPWIDE in NC chunks; F8: e4m3 weights; SL: the workgroup is a decoder
 // SLOT -- its image and its step index are two scalar loads at the top (an idle slot leaves before the first barrier: the test is
-// workgroup-uniform), tokens / position ids / head output / self-attention cache stay indexed by the slot.  Every step costs the
-// same at every t and cache rows past t are never used (self_load, self_compute), so a slot restarts at t = 0 without any clean-up.
+// workgroup-uniform), tokens / position ids / head output / self-attention cache stay indexed by the slot's rows b0 .. b0 + G - 1.  Every
+// step costs the same at every t and cache rows past t are never used (self_load, self_compute), so a slot restarts at t = 0 without any
+// clean-up.  A slot of G = 2 / 4 rows holds an image's beam group and reads the beam row table: self_load takes an entry only for
+// j < tdev, so the entries a reseated slot inherits from the image before are never used either, and self_compute writes
+// rows[b][tdev] = b before the update kernel re-parents columns 0 .. tdev in place -- the table needs no clean-up at a reseat.
 template <int G, int NC, bool F8, bool SL = false>
 __global__ __launch_bounds__(512) void decode_fused_kernel(const typename FusedArgs<F8, SL>::type p) {
     __shared__ Lds<G> sm;
     float (*scl)[SCL] = nullptr;                         // the layer's / the next layer's row scales: the e4m3 instances only
     if constexpr (F8) { __shared__ float scl_s[2][SCL]; scl = scl_s; }
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    static_assert(!SL || G == 1, "a slot holds one sequence");
+    static_assert(!SL || G == 1 || G == 2 || G == 4, "a slot holds one sequence or an image's 2 / 4 beams");
     const int b0 = blockIdx.x * G;
     int img = blockIdx.x, tdev;
     if constexpr (SL) {
@@ -756,7 +759,8 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     if (a.B % a.group) return kzv_fail(KZV_E_ARG, "decode_fused: rows must be a multiple of the group");
     if ((a.rows || a.slot_image) && (int64_t)a.B * a.T * HD >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "decode_fused: cache too large");
     if ((a.slot_image == nullptr) != (a.slot_t == nullptr)) return kzv_fail(KZV_E_ARG, "decode_fused: a slot's image and step tables go together");
-    if (a.slot_image && (a.group != 1 || a.rows || a.valid || a.tptr)) return kzv_fail(KZV_E_ARG, "decode_fused: slots are single greedy sequences (group 1, no row table, no key flags, no launch-wide step)");
+    if (a.slot_image && (a.valid || a.tptr)) return kzv_fail(KZV_E_ARG, "decode_fused: slots take no key flags and no launch-wide step");
+    if (a.slot_image && (a.group == 1) != (a.rows == nullptr)) return kzv_fail(KZV_E_ARG, "decode_fused: a slot is one greedy sequence without a row table, or a beam group of 2 / 4 with one");
     FusedP p;
     for (int i = 0; i < a.nlayers; ++i) {
         const KzvDecodeFusedLayer& l = a.layers[i];
@@ -772,19 +776,21 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
     const bool wide = a.npa > NPMAX;
 #define KZV_DF_PICK(F8_) (!wide ? (a.group == 1 ? decode_fused_kernel<1, 1, F8_> : a.group == 2 ? decode_fused_kernel<2, 1, F8_> : decode_fused_kernel<4, 1, F8_>) \
                                 : (a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS, F8_> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS, F8_> : decode_fused_kernel<4, KZV_DF_CHUNKS, F8_>))
+#define KZV_DF_PICK_SL(F8_) (!wide ? (a.group == 1 ? decode_fused_kernel<1, 1, F8_, true> : a.group == 2 ? decode_fused_kernel<2, 1, F8_, true> : decode_fused_kernel<4, 1, F8_, true>) \
+                                   : (a.group == 1 ? decode_fused_kernel<1, KZV_DF_CHUNKS, F8_, true> : a.group == 2 ? decode_fused_kernel<2, KZV_DF_CHUNKS, F8_, true> : decode_fused_kernel<4, KZV_DF_CHUNKS, F8_, true>))
     if (a.slot_image) {
         if (a.w8) {
             FusedPS8 ps;
             static_cast<FusedP&>(ps) = p;
             ps.w8 = (const char*)a.w8; ps.wave8 = kzv_decode_fused_pack8_bytes(a.nlayers) / 4; ps.sc8 = a.scales8;
             ps.slot_image = a.slot_image; ps.slot_t = a.slot_t;
-            void (*kern)(const FusedPS8) = wide ? decode_fused_kernel<1, KZV_DF_CHUNKS, true, true> : decode_fused_kernel<1, 1, true, true>;
+            void (*kern)(const FusedPS8) = KZV_DF_PICK_SL(true);
             hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, ps);
         } else {
             FusedPS ps;
             static_cast<FusedP&>(ps) = p;
             ps.slot_image = a.slot_image; ps.slot_t = a.slot_t;
-            void (*kern)(const FusedPS) = wide ? decode_fused_kernel<1, KZV_DF_CHUNKS, false, true> : decode_fused_kernel<1, 1, false, true>;
+            void (*kern)(const FusedPS) = KZV_DF_PICK_SL(false);
             hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, ps);
         }
     } else if (a.w8) {
@@ -797,6 +803,7 @@ int kzv_decode_fused_launch(const KzvDecodeFused& a, hipStream_t s) {
         void (*kern)(const FusedP) = KZV_DF_PICK(false);
         hipLaunchKernelGGL(kern, dim3(images), dim3(512), 0, s, p);
     }
+#undef KZV_DF_PICK_SL
 #undef KZV_DF_PICK
     return kzv_check_launch("decode_fused");
 }

@@ -104,8 +104,8 @@ struct KzvDecodeFused {
     int* rows; float eps;
     // e4m3 weights (both or neither): the stream and the row scales kzv_decode_fused_pack8 wrote; the layers' w* and whd are then not read
     const unsigned char* w8 = nullptr; const float* scales8 = nullptr;
-    // slot-refill decoding (both or neither; group 1, rows / valid / tptr null): workgroup b serves image slot_image[b] (< 0: idle) at
-    // step slot_t[b]; plane2 is then the POOL's image count * npa * Hd
+    // slot-refill decoding (both or neither; valid / tptr null; group 1 without rows, or a beam group of 2 / 4 with the row table):
+    // workgroup b serves image slot_image[b] (< 0: idle) at step slot_t[b]; plane2 is then the POOL's image count * npa * Hd
     const int* slot_image = nullptr; const int* slot_t = nullptr;
 };
 // the e4m3 copies of the linears the step streams, in the order its linear waves consume them, + one power-of-two scale per output row

@@ -356,62 +356,118 @@ extern "C" int kzv_decode_reorder(kzv_model* m, const int64_t* d_rows, int len, 
     return KZV_OK;
 }
 
-// ---- slot-refill greedy decoding (include/kzv.h: kzv_stream_*) -------------------------------------------------------------------
-static bool stream_supported(const kzv_model* m) {
-    return decode_one_launch_mode() && kzv_decode_fused_supported(m->Hd, m->c.dec_heads, m->Fd, m->Ld, 1, m->T, m->npa);
+// ---- slot-refill decoding (include/kzv.h: kzv_stream_*): greedy, one row per slot; or beam search, a slot holding an image's beam group ----
+static bool stream_supported(const kzv_model* m, int nb = 1) {
+    return decode_one_launch_mode() && kzv_decode_fused_supported(m->Hd, m->c.dec_heads, m->Fd, m->Ld, nb, m->T, m->npa) &&
+           (nb == 1 || ((nb == 2 || nb == 4) && m->B % nb == 0 && m->V <= 64 * 256));       // kzv_beam_topk ranks up to 16,384 columns
 }
 extern "C" int kzv_stream_decode_impl(const kzv_model* m) {
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_decode_impl: model not bound");
     return stream_supported(m) ? 1 : 0;
 }
+extern "C" int kzv_stream_beam_impl(const kzv_model* m, int num_beams) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_beam_impl: model not bound");
+    return (num_beams == 2 || num_beams == 4) && stream_supported(m, num_beams) ? 1 : 0;
+}
 static bool stream_e4m3(const kzv_model* m) { return m->dec_weights == KZV_DECODE_WEIGHTS_E4M3; }
 
-extern "C" int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids,
-                                float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit, void* stream) {
+// nb = 1: kzv_stream_begin; nb = 2 / 4: kzv_stream_begin_beams (slots = bound batch / nb)
+static int stream_begin(kzv_model* m, const char* who, int nb, int early, float length_penalty, float* d_out_scores, int pool_images, int n_images, int max_len,
+                        int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit,
+                        void* stream) {
     // what needs no bound state first: these are argument errors on any handle
-    if (!m) return kzv_fail(KZV_E_ARG, "stream_begin: null model");
-    if (!d_out_ids) return kzv_fail(KZV_E_ARG, "stream_begin: null out_ids");
-    if (max_len < 2) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d: a line is BOS and at least one token", max_len);
-    if (n_images < 1 || n_images > pool_images) return kzv_fail(KZV_E_ARG, "stream_begin: a wave of %d images for a pool of %d", n_images, pool_images);
-    if (ld_ids < max_len || (d_out_logprob && ld_logprob < max_len)) return kzv_fail(KZV_E_ARG, "stream_begin: output rows shorter than max_len");
-    if (!m->bound) return kzv_fail(KZV_E_STATE, "stream_begin: model not bound");
+    if (!m) return kzv_fail(KZV_E_ARG, "%s: null model", who);
+    if (nb != 1 && nb != 2 && nb != 4) return kzv_fail(KZV_E_ARG, "%s: num_beams %d: a slot holds 2 or 4 beams", who, nb);
+    if (!d_out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
+    if (max_len < 2) return kzv_fail(KZV_E_ARG, "%s: max_len %d: a line is BOS and at least one token", who, max_len);
+    if (n_images < 1 || n_images > pool_images) return kzv_fail(KZV_E_ARG, "%s: a wave of %d images for a pool of %d", who, n_images, pool_images);
+    if (ld_ids < max_len || (d_out_logprob && ld_logprob < max_len)) return kzv_fail(KZV_E_ARG, "%s: output rows shorter than max_len", who);
+    if (nb > 1 && d_out_logprob) return kzv_fail(KZV_E_ARG, "%s: a beam search returns no per-token log-probabilities (d_out_logprob must be null)", who);
+    if (!m->bound) return kzv_fail(KZV_E_STATE, "%s: model not bound", who);
     m->swave = false;
-    if (pool_images < m->B) return kzv_fail(KZV_E_ARG, "stream_begin: a pool of %d images is smaller than the %d slots", pool_images, m->B);
-    if (bos_id < 0 || bos_id >= m->V || eos_id < 0 || eos_id >= m->V) return kzv_fail(KZV_E_ARG, "stream_begin: BOS / EOS outside the vocabulary");
-    if (max_len > m->L) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d outside 2..%d (the bound length)", max_len, m->L);
-    if (max_len - 1 + m->c.pad_id >= m->c.max_pos) return kzv_fail(KZV_E_ARG, "stream_begin: max_len %d needs position id %d, the table has %d rows", max_len, max_len - 1 + m->c.pad_id, m->c.max_pos);
-    if (!stream_supported(m)) return kzv_fail(KZV_E_STATE, "stream_begin: this geometry has no slot-refill decoding (kzv_stream_decode_impl)");
+    if (m->B % nb) return kzv_fail(KZV_E_ARG, "%s: the %d bound rows are no multiple of %d beams", who, m->B, nb);
+    const int B = m->B, V = m->V, slots = B / nb;
+    if (pool_images < slots) return kzv_fail(KZV_E_ARG, "%s: a pool of %d images is smaller than the %d slots", who, pool_images, slots);
+    if (bos_id < 0 || bos_id >= m->V || eos_id < 0 || eos_id >= m->V) return kzv_fail(KZV_E_ARG, "%s: BOS / EOS outside the vocabulary", who);
+    if (max_len > m->L) return kzv_fail(KZV_E_ARG, "%s: max_len %d outside 2..%d (the bound length)", who, max_len, m->L);
+    if (max_len - 1 + m->c.pad_id >= m->c.max_pos) return kzv_fail(KZV_E_ARG, "%s: max_len %d needs position id %d, the table has %d rows", who, max_len, max_len - 1 + m->c.pad_id, m->c.max_pos);
+    if (!stream_supported(m, nb)) return kzv_fail(KZV_E_STATE, "%s: this geometry has no slot-refill decoding (kzv_stream_decode_impl / kzv_stream_beam_impl)", who);
     hipStream_t s = (hipStream_t)stream;
-    const int B = m->B, V = m->V;
     if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // it holds the last wave's outputs and counts
     const size_t bytes = (size_t)m->Ld * 2 * pool_images * m->npa * m->Hd * sizeof(bf16_t);
-    if (!reserve(m, m->spool, bytes)) return kzv_fail(KZV_E_HIP, "stream_begin: pool allocation (%zu bytes)", bytes);
+    if (!reserve(m, m->spool, bytes)) return kzv_fail(KZV_E_HIP, "%s: pool allocation (%zu bytes)", who, bytes);
     m->spool_images = pool_images;
-    if (!m->sstate || m->sstate_slots < B || m->sstate_V < V) {
-        // logits [B, V] | tokens [B] int64 | slot_image, slot_t, posids [B] | scratch [2 B] | counters [4]
-        const size_t sb = align_up((size_t)B * V * sizeof(float), 256) + (size_t)B * 8 + (size_t)B * 5 * 4 + 16;
-        if (!reserve(m, m->sstate, sb)) return kzv_fail(KZV_E_HIP, "stream_begin: slot state allocation (%zu bytes)", sb);
+    // logits [B, V] | tokens [B] int64 | slot_image, slot_t, posids [B] | scratch [2 B] | counters [4]; a beam wave adds
+    // run_seq, fin_seq [B, L] and fin_len [B] int64 | top_ix [2 B] int64 | run / fin scores [B], top_lp [2 B] | divisors [L + 1] | fin_done [B], unsat [B]
+    const int L = m->L;
+    const size_t sb = align_up((size_t)B * V * sizeof(float), 256) + (size_t)B * 8 + (size_t)B * 5 * 4 + 16 +
+                      (nb > 1 ? (size_t)B * (2 * L + 1 + 2) * 8 + (size_t)B * 4 * 4 + align_up((size_t)(L + 1) * 4, 8) + (size_t)B * 2 : 0);
+    if (!m->sstate || m->sstate_slots < B || m->sstate_V < V || m->sstate.capacity() < sb) {
+        if (!reserve(m, m->sstate, sb)) return kzv_fail(KZV_E_HIP, "%s: slot state allocation (%zu bytes)", who, sb);
         m->sstate_slots = B; m->sstate_V = V;
     }
     char* q = m->sstate.as<char>();
     m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
-    kzv_stream_state& st = m->sst;
-    st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
-    st.tokens = (int64_t*)q; q += (size_t)B * 8;
-    st.slot_image = (int32_t*)q; q += (size_t)B * 4;
-    st.slot_t = (int32_t*)q; q += (size_t)B * 4;
-    st.posids = (int32_t*)q; q += (size_t)B * 4;
-    st.scratch = (int32_t*)q; q += (size_t)B * 8;
-    st.counters = (int32_t*)q;
-    st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_logprob = d_out_logprob; st.ld_logprob = ld_logprob; st.limit = d_limit;
+    m->sbeams = nb > 1 ? nb : 0;
+    if (nb == 1) {
+        kzv_stream_state& st = m->sst;
+        st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
+        st.tokens = (int64_t*)q; q += (size_t)B * 8;
+        st.slot_image = (int32_t*)q; q += (size_t)B * 4;
+        st.slot_t = (int32_t*)q; q += (size_t)B * 4;
+        st.posids = (int32_t*)q; q += (size_t)B * 4;
+        st.scratch = (int32_t*)q; q += (size_t)B * 8;
+        st.counters = (int32_t*)q;
+        st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_logprob = d_out_logprob; st.ld_logprob = ld_logprob; st.limit = d_limit;
+    } else {
+        kzv_stream_beam_state& st = m->sbst;
+        st.slots = slots; st.n_images = n_images; st.num_beams = nb; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id;
+        st.eos_id = eos_id; st.early_stopping = early ? 1 : 0; st.reserved = 0;
+        st.tokens = (int64_t*)q; q += (size_t)B * 8;                       // 8-byte words first
+        st.run_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
+        st.fin_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
+        st.fin_len = (int64_t*)q; q += (size_t)B * 8;
+        m->stop_ix = (int64_t*)q; q += (size_t)B * 2 * 8;
+        st.run_scores = (float*)q; q += (size_t)B * 4;
+        st.fin_scores = (float*)q; q += (size_t)B * 4;
+        m->stop_lp = (float*)q; q += (size_t)B * 2 * 4;
+        st.posids = (int32_t*)q; q += (size_t)B * 4;
+        st.slot_image = (int32_t*)q; q += (size_t)slots * 4;
+        st.slot_t = (int32_t*)q; q += (size_t)slots * 4;
+        st.scratch = (int32_t*)q; q += (size_t)slots * 8;
+        st.counters = (int32_t*)q; q += 16;
+        float* div = (float*)q; q += align_up((size_t)(max_len + 1) * 4, 8);
+        st.fin_done = (uint8_t*)q; q += (size_t)B;
+        st.unsatisfied = (uint8_t*)q;
+        st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_score = d_out_scores; st.limit = d_limit; st.divisors = div;
+        // the divisors kzv_beam_update takes per call: (float)pow((double)n, (double)length_penalty), as a table since every slot has its own n
+        m->sdiv.assign((size_t)max_len + 1, 1.f);
+        for (int n = 1; n <= max_len; ++n) m->sdiv[n] = (float)pow((double)n, (double)length_penalty);
+        if (hipMemcpyAsync(div, m->sdiv.data(), sizeof(float) * m->sdiv.size(), hipMemcpyHostToDevice, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: divisor table copy", who);
+    }
     KZV_TRY(ensure_kv_cache(m));
+    if (nb > 1) { m->sbst.rows = m->rowtab[0].as<int>(); m->sbst.ld_rows = m->T; }       // ensure_kv_cache may have moved it
     KZV_TRY(ensure_dec_pack(m, s));
     if (stream_e4m3(m)) KZV_TRY(build_dec_pack8(m, s));
     m->rt_cur = -1;
-    if (hipMemsetAsync(m->hd_gelu, 0, sizeof(float) * (size_t)B * m->Hd, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_begin: memset");
+    if (hipMemsetAsync(m->hd_gelu, 0, sizeof(float) * (size_t)B * m->Hd, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: memset", who);
     m->train = false; m->have_fwd = false; m->have_dec = false;
     m->swave = true;
     return KZV_OK;
+}
+
+extern "C" int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids,
+                                float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit, void* stream) {
+    return stream_begin(m, "stream_begin", 1, 0, 1.f, nullptr, pool_images, n_images, max_len, bos_id, eos_id, d_out_ids, ld_ids, d_out_logprob, ld_logprob,
+                        d_limit, stream);
+}
+
+extern "C" int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_stopping, float length_penalty, float* d_out_scores, int pool_images,
+                                      int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob,
+                                      int64_t ld_logprob, const int32_t* d_limit, void* stream) {
+    if (num_beams != 2 && num_beams != 4) return kzv_fail(KZV_E_ARG, "stream_begin_beams: num_beams %d: a slot holds 2 or 4 beams", num_beams);
+    return stream_begin(m, "stream_begin_beams", num_beams, early_stopping, length_penalty, d_out_scores, pool_images, n_images, max_len, bos_id, eos_id,
+                        d_out_ids, ld_ids, d_out_logprob, ld_logprob, d_limit, stream);
 }
 
 extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
@@ -425,23 +481,31 @@ extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int 
 
 extern "C" int kzv_stream_start(kzv_model* m, void* stream) {
     if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_start: call kzv_stream_begin first");
-    return kzv_stream_seat_first(&m->sst, stream);
+    return m->sbeams ? kzv_stream_beam_seat_first(&m->sbst, stream) : kzv_stream_seat_first(&m->sst, stream);
 }
 
 static int stream_step_body(kzv_model* m, hipStream_t s) {
     KzvDecodeFused a;
+    const int nb = m->sbeams;
     KZV_TRY(fused_common(m, a, stream_e4m3(m), "stream_step"));
-    a.tokens = m->sst.tokens; a.posids = m->sst.posids;
     a.ckv = m->spool.as<bf16_t>(); a.plane2 = (int64_t)m->spool_images * m->npa * m->Hd;
-    a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t;
+    if (!nb) {
+        a.tokens = m->sst.tokens; a.posids = m->sst.posids;
+        a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t;
+    } else {                                     // a slot's workgroup serves its nb rows through the handle's first row table
+        a.tokens = m->sbst.tokens; a.posids = m->sbst.posids;
+        a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.rows = m->sbst.rows;
+    }
     KZV_TRY(kzv_decode_fused_launch(a, s));
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
-    return kzv_stream_update(&m->sst, m->slogits, m->V, s);
+    if (!nb) return kzv_stream_update(&m->sst, m->slogits, m->V, s);
+    KZV_TRY(kzv_beam_topk(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
+    return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);
 }
 
 extern "C" int kzv_stream_step(kzv_model* m, int graph, void* stream) {
     if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_step: call kzv_stream_begin first");
-    if (!stream_supported(m)) return kzv_fail(KZV_E_STATE, "stream_step: the geometry or the step mode changed since kzv_stream_begin");
+    if (!stream_supported(m, m->sbeams ? m->sbeams : 1)) return kzv_fail(KZV_E_STATE, "stream_step: the geometry or the step mode changed since kzv_stream_begin");
     hipStream_t s = (hipStream_t)stream;
     if (!graph) return stream_step_body(m, s);
     if (!stream) return kzv_fail(KZV_E_ARG, "stream_step: graph replay needs a non-default stream (stream capture)");
@@ -452,13 +516,24 @@ extern "C" int kzv_stream_step(kzv_model* m, int graph, void* stream) {
     return KZV_OK;
 }
 
-extern "C" int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream) {
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_poll: call kzv_stream_begin first");
-    if (!finished || !steps) return kzv_fail(KZV_E_ARG, "stream_poll: null result");
-    int32_t c[3] = {0, 0, 0};
-    if (hipMemcpyAsync(c, m->sst.counters, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+static int stream_poll(kzv_model* m, const char* who, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream) {
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "%s: call kzv_stream_begin first", who);
+    if (!finished || !steps) return kzv_fail(KZV_E_ARG, "%s: null result", who);
+    int32_t c[4] = {0, 0, 0, 0};
+    const int n = m->sbeams ? 4 : 3;
+    if (hipMemcpyAsync(c, m->sbeams ? m->sbst.counters : m->sst.counters, sizeof(int32_t) * n, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
         hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-        return kzv_fail(KZV_E_HIP, "stream_poll: copy");
+        return kzv_fail(KZV_E_HIP, "%s: copy", who);
     *finished = c[1]; *steps = c[2];
+    if (pad_tokens) *pad_tokens = c[3];
     return KZV_OK;
+}
+
+extern "C" int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream) {
+    return stream_poll(m, "stream_poll", finished, steps, nullptr, stream);
+}
+
+extern "C" int kzv_stream_poll_beams(kzv_model* m, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream) {
+    if (m && m->bound && m->swave && !pad_tokens) return kzv_fail(KZV_E_ARG, "stream_poll_beams: null result");
+    return stream_poll(m, "stream_poll_beams", finished, steps, pad_tokens, stream);
 }

@@ -119,6 +119,11 @@ struct kzv_model_plain {
     // state and logits inside it, the wave in progress
     int spool_images = 0, sstate_slots = 0, sstate_V = 0;
     kzv_stream_state sst = {}; float* slogits = nullptr; bool swave = false;
+    // beam search on the slots (kzv_stream_begin_beams): beams per slot (0: the wave is greedy), the beam state, the ranking buffers, and
+    // the host copy of the divisor table, kept for as long as the asynchronous copy to the device may still read it (until the next begin)
+    int sbeams = 0;
+    kzv_stream_beam_state sbst = {}; float* stop_lp = nullptr; int64_t* stop_ix = nullptr;
+    std::vector<float> sdiv;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU

@@ -68,6 +68,15 @@ class kzv_stream_state(C.Structure):
         ("limit", C.c_void_p)]
 
 
+class kzv_stream_beam_state(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("slots", "n_images", "num_beams", "max_len", "vocab", "bos_id", "eos_id", "pad_id", "early_stopping",
+                                         "reserved")] + [
+        ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("tokens", C.c_void_p), ("posids", C.c_void_p), ("run_seq", C.c_void_p),
+        ("fin_seq", C.c_void_p), ("run_scores", C.c_void_p), ("fin_scores", C.c_void_p), ("fin_done", C.c_void_p), ("fin_len", C.c_void_p),
+        ("unsatisfied", C.c_void_p), ("counters", C.c_void_p), ("scratch", C.c_void_p), ("out_ids", C.c_void_p), ("ld_ids", C.c_int64),
+        ("out_score", C.c_void_p), ("limit", C.c_void_p), ("divisors", C.c_void_p), ("rows", C.c_void_p), ("ld_rows", C.c_int64)]
+
+
 class kzv_gemm_tn_args(C.Structure):
     _fields_ = [("P", C.c_void_p), ("ldp", C.c_int64), ("Q", C.c_void_p), ("ldq", C.c_int64),
                 ("OUT", C.c_void_p), ("ldo", C.c_int64),
@@ -255,6 +264,12 @@ SYMBOLS = {
     "kzv_stream_start": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kzv_stream_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "kzv_stream_poll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "kzv_stream_beam_seat_first": (C.c_int, [C.POINTER(kzv_stream_beam_state), C.c_void_p]),
+    "kzv_stream_beam_update": (C.c_int, [C.POINTER(kzv_stream_beam_state), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_stream_beam_impl": (C.c_int, [C.c_void_p, C.c_int]),
+    "kzv_stream_begin_beams": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "kzv_stream_poll_beams": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "kzv_lanczos_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "kzv_preprocess_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -70,6 +70,9 @@ class TrOCRModel:
         self._keep = None                  # inputs of the last engine call (kept alive; align_last reads the labels)
         self.last_active_length = 0
         self.last_stream_steps = 0
+        self.last_generate_steps = 0
+        self.last_stream_pad_fallbacks = 0
+        self._stream_beams = 4
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
         # image_size is the WIDEST crop; batches whose width is one of `width_buckets` (multiples of the patch width, <= it)
         # run with fewer patch tokens and the position rows of the same (h, w) cells (include/kzv.h: kzv_set_image_width).
@@ -482,7 +485,10 @@ class TrOCRModel:
         if graph:
             side.wait_stream(cur)
 
+        self.last_generate_steps = 0             # decoder steps this call issued (those run past the end before the host looked included)
+
         def step(t, ids):
+            self.last_generate_steps += 1
             if not use_cache:
                 ids = ids.contiguous()
                 state["ids"] = ids                                        # keep alive until the kernels have run
@@ -546,6 +552,20 @@ class TrOCRModel:
             L.check(rc, "kzv_stream_decode_impl")
         return "slot-refill" if rc == 1 else "static"
 
+    def stream_beam_impl_for(self, num_beams: int) -> str:
+        """"slot-refill" | "static": what ``generate_stream(num_beams=num_beams)`` on this model runs (kzv_stream_beam_impl: 2 or 4 beams,
+        the bound rows a multiple of them, and stream_decode_impl's conditions for that many rows per image).  "static" is lockstep
+        ``generate(num_beams=num_beams)`` over batches of ``slots``."""
+        rc = L.load().kzv_stream_beam_impl(self._h, int(num_beams))
+        if rc < 0:
+            L.check(rc, "kzv_stream_beam_impl")
+        return "slot-refill" if rc == 1 else "static"
+
+    @property
+    def stream_beam_impl(self) -> str:
+        """``stream_beam_impl_for`` the beam count of the last ``generate_stream(num_beams > 1)`` call (4 before any)."""
+        return self.stream_beam_impl_for(self._stream_beams)
+
     @staticmethod
     def _waves(pixel_values, wave: int):
         """[N, C, H, W] or an iterable of such batches -> tensors of exactly ``wave`` images (the last one shorter)."""
@@ -563,7 +583,8 @@ class TrOCRModel:
             yield torch.cat(held) if len(held) > 1 else held[0]
 
     def generate_stream(self, pixel_values, max_length: int = 128, slots: int | None = None, limits=None, return_logprobs: bool = False,
-                        pool_bytes: int = 4 << 30):
+                        pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
+                        return_scores: bool = False):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -576,9 +597,30 @@ class TrOCRModel:
         padding -- and with ``return_logprobs`` also fp32 of the same shape, the log-probability of every emitted token at its column.
         Without ``limits`` each row equals the matching row of ``generate(num_beams=1)``; with them, that row cut at the limit.
         Where ``stream_decode_impl`` says "static" this IS ``generate(num_beams=1)`` over batches of ``slots`` (log-probabilities then
-        from ``align``)."""
+        from ``align``).
+
+        ``num_beams`` > 1: beam search with ``generate``'s rules (``early_stopping``, ``length_penalty``) -- what the reference asks for
+        on every validation and test image.  With 2 or 4 beams a slot holds an image's whole beam group (``slots * num_beams`` decoder
+        rows are bound) and takes the next image the step after its search has ended (kzv/stream.py: beam_stream); every row equals
+        the matching row of ``generate(num_beams=num_beams)``, with ``limits`` that of ``generate(max_length=limit)``.  Other beam
+        counts, or ``stream_beam_impl_for(num_beams) == "static"``, run ``generate`` over batches of ``slots``: the same rows.
+        ``return_scores``: also fp32 [N], the winner's sum of log-probabilities / generated length ** length_penalty (HF's
+        ``sequences_scores``; on the static path from ``align``).  ``return_logprobs`` is greedy only: per-token log-probabilities of
+        a beam winner are not produced.  The slots assume that no running beam holds padding; a wave in which one took ``pad_id`` is
+        decoded again by ``generate`` and counted in ``last_stream_pad_fallbacks``."""
         import torch
         c = self.cfg
+        nb = int(num_beams)
+        if nb < 1:
+            raise ValueError("num_beams must be positive")
+        if nb > 1 and return_logprobs:
+            raise ValueError("return_logprobs is greedy only: a beam search returns sequence scores (return_scores)")
+        if nb == 1 and return_scores:
+            raise ValueError("return_scores needs num_beams > 1 (greedy decoding returns per-token log-probabilities: return_logprobs)")
+        beams = None if nb == 1 else (nb, bool(early_stopping), float(length_penalty))
+        if beams:
+            self._stream_beams = nb
+        self.last_stream_pad_fallbacks = 0       # running beams that took padding in the waves decoded again by generate
         Lh = min(max_length, c.max_pos - c.pad_id - 1)
         if Lh < 2:
             raise ValueError("max_length must be at least 2")
@@ -600,16 +642,43 @@ class TrOCRModel:
             lim = None if lim_all is None else lim_all[done:done + n]
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
-            ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs)
+            ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams)
             ids_out.append(ids); lp_out.append(lp); done += n
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
         if return_logprobs:
             return ids[:, :width], torch.cat(lp_out)[:, :width]
+        if return_scores:
+            return ids[:, :width], torch.cat(lp_out)
         return ids[:, :width]
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool):
-        """One wave of generate_stream: ids [n, Lh] (and log-probabilities [n, Lh] or None)."""
+    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams):
+        """``generate(num_beams=nb)`` over batches of ``slots``: ids [n, Lh] and the winners' scores [n] (from a teacher-forced pass).  With
+        limits, the images of every distinct limit are decoded with it as their max_length."""
+        import torch
+        c = self.cfg
+        nb, early, lpen = beams
+        n, dev = px.shape[0], self.device
+        ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
+        score = torch.zeros(n, dtype=torch.float32, device=dev)
+        lim = None if lim is None else lim.cpu().clamp(max=Lh)
+        groups = [(Lh, torch.arange(n))] if lim is None else [(int(v), (lim == v).nonzero().reshape(-1)) for v in lim.unique().tolist()]
+        for width, idx in groups:
+            for a in range(0, idx.numel(), slots):
+                sel = idx[a:a + slots]
+                sub = px[sel.to(px.device)]
+                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen)
+                rows = torch.full((sel.numel(), Lh), c.pad_id, dtype=torch.int64, device=dev)
+                rows[:, :g.shape[1]] = g
+                sc = self.align(sub, rows)
+                live = sc["live"].float()
+                ids[sel.to(dev)] = rows
+                score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
+        return ids, score
+
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None):
+        """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
+        length_penalty): ids [n, Lh] and the winners' scores [n]."""
         import torch
         from . import stream as ST
         c = self.cfg
@@ -617,8 +686,14 @@ class TrOCRModel:
         n = px.shape[0]
         dev = self.device
         self._check_inputs(px[:1])                                # geometry checks + the active crop width
-        self._bind(slots, Lh)
-        if self.stream_decode_impl == "static":
+        nb = beams[0] if beams else 1
+        if beams and nb not in (2, 4):
+            return self._static_beam_wave(px, Lh, slots, lim, beams)
+        rows = slots * nb                                         # decoder rows: a slot holds one sequence, or an image's beam group
+        self._bind(rows, Lh)
+        if beams and self.stream_beam_impl_for(nb) == "static":
+            return self._static_beam_wave(px, Lh, slots, lim, beams)
+        if not beams and self.stream_decode_impl == "static":
             ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
             lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
             for a in range(0, n, slots):
@@ -636,9 +711,10 @@ class TrOCRModel:
         ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
         ids[:, 0] = c.bos_id
         lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
+        score = torch.zeros(n, dtype=torch.float32, device=dev) if beams else None
         limd = None if lim is None else lim.to(dev).contiguous()
-        pool = -(-n // slots) * slots
-        divisors = [d for d in range(1, slots + 1) if slots % d == 0]
+        pool = -(-n // rows) * rows
+        divisors = [d for d in range(1, rows + 1) if rows % d == 0]
         graph = os.environ.get("KZV_DECODE_GRAPH", "1") != "0"
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev) if graph else cur
@@ -648,10 +724,14 @@ class TrOCRModel:
         try:
             with torch.cuda.stream(side):
                 st = L.stream_handle()
-                L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
+                if beams:
+                    L.check(lib.kzv_stream_begin_beams(self._h, nb, 1 if beams[1] else 0, beams[2], score.data_ptr(), pool, n, Lh, c.bos_id, c.eos_id,
+                                                       ids.data_ptr(), Lh, None, 0, L.ptr(limd), st), "stream_begin_beams")
+                else:
+                    L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
                 a = 0
                 while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
-                    k = min(slots, n - a)                         # is filled by repeating its last image
+                    k = min(rows, n - a)                          # is filled by repeating its last image
                     d = next(x for x in divisors if x >= k)
                     chunk = px[a:a + k].to(dev, dtype=torch.float32)
                     if d > k:
@@ -662,13 +742,16 @@ class TrOCRModel:
                     a += k
                 L.check(lib.kzv_stream_start(self._h, st), "stream_start")
                 bound = ST.step_bound(n, slots, Lh)
-                fin, took = C.c_int32(0), C.c_int32(0)
+                fin, took, pads = C.c_int32(0), C.c_int32(0), C.c_int32(0)
                 steps = 0
                 while True:
                     L.check(lib.kzv_stream_step(self._h, 1 if graph else 0, st), "stream_step")
                     steps += 1
                     if steps % 8 == 0 or steps >= bound:          # the host only looks: selection and seating are the device's
-                        L.check(lib.kzv_stream_poll(self._h, C.byref(fin), C.byref(took), st), "stream_poll")
+                        if beams:
+                            L.check(lib.kzv_stream_poll_beams(self._h, C.byref(fin), C.byref(took), C.byref(pads), st), "stream_poll_beams")
+                        else:
+                            L.check(lib.kzv_stream_poll(self._h, C.byref(fin), C.byref(took), st), "stream_poll")
                         if fin.value >= n:
                             break
                         if steps >= bound:
@@ -676,11 +759,14 @@ class TrOCRModel:
                 self.last_stream_steps += took.value
             if graph:
                 cur.wait_stream(side)
-                for t_ in [ids] + keep + [x for x in (lp, limd) if x is not None]:
+                for t_ in [ids] + keep + [x for x in (lp, score, limd) if x is not None]:
                     t_.record_stream(cur)
-            return ids, lp
         finally:
             self.training = was
+        if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
+            self.last_stream_pad_fallbacks += pads.value
+            return self._static_beam_wave(px, Lh, slots, lim, beams)
+        return ids, (score if beams else lp)
 
     def recognize_many(self, pixel_values, **kw) -> list[dict]:
         """``generate_stream`` with its own log-probabilities: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD),

@@ -106,3 +106,183 @@ def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int,
                 raise RuntimeError(f"greedy_stream: {steps} steps for {n_images} images over {slots} slots exceed the bound {bound}")
     out = (st["out_ids"], st["out_logprob"]) if return_logprobs else st["out_ids"]
     return (out, st) if return_state else out
+
+
+# ---- beam search on device-refilled slots ------------------------------------------------------------------------------------------------
+# A slot holds an image's whole beam GROUP (nb decoder rows slot * nb .. slot * nb + nb - 1) at its own step index; the step after the
+# image's search has ended the slot holds the next image that has no slot yet.  Beam search is independent per image, so per image the
+# result is that of beam.beam_search run on it alone.  ``beam_select_seat`` is what happens between two decoder steps once the 2 * nb
+# best continuations of every slot are ranked (kzv_beam_topk); ``beam_stream`` is the loop around it.  On the GPU the same thing is
+# csrc/decode.hip: stream_beam_update_kernel, stream_beam_seat_kernel (kzv_stream_beam_update), pinned against this state for state.
+#
+# State, beyond slot_image / slot_t [slots] as above:
+#   tokens int64, posids int32 [slots * nb]    the next step's input of every beam row
+#   run_seq, fin_seq int64 [slots, nb, L]      running / finished token rows; columns past a slot's step hold an EARLIER image's tokens
+#                                              after a reseat and are never read (never cleared either)
+#   run_sc, fin_sc fp32 [slots, nb]; fin_done u8, fin_len int64 [slots, nb]; unsat u8 [slots]       as in beam.beam_search
+#   counters int32 [4]    next image without a slot, searches ended, steps taken while a search was open, running continuations that
+#                         took pad_id (a prefix with padding breaks "position = step + 1 + pad_id, every cached key usable")
+#   out_ids int64 [N, L]  BOS, the best finished hypothesis, then padding;  out_score fp32 [N]: its score (HF sequences_scores)
+#   rowtab int32 [slots * nb, ld] (optional): the beam row table the step kernel reads; re-parented in place
+NEG = -1.0e9
+
+
+def divisor_table(max_len: int, length_penalty: float, device="cpu"):
+    """fp32 [max_len + 1]: entry n = float(n ** length_penalty) computed in double, rounded once (what beam_search divides by at
+    generated length n); entry 0 is 1 and never used."""
+    import torch
+    return torch.tensor([1.0] + [float(n ** length_penalty) for n in range(1, max_len + 1)], dtype=torch.float64).to(torch.float32).to(device)
+
+
+def new_beam_state(n_images: int, slots: int, num_beams: int, max_len: int, pad_id: int, bos_id: int, device, want_scores: bool = True,
+                   rowtab_ld: int = 0):
+    """The state with the first min(slots, n_images) images seated in slot order (kzv_stream_beam_seat_first)."""
+    import torch
+    nb = num_beams
+    s = torch.arange(slots, dtype=torch.int32, device=device)
+    out_ids = torch.full((n_images, max_len), pad_id, dtype=torch.int64, device=device)
+    out_ids[:, 0] = bos_id
+    run_seq = torch.full((slots, nb, max_len), pad_id, dtype=torch.int64, device=device)
+    run_seq[:, :, 0] = bos_id
+    run_sc = torch.zeros(slots, nb, device=device)
+    run_sc[:, 1:] = NEG
+    return {
+        "slot_image": torch.where(s < n_images, s, torch.full_like(s, -1)),
+        "slot_t": torch.zeros(slots, dtype=torch.int32, device=device),
+        "tokens": torch.full((slots * nb,), bos_id, dtype=torch.int64, device=device),
+        "posids": torch.full((slots * nb,), pad_id + 1, dtype=torch.int32, device=device),
+        "run_seq": run_seq, "fin_seq": run_seq.clone(),
+        "run_sc": run_sc, "fin_sc": torch.full((slots, nb), NEG, device=device),
+        "fin_done": torch.zeros(slots, nb, dtype=torch.uint8, device=device),
+        "fin_len": torch.ones(slots, nb, dtype=torch.int64, device=device),
+        "unsat": torch.ones(slots, dtype=torch.uint8, device=device),
+        "counters": torch.tensor([min(slots, n_images), 0, 0, 0], dtype=torch.int32, device=device),
+        "out_ids": out_ids,
+        "out_score": torch.zeros(n_images, dtype=torch.float32, device=device) if want_scores else None,
+        "rowtab": torch.zeros(slots * nb, rowtab_ld, dtype=torch.int32, device=device) if rowtab_ld else None,
+    }
+
+
+def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int,
+                     early_stopping=True, length_penalty: float = 1.0, limit=None, divisors=None):
+    """One step's beam bookkeeping and seating.  ``top_lp`` / ``top_ix`` [slots, 2 nb]: the ranked continuations of every slot (flat
+    index beam * vocab + token; rows of idle slots are ignored).  A live slot holding image i at cur = slot_t + 1 does the body of
+    beam.beam_search's loop for B = 1 with max_len = min(limit[i], max_len); equal scores rank by the smaller index (a stable sort:
+    what the kernel's scalar ranking does).  The search has ended when beam_search's ``go_on`` is false for that image: then
+    out_ids[i] = fin_seq[0][:fin_len[0]] and out_score[i] = fin_sc[0], and the slot is seated as in select_seat, its beam state back
+    at the start.  Returns ``st``."""
+    import torch
+    dev = top_lp.device
+    nb, K, L, V = num_beams, 2 * num_beams, max_len, vocab
+    S = st["slot_image"].numel()
+    img, t = st["slot_image"], st["slot_t"]
+    live = img >= 0
+    i64 = img.clamp(min=0).long()
+    cur = (t.long() + 1).clamp(max=L - 1)                                                  # [S]
+    lim = torch.full_like(t, L) if limit is None else limit.to(dev, dtype=torch.int32)[i64].clamp(max=L)
+    div = divisor_table(L, length_penalty, dev) if divisors is None else divisors
+    d = div[cur].view(S, 1)                                                                # (cur + 1 - prompt) ** length_penalty, as fp32
+    run_seq, fin_seq, run_sc, fin_sc = st["run_seq"], st["fin_seq"], st["run_sc"], st["fin_sc"]
+    fin_done, fin_len, unsat = st["fin_done"].bool(), st["fin_len"], st["unsat"].bool().view(S, 1)
+    top_lp = top_lp.float()
+    src, tok = top_ix // V, top_ix % V
+    cand = run_seq.gather(1, src.unsqueeze(-1).expand(S, K, L)).clone()
+    cand.scatter_(2, cur.view(S, 1, 1).expand(S, K, 1), tok.unsqueeze(-1))
+    hits = (tok == eos_id) | (cur + 1 >= lim.long()).view(S, 1)
+    # running beams of the next step: the best nb continuations that did not stop
+    s2 = top_lp + hits.float() * NEG
+    nxt_ix = torch.sort(s2, dim=1, descending=True, stable=True)[1][:, :nb]
+    n_run_seq = cand.gather(1, nxt_ix.unsqueeze(-1).expand(S, nb, L))
+    n_run_sc = s2.gather(1, nxt_ix)
+    parent = src.gather(1, nxt_ix)                                                         # [S, nb]: the beam of the slot each one continues
+    n_tok = tok.gather(1, nxt_ix)
+    took_pad = (n_tok == pad_id) & ~hits.gather(1, nxt_ix)
+    # finished list: stopped continuations of rank < nb, normalised by the generated length
+    top_mask = (torch.arange(K, device=dev) < nb).view(1, K)
+    just = hits & top_mask
+    full = fin_done.all(dim=1, keepdim=True) & (early_stopping is True)
+    fsc = top_lp / d
+    fsc = fsc + full.float() * NEG + (~unsat).float() * NEG + (~just).float() * NEG
+    m_sc = torch.cat((fin_sc, fsc), dim=1)
+    m_ix = torch.sort(m_sc, dim=1, descending=True, stable=True)[1][:, :nb]
+    n_fin_seq = torch.cat((fin_seq, cand), dim=1).gather(1, m_ix.unsqueeze(-1).expand(S, nb, L))
+    n_fin_sc = m_sc.gather(1, m_ix)
+    n_fin_done = torch.cat((fin_done, just), dim=1).gather(1, m_ix)
+    n_fin_len = torch.cat((fin_len, (cur + 1).view(S, 1).expand(S, K)), dim=1).gather(1, m_ix)
+    best_open = n_run_sc[:, :1] / d
+    worst_fin = torch.where(n_fin_done, n_fin_sc.min(dim=1, keepdim=True)[0], torch.full_like(n_fin_sc, NEG))
+    n_unsat = unsat & (best_open > worst_fin).any(dim=-1, keepdim=True)
+    go_on = n_unsat[:, 0] & ~(n_fin_done.all(dim=1) & (early_stopping is True)) & ~hits.all(dim=1)
+    ended = live & ~go_on
+    go_on = live & go_on
+    # the ended searches' results: only fin_len[0] tokens are written (what lies behind them in fin_seq may be another image's)
+    rows = i64[ended]
+    if rows.numel():
+        col = torch.arange(L, device=dev).view(1, L)
+        keep = col < n_fin_len[ended][:, :1]
+        st["out_ids"][rows] = torch.where(keep, n_fin_seq[ended][:, 0], torch.full_like(n_fin_seq[ended][:, 0], pad_id))
+        if st.get("out_score") is not None:
+            st["out_score"][rows] = n_fin_sc[ended][:, 0]
+    # seats: the slots whose searches ended take the next images in ascending slot order
+    e32 = ended.to(torch.int32)
+    n_ended = e32.sum().to(torch.int32)
+    c = st["counters"]
+    cand_img = c[0] + torch.cumsum(e32, 0).to(torch.int32) - e32
+    seated = torch.where(cand_img < n_images, cand_img, torch.full_like(cand_img, -1))
+    g1, g2, g3 = go_on.view(S, 1), go_on.view(S, 1, 1), ended.view(S, 1)
+    first = (torch.arange(nb, device=dev) == 0).view(1, nb)
+    st["run_seq"] = torch.where(g2, n_run_seq, run_seq)
+    st["fin_seq"] = torch.where(g2, n_fin_seq, fin_seq)
+    st["run_sc"] = torch.where(g3, torch.where(first, torch.zeros_like(run_sc), torch.full_like(run_sc, NEG)), torch.where(g1, n_run_sc, run_sc))
+    st["fin_sc"] = torch.where(g3, torch.full_like(fin_sc, NEG), torch.where(g1, n_fin_sc, fin_sc))
+    st["fin_done"] = torch.where(g3, torch.zeros_like(fin_done), torch.where(g1, n_fin_done, fin_done)).to(torch.uint8)
+    st["fin_len"] = torch.where(g3, torch.ones_like(fin_len), torch.where(g1, n_fin_len, fin_len))
+    st["unsat"] = torch.where(ended, torch.ones_like(ended), torch.where(go_on, n_unsat[:, 0], unsat[:, 0])).to(torch.uint8)
+    if st.get("rowtab") is not None:                       # new[i][j] = old[parent_i][j] for j <= slot_t (the step wrote old[b][slot_t] = b)
+        rt = st["rowtab"]
+        ld = rt.shape[1]
+        old = rt.view(S, nb, ld)
+        moved = old.gather(1, parent.unsqueeze(-1).expand(S, nb, ld))
+        upto = (torch.arange(ld, device=dev).view(1, 1, ld) <= t.view(S, 1, 1)) & g2
+        st["rowtab"] = torch.where(upto, moved, old).view(S * nb, ld).contiguous()
+    tk, ps = st["tokens"].view(S, nb), st["posids"].view(S, nb)
+    st["tokens"] = torch.where(g3, torch.full_like(tk, bos_id), torch.where(g1, n_tok, tk)).reshape(-1)
+    st["posids"] = torch.where(g3, torch.full_like(ps, pad_id + 1), torch.where(g1, (cur + 1 + pad_id).to(torch.int32).view(S, 1).expand(S, nb), ps)).reshape(-1)
+    st["slot_image"] = torch.where(ended, seated, img)
+    st["slot_t"] = torch.where(ended, torch.zeros_like(t), torch.where(go_on, t + 1, t))
+    n_pad = (took_pad & g1).sum().to(torch.int32)
+    st["counters"] = torch.stack((torch.clamp(c[0] + n_ended, max=n_images), c[1] + n_ended, c[2] + (c[1] < n_images), c[3] + n_pad)).to(torch.int32)
+    return st
+
+
+def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int, device,
+                early_stopping=True, length_penalty: float = 1.0, limits=None, topk=None, poll: int = 8, return_state: bool = False):
+    """Beam search of ``n_images`` images over ``slots`` slots of ``num_beams`` decoder rows.  ``step_fn(state) -> logits [slots * nb, V]``
+    runs one decoder step for every row: row slot * nb + i feeds state["tokens"][row] at step state["slot_t"][slot] for image
+    state["slot_image"][slot], its prefix state["run_seq"][slot][i][:slot_t + 1] (idle slots may return anything finite).
+    ``topk(logits, run_sc) -> (top_lp, top_ix)``: optional fused ranking as in beam.beam_search.  Returns (out_ids [N, max_len],
+    out_score [N]) (and the final state with ``return_state``)."""
+    import torch
+    nb, K = num_beams, 2 * num_beams
+    st = new_beam_state(n_images, slots, nb, max_len, pad_id, bos_id, device)
+    lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
+    div = divisor_table(max_len, length_penalty, device)
+    bound = step_bound(n_images, slots, max_len)
+    steps = 0
+    while True:
+        raw = step_fn(st)
+        if topk is not None:
+            top_lp, top_ix = topk(raw, st["run_sc"])
+        else:
+            acc = torch.log_softmax(raw.float(), dim=-1).view(slots, nb, vocab) + st["run_sc"].unsqueeze(-1)
+            top_lp, top_ix = acc.view(slots, nb * vocab).topk(K, dim=1)
+        st = beam_select_seat(top_lp, top_ix, st, n_images=n_images, num_beams=nb, max_len=max_len, vocab=vocab, pad_id=pad_id, bos_id=bos_id,
+                              eos_id=eos_id, early_stopping=early_stopping, length_penalty=length_penalty, limit=lim, divisors=div)
+        steps += 1
+        if steps % poll == 0 or steps >= bound:
+            if int(st["counters"][1]) >= n_images:
+                break
+            if steps >= bound:
+                raise RuntimeError(f"beam_stream: {steps} steps for {n_images} images over {slots} slots exceed the bound {bound}")
+    out = (st["out_ids"], st["out_score"])
+    return (out, st) if return_state else out

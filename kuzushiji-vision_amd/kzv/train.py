@@ -62,9 +62,11 @@ def parse_args(argv=None):
     p.add_argument("--decode_weights", type=str, default="bf16", choices=["bf16", "e4m3"],
                    help="e4m3 (an extension): validation / test decodes read the decoder's streamed linears as e4m3 with a power-of-two "
                         "scale per output row where the one-launch generation step runs (kzv.quant states what that equals); training is untouched")
-    p.add_argument("--test_decode", type=str, default="beam", choices=["beam", "stream"],
+    p.add_argument("--test_decode", type=str, default="beam", choices=["beam", "stream", "stream-beam"],
                    help="stream (an extension): the test phase also logs test_cer_greedy from ONE slot-refill greedy decode over the whole test "
-                        "loader (TrOCRModel.generate_stream); beam = the reference's test phase alone")
+                        "loader (TrOCRModel.generate_stream); stream-beam (an extension): it also logs test_cer_stream_beam from ONE "
+                        "generate_stream(num_beams=4) over it, the test step's own beam search on refilled slots; beam = the reference's test "
+                        "phase alone")
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize / pad / normalise the decoded crops on the GPU (kzv.preprocess; byte-exact with the PIL transform)")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
@@ -282,7 +284,7 @@ def main(argv=None):
             box = [path]
             torch.distributed.broadcast_object_list(box, src=0)
             path = box[0]
-        main.test_metrics = run_test(model, test_loader, ckpt_path=path, rank=rank, stream_decode=args.test_decode == "stream")
+        main.test_metrics = run_test(model, test_loader, ckpt_path=path, rank=rank, stream_decode={"stream": True, "stream-beam": "stream-beam"}.get(args.test_decode, False))
     if world > 1:
         torch.distributed.destroy_process_group()
     if tmp is not None:

@@ -225,11 +225,13 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     return ck
 
 
-def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0, stream_decode: bool = False):
+def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0, stream_decode: bool | str = False):
     """``trainer.test(model, test_loader, ckpt_path="best")`` (scripts/train_trocr.py:193-195): load the best checkpoint,
     switch the optimizer to its eval parameters (on_test_epoch_start, trocr_model.py:441-445), run test_step over the
-    loader, report the epoch means of test_loss / test_cer.  ``stream_decode`` (an extension): also ``test_cer_greedy``, the mean CER
-    of ONE slot-refill greedy decode over the whole loader (``generate_stream``); test_step itself is untouched."""
+    loader, report the epoch means of test_loss / test_cer.  ``stream_decode`` (an extension): True also reports ``test_cer_greedy``,
+    the mean CER of ONE slot-refill greedy decode over the whole loader (``generate_stream``); "stream-beam" instead reports
+    ``test_cer_stream_beam`` from ONE ``generate_stream(num_beams=4)`` over it, test_step's own decode on refilled slots; test_step
+    itself is untouched."""
     if ckpt_path:
         load_checkpoint(model, model.optimizers(), ckpt_path)
     model.eval()
@@ -240,13 +242,14 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
     keys = ("test_loss", "test_cer")
     if stream_decode and model.tokenizer is not None:
         import torch
-        model.logged.pop("test_cer_greedy", None)
-        gen = model.generate_stream(b["pixel_values"] for b in test_loader)
+        key, kw = ("test_cer_stream_beam", {"num_beams": 4, "early_stopping": True}) if stream_decode == "stream-beam" else ("test_cer_greedy", {})
+        model.logged.pop(key, None)
+        gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw)
         preds = model.tokenizer.batch_decode(gen, skip_special_tokens=True)
         tgts = model.tokenizer.batch_decode(torch.cat([b["labels"] for b in test_loader]), skip_special_tokens=True)
         for p, t in zip(preds, tgts):
-            model.log("test_cer_greedy", model.calculate_cer(p, t))
-        keys += ("test_cer_greedy",)
+            model.log(key, model.calculate_cer(p, t))
+        keys += (key,)
     if model.optimizers() is not None:
         model.optimizers().train()
     out = {k: (sum(model.logged[k]) / len(model.logged[k]) if model.logged.get(k) else float("nan")) for k in keys}

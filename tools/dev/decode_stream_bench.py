@@ -5,7 +5,11 @@ no EOS, so the limits ARE the stop times, which is bench.py's label distribution
 Baseline: generate(num_beams=1, max_length=Lh) over batches of --batch with the same truncation (that code is what the parent commit
 ships).  The two are alternated, each timing includes the encoder and ends on a synchronise; per cell the median of --reps and the
 spread (max - min).  Steps: the stream's own counter; lockstep = sum over batches of (longest limit - 1).
-   python tools/dev/decode_stream_bench.py [--images 4096] [--layers 6 12] [--reps 3] [--slots N] [--batch 256] [--weights bf16 e4m3]"""
+--beams 4 (the table of profiles/decode_stream_beam.md): generate_stream(num_beams=4) against generate(num_beams=4) over the same batches.
+A beam search cut at a limit is the search with that max_length, not a cut of a longer one, so the lockstep arm (one max_length per batch)
+returns other rows than the stream and the tokens are not compared here (tests/test_stream_beam_gpu.py does, per limit); lockstep steps =
+the decoder steps generate issued (last_generate_steps).
+   python tools/dev/decode_stream_bench.py [--images 4096] [--layers 6 12] [--reps 3] [--slots N] [--batch 256] [--weights bf16 e4m3] [--beams 4]"""
 import argparse, dataclasses, os, statistics, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.environ.get("KZV_PKG") or os.path.join(ROOT, "kuzushiji-vision_amd"))
@@ -23,9 +27,11 @@ ap.add_argument("--slots", type=int, default=0, help="0 = the device's compute-u
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--weights", nargs="*", default=["bf16"])
 ap.add_argument("--max_length", type=int, default=128)
+ap.add_argument("--beams", type=int, default=1, help="1 = greedy; 2 / 4 = beam search on the slots against generate(num_beams) in lockstep")
 a = ap.parse_args()
 lib = L.load()
-print(f"library {L.LIB_PATH}; {a.images} crops; lockstep batches of {a.batch}")
+print(f"library {L.LIB_PATH}; {a.images} crops; lockstep batches of {a.batch}; {a.beams} beam(s)")
+beam_kw = {} if a.beams == 1 else {"num_beams": a.beams}
 print("| layers | weights | limits | lockstep steps | stream steps | step ratio | lockstep ms (spread) | stream ms (spread) | time ratio |")
 print("|---|---|---|---|---|---|---|---|---|")
 
@@ -36,9 +42,9 @@ def lockstep(m, x, limits, Lh):
     for s in range(0, x.shape[0], a.batch):
         # the batch stops where its longest limit does: generate() has no per-row limit, so the baseline is GIVEN that bound
         top = int(limits[s:s + a.batch].max())
-        g = m.generate(x[s:s + a.batch], max_length=top, num_beams=1)
+        g = m.generate(x[s:s + a.batch], max_length=top, num_beams=a.beams)
         out[s:s + g.shape[0], :g.shape[1]] = g
-        steps += g.shape[1] - 1
+        steps += g.shape[1] - 1 if a.beams == 1 else m.last_generate_steps
     cols = torch.arange(Lh, device=x.device).view(1, Lh)
     return torch.where(cols >= limits.to(x.device).view(-1, 1), torch.full_like(out, m.cfg.pad_id), out), steps
 
@@ -55,20 +61,23 @@ for layers in a.layers:
     for fmt in a.weights:
         with tempfile.TemporaryDirectory() as tmp:
             m = TrOCRModel(cfg.encoder_config_dict(), build_decoder_dir(os.path.join(tmp, "d"), cfg), init_seed=1, load_tokenizer=False, decode_weights=fmt)
+        if a.beams > 1:                                                            # an untrained model ranks padding like any token; a fitted one never
+            m.state_dict_views()["decoder.lm_head.bias"][cfg.pad_id] -= 8.0        # emits it inside a line, and a beam that took it would send the wave to generate()
         m.eval()
         slots = a.slots or None
         for name, limits in cases.items():
             want, lock_steps = lockstep(m, x, limits, Lh)                         # warm both: binds, packs, graphs
-            got = m.generate_stream(x, max_length=Lh, slots=slots, limits=limits)
-            assert m.stream_decode_impl == "slot-refill"
-            same = bool(torch.equal(torch.nn.functional.pad(got, (0, Lh - got.shape[1]), value=cfg.pad_id), want))
+            got = m.generate_stream(x, max_length=Lh, slots=slots, limits=limits, **beam_kw)
+            assert (m.stream_decode_impl if a.beams == 1 else m.stream_beam_impl) == "slot-refill"
+            assert m.last_stream_pad_fallbacks == 0, "a wave fell back to the lockstep search: the stream arm would time both"
+            same = a.beams > 1 or bool(torch.equal(torch.nn.functional.pad(got, (0, Lh - got.shape[1]), value=cfg.pad_id), want))
             ts = {"lock": [], "stream": []}
             for _ in range(a.reps):
                 torch.cuda.synchronize(); t0 = time.perf_counter()
                 lockstep(m, x, limits, Lh)
                 torch.cuda.synchronize(); ts["lock"].append((time.perf_counter() - t0) * 1e3)
                 torch.cuda.synchronize(); t0 = time.perf_counter()
-                m.generate_stream(x, max_length=Lh, slots=slots, limits=limits)
+                m.generate_stream(x, max_length=Lh, slots=slots, limits=limits, **beam_kw)
                 torch.cuda.synchronize(); ts["stream"].append((time.perf_counter() - t0) * 1e3)
             med = {k: statistics.median(v) for k, v in ts.items()}
             spr = {k: max(v) - min(v) for k, v in ts.items()}
