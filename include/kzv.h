@@ -128,6 +128,12 @@ int kzv_cross_attention(kzv_model* m, int layer, float* d_map, int64_t ld_map, f
 /* Per-position log-probabilities of the labels of the last kzv_forward_loss, [B, t_active] each: kzv_token_scores' outputs on the
  * vocabulary GEMM re-run from the saved LM-head input (valid after the one-launch head + CE path too, which never wrote logits). */
 int kzv_score_tokens(kzv_model* m, float* d_logprob, int64_t* d_top1, float* d_top1_logprob, void* stream);
+/* The k (1..8) best tokens of every label position of the last kzv_forward_loss and their log-probabilities, best first: d_ids int32
+ * and d_logprob fp32, [B, t_active, k] each -- kzv_token_topk's outputs on the same re-run vocabulary GEMM.  Replaces HF's
+ * output_scores=True, scores[t].log_softmax(-1).topk(k), for which fp32 logits [B, t_active, vocab] would have to cross the ABI.  State
+ * rules, validity (after the one-launch head + CE path too) and workspace use are kzv_score_tokens': entry 0 is its top1 / top1_logprob,
+ * and kzv_backward afterwards still works.  KZV_E_ARG: k outside 1..8, a null result array. */
+int kzv_score_tokens_topk(kzv_model* m, int k, int32_t* d_ids, float* d_logprob, void* stream);
 
 /* Encoder only (ViTEncoder.forward + encoder_decoder_proj + the cross-attention K/V of every decoder layer) for n_images
  * crops [n_images, C, H, W], n_images dividing the bound batch: the bound batch counts DECODER rows, and beam search runs
@@ -268,6 +274,13 @@ typedef struct kzv_stream_state {
 } kzv_stream_state;
 int kzv_stream_seat_first(const kzv_stream_state* st, void* stream);
 int kzv_stream_update(const kzv_stream_state* st, const float* d_logits, int64_t ld, void* stream);
+/* The alternatives of one step, from the same logits and BEFORE kzv_stream_update (which replaces slot_image / slot_t): per live slot
+ * (image i at step t, t + 1 < max_len) d_alt_ids[i][t + 1][0..k) / d_alt_logprob[i][t + 1][0..k) = kzv_token_topk of the slot's row, so
+ * entry 0 is the token kzv_stream_update emits and its out_logprob.  Idle slots write nothing; the caller fills the arrays (int32 / fp32
+ * [n_images, ld_alt >= max_len * k]) beforehand.  Reads slots, n_images, max_len, vocab, slot_image and slot_t of the state only.  HF:
+ * generate(output_scores=True) -> scores[t].log_softmax(-1).topk(k).  KZV_E_ARG as kzv_token_topk's, and for ld_alt < max_len * k. */
+int kzv_stream_topk(const kzv_stream_state* st, const float* d_logits, int64_t ld, int k, int32_t* d_alt_ids, float* d_alt_logprob,
+                    int64_t ld_alt, void* stream);
 /* On the model handle (the bound batch = the slot count; the bound label length >= max_len).
  * kzv_stream_decode_impl: 1 where the bound geometry gets slot-refill decoding -- exactly where the one-launch step serves one row per
  * image (hidden 256, 4 heads, FFN 768, <= 12 layers, <= 128 cached and <= 320 patch keys) and kzv_set_decode_one_launch is on -- else 0;
@@ -290,6 +303,13 @@ int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int firs
 int kzv_stream_start(kzv_model* m, void* stream);
 int kzv_stream_step(kzv_model* m, int graph, void* stream);
 int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream);
+/* Alternatives for the greedy wave just begun: after kzv_stream_begin and before kzv_stream_start.  Every kzv_stream_step then runs
+ * kzv_stream_topk between the vocabulary GEMM and selection -- one more kernel node of the same single chain -- into d_alt_ids /
+ * d_alt_logprob [n_images, ld_alt >= max_len * k], which the caller has filled (-1 / 0) and keeps alive for the wave.  k = 0 switches it
+ * off again; the next kzv_stream_begin clears it; when not set a step launches exactly what it launches without this call.  Launches
+ * nothing itself.  KZV_E_STATE outside a begun greedy wave and for beam waves (a beam winner's per-token values are not produced on the
+ * slots); KZV_E_ARG for k outside 0..8, null arrays, ld_alt < max_len * k. */
+int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, float* d_alt_logprob, int64_t ld_alt, void* stream);
 
 /* ---- Beam search on the same slots (opt-in; kzv/stream.py: beam_select_seat / beam_stream state the bookkeeping in torch ops) ------------
  * Serves decoder.generate(num_beams = 4, early_stopping = True, max_length = 128) as the reference asks for it on every validation and
@@ -646,6 +666,14 @@ int kzv_attn_probs(const kzv_attn_probs_args* a, void* stream);
  * log-probability.  Each output [rows_b, T], any of them NULL. */
 int kzv_token_scores(const float* logits, int64_t ld, const int64_t* targets, int64_t ld_targets, int rows_b, int T, int vocab, int pad_id,
                      float* logprob, int64_t* top1, float* top1_logprob, void* stream);
+/* The k (1..8) best columns of every fp32 logits row [rows, ld] and their log-softmax values (logit - log-sum-exp over `vocab` columns,
+ * maximum subtracted first), one wave per row in ONE pass: ids int32 and logprob fp32, [rows, k] each, best first.  Replaces HF's
+ * output_scores=True, scores[t].log_softmax(-1).topk(k).  Order: descending logit, ties by ascending column -- kzv_token_scores' first
+ * arg-max rule, so entry 0 is its top1 / top1_logprob.  -inf logits are legal: they rank last (ties by column) with log-probability
+ * -inf.  Where vocab < k the surplus entries are id -1, logprob -inf.  Rows holding NaN have unspecified order; every id stays in
+ * [-1, vocab).  Bit-reproducible (no atomics).  KZV_E_ARG: null pointers, k outside 1..8, vocab < 1, ld < vocab, rows outside
+ * 1..2^31-1. */
+int kzv_token_topk(const float* logits, int64_t ld, int64_t rows, int vocab, int k, int32_t* ids, float* logprob, void* stream);
 
 /* ------------------------------------------------------------- the ResNet / BiLSTM / CTC model of ocr_lightning/model.py
  * (SURVEY.md section 8(f), row N3).  Per-op entry points; the host mirror kzv/ocr_model.py strings them together the way

@@ -18,6 +18,7 @@
 // replaced by 0 before anything accumulates (no -inf anywhere: exp2 never sees a NaN).
 // Rounding points: q, k bf16 (exact products, fp32 accumulation in the MFMA); s * sc - lse, exp2, the head sum and the row state fp32.
 #include "attention_common.h"
+#include "row_scan.h"
 
 namespace {
 
@@ -127,16 +128,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsP p) {
 // ---- per-token scores: one wave per logits row --------------------------------------------------------------------------------------
 // Row b * T + t is scored against targets[b][t + 1] (kzv_ce_fwd_bwd's indexing).  ONE pass over the row, 16 bytes per lane: each lane
 // keeps the maximum of its columns, its first column and the sum of exp(x - max) under that maximum (rescaled when the maximum moves);
-// the lanes are then combined by xor shuffles under the row maximum -- a fixed order.
-struct RowScan {
-    float mx = -INFINITY, se = 0.f;
-    int arg = 0x7fffffff;                                    // "no column yet": loses every tie
-    __device__ __forceinline__ void take(float x, int col) {
-        if (x > mx) { se *= __expf(mx - x); mx = x; arg = col; }      // ascending columns: strict > keeps the first
-        if (mx > -INFINITY) se += __expf(x - mx);                     // (a -inf column before any finite one adds nothing)
-    }
-};
-
+// the lanes are then combined by xor shuffles under the row maximum -- a fixed order (row_scan.h, shared with token_topk.hip).
 __global__ __launch_bounds__(256) void token_scores_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ targets,
                                                            int64_t ld_targets, int rows, int T, int vocab, int pad_id, int vec,
                                                            float* __restrict__ logprob, int64_t* __restrict__ top1, float* __restrict__ top1_logprob) {
@@ -153,19 +145,13 @@ __global__ __launch_bounds__(256) void token_scores_kernel(const float* __restri
     for (int j = 4 * nv + lane; j < vocab; j += 64) st.take(lr[j], j);
     float mx = st.mx;
     int arg = st.arg;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mx, o, 64);
-        const int oa = __shfl_xor(arg, o, 64);
-        if (ov > mx || (ov == mx && oa < arg)) { mx = ov; arg = oa; }
-    }
-    const float se = wave_sum(st.arg == 0x7fffffff ? 0.f : st.se * __expf(st.mx - mx));
-    const float lse = mx + __logf(se);
+    wave_first_argmax(mx, arg);
+    const float lse = wave_lse(st, mx);
     if (lane == 0) {
         const int b = row / T, t = row - b * T;
         const int64_t tgt = targets[(int64_t)b * ld_targets + t + 1];
         if (logprob) logprob[row] = (tgt == pad_id || tgt < 0 || tgt >= vocab) ? 0.f : lr[tgt] - lse;
-        if (top1) top1[row] = arg == 0x7fffffff ? 0 : arg;   // (a row without a finite maximum)
+        if (top1) top1[row] = arg == ROW_NO_COL ? 0 : arg;   // (a row without a finite maximum)
         if (top1_logprob) top1_logprob[row] = mx - lse;
     }
 }

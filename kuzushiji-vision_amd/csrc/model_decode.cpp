@@ -409,6 +409,7 @@ static int stream_begin(kzv_model* m, const char* who, int nb, int early, float 
     char* q = m->sstate.as<char>();
     m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
     m->sbeams = nb > 1 ? nb : 0;
+    m->stopk = 0;                                // kzv_stream_set_topk belongs to one wave
     if (nb == 1) {
         kzv_stream_state& st = m->sst;
         st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
@@ -470,6 +471,18 @@ extern "C" int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_sto
                         d_out_ids, ld_ids, d_out_logprob, ld_logprob, d_limit, stream);
 }
 
+extern "C" int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, float* d_alt_logprob, int64_t ld_alt, void* stream) {
+    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_topk: call kzv_stream_begin first");
+    if (m->sbeams) return kzv_fail(KZV_E_STATE, "stream_set_topk: the wave is a beam search (alternatives are greedy only)");
+    if (k < 0 || k > 8) return kzv_fail(KZV_E_ARG, "stream_set_topk: k must be in 0..8 (got %d; 0 switches the alternatives off)", k);
+    if (k && (!d_alt_ids || !d_alt_logprob)) return kzv_fail(KZV_E_ARG, "stream_set_topk: null result array");
+    if (k && ld_alt < (int64_t)m->sst.max_len * k) return kzv_fail(KZV_E_ARG, "stream_set_topk: ld_alt %lld < max_len * k = %lld", (long long)ld_alt, (long long)m->sst.max_len * k);
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
+    m->stopk = k; m->salt_ids = k ? d_alt_ids : nullptr; m->salt_lp = k ? d_alt_logprob : nullptr; m->sld_alt = k ? ld_alt : 0;
+    return KZV_OK;
+}
+
 extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_encode: model not bound");
     if (!m->swave) return kzv_fail(KZV_E_STATE, "stream_encode: call kzv_stream_begin first");
@@ -498,7 +511,10 @@ static int stream_step_body(kzv_model* m, hipStream_t s) {
     }
     KZV_TRY(kzv_decode_fused_launch(a, s));
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
-    if (!nb) return kzv_stream_update(&m->sst, m->slogits, m->V, s);
+    if (!nb) {                                   // the alternatives read slot_image / slot_t before seating replaces them
+        if (m->stopk) KZV_TRY(kzv_stream_topk(&m->sst, m->slogits, m->V, m->stopk, m->salt_ids, m->salt_lp, m->sld_alt, s));
+        return kzv_stream_update(&m->sst, m->slogits, m->V, s);
+    }
     KZV_TRY(kzv_beam_topk(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
     return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);
 }

@@ -119,6 +119,8 @@ struct kzv_model_plain {
     // state and logits inside it, the wave in progress
     int spool_images = 0, sstate_slots = 0, sstate_V = 0;
     kzv_stream_state sst = {}; float* slogits = nullptr; bool swave = false;
+    // alternatives of a greedy wave (kzv_stream_set_topk): candidates per position (0: off) and the caller's arrays [n_images, sld_alt]
+    int stopk = 0; int32_t* salt_ids = nullptr; float* salt_lp = nullptr; int64_t sld_alt = 0;
     // beam search on the slots (kzv_stream_begin_beams): beams per slot (0: the wave is greedy), the beam state, the ranking buffers, and
     // the host copy of the divisor table, kept for as long as the asynchronous copy to the device may still read it (until the next begin)
     int sbeams = 0;

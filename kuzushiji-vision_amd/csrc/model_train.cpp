@@ -569,6 +569,15 @@ extern "C" int kzv_score_tokens(kzv_model* m, float* d_logprob, int64_t* d_top1,
     return kzv_token_scores(m->logits, m->Vp, m->labels, m->L, m->B, m->Ta, m->V, m->c.pad_id, d_logprob, d_top1, d_top1_logprob, stream);
 }
 
+extern "C" int kzv_score_tokens_topk(kzv_model* m, int k, int32_t* d_ids, float* d_logprob, void* stream) {
+    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "score_tokens_topk: model not bound");
+    if (!m->have_dec) return kzv_fail(KZV_E_STATE, "score_tokens_topk: call kzv_forward_loss first (its decoder activations are gone or were never computed)");
+    if (k < 1 || k > 8 || !d_ids || !d_logprob) return kzv_fail(KZV_E_ARG, "score_tokens_topk: k in 1..8 and two result arrays [B, t_active, k]");
+    // kzv_score_tokens' vocabulary GEMM, then the k best columns of every packed row
+    KZV_TRY(lin_fwd(m, m->word, m->hd_ln, m->Hd, m->B * m->Ta, m->logits, m->Vp, KZV_EPI_F32, (hipStream_t)stream, {.n = m->Vp}));
+    return kzv_token_topk(m->logits, m->Vp, (int64_t)m->B * m->Ta, m->V, k, d_ids, d_logprob, stream);
+}
+
 extern "C" int kzv_backward_segments(const kzv_model* m) { return m ? m->Le + 2 : 0; }
 
 extern "C" int kzv_backward_segment_range(const kzv_model* m, int seg, int64_t* lo, int64_t* hi) {

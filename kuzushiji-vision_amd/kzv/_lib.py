@@ -200,6 +200,8 @@ SYMBOLS = {
     "kzv_token_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "kzv_cross_attention": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, _P, _P]),
     "kzv_score_tokens": (C.c_int, [_P, _P, _P, _P, _P]),
+    "kzv_score_tokens_topk": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "kzv_token_topk": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     "kzv_drop_key": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "kzv_debug_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "kzv_debug_attn_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
@@ -258,6 +260,8 @@ SYMBOLS = {
     "kzv_beam_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kzv_stream_seat_first": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p]),
     "kzv_stream_update": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_void_p]),
+    "kzv_stream_topk": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "kzv_stream_set_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "kzv_stream_decode_impl": (C.c_int, [C.c_void_p]),
     "kzv_stream_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "kzv_stream_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

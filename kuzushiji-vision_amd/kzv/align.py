@@ -55,7 +55,8 @@ def pad_rows(x, width: int, fill=0):
     return out
 
 
-def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: int, eos_id: int, texts=None, to_strings=None) -> list[dict]:
+def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: int, eos_id: int, texts=None, to_strings=None,
+                  alternatives=None) -> list[dict]:
     """One record per image from ids [B, L] (BOS first, PAD after the end) and the per-position arrays [B, L - 1] (centroid
     [B, L - 1, 2] in pixels, (y, x)):
 
@@ -68,7 +69,14 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
       centroids     (y, x) in pixels per token; peak_patches: the arg-max patch per token
 
     A row stops at its first EOS or PAD target; a generation that is BOS, EOS only gives empty lists and the EOS's own
-    probability as confidence."""
+    probability as confidence.
+
+    ``alternatives`` = (alt_ids, alt_logprob), [B, L - 1, k] each (kzv_score_tokens_topk / kzv_stream_topk: the k best tokens of
+    every position, best first, -1 where there is none), adds two keys:
+
+      alternatives  per token of ``tokens`` a list of up to k dicts {"token", "string", "logprob"} in rank order (entries with
+                    id -1 dropped; ``string`` from ``to_strings``, else None)
+      margins       per token the first alternative's log-probability minus the second's; inf with a single candidate"""
     ids = np.asarray(ids)
     logprob = np.asarray(logprob, dtype=np.float64)
     centroid = np.asarray(centroid, dtype=np.float64)
@@ -77,9 +85,13 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
     if logprob.shape != (B, L - 1) or peak_patch.shape != (B, L - 1) or centroid.shape != (B, L - 1, 2):
         raise ValueError(f"per-position arrays must be [B, L - 1] = {(B, L - 1)} (centroid [B, L - 1, 2]); got "
                          f"{logprob.shape}, {centroid.shape}, {peak_patch.shape}")
+    if alternatives is not None:
+        alt_ids, alt_lp = (np.asarray(a) for a in alternatives)
+        if alt_ids.ndim != 3 or alt_ids.shape[:2] != (B, L - 1) or alt_lp.shape != alt_ids.shape:
+            raise ValueError(f"alternatives must be two [B, L - 1, k] = {(B, L - 1, 'k')} arrays; got {alt_ids.shape}, {alt_lp.shape}")
     records = []
     for b in range(B):
-        tokens, lps, cents, peaks, scored = [], [], [], [], []
+        tokens, lps, cents, peaks, scored, alts, margins = [], [], [], [], [], [], []
         for t in range(L - 1):
             tok = int(ids[b, t + 1])
             if tok == pad_id or int(ids[b, t]) == pad_id:
@@ -93,6 +105,11 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
             lps.append(float(logprob[b, t]))
             cents.append((float(centroid[b, t, 0]), float(centroid[b, t, 1])))
             peaks.append(int(peak_patch[b, t]))
+            if alternatives is not None:
+                cand = [(int(i), float(p)) for i, p in zip(alt_ids[b, t], alt_lp[b, t]) if int(i) >= 0]
+                strs = [None] * len(cand) if to_strings is None else list(to_strings([i for i, _ in cand]))
+                alts.append([{"token": i, "string": s, "logprob": p} for (i, p), s in zip(cand, strs)])
+                margins.append(cand[0][1] - cand[1][1] if len(cand) > 1 and cand[1][1] > -math.inf else math.inf)
         records.append({
             "text": None if texts is None else texts[b],
             "tokens": tokens,
@@ -102,4 +119,7 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
             "centroids": cents,
             "peak_patches": peaks,
         })
+        if alternatives is not None:
+            records[-1]["alternatives"] = alts
+            records[-1]["margins"] = margins
     return records

@@ -345,13 +345,17 @@ class TrOCRModel:
         L.check(lib.kzv_backward(self._h, st), "kzv_backward")
 
     # ------------------------------------------------------------------ per-character confidence and position
-    def align_last(self, layer=-1, want_map: bool = False):
+    def align_last(self, layer=-1, want_map: bool = False, top_k: int = 0):
         """Scores and cross-attention of the LAST ``forward_loss`` / ``forward(pixel_values, labels)`` on this model, read back from
         its saved activations (kzv_score_tokens, kzv_cross_attention); see ``align`` for the result.  Raises KzvError when a
-        generate, a rebind or a change of geometry has replaced those activations.  A pending ``backward`` still works."""
+        generate, a rebind or a change of geometry has replaced those activations.  A pending ``backward`` still works.  ``top_k`` in
+        1..8 adds ``alt_ids`` / ``alt_logprob`` (kzv_score_tokens_topk)."""
         import torch
         from . import align as A
         c = self.cfg
+        top_k = int(top_k)
+        if not 0 <= top_k <= 8:
+            raise ValueError("top_k must be in 0..8")
         lib = L.load()
         st = L.stream_handle()
         if self._keep is None:
@@ -395,9 +399,15 @@ class TrOCRModel:
         }
         if want_map:
             out["map"] = A.pad_rows(amap, T)
+        if top_k:
+            alt_ids = torch.empty(B, Ta, top_k, dtype=torch.int32, device=dev)
+            alt_lp = torch.empty(B, Ta, top_k, dtype=torch.float32, device=dev)
+            L.check(lib.kzv_score_tokens_topk(self._h, top_k, alt_ids.data_ptr(), alt_lp.data_ptr(), st), "kzv_score_tokens_topk")
+            out["alt_ids"] = A.pad_rows(alt_ids.long(), T, -1)
+            out["alt_logprob"] = A.pad_rows(alt_lp, T)
         return out
 
-    def align(self, pixel_values, labels, layer=-1, want_map: bool = False):
+    def align(self, pixel_values, labels, layer=-1, want_map: bool = False, top_k: int = 0):
         """Per-position confidence and position of ``labels`` [B, L] on the crops: one eval-mode teacher-forced pass (no logits
         are materialised for the caller; trailing padding is trimmed as in training), then the two read-backs.  Returns device
         tensors padded back to [B, L - 1]; row t belongs to the token labels[:, t + 1]:
@@ -408,6 +418,9 @@ class TrOCRModel:
           row_sum                       the sum of the weights (1 up to rounding: a health value)
           map [B, L - 1, n_patches]     the weights themselves, when ``want_map``
           live                          decoder input and target both non-pad (other rows are padding or zeros)
+          alt_ids, alt_logprob [B, L - 1, k]  with ``top_k`` = k in 1..8: the k best tokens of every position and their
+                                        log-probabilities, best first, ties by the smaller id (entry 0 = top1 / top1_logprob; HF:
+                                        output_scores=True, scores[t].log_softmax(-1).topk(k)); -1 / 0 in the trimmed padding
 
         ``layer``: a decoder layer (negative from the end) or a sequence of them, whose maps are averaged (HF:
         ``cross_attentions[layer].mean(1)``)."""
@@ -417,26 +430,29 @@ class TrOCRModel:
             self.forward_loss(pixel_values, labels, want_logits=False, seed=0)
         finally:
             self.training = was
-        return self.align_last(layer, want_map)
+        return self.align_last(layer, want_map, top_k)
 
-    def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1) -> list[dict]:
+    def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0) -> list[dict]:
         """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
         ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
         ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
-        pixels) and ``peak_patches`` (kzv/align.py: build_records)."""
+        pixels) and ``peak_patches`` (kzv/align.py: build_records).  ``top_k`` in 1..8 adds ``alternatives`` (per token the k best
+        candidates of the teacher-forced pass with their log-probabilities) and ``margins``; after a beam search the chosen token
+        need not be the first alternative."""
         import torch
         from . import align as A
         c = self.cfg
         gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True)
         if gen.shape[1] < 2:                                  # labels need a target column
             gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
-        out = self.align(pixel_values, gen, layer=layer)
+        out = self.align(pixel_values, gen, layer=layer, top_k=top_k)
         ids = gen.cpu().numpy()
         tok = self.tokenizer
+        alts = (out["alt_ids"].cpu().numpy(), out["alt_logprob"].cpu().numpy()) if top_k else None
         return A.build_records(ids, out["logprob"].cpu().numpy(), out["centroid"].cpu().numpy(), out["peak_patch"].cpu().numpy(),
                                pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
-                               to_strings=None if tok is None else tok.convert_ids_to_tokens)
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
 
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True):
@@ -584,7 +600,7 @@ class TrOCRModel:
 
     def generate_stream(self, pixel_values, max_length: int = 128, slots: int | None = None, limits=None, return_logprobs: bool = False,
                         pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
-                        return_scores: bool = False):
+                        return_scores: bool = False, top_k: int = 0):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -607,12 +623,24 @@ class TrOCRModel:
         ``return_scores``: also fp32 [N], the winner's sum of log-probabilities / generated length ** length_penalty (HF's
         ``sequences_scores``; on the static path from ``align``).  ``return_logprobs`` is greedy only: per-token log-probabilities of
         a beam winner are not produced.  The slots assume that no running beam holds padding; a wave in which one took ``pad_id`` is
-        decoded again by ``generate`` and counted in ``last_stream_pad_fallbacks``."""
+        decoded again by ``generate`` and counted in ``last_stream_pad_fallbacks``.
+
+        ``top_k`` in 1..8 (greedy only): the call returns ``(ids, logprobs, alt_ids, alt_logprob)``, the last two int64 / fp32
+        [N, width, top_k]: at every emitted column the k best tokens of that step and their log-probabilities, best first (entry 0 is
+        the emitted token; kzv_stream_topk, one more kernel per step and no second pass); -1 / 0 in column 0 and past a line's end.  On
+        the static path they come from ``align(..., top_k=top_k)``."""
         import torch
         c = self.cfg
         nb = int(num_beams)
+        top_k = int(top_k)
         if nb < 1:
             raise ValueError("num_beams must be positive")
+        if not 0 <= top_k <= 8:
+            raise ValueError("top_k must be in 0..8")
+        if nb > 1 and top_k:
+            raise ValueError("top_k is greedy only: a beam winner's per-token candidates are not produced on the slots (recognize(top_k=...) scores them in a teacher-forced pass)")
+        if top_k:
+            return_logprobs = True
         if nb > 1 and return_logprobs:
             raise ValueError("return_logprobs is greedy only: a beam search returns sequence scores (return_scores)")
         if nb == 1 and return_scores:
@@ -630,7 +658,7 @@ class TrOCRModel:
         if slots < 1:
             raise ValueError("slots must be positive")
         lim_all = None if limits is None else torch.as_tensor(limits, dtype=torch.int32).reshape(-1).clamp(min=2)
-        ids_out, lp_out, done = [], [], 0
+        ids_out, lp_out, alt_out, done = [], [], [], 0
         self.last_stream_steps = 0               # decoder steps the last call took (every wave; the static path leaves 0)
         src = iter((pixel_values,) if torch.is_tensor(pixel_values) else pixel_values)
         first_batch = next(src)
@@ -642,10 +670,17 @@ class TrOCRModel:
             lim = None if lim_all is None else lim_all[done:done + n]
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
-            ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams)
+            if top_k:
+                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k)
+                alt_out.append(alts)
+            else:
+                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams)
             ids_out.append(ids); lp_out.append(lp); done += n
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
+        if top_k:
+            return (ids[:, :width], torch.cat(lp_out)[:, :width], torch.cat([a[0] for a in alt_out])[:, :width].long(),
+                    torch.cat([a[1] for a in alt_out])[:, :width])
         if return_logprobs:
             return ids[:, :width], torch.cat(lp_out)[:, :width]
         if return_scores:
@@ -676,9 +711,10 @@ class TrOCRModel:
                 score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
         return ids, score
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None):
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0):
         """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
-        length_penalty): ids [n, Lh] and the winners' scores [n]."""
+        length_penalty): ids [n, Lh] and the winners' scores [n]; with ``top_k`` (greedy) a third result, (alt_ids int32, alt_logprob)
+        [n, Lh, top_k]."""
         import torch
         from . import stream as ST
         c = self.cfg
@@ -696,6 +732,8 @@ class TrOCRModel:
         if not beams and self.stream_decode_impl == "static":
             ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
             lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
+            alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
+            alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
             for a in range(0, n, slots):
                 g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1)
                 ids[a:a + g.shape[0], :g.shape[1]] = g
@@ -703,15 +741,21 @@ class TrOCRModel:
                 ids = torch.where(torch.arange(Lh, device=dev).view(1, Lh) >= lim.to(dev).view(n, 1), torch.full_like(ids, c.pad_id), ids)
             if want_lp:
                 for a in range(0, n, slots):
-                    sc = self.align(px[a:a + slots], ids[a:a + slots])
+                    sc = self.align(px[a:a + slots], ids[a:a + slots], top_k=top_k)
                     lp[a:a + slots, 1:] = torch.where(sc["live"], sc["logprob"], torch.zeros_like(sc["logprob"]))
-            return ids, lp
+                    if top_k:
+                        lv = sc["live"].unsqueeze(-1)
+                        alt_ids[a:a + slots, 1:] = torch.where(lv, sc["alt_ids"], torch.full_like(sc["alt_ids"], -1)).to(torch.int32)
+                        alt_lp[a:a + slots, 1:] = torch.where(lv, sc["alt_logprob"], torch.zeros_like(sc["alt_logprob"]))
+            return (ids, lp, (alt_ids, alt_lp)) if top_k else (ids, lp)
         was = self.training
         self.training = False
         ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
         ids[:, 0] = c.bos_id
         lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
         score = torch.zeros(n, dtype=torch.float32, device=dev) if beams else None
+        alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
+        alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
         limd = None if lim is None else lim.to(dev).contiguous()
         pool = -(-n // rows) * rows
         divisors = [d for d in range(1, rows + 1) if rows % d == 0]
@@ -729,6 +773,8 @@ class TrOCRModel:
                                                        ids.data_ptr(), Lh, None, 0, L.ptr(limd), st), "stream_begin_beams")
                 else:
                     L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
+                    if top_k:
+                        L.check(lib.kzv_stream_set_topk(self._h, top_k, alt_ids.data_ptr(), alt_lp.data_ptr(), Lh * top_k, st), "stream_set_topk")
                 a = 0
                 while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
                     k = min(rows, n - a)                          # is filled by repeating its last image
@@ -759,31 +805,40 @@ class TrOCRModel:
                 self.last_stream_steps += took.value
             if graph:
                 cur.wait_stream(side)
-                for t_ in [ids] + keep + [x for x in (lp, score, limd) if x is not None]:
+                for t_ in [ids] + keep + [x for x in (lp, score, limd, alt_ids, alt_lp) if x is not None]:
                     t_.record_stream(cur)
         finally:
             self.training = was
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
             self.last_stream_pad_fallbacks += pads.value
             return self._static_beam_wave(px, Lh, slots, lim, beams)
+        if top_k:
+            return ids, lp, (alt_ids, alt_lp)
         return ids, (score if beams else lp)
 
-    def recognize_many(self, pixel_values, **kw) -> list[dict]:
+    def recognize_many(self, pixel_values, top_k: int = 0, **kw) -> list[dict]:
         """``generate_stream`` with its own log-probabilities: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD),
         ``token_strings``, ``logprobs`` and ``confidence`` = exp(mean log-probability over the tokens, EOS included) -- ``recognize``'s
         definitions, for greedy decoding, with no teacher-forced second pass.  It returns NO centroids or peak patches: those come
-        from the cross-attention maps of a teacher-forced pass, which ``recognize`` runs.  ``kw``: generate_stream's arguments."""
+        from the cross-attention maps of a teacher-forced pass, which ``recognize`` runs.  ``kw``: generate_stream's arguments; with
+        ``top_k`` in 1..8 every record also holds ``alternatives`` and ``margins`` (build_records), taken from the stream's own steps."""
         import numpy as np
         from . import align as A
         c = self.cfg
-        gen, lp = self.generate_stream(pixel_values, return_logprobs=True, **kw)
+        top_k = int(top_k)
+        alts = None
+        if top_k:
+            gen, lp, a_ids, a_lp = self.generate_stream(pixel_values, return_logprobs=True, top_k=top_k, **kw)
+            alts = (a_ids[:, 1:].cpu().numpy(), a_lp[:, 1:].cpu().numpy())
+        else:
+            gen, lp = self.generate_stream(pixel_values, return_logprobs=True, **kw)
         ids = gen.cpu().numpy()
         B, W = ids.shape
         tok = self.tokenizer
         recs = A.build_records(ids, lp[:, 1:].cpu().numpy(), np.zeros((B, W - 1, 2)), np.zeros((B, W - 1), dtype=np.int64),
                                pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
-                               to_strings=None if tok is None else tok.convert_ids_to_tokens)
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
         for r in recs:
             del r["centroids"], r["peak_patches"]
         return recs

@@ -18,17 +18,39 @@ State (a dict of tensors; out_ids / out_logprob are written in place, the others
   counters   int32 [3]       next image without a slot, lines ended, steps taken while a line was open
   out_ids    int64 [N, L]    BOS, the tokens, EOS if emitted, then padding
   out_logprob fp32 [N, L]    optional: log-probability of out_ids[i][j] at [i][j] (0 at BOS and padding)
+  alt_ids    int32 [N, L, k] optional (``top_k``): the k best tokens at [i][j], best first (kzv_stream_topk); -1 in columns never scored
+  alt_logprob fp32 [N, L, k] optional: their log-probabilities; 0 in columns never scored
 """
 from __future__ import annotations
 
 
-def new_state(n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int, device, want_logprobs: bool = False):
-    """The state with the first min(slots, n_images) images seated in slot order (kzv_stream_seat_first)."""
+def topk_rows(logits, k: int):
+    """The k best columns of every row of ``logits`` [R, V] and their log-softmax values, best first: descending logit, ties by
+    ascending column (a stable sort), so entry 0 is select_seat's token; where V < k the surplus entries are -1 / -inf
+    (kzv_token_topk).  Returns (int32 [R, k], fp32 [R, k])."""
     import torch
+    x = logits.float()
+    R, V = x.shape
+    order = torch.sort(x, dim=-1, descending=True, stable=True)[1][:, :k]
+    lp = torch.log_softmax(x, dim=-1).gather(1, order)
+    lp = torch.where(x.gather(1, order) == float("-inf"), torch.full_like(lp, float("-inf")), lp)      # (an all -inf row: not NaN)
+    ids = order.to(torch.int32)
+    if V < k:
+        ids = torch.cat((ids, torch.full((R, k - V), -1, dtype=torch.int32, device=x.device)), dim=1)
+        lp = torch.cat((lp, torch.full((R, k - V), float("-inf"), dtype=lp.dtype, device=x.device)), dim=1)
+    return ids, lp
+
+
+def new_state(n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int, device, want_logprobs: bool = False, top_k: int = 0):
+    """The state with the first min(slots, n_images) images seated in slot order (kzv_stream_seat_first).  ``top_k`` in 1..8 adds the
+    alternatives (alt_ids / alt_logprob, -1 / 0 throughout)."""
+    import torch
+    if not 0 <= int(top_k) <= 8:
+        raise ValueError("top_k must be in 0..8")
     s = torch.arange(slots, dtype=torch.int32, device=device)
     out_ids = torch.full((n_images, max_len), pad_id, dtype=torch.int64, device=device)
     out_ids[:, 0] = bos_id
-    return {
+    st = {
         "slot_image": torch.where(s < n_images, s, torch.full_like(s, -1)),
         "slot_t": torch.zeros(slots, dtype=torch.int32, device=device),
         "tokens": torch.full((slots,), bos_id, dtype=torch.int64, device=device),
@@ -37,6 +59,10 @@ def new_state(n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int,
         "out_ids": out_ids,
         "out_logprob": torch.zeros(n_images, max_len, dtype=torch.float32, device=device) if want_logprobs else None,
     }
+    if top_k:                                    # (the keys exist only when asked for)
+        st["alt_ids"] = torch.full((n_images, max_len, int(top_k)), -1, dtype=torch.int32, device=device)
+        st["alt_logprob"] = torch.zeros(n_images, max_len, int(top_k), dtype=torch.float32, device=device)
+    return st
 
 
 def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, limit=None):
@@ -45,7 +71,8 @@ def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id:
     out_logprob[i][t + 1] = max - logsumexp; the line has ended when token == eos_id, t + 2 >= limit[i] or t + 2 >= max_len.
     Then the slots whose lines ended take the images counters[0], counters[0] + 1, ... in ascending slot order (an exclusive prefix
     sum over the ended flags) at step 0 / BOS, or go idle when no image is left; the others advance.  ``limit``: optional int32
-    [n_images], the most tokens, BOS included, an image may get.  Returns ``st``."""
+    [n_images], the most tokens, BOS included, an image may get.  Where the state holds alternatives (new_state's ``top_k``),
+    alt_ids / alt_logprob[i][t + 1] = topk_rows of the slot's row.  Returns ``st``."""
     import torch
     dev = logits.device
     img, t = st["slot_image"], st["slot_t"]
@@ -63,6 +90,10 @@ def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id:
     st["out_ids"][rows, colsw] = tok[live]
     if st.get("out_logprob") is not None:
         st["out_logprob"][rows, colsw] = lp[live]
+    if st.get("alt_ids") is not None:
+        a_ids, a_lp = topk_rows(x[live], st["alt_ids"].shape[-1])
+        st["alt_ids"][rows, colsw] = a_ids
+        st["alt_logprob"][rows, colsw] = a_lp
     e32 = ended.to(torch.int32)
     n_ended = e32.sum().to(torch.int32)
     nxt = st["counters"][0]
@@ -86,13 +117,14 @@ def step_bound(n_images: int, slots: int, max_len: int) -> int:
 
 
 def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, limits=None,
-                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False):
+                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False, top_k: int = 0):
     """Greedy decoding of ``n_images`` images over ``slots`` decoder slots.  ``step_fn(state) -> logits [slots, V]`` runs one decoder
     step for every slot: slot b feeds state["tokens"][b] at step state["slot_t"][b] for image state["slot_image"][b] (idle slots may
     return anything).  The counters are looked at every ``poll``-th step; RuntimeError once the steps exceed ``step_bound``.
-    Returns out_ids [N, max_len] (and out_logprob with ``return_logprobs``; and the final state with ``return_state``)."""
+    Returns out_ids [N, max_len] (and out_logprob with ``return_logprobs``; and the final state with ``return_state``, which holds
+    the alternatives asked for with ``top_k``)."""
     import torch
-    st = new_state(n_images, slots, max_len, pad_id, bos_id, device, return_logprobs)
+    st = new_state(n_images, slots, max_len, pad_id, bos_id, device, return_logprobs, top_k)
     lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
     bound = step_bound(n_images, slots, max_len)
     steps = 0
