@@ -9,7 +9,9 @@ modeling_roberta.py:186-326, 421-464, as driven by src/models/trocr_model.py:306
   * at the benchmark geometry (160 patch keys, 127 cached keys, 12 decoder layers = the kernel's limits) for beam 4 and greedy;
   * generate() end to end in both modes.
 The cached step itself is pinned against the teacher-forced pass and the reference's step-wise decode in test_model_gpu.py /
-test_trained_gpu.py (their 256-wide case takes the one-launch path by default)."""
+test_trained_gpu.py (their 256-wide case takes the one-launch path by default).
+These are recipe weights, whose attention is uniform: the comparisons here pin layout, launch geometry and the agreement of the paths;
+the arithmetic of the attention (softmax scale, online-softmax correction, ancestor rows) is pinned in test_decode_peaked_gpu.py."""
 import dataclasses
 
 import numpy as np

@@ -10,7 +10,9 @@ go wrong -- one real key in the second 160, one full 8-key iteration of it, the 
     and 5.0e-3 (per-operation 4.7e-3);
   * generate() over a width-bucket switch across the 160-key boundary on the graph-replayed step, in both modes;
   * more images than compute units at 256 patches;
-  * 321 patches and 3 rows per image stay on the launch-per-operation path and say so."""
+  * 321 patches and 3 rows per image stay on the launch-per-operation path and say so.
+These are recipe weights, whose attention is uniform (the online softmax's correction is about 1): the comparisons here pin layout,
+launch geometry and the agreement of the paths; the arithmetic of the attention is pinned in test_decode_peaked_gpu.py."""
 import dataclasses
 
 import numpy as np

@@ -2,7 +2,9 @@
 tiny-depth models with head_dim 64 and 96 at 2048 x 64 (513 tokens), 64 x 1280 (321) and 1024 x 64 with 8 x 8 patches (1,025),
 whose encoder self-attention and decoder cross-attention run on the K/V-streaming kernels.  Logits against the fp32 oracle,
 training gradients against the oracle with the step's own dropout masks replayed, trimmed == untrimmed, generation with and
-without the cache over 513 and 1,025 patch keys (the chunked decode instance beyond 320 keys), and the CLI end to end."""
+without the cache over 513 and 1,025 patch keys (the chunked decode instance beyond 320 keys), and the CLI end to end.
+These are recipe weights, whose attention is uniform: the generation comparisons here pin layout, launch geometry and the agreement of
+the paths; the arithmetic of the decode attention (its online-softmax correction) is pinned in test_decode_peaked_gpu.py."""
 import dataclasses
 import gc
 import os
