@@ -674,6 +674,35 @@ int kzv_token_scores(const float* logits, int64_t ld, const int64_t* targets, in
  * [-1, vocab).  Bit-reproducible (no atomics).  KZV_E_ARG: null pointers, k outside 1..8, vocab < 1, ld < vocab, rows outside
  * 1..2^31-1. */
 int kzv_token_topk(const float* logits, int64_t ld, int64_t rows, int vocab, int k, int32_t* ids, float* logprob, void* stream);
+/* Levenshtein distance, edit counts, alignment and per-character error counts of n (prediction row, label row) pairs of token ids, one
+ * wave per pair (csrc/edit_distance.hip).  Replaces tokenizer.batch_decode(skip_special_tokens=True) of both sides + calculate_cer's
+ * editdistance per line (src/models/trocr_model.py:373-379, 400-410) for a tokenizer of one character per token, where the distance over
+ * the ids IS the string distance.  From each int64 row every id that equals one of the n_special (0..8) `special` values, wherever it
+ * stands, and every id outside [0, vocab) is dropped (nothing is cut at the first EOS); what is left, at most 128 ids, is the line.
+ *   dist, ref_len, pred_len  int32 [n]: unit-cost distance and the two compacted lengths (CER = dist / ref_len on the host)
+ *   ops          int32 [n, 4], optional: correct, substituted, deleted (label tokens), inserted (predicted tokens); the last three sum to dist
+ *   ref_to_pred  int32 [n, ld_align], optional: per COMPACTED label index the compacted prediction index it is aligned to, -1 where the
+ *                label token is deleted, -2 from ref_len on; columns [0, width_ref) are written
+ *   pred_to_ref  likewise per compacted prediction index: -1 = inserted, -2 from pred_len on; columns [0, width_pred) are written
+ *   char_stats   int32 [vocab, 5], optional, ACCUMULATED (the caller zeroes it; several calls sum over a dataset): per id its occurrences
+ *                as a label token, of these correct / substituted / deleted, and its insertions as a predicted token.  Integer atomics:
+ *                the same table in every run.
+ * The alignment is the walk back from the last cell of the Wagner-Fischer matrix under ONE FIXED PREFERENCE: diagonal (match or
+ * substitution) if it attains the cell's minimum, else up (deletion of a label token), else left (insertion of a predicted token);
+ * kzv/metrics.py: edit_stats_reference states it in numpy.  With ops, both alignment arrays and char_stats null the distance-only
+ * instance runs, which keeps no direction bits.  No model handle; n == 0 returns KZV_OK and launches nothing.
+ * KZV_E_ARG, before any launch: null arguments, pred / ref / dist / ref_len / pred_len null (n > 0), a width outside 1..128, a leading dimension
+ * smaller than its width, n_special outside 0..8, vocab < 1, n < 0, exactly one of the two alignment arrays, ld_align smaller than a width. */
+typedef struct kzv_edit_args {
+    const int64_t* pred; int64_t ld_pred;    /* [n, ld_pred >= width_pred] */
+    const int64_t* ref;  int64_t ld_ref;     /* [n, ld_ref  >= width_ref]  */
+    int32_t n, width_pred, width_ref, vocab, n_special, special[8];
+    int32_t *dist, *ref_len, *pred_len;      /* [n] */
+    int32_t* ops;                            /* optional [n, 4] */
+    int32_t* ref_to_pred; int32_t* pred_to_ref; int64_t ld_align;   /* optional, ld_align >= max(width_pred, width_ref) */
+    int32_t* char_stats;                     /* optional [vocab, 5], accumulated */
+} kzv_edit_args;
+int kzv_edit_distance(const kzv_edit_args* a, void* stream);
 
 /* ------------------------------------------------------------- the ResNet / BiLSTM / CTC model of ocr_lightning/model.py
  * (SURVEY.md section 8(f), row N3).  Per-op entry points; the host mirror kzv/ocr_model.py strings them together the way

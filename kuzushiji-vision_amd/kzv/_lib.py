@@ -77,6 +77,14 @@ class kzv_stream_beam_state(C.Structure):
         ("out_score", C.c_void_p), ("limit", C.c_void_p), ("divisors", C.c_void_p), ("rows", C.c_void_p), ("ld_rows", C.c_int64)]
 
 
+class kzv_edit_args(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("ld_pred", C.c_int64), ("ref", C.c_void_p), ("ld_ref", C.c_int64),
+                ("n", C.c_int32), ("width_pred", C.c_int32), ("width_ref", C.c_int32), ("vocab", C.c_int32), ("n_special", C.c_int32),
+                ("special", C.c_int32 * 8),
+                ("dist", C.c_void_p), ("ref_len", C.c_void_p), ("pred_len", C.c_void_p), ("ops", C.c_void_p),
+                ("ref_to_pred", C.c_void_p), ("pred_to_ref", C.c_void_p), ("ld_align", C.c_int64), ("char_stats", C.c_void_p)]
+
+
 class kzv_gemm_tn_args(C.Structure):
     _fields_ = [("P", C.c_void_p), ("ldp", C.c_int64), ("Q", C.c_void_p), ("ldq", C.c_int64),
                 ("OUT", C.c_void_p), ("ldo", C.c_int64),
@@ -202,6 +210,7 @@ SYMBOLS = {
     "kzv_score_tokens": (C.c_int, [_P, _P, _P, _P, _P]),
     "kzv_score_tokens_topk": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "kzv_token_topk": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
+    "kzv_edit_distance": (C.c_int, [C.POINTER(kzv_edit_args), _P]),
     "kzv_drop_key": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "kzv_debug_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "kzv_debug_attn_dropout_mask": (C.c_int, [C.c_uint32, C.c_float, C.c_int64, C.c_int32, C.c_int32, _P, _P]),

@@ -843,6 +843,61 @@ class TrOCRModel:
             del r["centroids"], r["peak_patches"]
         return recs
 
+    # ------------------------------------------------------------------ evaluation on the device (kzv/metrics.py)
+    @property
+    def one_char_tokenizer(self) -> bool:
+        """Whether the tokenizer is one character per token (metrics.is_one_char_tokenizer), i.e. whether the id-level edit distance
+        equals the reference's string-level one.  Checked once per model; False without a tokenizer."""
+        if getattr(self, "_one_char", None) is None:
+            from . import metrics as M
+            self._one_char = self.tokenizer is not None and bool(M.is_one_char_tokenizer(self.tokenizer))
+        return self._one_char
+
+    def _edit_special_ids(self) -> list[int]:
+        if self.tokenizer is None:             # no tokenizer to ask: the specials the geometry names
+            return sorted({self.cfg.pad_id, self.cfg.bos_id, self.cfg.eos_id})
+        if not self.one_char_tokenizer:
+            raise ValueError("the device evaluation needs a tokenizer of one character per token with at most 8 specials; "
+                             "score this model's lines with batch_decode + calculate_cer")
+        return [int(i) for i in self.tokenizer.all_special_ids]
+
+    def cer_of(self, generated_ids, labels) -> list[float]:
+        """Per-line CER of ``generated_ids`` [N, <= 128] against ``labels`` [N, <= 128], computed from the ids on the device (one
+        kzv_edit_distance, the distance-only kernel): the values ``calculate_cer`` returns for the two ``batch_decode``d strings, ==."""
+        import torch
+        from . import metrics as M
+        gen = torch.as_tensor(generated_ids).to(self.device)
+        st = M.edit_stats(gen, torch.as_tensor(labels).to(self.device), self._edit_special_ids(), self.cfg.vocab, ops=False)
+        return M.cer_values(st["dist"], st["ref_len"], st["pred_len"])
+
+    def evaluate_many(self, pixel_values, labels, num_beams: int = 1, top: int = 20, **generate_stream_kw) -> dict:
+        """``generate_stream`` over the images followed by ONE kzv_edit_distance against ``labels`` ([N, <= 128] ids, or an iterable of
+        such batches in the images' order).  Returns ``cer`` (the mean of the per-line CER: the reference's test_cer), ``cer_corpus``
+        (sum of distances / sum of label lengths), ``exact`` (share of lines with distance 0), ``substitutions`` / ``deletions`` /
+        ``insertions`` / ``ref_chars`` (totals), ``per_line`` (numpy arrays ``cer``, ``dist``, ``ref_len``, ``pred_len``, ``ops``),
+        ``characters`` (metrics.character_table: the ``top`` characters with the most errors) and ``ids`` (the generated rows).  The
+        same call serves geometries where generate_stream runs ``generate``: it needs only the ids."""
+        import numpy as np
+        import torch
+        from . import metrics as M
+        special = self._edit_special_ids()
+        for k in ("return_logprobs", "return_scores", "top_k"):
+            if generate_stream_kw.get(k):
+                raise ValueError(f"evaluate_many scores the ids only: {k} is not served")
+        gen = self.generate_stream(pixel_values, num_beams=num_beams, **generate_stream_kw)
+        lab = labels if torch.is_tensor(labels) else torch.cat([torch.as_tensor(b) for b in labels])
+        st = M.edit_stats(gen, lab.to(gen.device), special, self.cfg.vocab, char_stats=True)
+        dist, ref_len, pred_len, ops = (st[k].cpu().numpy() for k in ("dist", "ref_len", "pred_len", "ops"))
+        cers = M.cer_values(dist, ref_len, pred_len)
+        tot = ops.astype(np.int64).sum(axis=0)
+        chars = int(ref_len.astype(np.int64).sum())
+        return {"cer": sum(cers) / len(cers) if cers else 0.0,
+                "cer_corpus": int(dist.astype(np.int64).sum()) / chars if chars else 0.0,
+                "exact": float((dist == 0).mean()) if len(cers) else 0.0,
+                "substitutions": int(tot[1]), "deletions": int(tot[2]), "insertions": int(tot[3]), "ref_chars": chars,
+                "per_line": {"cer": np.asarray(cers, dtype=np.float64), "dist": dist, "ref_len": ref_len, "pred_len": pred_len, "ops": ops},
+                "characters": M.character_table(st["char_stats"], self.tokenizer, top=top), "ids": gen}
+
     # ------------------------------------------------------------------ Lightning-shaped steps (:323-398)
     def training_step(self, batch, batch_idx):
         loss, _ = self.forward_loss(batch["pixel_values"], batch["labels"], want_logits=False)

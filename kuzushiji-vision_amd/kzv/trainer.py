@@ -231,7 +231,10 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
     loader, report the epoch means of test_loss / test_cer.  ``stream_decode`` (an extension): True also reports ``test_cer_greedy``,
     the mean CER of ONE slot-refill greedy decode over the whole loader (``generate_stream``); "stream-beam" instead reports
     ``test_cer_stream_beam`` from ONE ``generate_stream(num_beams=4)`` over it, test_step's own decode on refilled slots; test_step
-    itself is untouched."""
+    itself is untouched.  In the stream modes, where the tokenizer is one character per token (``model.one_char_tokenizer``), the
+    per-line values are computed from the ids on the device (kzv.metrics.edit_stats: the same values, ==) and rank 0 logs one more
+    line: substitutions / deletions / insertions, corpus CER and the ten characters with the most errors; other tokenizers keep
+    batch_decode + calculate_cer."""
     if ckpt_path:
         load_checkpoint(model, model.optimizers(), ckpt_path)
     model.eval()
@@ -240,19 +243,41 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
     for j, b in enumerate(test_loader):
         model.test_step(b, j)
     keys = ("test_loss", "test_cer")
+    detail = None
     if stream_decode and model.tokenizer is not None:
         import torch
         key, kw = ("test_cer_stream_beam", {"num_beams": 4, "early_stopping": True}) if stream_decode == "stream-beam" else ("test_cer_greedy", {})
         model.logged.pop(key, None)
         gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw)
-        preds = model.tokenizer.batch_decode(gen, skip_special_tokens=True)
-        tgts = model.tokenizer.batch_decode(torch.cat([b["labels"] for b in test_loader]), skip_special_tokens=True)
-        for p, t in zip(preds, tgts):
-            model.log(key, model.calculate_cer(p, t))
+        labels = torch.cat([b["labels"] for b in test_loader])
+        from . import metrics as M
+        if model.one_char_tokenizer and gen.shape[1] <= M.MAX_WIDTH and labels.shape[1] <= M.MAX_WIDTH:
+            # one character per token: the same per-line values from the ids, on the device (include/kzv.h: kzv_edit_distance)
+            st = M.edit_stats(gen, labels.to(gen.device), model.tokenizer.all_special_ids, model.cfg.vocab, char_stats=True)
+            for v in M.cer_values(st["dist"], st["ref_len"], st["pred_len"]):
+                model.log(key, v)
+            detail = _edit_detail(M, st, model.tokenizer)
+        else:
+            preds = model.tokenizer.batch_decode(gen, skip_special_tokens=True)
+            tgts = model.tokenizer.batch_decode(labels, skip_special_tokens=True)
+            for p, t in zip(preds, tgts):
+                model.log(key, model.calculate_cer(p, t))
         keys += (key,)
     if model.optimizers() is not None:
         model.optimizers().train()
     out = {k: (sum(model.logged[k]) / len(model.logged[k]) if model.logged.get(k) else float("nan")) for k in keys}
     if rank == 0:
         log(" ".join(f"{k} {out[k]:.4f}" for k in keys))
+        if detail:
+            log(detail)
     return out
+
+
+def _edit_detail(M, st, tokenizer) -> str:
+    """One line for the log: substitutions / deletions / insertions, corpus CER and the ten characters with the most errors."""
+    ops = st["ops"].sum(dim=0).tolist()
+    chars, dist = int(st["ref_len"].sum()), int(st["dist"].sum())
+    worst = " ".join(f"{r['char']}:{r['substituted'] + r['deleted'] + r['inserted']}/{r['count']}"
+                     for r in M.character_table(st["char_stats"], tokenizer, top=10) if r["substituted"] + r["deleted"] + r["inserted"])
+    return (f"edits S {ops[1]} D {ops[2]} I {ops[3]} over {chars} label characters, corpus CER "
+            f"{dist / chars if chars else 0.0:.4f}; most errors (errors/occurrences): {worst or '-'}")
