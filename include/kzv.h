@@ -159,6 +159,48 @@ int kzv_decode_reorder(kzv_model* m, const int64_t* d_rows, int len, void* strea
  * equal scores rank by the smaller flat index.  d_top_scores [batch, k] fp32, d_top_index [batch, k] int64 = beam * vocab + token. */
 int kzv_beam_topk(const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
                   float* d_top_scores, int64_t* d_top_index, void* stream);
+/* The same ranking over rows that already hold log-probabilities (what kzv_logits_process leaves with normalise != 0): no second
+ * normalisation, a continuation is d_logprobs[row][token] + the beam's score, -inf entries (banned tokens) never rank.  Arguments and
+ * errors as kzv_beam_topk's; the same kernel with its log-sum-exp phase compiled out.  Where fewer than k continuations lie above -inf
+ * the surplus entries are -inf at index 0 (inside every table).  kzv_stream_set_controls and the Python layer refuse the masks that
+ * lead there by themselves (fewer than 2 tokens left); an n-gram ban on top of a two- or three-token mask can still get there, and
+ * the search then carries -inf entries as HF's own top-k does. */
+int kzv_beam_rank_logprobs(const float* d_logprobs, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
+                           float* d_top_scores, int64_t* d_top_index, void* stream);
+/* Generation controls on one step's scores, in place -- transformers' repetition_penalty, no_repeat_ngram_size, min_length and
+ * suppress_tokens with HF's semantics (kzv/controls.py: process_reference is the readable statement).  For row r of logits [rows, ld]
+ * with token history h[0 .. n), BOS included (exactly the input_ids HF hands its logits processors):
+ *   repetition_penalty p (> 0; 1 = off): every distinct token v of h once, x[v] = x[v] < 0 ? x[v] * p : x[v] / p (a true fp32 division);
+ *   no_repeat_ngram_size g (0 = off, 1..8): nothing while n + 1 < g; else for every i in 0 .. n - g with h[i .. i + g - 1) ==
+ *     h[n - g + 1 .. n): x[h[i + g - 1]] = -inf (g = 1 bans every token of h);
+ *   min_length L (0 = off): x[eos_id] = -inf while n < L;
+ *   suppress_mask (optional, device, (vocab + 31) / 32 words, bit v % 32 of word v / 32): x[v] = -inf for every set bit.
+ * The last three only write -inf and the penalty maps -inf to -inf, so their order does not matter.
+ * normalise != 0: the row is first replaced by its log-softmax, (x - max) - log(sum exp(x - max)), reduced in the order of kzv_beam_topk's
+ * first phase (per wave: maximum, then the sum against it; then the four waves merged), and the controls act on that -- what HF's beam search hands its processors; kzv_beam_rank_logprobs then ranks the rows.
+ * Where the history lies (never copied):
+ *   slot_image == NULL (lockstep)          h = ids[r][0 .. t + 1), t the host scalar;
+ *   slot_image, by_image != 0 (greedy slots, group = 1)   h = ids[slot_image[r]][0 .. slot_t[r] + 1): ids = the wave's out_ids;
+ *   slot_image, by_image == 0 (beam slots, group = beams) h = ids[r][0 .. slot_t[r / group] + 1): ids = the wave's run_seq;
+ * in the slot cases the step index is read from device memory (one captured graph serves every step), and the rows of a slot with
+ * slot_image < 0 (idle) or >= n_images are left as they are.  A history is read up to ld_ids tokens at most; tokens outside the vocabulary
+ * are skipped.  One workgroup per row; the two token bitmasks live in LDS, hence vocab <= 16,384.
+ * KZV_E_ARG before any launch: null args / logits / ids, rows < 1, vocab outside 1..16,384, ld < vocab, ld_ids < 1, g outside 0..8,
+ * p <= 0 (or NaN), min_length < 0, EOS outside the vocabulary while min_length > 0, one of slot_image / slot_t without the other, rows no
+ * multiple of group, t < 0 in the lockstep case. */
+typedef struct kzv_logits_process_args {
+    float* logits; int64_t ld;                           /* [rows, ld >= vocab], edited in place */
+    int32_t rows, vocab;
+    const int64_t* ids; int64_t ld_ids;                  /* token histories */
+    int32_t t;                                           /* lockstep: the step index, history length t + 1 */
+    int32_t group;                                       /* slot cases: rows per slot */
+    const int32_t* slot_image; const int32_t* slot_t;    /* slot cases: [rows / group] */
+    int32_t by_image, n_images;
+    int32_t no_repeat_ngram_size, min_length, eos_id, normalise;
+    float repetition_penalty; int32_t reserved;
+    const uint32_t* suppress_mask;
+} kzv_logits_process_args;
+int kzv_logits_process(const kzv_logits_process_args* args, void* stream);
 /* The inputs of decoder step t from the token table d_ids [batch, ld_ids]: d_tokens [batch] = column t, d_posids [batch] = its
  * RoBERTa position id (t + 1 + pad_id, or pad_id for padding), d_valid[:, t] = token != pad. */
 int kzv_decode_prep(const int64_t* d_ids, int64_t ld_ids, int t, int pad_id, int batch, int64_t* d_tokens, uint8_t* d_valid, int64_t ld_valid,
@@ -366,6 +408,24 @@ int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_stopping, floa
                            int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob, int64_t ld_logprob,
                            const int32_t* d_limit, void* stream);
 int kzv_stream_poll_beams(kzv_model* m, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream);
+/* Generation controls for the wave just begun (greedy or beams): after kzv_stream_begin / kzv_stream_begin_beams and before
+ * kzv_stream_start.  Every kzv_stream_step then runs kzv_logits_process as one more kernel node of the same single chain, between the
+ * vocabulary GEMM and kzv_stream_topk / selection in a greedy wave (histories: the wave's out_ids); in a beam wave the normalising
+ * kzv_logits_process plus kzv_beam_rank_logprobs take kzv_beam_topk's place (histories: the slots' running token rows).  The selection's
+ * log-probabilities and the alternatives of kzv_stream_set_topk are then those of the processed row.  suppress_mask: optional HOST array
+ * of (vocab + 31) / 32 words; the library keeps a device copy of its own, the caller's array need not outlive the call.  The setting
+ * belongs to one wave: the next begin clears it.  With every control neutral (0, 1.0, 0, no mask bit set), or when not called, a step
+ * launches exactly what it launches without this call.  Launches no kernel itself.  KZV_E_STATE outside a begun wave; KZV_E_ARG for null
+ * controls, no_repeat_ngram_size outside 0..8, repetition_penalty <= 0, min_length < 0, a mask that suppresses EOS, a vocabulary beyond
+ * 16,384, and in a beam wave a mask that leaves fewer than 2 tokens (the 2 * num_beams continuations a step ranks would not exist). */
+typedef struct kzv_logits_controls {
+    int32_t no_repeat_ngram_size;                        /* 0 = off, 1..8 */
+    float repetition_penalty;                            /* > 0; 1 = off */
+    int32_t min_length;                                  /* 0 = off; tokens, BOS included, before EOS may be chosen */
+    int32_t reserved;
+    const uint32_t* suppress_mask;                       /* optional, host */
+} kzv_logits_controls;
+int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* controls, void* stream);
 
 /* loss.backward() for the step above: fills the bound fp32 grad buffer (which must be zero on entry;
  * kzv_zero_grads does that).  Backward is split in `kzv_backward_segments()` segments so the host can

@@ -359,7 +359,9 @@ __global__ void kv_rows_kernel(const int* __restrict__ src, int* __restrict__ ds
 struct Cand { float v; int i; };
 __device__ __forceinline__ bool cand_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
-template <int KM, int E>
+// LSE = false (kzv_beam_rank_logprobs): the rows already hold log-probabilities (kzv_logits_process has normalised and processed them; a
+// banned token is -inf and never enters a list), so the log-sum-exp phase is compiled out and a continuation is x + beam score.
+template <int KM, int E, bool LSE = true>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ run_sc, int nb, int V, int K,
                                                         float* __restrict__ out_lp, int64_t* __restrict__ out_ix) {
     constexpr int NBM = 8;
@@ -369,6 +371,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
     const float* base = logits + (int64_t)img * nb * ld;
     // ---- per-row log-sum-exp: local (max, sum) over this thread's E tokens, then across the workgroup ----
     float lm[NBM], ls[NBM];
+    float rmx[NBM], rlse[NBM];
+    if constexpr (LSE) {
 #pragma unroll
     for (int k = 0; k < NBM; ++k) {
         lm[k] = -INFINITY; ls[k] = 0.f;
@@ -389,7 +393,6 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
 #pragma unroll
         for (int k = 0; k < NBM; ++k) { s_m[w][k] = lm[k]; s_s[w][k] = ls[k]; }
     __syncthreads();
-    float rmx[NBM], rlse[NBM];
 #pragma unroll
     for (int k = 0; k < NBM; ++k) {
         const float M = fmaxf(fmaxf(s_m[0][k], s_m[1][k]), fmaxf(s_m[2][k], s_m[3][k]));
@@ -398,6 +401,7 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
         for (int q = 0; q < 4; ++q) S += (s_m[q][k] == -INFINITY) ? 0.f : s_s[q][k] * expf(s_m[q][k] - M);
         rmx[k] = M; rlse[k] = logf(S);
     }
+    }                                            // if constexpr (LSE): the block keeps its former indentation
     // ---- this thread's best KM continuations, best first (flat indices arrive in increasing order: ties keep the smaller) ----
     float tv[KM]; int ti[KM];
 #pragma unroll
@@ -412,7 +416,7 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int v = tid + e * 256;
-                const float val = ((x[e] - rmx[k]) - rlse[k]) + sc;
+                const float val = LSE ? ((x[e] - rmx[k]) - rlse[k]) + sc : x[e] + sc;
                 if (v < V && val > tv[KM - 1]) {
                     tv[KM - 1] = val; ti[KM - 1] = k * V + v;
 #pragma unroll
@@ -448,6 +452,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
                 const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64); const int ol = __shfl_xor(bl, o, 64);
                 if (cand_better(ov, oi, bv, bi)) { bv = ov; bi = oi; bl = ol; }
             }
+            // (fewer than K continuations above -inf, possible under a mask only: the empty entries come out as -inf at index 0, inside the tables)
+            if (!LSE && bi == 0x7fffffff) bi = 0;
             if (lane == 0) { out_lp[(int64_t)img * K + r] = bv; out_ix[(int64_t)img * K + r] = bi; }
             if (lane == bl) { cv = -INFINITY; ci = 0x7fffffff; }
         }
@@ -982,22 +988,40 @@ extern "C" int kzv_stream_beam_update(const kzv_stream_beam_state* st, const flo
     return kzv_check_launch("stream_beam_update");
 }
 
-extern "C" int kzv_beam_topk(const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
-                             float* d_top_scores, int64_t* d_top_index, void* stream) {
-    if (!d_logits || !d_beam_scores || !d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "beam_topk: null operand");
-    if (batch < 1 || num_beams < 1 || num_beams > 8 || vocab < 1 || ld < vocab) return kzv_fail(KZV_E_ARG, "beam_topk: 1..8 beams, ld >= vocab");
-    if (k < 1 || k > 16 || (int64_t)k > (int64_t)num_beams * vocab) return kzv_fail(KZV_E_ARG, "beam_topk: 1..16 continuations, at most beams * vocab");
-    if ((int64_t)num_beams * vocab >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "beam_topk: beams * vocab beyond 32-bit flat indices");
-    if (vocab > 64 * 256) return kzv_fail(KZV_E_ARG, "beam_topk: vocab beyond 16,384");
+static int beam_topk_args(const char* who, const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
+                          const float* d_top_scores, const int64_t* d_top_index) {
+    if (!d_logits || !d_beam_scores || !d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "%s: null operand", who);
+    if (batch < 1 || num_beams < 1 || num_beams > 8 || vocab < 1 || ld < vocab) return kzv_fail(KZV_E_ARG, "%s: 1..8 beams, ld >= vocab", who);
+    if (k < 1 || k > 16 || (int64_t)k > (int64_t)num_beams * vocab) return kzv_fail(KZV_E_ARG, "%s: 1..16 continuations, at most beams * vocab", who);
+    if ((int64_t)num_beams * vocab >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "%s: beams * vocab beyond 32-bit flat indices", who);
+    if (vocab > 64 * 256) return kzv_fail(KZV_E_ARG, "%s: vocab beyond 16,384", who);
+    return KZV_OK;
+}
+
+template <bool LSE>
+static int beam_topk_launch(const char* who, const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
+                            float* d_top_scores, int64_t* d_top_index, void* stream) {
+    const int rc = beam_topk_args(who, d_logits, ld, d_beam_scores, batch, num_beams, vocab, k, d_top_scores, d_top_index);
+    if (rc != KZV_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-#define KZV_BT(KM, E) hipLaunchKernelGGL((beam_topk_kernel<KM, E>), dim3(batch), dim3(256), 0, s, d_logits, ld, d_beam_scores, num_beams, vocab, k, d_top_scores, d_top_index)
+#define KZV_BT(KM, E) hipLaunchKernelGGL((beam_topk_kernel<KM, E, LSE>), dim3(batch), dim3(256), 0, s, d_logits, ld, d_beam_scores, num_beams, vocab, k, d_top_scores, d_top_index)
 #define KZV_BT_E(KM) do { if (vocab <= 4 * 256) KZV_BT(KM, 4); else if (vocab <= 20 * 256) KZV_BT(KM, 20); else KZV_BT(KM, 64); } while (0)
     if (k <= 4) KZV_BT_E(4);
     else if (k <= 8) KZV_BT_E(8);
     else KZV_BT_E(16);
 #undef KZV_BT_E
 #undef KZV_BT
-    return kzv_check_launch("beam_topk");
+    return kzv_check_launch(who);
+}
+
+extern "C" int kzv_beam_topk(const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
+                             float* d_top_scores, int64_t* d_top_index, void* stream) {
+    return beam_topk_launch<true>("beam_topk", d_logits, ld, d_beam_scores, batch, num_beams, vocab, k, d_top_scores, d_top_index, stream);
+}
+
+extern "C" int kzv_beam_rank_logprobs(const float* d_logprobs, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
+                                      float* d_top_scores, int64_t* d_top_index, void* stream) {
+    return beam_topk_launch<false>("beam_rank_logprobs", d_logprobs, ld, d_beam_scores, batch, num_beams, vocab, k, d_top_scores, d_top_index, stream);
 }
 
 extern "C" int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,

@@ -410,6 +410,7 @@ static int stream_begin(kzv_model* m, const char* who, int nb, int early, float 
     m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
     m->sbeams = nb > 1 ? nb : 0;
     m->stopk = 0;                                // kzv_stream_set_topk belongs to one wave
+    m->sctl_on = false; m->smask_on = false;     // and so does kzv_stream_set_controls
     if (nb == 1) {
         kzv_stream_state& st = m->sst;
         st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
@@ -483,6 +484,51 @@ extern "C" int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, floa
     return KZV_OK;
 }
 
+extern "C" int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* c, void* stream) {
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_controls: call kzv_stream_begin / kzv_stream_begin_beams first");
+    if (!c) return kzv_fail(KZV_E_ARG, "stream_set_controls: null controls");
+    if (c->no_repeat_ngram_size < 0 || c->no_repeat_ngram_size > 8) return kzv_fail(KZV_E_ARG, "stream_set_controls: no_repeat_ngram_size %d outside 0..8", c->no_repeat_ngram_size);
+    if (!(c->repetition_penalty > 0.f)) return kzv_fail(KZV_E_ARG, "stream_set_controls: repetition_penalty must be positive (got %g)", (double)c->repetition_penalty);
+    if (c->min_length < 0) return kzv_fail(KZV_E_ARG, "stream_set_controls: min_length must not be negative");
+    if (m->V > 64 * 256) return kzv_fail(KZV_E_ARG, "stream_set_controls: vocabulary %d beyond 16,384", m->V);
+    const int words = (m->V + 31) / 32, eos = m->sbeams ? m->sbst.eos_id : m->sst.eos_id;
+    bool any = false;
+    if (c->suppress_mask) {
+        if ((c->suppress_mask[eos >> 5] >> (eos & 31)) & 1u) return kzv_fail(KZV_E_ARG, "stream_set_controls: the mask suppresses EOS (%d): no line could end", eos);
+        int left = m->V;                         // tokens the mask leaves (bits past the vocabulary do not count)
+        for (int i = 0; i < words; ++i) left -= __builtin_popcount(c->suppress_mask[i] & (i == words - 1 && (m->V & 31) ? (1u << (m->V & 31)) - 1u : ~0u));
+        any = left < m->V;
+        // a beam step ranks 2 * num_beams continuations of num_beams rows: with one token left they do not exist
+        if (m->sbeams && left < 2) return kzv_fail(KZV_E_ARG, "stream_set_controls: the mask leaves %d token(s), a beam wave needs at least 2", left);
+    }
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
+    m->sctl = *c; m->sctl.suppress_mask = nullptr; m->smask_on = false;
+    if (any) {                                   // a copy on the stream, no kernel: the steps that follow read it
+        m->smask_h.assign(c->suppress_mask, c->suppress_mask + words);
+        if (!reserve(m, m->smask, sizeof(uint32_t) * (size_t)words)) return kzv_fail(KZV_E_HIP, "stream_set_controls: mask allocation");
+        if (hipMemcpyAsync(m->smask.as<uint32_t>(), m->smask_h.data(), sizeof(uint32_t) * (size_t)words, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+            return kzv_fail(KZV_E_HIP, "stream_set_controls: mask copy");
+        m->smask_on = true;
+    }
+    m->sctl_on = any || c->no_repeat_ngram_size != 0 || c->repetition_penalty != 1.f || c->min_length != 0;
+    return KZV_OK;
+}
+
+// the wave's controls on the step's logits: one more node between the vocabulary GEMM and what reads the rows (order: repetition penalty,
+// n-gram ban, minimum length, suppression -- immaterial, see logits_process.hip)
+static int stream_process(kzv_model* m, hipStream_t s) {
+    const int nb = m->sbeams;
+    kzv_logits_process_args a;
+    memset(&a, 0, sizeof(a));
+    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
+    if (!nb) { a.ids = m->sst.out_ids; a.ld_ids = m->sst.ld_ids; a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; a.eos_id = m->sst.eos_id; }
+    else { a.ids = m->sbst.run_seq; a.ld_ids = m->sbst.max_len; a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; a.eos_id = m->sbst.eos_id; }
+    a.no_repeat_ngram_size = m->sctl.no_repeat_ngram_size; a.repetition_penalty = m->sctl.repetition_penalty; a.min_length = m->sctl.min_length;
+    a.suppress_mask = m->smask_on ? m->smask.as<uint32_t>() : nullptr;
+    a.normalise = nb ? 1 : 0;
+    return kzv_logits_process(&a, s);
+}
+
 extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
     if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_encode: model not bound");
     if (!m->swave) return kzv_fail(KZV_E_STATE, "stream_encode: call kzv_stream_begin first");
@@ -511,6 +557,13 @@ static int stream_step_body(kzv_model* m, hipStream_t s) {
     }
     KZV_TRY(kzv_decode_fused_launch(a, s));
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
+    if (m->sctl_on) {                            // neutral controls: nothing is added to the chain
+        KZV_TRY(stream_process(m, s));
+        if (nb) {                                // the rows are processed log-probabilities now: ranked without a second normalisation
+            KZV_TRY(kzv_beam_rank_logprobs(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
+            return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);
+        }
+    }
     if (!nb) {                                   // the alternatives read slot_image / slot_t before seating replaces them
         if (m->stopk) KZV_TRY(kzv_stream_topk(&m->sst, m->slogits, m->V, m->stopk, m->salt_ids, m->salt_lp, m->sld_alt, s));
         return kzv_stream_update(&m->sst, m->slogits, m->V, s);

@@ -126,6 +126,11 @@ struct kzv_model_plain {
     int sbeams = 0;
     kzv_stream_beam_state sbst = {}; float* stop_lp = nullptr; int64_t* stop_ix = nullptr;
     std::vector<float> sdiv;
+    // generation controls of the wave (kzv_stream_set_controls): on only while a control is not neutral; the host copy of the suppress mask,
+    // kept like sdiv, and whether kzv_model::smask holds it
+    bool sctl_on = false, smask_on = false;
+    kzv_logits_controls sctl = {};
+    std::vector<uint32_t> smask_h;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU
@@ -162,6 +167,8 @@ struct kzv_model : kzv_model_plain {
     // slot-refill decoding: the pool of cross-attention K/V in decode layout ([layer][K|V][pool image][head][key][64]), the slots' state
     // and logits (one allocation, sized by the bound batch)
     KzvDevBuf spool, sstate;
+    // the device copy of a wave's suppress mask ((vocab + 31) / 32 words)
+    KzvDevBuf smask;
     hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
     const void* dg_key[3][6] = {};
     int64_t dg_ld[3] = {0, 0, 0};

@@ -77,6 +77,18 @@ class kzv_stream_beam_state(C.Structure):
         ("out_score", C.c_void_p), ("limit", C.c_void_p), ("divisors", C.c_void_p), ("rows", C.c_void_p), ("ld_rows", C.c_int64)]
 
 
+class kzv_logits_process_args(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("vocab", C.c_int32), ("ids", C.c_void_p), ("ld_ids", C.c_int64),
+                ("t", C.c_int32), ("group", C.c_int32), ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("by_image", C.c_int32),
+                ("n_images", C.c_int32), ("no_repeat_ngram_size", C.c_int32), ("min_length", C.c_int32), ("eos_id", C.c_int32),
+                ("normalise", C.c_int32), ("repetition_penalty", C.c_float), ("reserved", C.c_int32), ("suppress_mask", C.c_void_p)]
+
+
+class kzv_logits_controls(C.Structure):
+    _fields_ = [("no_repeat_ngram_size", C.c_int32), ("repetition_penalty", C.c_float), ("min_length", C.c_int32), ("reserved", C.c_int32),
+                ("suppress_mask", C.c_void_p)]
+
+
 class kzv_edit_args(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("ld_pred", C.c_int64), ("ref", C.c_void_p), ("ld_ref", C.c_int64),
                 ("n", C.c_int32), ("width_pred", C.c_int32), ("width_ref", C.c_int32), ("vocab", C.c_int32), ("n_special", C.c_int32),
@@ -267,6 +279,10 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "kzv_beam_update": (C.c_int, [C.POINTER(kzv_beam_state), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kzv_beam_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_beam_rank_logprobs": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_logits_process": (C.c_int, [C.POINTER(kzv_logits_process_args), C.c_void_p]),
+    "kzv_test_logits_process_calls": (C.c_int64, []),      # test hook (csrc/logits_process.hip), not declared in include/kzv.h
+    "kzv_stream_set_controls": (C.c_int, [C.c_void_p, C.POINTER(kzv_logits_controls), C.c_void_p]),
     "kzv_stream_seat_first": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p]),
     "kzv_stream_update": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_void_p]),
     "kzv_stream_topk": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -29,13 +29,18 @@ from __future__ import annotations
 NEG = -1.0e9
 
 
-def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, update=None):
+def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, update=None, process=None):
     """``num_beams=1``: argmax per step; finished rows emit padding; stops when every row has emitted EOS.
     ``update(logits, ids, t, done) -> running`` (optional, kzv_greedy_update): the selection in one launch; running[t] = rows
-    still running after step t."""
+    still running after step t.
+    ``process(logits, ids, n) -> logits`` (optional; kzv/controls.py: GenerationControls.hook): generation controls on the step's raw
+    logits given the histories ids[:, :n] -- where HF's greedy loop applies its logits processors.  None: what this computed before."""
     import torch
     ids = torch.full((batch, max_len), pad_id, dtype=torch.int64, device=device)
     ids[:, 0] = bos_id
+    if process is not None:
+        raw_step = step
+        step = lambda t, ids_: process(raw_step(t, ids_), ids_, t + 1)      # noqa: E731
     if update is not None:
         # the stop test costs a host round trip: taken every 4th step; the steps run past the end only write padding, and the
         # per-step counters say where the end was
@@ -62,11 +67,17 @@ def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int
 
 
 def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int,
-                device, early_stopping=True, length_penalty: float = 1.0, topk=None, update=None):
+                device, early_stopping=True, length_penalty: float = 1.0, topk=None, update=None, process=None):
     """``topk(logits [B * nb, vocab] fp32, run_sc [B, nb]) -> (top_lp [B, 2 nb], top_ix [B, 2 nb])``: optional fused ranking
     (kzv_beam_topk on the GPU); None = the torch expression of the same thing below.
-    ``update``: optional fused bookkeeping (kzv_beam_update); with it the loop below is replaced by beam_search_fused."""
+    ``update``: optional fused bookkeeping (kzv_beam_update); with it the loop below is replaced by beam_search_fused.
+    ``process(logp, ids, n) -> logp`` (optional; GenerationControls.hook): generation controls on ``log_softmax(logits)`` given the
+    histories ids[:, :n], before the beam score is added and with no second normalisation -- where HF's beam search applies its logits
+    processors.  It belongs to the torch expression: a caller that passes ``topk`` processes inside ``step`` and passes a ranking over
+    log-probabilities (make_device_hooks(logprobs=True)).  None: what this computed before."""
     import torch
+    if process is not None and topk is not None:
+        raise ValueError("beam_search: `process` belongs to the torch ranking; with `topk` process inside `step` and rank log-probabilities")
     if update is not None and topk is not None:
         return beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, bos_id, eos_id, device, early_stopping,
                                  length_penalty, topk, update)
@@ -90,6 +101,8 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
             top_lp, top_ix = topk(raw, run_sc)
         else:
             logp = torch.log_softmax(raw.float(), dim=-1)
+            if process is not None:
+                logp = process(logp, run_seq.view(B * nb, max_len), cur)
             acc = logp.view(B, nb, vocab) + run_sc.unsqueeze(-1)
         # top K of the nb * vocab continuations in two stages (the K best overall are among each beam's K best): one
         # single-block top-k per beam row instead of a multi-pass radix select over nb * vocab entries per batch element
@@ -170,9 +183,10 @@ def beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, b
     return (out, st) if return_state else out
 
 
-def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, length_penalty, device):
+def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, length_penalty, device, logprobs: bool = False):
     """(topk, update) for beam_search on the GPU: kzv_beam_topk and kzv_beam_update through the C ABI, on the current stream,
-    writing into buffers allocated here once."""
+    writing into buffers allocated here once.  ``logprobs``: the step hands over processed log-probabilities (the normalising
+    kzv_logits_process has run on them), so ``topk`` is kzv_beam_rank_logprobs, which does not normalise again."""
     import ctypes as C
     import torch
     from . import _lib as L
@@ -187,8 +201,9 @@ def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, 
     def topk(raw, run_sc):                # log_softmax + beam score + top 2 * nb per image in one launch
         sc = run_sc.contiguous()
         keep["sc"] = sc
-        L.check(lib.kzv_beam_topk(raw.data_ptr(), raw.stride(0), sc.data_ptr(), B, nb, vocab, 2 * nb, top_lp.data_ptr(), top_ix.data_ptr(),
-                                  L.stream_handle()), "beam_topk")
+        rank = lib.kzv_beam_rank_logprobs if logprobs else lib.kzv_beam_topk
+        L.check(rank(raw.data_ptr(), raw.stride(0), sc.data_ptr(), B, nb, vocab, 2 * nb, top_lp.data_ptr(), top_ix.data_ptr(),
+                     L.stream_handle()), "beam_rank_logprobs" if logprobs else "beam_topk")
         return top_lp, top_ix
 
     def update(st, lp, ix, cur):          # everything between two decoder steps in one launch

@@ -73,6 +73,11 @@ class TrOCRModel:
         self.last_generate_steps = 0
         self.last_stream_pad_fallbacks = 0
         self._stream_beams = 4
+        # what lockstep ``generate`` runs for its generation controls: "device" (kzv_logits_process) or "reference" (the torch statement
+        # kzv/controls.py::process_reference on the same step scores; the tests' cross-check, far slower)
+        self.controls_impl = "device"
+        # generation controls of the validation / test decodes (``forward`` without labels): generate's keywords; empty = the reference's
+        self.decode_controls = {}
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
         # image_size is the WIDEST crop; batches whose width is one of `width_buckets` (multiples of the patch width, <= it)
         # run with fewer patch tokens and the position rows of the same (h, w) cells (include/kzv.h: kzv_set_image_width).
@@ -335,7 +340,8 @@ class TrOCRModel:
             loss, logits = self.forward_loss(pixel_values, labels, want_logits=True)
             return {"logits": logits, "loss": loss.clone().reshape(())}
         # trocr_model.py:306-316: max_length=128, num_beams=4, early_stopping=True
-        return {"generated_ids": self.generate(pixel_values, max_length=128, num_beams=4, early_stopping=True), "logits": None}
+        return {"generated_ids": self.generate(pixel_values, max_length=128, num_beams=4, early_stopping=True, **self.decode_controls),
+                "logits": None}
 
     def backward(self) -> None:
         """loss.backward() of the last training-mode forward: fills flat_grads (zeroed first)."""
@@ -432,17 +438,22 @@ class TrOCRModel:
             self.training = was
         return self.align_last(layer, want_map, top_k)
 
-    def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0) -> list[dict]:
+    def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0,
+                  no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None,
+                  allowed_tokens=None) -> list[dict]:
         """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
         ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
         ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
         pixels) and ``peak_patches`` (kzv/align.py: build_records).  ``top_k`` in 1..8 adds ``alternatives`` (per token the k best
         candidates of the teacher-forced pass with their log-probabilities) and ``margins``; after a beam search the chosen token
-        need not be the first alternative."""
+        need not be the first alternative.  The generation controls are ``generate``'s and steer the decode only: the align-based
+        values (log-probabilities, confidence, alternatives) stay the model's own, so a token the controls forced may carry a low one."""
         import torch
         from . import align as A
         c = self.cfg
-        gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True)
+        gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
+                            no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
+                            suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens)
         if gen.shape[1] < 2:                                  # labels need a target column
             gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
         out = self.align(pixel_values, gen, layer=layer, top_k=top_k)
@@ -455,8 +466,12 @@ class TrOCRModel:
                                to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
 
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
-                 length_penalty: float = 1.0, use_cache: bool = True):
+                 length_penalty: float = 1.0, use_cache: bool = True, return_scores: bool = False,
+                 no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None):
         """Decode from BOS.  The encoder (and the cross-attention K/V of every decoder layer) runs ONCE.
+        ``return_scores`` (beam search on the device hooks only, i.e. 2..8 beams on the GPU): returns ``(ids, scores)``, scores fp32 [B] =
+        the winners' sum of log-probabilities / generated length ** length_penalty (HF's ``sequences_scores``), read off the search's own
+        state -- under generation controls the sum of the PROCESSED log-probabilities, which a teacher-forced pass cannot give.
         use_cache=True (default): each step feeds the newest token through the decoder against cached self-attention keys
         and values (kzv_decode_step); beam steps re-order the cache rows (kzv_decode_reorder).
         use_cache=False: each step is a decoder-only teacher-forced pass over the whole prefix (kzv_decode_logits), whose
@@ -464,10 +479,24 @@ class TrOCRModel:
 
         Token selection (greedy for num_beams == 1, else beam search with HF's rules) is kzv/beam.py, pinned on the CPU
         against transformers' own ``generate``; the reference asks for ``num_beams=4, early_stopping=True``
-        (trocr_model.py:306-316).  The step logits come from this engine."""
+        (trocr_model.py:306-316).  The step logits come from this engine.
+
+        Generation controls, with ``transformers.generate``'s names and semantics (kzv/controls.py; every default is off, and with all
+        of them off nothing is launched for them): ``no_repeat_ngram_size`` g in 1..8 (no g-gram occurs twice), ``repetition_penalty``
+        p > 0 (the scores of tokens already emitted are divided by p, or multiplied where negative), ``min_length`` (no EOS before the
+        line holds that many tokens, BOS included; ``max_length`` still ends it), ``suppress_tokens`` (ids never chosen) or its
+        complement ``allowed_tokens`` (EOS is always kept).  They act on every step's scores on the device (kzv_logits_process): on the
+        raw logits for greedy decoding, on log_softmax(logits) before the beam score is added for beam search, as HF does."""
         import torch
         from . import beam as BM
+        from . import controls as CT
         c = self.cfg
+        ctl = CT.from_kwargs(c.eos_id, no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens, allowed_tokens)
+        ctl_mask = None
+        if ctl is not None:
+            ctl.check(c.vocab, c.eos_id, num_beams)
+            ctl_mask = ctl.mask(c.vocab, c.eos_id)
+            ctl_mask = None if ctl_mask is None else ctl_mask.to(self.device)
         px = self._check_inputs(pixel_values)
         B = px.shape[0]
         Lh = min(max_length, c.max_pos - c.pad_id - 1)
@@ -475,6 +504,8 @@ class TrOCRModel:
         was = self.training
         self.training = False
         nb = max(1, int(num_beams))
+        if return_scores and nb == 1:
+            raise ValueError("return_scores needs num_beams > 1")
         BB = B * nb
         # cached decoding runs the encoder and the cross-attention K/V once per IMAGE (kzv_encode_images): beams share them, and no
         # teacher-forced decoder pass is spent on the BOS-only prompt
@@ -530,29 +561,63 @@ class TrOCRModel:
                 state["valid"].copy_(state["valid"][rows])                # in place: the graph holds this buffer's address
                 L.check(lib.kzv_decode_reorder(self._h, rows.data_ptr(), n_keys, L.stream_handle()), "decode_reorder")
 
+        def controls_hook(scores, ids, n, normalise=0):
+            """The controls on ``scores`` [BB, V] in place, histories ids[:, :n] (kzv_logits_process; ``controls_impl`` = "reference"
+            substitutes the torch statement on the same scores: the whole-decode tests compare the two)."""
+            if self.controls_impl == "reference":
+                x = torch.log_softmax(scores, dim=-1) if normalise else scores
+                scores.copy_(CT.process_reference(x, ids[:, :n], ctl, c.eos_id))
+                return scores
+            if scores.stride(1) != 1 or ids.stride(1) != 1:
+                raise ValueError("controls: scores and ids must be dense along their rows")
+            a = L.kzv_logits_process_args(logits=scores.data_ptr(), ld=scores.stride(0), rows=scores.shape[0], vocab=c.vocab, ids=ids.data_ptr(),
+                                          ld_ids=ids.stride(0), t=n - 1, group=1, slot_image=None, slot_t=None, by_image=0, n_images=0,
+                                          no_repeat_ngram_size=ctl.no_repeat_ngram_size, min_length=ctl.min_length, eos_id=c.eos_id,
+                                          normalise=1 if normalise else 0, repetition_penalty=ctl.repetition_penalty, reserved=0,
+                                          suppress_mask=L.ptr(ctl_mask))
+            L.check(lib.kzv_logits_process(C.byref(a), L.stream_handle()), "logits_process")
+            return scores
+
         topk = update = None
+        process = controls_hook if ctl is not None else None
+        raw_step = step
+
+        def step_logprobs(t, ids):               # beams on the device ranking: normalise + process here, rank log-probabilities after
+            return controls_hook(raw_step(t, ids), ids, t + 1, normalise=1)
 
         try:
             with torch.cuda.stream(side):
                 # the hooks allocate and zero their flag / top-k buffers: on the stream whose kernels read them
                 if nb > 1 and nb <= 8 and self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0":
-                    topk, update = BM.make_device_hooks(B, nb, Lh, c.vocab, c.eos_id, early_stopping, length_penalty, self.device)
+                    topk, update = BM.make_device_hooks(B, nb, Lh, c.vocab, c.eos_id, early_stopping, length_penalty, self.device,
+                                                        logprobs=ctl is not None)
                     if os.environ.get("KZV_BEAM_UPDATE", "1") == "0":
                         update = None
+                    if ctl is not None:
+                        step, process = step_logprobs, None
                 if use_cache:
                     L.check(lib.kzv_set_active_length(self._h, 1), "set_active_length")
                     L.check(lib.kzv_decode_begin(self._h, L.stream_handle()), "decode_begin")
                 if nb == 1:
                     gupd = BM.make_greedy_hook(B, c.vocab, c.pad_id, c.eos_id, self.device, Lh) if self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0" else None
-                    out = BM.greedy(step, B, Lh, c.pad_id, c.bos_id, c.eos_id, self.device, update=gupd)
+                    out = BM.greedy(step, B, Lh, c.pad_id, c.bos_id, c.eos_id, self.device, update=gupd, process=process)
+                elif return_scores:                               # (what beam_search runs with both hooks; the state holds the scores)
+                    if topk is None or update is None:
+                        raise ValueError("return_scores needs the device beam hooks (2..8 beams on the GPU, KZV_BEAM_TOPK / KZV_BEAM_UPDATE on)")
+                    out, bst = BM.beam_search_fused(step, reorder, B, nb, Lh, c.vocab, c.pad_id, c.bos_id, c.eos_id, self.device, early_stopping,
+                                                    length_penalty, topk, update, return_state=True)
+                    scores = bst["fin_sc"][:, 0].clone()
                 else:
                     out = BM.beam_search(step, reorder, B, nb, Lh, c.vocab, c.pad_id, c.bos_id, c.eos_id, self.device,
-                                         early_stopping=early_stopping, length_penalty=length_penalty, topk=topk, update=update)
+                                         early_stopping=early_stopping, length_penalty=length_penalty, topk=topk, update=update,
+                                         process=process)
             if graph:
                 cur.wait_stream(side)
-                for t_ in (out, step_logits, posids, tok_buf, state["valid"], px):
+                for t_ in (out, step_logits, posids, tok_buf, state["valid"], px) + (() if ctl_mask is None else (ctl_mask,)):
                     t_.record_stream(cur)
-            return out
+                if return_scores:
+                    scores.record_stream(cur)
+            return (out, scores) if return_scores else out
         finally:
             self.training = was
 
@@ -600,7 +665,8 @@ class TrOCRModel:
 
     def generate_stream(self, pixel_values, max_length: int = 128, slots: int | None = None, limits=None, return_logprobs: bool = False,
                         pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
-                        return_scores: bool = False, top_k: int = 0):
+                        return_scores: bool = False, top_k: int = 0,
+                        no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -628,9 +694,22 @@ class TrOCRModel:
         ``top_k`` in 1..8 (greedy only): the call returns ``(ids, logprobs, alt_ids, alt_logprob)``, the last two int64 / fp32
         [N, width, top_k]: at every emitted column the k best tokens of that step and their log-probabilities, best first (entry 0 is
         the emitted token; kzv_stream_topk, one more kernel per step and no second pass); -1 / 0 in column 0 and past a line's end.  On
-        the static path they come from ``align(..., top_k=top_k)``."""
+        the static path they come from ``align(..., top_k=top_k)``.
+
+        Generation controls (``generate``'s five keywords, same semantics; defaults off): every step of a wave runs kzv_logits_process as
+        one more node of its captured chain (kzv_stream_set_controls), on each slot's own history; a beam wave normalises, processes and
+        ranks without normalising again.  Every row still equals the matching row of ``generate`` called with the same controls, and
+        the two fallbacks -- "static" geometries and a beam wave decoded again after a padding continuation -- carry them too.  With
+        controls on, ``return_logprobs`` and the ``top_k`` alternatives are those of the PROCESSED row (HF's
+        ``scores[t].log_softmax(-1)``): a banned token never appears among the alternatives (it ranks last at -inf).  On the static path
+        the log-probabilities stay the model's own (``align``).  Tip: ``suppress_tokens=[pad_id]`` removes the cause of the beam
+        stream's re-decode -- no running beam can take padding."""
         import torch
+        from . import controls as CT
         c = self.cfg
+        ctl = CT.from_kwargs(c.eos_id, no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens, allowed_tokens)
+        if ctl is not None:
+            ctl.check(c.vocab, c.eos_id, num_beams)   # before any wave runs
         nb = int(num_beams)
         top_k = int(top_k)
         if nb < 1:
@@ -671,10 +750,10 @@ class TrOCRModel:
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
             if top_k:
-                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k)
+                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl)
                 alt_out.append(alts)
             else:
-                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams)
+                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl)
             ids_out.append(ids); lp_out.append(lp); done += n
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
@@ -687,7 +766,15 @@ class TrOCRModel:
             return ids[:, :width], torch.cat(lp_out)
         return ids[:, :width]
 
-    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams):
+    @staticmethod
+    def _controls_kw(ctl) -> dict:
+        """``generate``'s keywords for the controls of a wave (none when they are off)."""
+        if ctl is None:
+            return {}
+        return {"no_repeat_ngram_size": ctl.no_repeat_ngram_size, "repetition_penalty": ctl.repetition_penalty, "min_length": ctl.min_length,
+                "suppress_tokens": ctl.suppress_tokens, "allowed_tokens": ctl.allowed_tokens}
+
+    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams, ctl=None):
         """``generate(num_beams=nb)`` over batches of ``slots``: ids [n, Lh] and the winners' scores [n] (from a teacher-forced pass).  With
         limits, the images of every distinct limit are decoded with it as their max_length."""
         import torch
@@ -702,7 +789,7 @@ class TrOCRModel:
             for a in range(0, idx.numel(), slots):
                 sel = idx[a:a + slots]
                 sub = px[sel.to(px.device)]
-                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen)
+                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen, **self._controls_kw(ctl))
                 rows = torch.full((sel.numel(), Lh), c.pad_id, dtype=torch.int64, device=dev)
                 rows[:, :g.shape[1]] = g
                 sc = self.align(sub, rows)
@@ -711,10 +798,10 @@ class TrOCRModel:
                 score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
         return ids, score
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0):
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None):
         """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
         length_penalty): ids [n, Lh] and the winners' scores [n]; with ``top_k`` (greedy) a third result, (alt_ids int32, alt_logprob)
-        [n, Lh, top_k]."""
+        [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off)."""
         import torch
         from . import stream as ST
         c = self.cfg
@@ -724,18 +811,18 @@ class TrOCRModel:
         self._check_inputs(px[:1])                                # geometry checks + the active crop width
         nb = beams[0] if beams else 1
         if beams and nb not in (2, 4):
-            return self._static_beam_wave(px, Lh, slots, lim, beams)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
         rows = slots * nb                                         # decoder rows: a slot holds one sequence, or an image's beam group
         self._bind(rows, Lh)
         if beams and self.stream_beam_impl_for(nb) == "static":
-            return self._static_beam_wave(px, Lh, slots, lim, beams)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
         if not beams and self.stream_decode_impl == "static":
             ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
             lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
             alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
             alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
             for a in range(0, n, slots):
-                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1)
+                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1, **self._controls_kw(ctl))
                 ids[a:a + g.shape[0], :g.shape[1]] = g
             if lim is not None:
                 ids = torch.where(torch.arange(Lh, device=dev).view(1, Lh) >= lim.to(dev).view(n, 1), torch.full_like(ids, c.pad_id), ids)
@@ -775,6 +862,11 @@ class TrOCRModel:
                     L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
                     if top_k:
                         L.check(lib.kzv_stream_set_topk(self._h, top_k, alt_ids.data_ptr(), alt_lp.data_ptr(), Lh * top_k, st), "stream_set_topk")
+                if ctl is not None:                               # one more node per step; the library copies the (host) mask
+                    mk = ctl.mask(c.vocab, c.eos_id)
+                    cc = L.kzv_logits_controls(no_repeat_ngram_size=ctl.no_repeat_ngram_size, repetition_penalty=ctl.repetition_penalty,
+                                               min_length=ctl.min_length, reserved=0, suppress_mask=None if mk is None else mk.data_ptr())
+                    L.check(lib.kzv_stream_set_controls(self._h, C.byref(cc), st), "stream_set_controls")
                 a = 0
                 while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
                     k = min(rows, n - a)                          # is filled by repeating its last image
@@ -811,7 +903,7 @@ class TrOCRModel:
             self.training = was
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
             self.last_stream_pad_fallbacks += pads.value
-            return self._static_beam_wave(px, Lh, slots, lim, beams)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
         if top_k:
             return ids, lp, (alt_ids, alt_lp)
         return ids, (score if beams else lp)
@@ -821,7 +913,9 @@ class TrOCRModel:
         ``token_strings``, ``logprobs`` and ``confidence`` = exp(mean log-probability over the tokens, EOS included) -- ``recognize``'s
         definitions, for greedy decoding, with no teacher-forced second pass.  It returns NO centroids or peak patches: those come
         from the cross-attention maps of a teacher-forced pass, which ``recognize`` runs.  ``kw``: generate_stream's arguments; with
-        ``top_k`` in 1..8 every record also holds ``alternatives`` and ``margins`` (build_records), taken from the stream's own steps."""
+        ``top_k`` in 1..8 every record also holds ``alternatives`` and ``margins`` (build_records), taken from the stream's own steps.
+        The generation controls (``no_repeat_ngram_size``, ``repetition_penalty``, ``min_length``, ``suppress_tokens``, ``allowed_tokens``)
+        go through ``kw``; log-probabilities, confidence and alternatives are then those of the processed rows (generate_stream)."""
         import numpy as np
         from . import align as A
         c = self.cfg
@@ -876,7 +970,8 @@ class TrOCRModel:
         (sum of distances / sum of label lengths), ``exact`` (share of lines with distance 0), ``substitutions`` / ``deletions`` /
         ``insertions`` / ``ref_chars`` (totals), ``per_line`` (numpy arrays ``cer``, ``dist``, ``ref_len``, ``pred_len``, ``ops``),
         ``characters`` (metrics.character_table: the ``top`` characters with the most errors) and ``ids`` (the generated rows).  The
-        same call serves geometries where generate_stream runs ``generate``: it needs only the ids."""
+        same call serves geometries where generate_stream runs ``generate``: it needs only the ids.  The generation controls of
+        generate_stream (``no_repeat_ngram_size=3`` is what the stock TrOCR generation configs ship with) pass through its keywords."""
         import numpy as np
         import torch
         from . import metrics as M

@@ -65,19 +65,24 @@ def new_state(n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int,
     return st
 
 
-def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, limit=None):
+def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, limit=None, process=None):
     """One step's selection and seating.  ``logits`` [slots, V] are the next-token logits of every slot (rows of idle slots are
     ignored).  Per live slot holding image i at step t: token = the FIRST arg-max column; out_ids[i][t + 1] = token;
     out_logprob[i][t + 1] = max - logsumexp; the line has ended when token == eos_id, t + 2 >= limit[i] or t + 2 >= max_len.
     Then the slots whose lines ended take the images counters[0], counters[0] + 1, ... in ascending slot order (an exclusive prefix
     sum over the ended flags) at step 0 / BOS, or go idle when no image is left; the others advance.  ``limit``: optional int32
     [n_images], the most tokens, BOS included, an image may get.  Where the state holds alternatives (new_state's ``top_k``),
-    alt_ids / alt_logprob[i][t + 1] = topk_rows of the slot's row.  Returns ``st``."""
+    alt_ids / alt_logprob[i][t + 1] = topk_rows of the slot's row.
+    ``process(logits, hist [slots, L], lens [slots], live [slots]) -> logits`` (optional; kzv/controls.py: GenerationControls.rows_hook):
+    generation controls on the raw logits, slot s with the history out_ids[slot_image[s]][:slot_t[s] + 1]; token, log-probability and
+    alternatives are then those of the processed row.  None: what this computed before.  Returns ``st``."""
     import torch
     dev = logits.device
     img, t = st["slot_image"], st["slot_t"]
     live = img >= 0
     x = logits.float()
+    if process is not None:
+        x = process(x, st["out_ids"][img.clamp(min=0).long()], t.long() + 1, live)
     mx = x.max(dim=-1, keepdim=True)[0]
     V = x.shape[-1]
     cols = torch.arange(V, device=dev).expand_as(x)
@@ -117,19 +122,20 @@ def step_bound(n_images: int, slots: int, max_len: int) -> int:
 
 
 def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, limits=None,
-                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False, top_k: int = 0):
+                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False, top_k: int = 0, process=None):
     """Greedy decoding of ``n_images`` images over ``slots`` decoder slots.  ``step_fn(state) -> logits [slots, V]`` runs one decoder
     step for every slot: slot b feeds state["tokens"][b] at step state["slot_t"][b] for image state["slot_image"][b] (idle slots may
     return anything).  The counters are looked at every ``poll``-th step; RuntimeError once the steps exceed ``step_bound``.
     Returns out_ids [N, max_len] (and out_logprob with ``return_logprobs``; and the final state with ``return_state``, which holds
-    the alternatives asked for with ``top_k``)."""
+    the alternatives asked for with ``top_k``).  ``process``: select_seat's optional hook."""
     import torch
     st = new_state(n_images, slots, max_len, pad_id, bos_id, device, return_logprobs, top_k)
     lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
     bound = step_bound(n_images, slots, max_len)
     steps = 0
     while True:
-        st = select_seat(step_fn(st), st, n_images=n_images, max_len=max_len, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, limit=lim)
+        st = select_seat(step_fn(st), st, n_images=n_images, max_len=max_len, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, limit=lim,
+                         process=process)
         steps += 1
         if steps % poll == 0 or steps >= bound:
             if int(st["counters"][1]) >= n_images:
@@ -288,13 +294,20 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
 
 
 def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int, device,
-                early_stopping=True, length_penalty: float = 1.0, limits=None, topk=None, poll: int = 8, return_state: bool = False):
+                early_stopping=True, length_penalty: float = 1.0, limits=None, topk=None, poll: int = 8, return_state: bool = False,
+                process=None):
     """Beam search of ``n_images`` images over ``slots`` slots of ``num_beams`` decoder rows.  ``step_fn(state) -> logits [slots * nb, V]``
     runs one decoder step for every row: row slot * nb + i feeds state["tokens"][row] at step state["slot_t"][slot] for image
     state["slot_image"][slot], its prefix state["run_seq"][slot][i][:slot_t + 1] (idle slots may return anything finite).
     ``topk(logits, run_sc) -> (top_lp, top_ix)``: optional fused ranking as in beam.beam_search.  Returns (out_ids [N, max_len],
-    out_score [N]) (and the final state with ``return_state``)."""
+    out_score [N]) (and the final state with ``return_state``).
+    ``process(logp, hist [slots * nb, L], lens [slots * nb], live [slots * nb]) -> logp`` (optional; GenerationControls.rows_hook):
+    generation controls on ``log_softmax(logits)``, row slot * nb + i with the history run_seq[slot][i][:slot_t[slot] + 1], before the
+    beam score is added and with no second normalisation.  It belongs to the torch ranking (not combined with ``topk``).  None: what
+    this computed before."""
     import torch
+    if process is not None and topk is not None:
+        raise ValueError("beam_stream: `process` belongs to the torch ranking")
     nb, K = num_beams, 2 * num_beams
     st = new_beam_state(n_images, slots, nb, max_len, pad_id, bos_id, device)
     lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
@@ -306,7 +319,11 @@ def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int
         if topk is not None:
             top_lp, top_ix = topk(raw, st["run_sc"])
         else:
-            acc = torch.log_softmax(raw.float(), dim=-1).view(slots, nb, vocab) + st["run_sc"].unsqueeze(-1)
+            logp = torch.log_softmax(raw.float(), dim=-1)
+            if process is not None:
+                logp = process(logp, st["run_seq"].view(slots * nb, max_len), (st["slot_t"].long() + 1).repeat_interleave(nb),
+                               (st["slot_image"] >= 0).repeat_interleave(nb))
+            acc = logp.view(slots, nb, vocab) + st["run_sc"].unsqueeze(-1)
             top_lp, top_ix = acc.view(slots, nb * vocab).topk(K, dim=1)
         st = beam_select_seat(top_lp, top_ix, st, n_images=n_images, num_beams=nb, max_len=max_len, vocab=vocab, pad_id=pad_id, bos_id=bos_id,
                               eos_id=eos_id, early_stopping=early_stopping, length_penalty=length_penalty, limit=lim, divisors=div)

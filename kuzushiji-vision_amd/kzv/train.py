@@ -67,6 +67,15 @@ def parse_args(argv=None):
                         "loader (TrOCRModel.generate_stream); stream-beam (an extension): it also logs test_cer_stream_beam from ONE "
                         "generate_stream(num_beams=4) over it, the test step's own beam search on refilled slots; beam = the reference's test "
                         "phase alone")
+    p.add_argument("--no_repeat_ngram_size", type=int, default=0,
+                   help="generation control of the validation / test decodes (an extension; transformers.generate's name and rule): no "
+                        "n-gram of this size occurs twice in a decoded line; 0 = off, the reference's behaviour")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="generation control of the validation / test decodes: scores of tokens already emitted are divided by it (multiplied "
+                        "where negative); 1.0 = off, the reference's behaviour")
+    p.add_argument("--min_length", type=int, default=0,
+                   help="generation control of the validation / test decodes: no EOS before a line holds this many tokens, BOS included; "
+                        "0 = off, the reference's behaviour")
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize / pad / normalise the decoded crops on the GPU (kzv.preprocess; byte-exact with the PIL transform)")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
@@ -234,6 +243,9 @@ def main(argv=None):
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
                        fp8=args.precision == "fp8-mixed", long_sequences=True, decode_weights=args.decode_weights)
     model._step_seed = 1_000_003 * rank
+    model.decode_controls = {k: v for k, v, off in (("no_repeat_ngram_size", args.no_repeat_ngram_size, 0),
+                                                    ("repetition_penalty", args.repetition_penalty, 1.0),
+                                                    ("min_length", args.min_length, 0)) if v != off}
     if rank == 0:
         c = model.cfg
         print(f"encoder attention: {model.encoder_attention_impl} (head_dim {c.enc_hidden // c.enc_heads}, {c.enc_seq} tokens)")

@@ -248,7 +248,7 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
         import torch
         key, kw = ("test_cer_stream_beam", {"num_beams": 4, "early_stopping": True}) if stream_decode == "stream-beam" else ("test_cer_greedy", {})
         model.logged.pop(key, None)
-        gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw)
+        gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw, **getattr(model, "decode_controls", {}))
         labels = torch.cat([b["labels"] for b in test_loader])
         from . import metrics as M
         if model.one_char_tokenizer and gen.shape[1] <= M.MAX_WIDTH and labels.shape[1] <= M.MAX_WIDTH:
