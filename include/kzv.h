@@ -917,6 +917,33 @@ int kzv_lanczos_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk, 
 int kzv_preprocess_lines(const uint8_t* rgb, const kzv_line_desc* desc, const int32_t* coef, int n, int target_h, int target_w,
                          int64_t max_tmp_pixels, const float* lut256, uint8_t* tmp, float* out, void* stream);
 
+/* ------------------------------------------------------------------ training-time augmentation of line crops (csrc/augment.hip)
+ * The reference's augmentation vocabulary (T.RandomAffine of scripts/train_stackganv2_bcr_char.py:54; rotation, brightness /
+ * contrast, noise and blur of src/utils/augmentation.py:35-98; the TrOCR recipe's stroke dilation / erosion) as ONE launch over a
+ * batch of the crops `forward` takes: in = [n, 3, H, W] fp32 in [-1, 1] (white = +1), params = n device structs (the host draws
+ * them: kzv/augment.py), out = same shape.  A pure function of (in, params); per output pixel, in this fixed order:
+ *   1. affine warp: sx = m0*x + m1*y + m2, sy = m3*x + m4*y + m5 (output pixel -> source pixel, pixel-index units), sx clamped to
+ *      [-1, W] and sy to [-1, H] before floor; four bilinear taps, a tap outside the canvas is +1; a + fx*(b - a), then
+ *      top + fy*(bot - top), so an identity map returns its input bit for bit.
+ *      torch: grid_sample(x - 1, grid, 'bilinear', 'zeros', align_corners=False) + 1, grid = ((2*sx + 1)/W - 1, (2*sy + 1)/H - 1).
+ *   2. stroke morphology on the warped image: morph 1 = 3x3 maximum (ink is dark: strokes thin), 2 = 3x3 minimum, neighbours
+ *      outside the canvas skipped.  torch: max_pool2d(x, 3, 1, 1) / -max_pool2d(-x, 3, 1, 1).
+ *   3. separable 7-tap blur, horizontal then vertical, indices clamped to the canvas (replicate); {0,0,0,1,0,0,0} is exact identity.
+ *   4. out = clamp(contrast*v + brightness + noise_sigma*g, -1, 1), g = (b0 + b1 + b2 + b3 - 510) * (1/147.80) with b0..b3 the four
+ *      bytes of hash32(e * 0x9E3779B9 + noise_key), hash32 = the dropout sites' counter hash, e = (c*H + y)*W + x (a sum of four
+ *      bytes has variance 4 * 65535/12 = 21845 = 147.80^2: g has unit variance; integer-exact, so numpy reproduces it).
+ * KZV_E_ARG before any launch: a null pointer, n < 1, H or W < 1, 3*H*W >= 2^32, 2^24 or more tiles (a tile = 32x64 pixels of one
+ * channel of one crop, 256 threads, and a launch carries fewer than 2^32 threads: n * 3 * ceil(H/32) * ceil(W/64) < 2^24; split a
+ * larger batch), or `out` overlapping `in` (the kernel gathers: it cannot run in place). */
+typedef struct {
+    float m[6];                 /* inverse map, output pixel -> source pixel */
+    float blur[7];              /* 7-tap blur weights */
+    float contrast, brightness, noise_sigma;
+    uint32_t noise_key;         /* per-image hash key */
+    int32_t morph;              /* 0 none, 1 thinner strokes (3x3 max), 2 thicker strokes (3x3 min) */
+} kzv_augment_params;           /* 72 bytes */
+int kzv_augment_lines(const float* in, const kzv_augment_params* params, int n, int H, int W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,11 @@ class kzv_line_desc(C.Structure):
                 ("new_w", C.c_int32), ("paste_x", C.c_int32), ("paste_y", C.c_int32), ("hk_size", C.c_int32), ("vk_size", C.c_int32)]
 
 
+class kzv_augment_params(C.Structure):
+    _fields_ = [("m", C.c_float * 6), ("blur", C.c_float * 7), ("contrast", C.c_float), ("brightness", C.c_float),
+                ("noise_sigma", C.c_float), ("noise_key", C.c_uint32), ("morph", C.c_int32)]
+
+
 SYMBOLS = {
     "kzv_last_error": (C.c_char_p, []),
     "kzv_version": (C.c_int, []),
@@ -302,6 +307,7 @@ SYMBOLS = {
     "kzv_lanczos_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "kzv_preprocess_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_augment_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "kzv_prof_collect": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
 }
 

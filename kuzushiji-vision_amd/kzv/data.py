@@ -362,10 +362,15 @@ class BucketBatchSampler:
         return iter(self._batches()[self.rank::self.world])
 
 
-def make_loader(dataset, batch_size, shuffle, seed=42, rank=0, world=1, drop_last=False, num_workers=0, preprocessor=None):
+def make_loader(dataset, batch_size, shuffle, seed=42, rank=0, world=1, drop_last=False, num_workers=0, preprocessor=None, augment=None,
+                train=None):
     """DataLoader over an EpochSampler (per-epoch reshuffle, DistributedSampler-style shard).  drop_last defaults to
     False like the reference's loaders.  `preprocessor` (kzv.preprocess.DevicePreprocessor): for datasets built with
-    device_preprocess=True.  The returned loader exposes ``set_epoch``."""
+    device_preprocess=True.  `augment` = (kzv.augment.DeviceAugment, AugmentConfig, seed): training loaders only, the outermost
+    wrapper, so files, device preprocessing, synthetic data and width buckets are augmented alike; None (default) builds no
+    wrapper.  `train` says whether this is a training loader; None (default) takes it from `shuffle`.  `augment` on a loader that is
+    not a training loader is a ValueError, never a silent no-op: an unshuffled training loader (an overfit or debug run) passes
+    train=True, validation and test loaders leave `augment` out.  The returned loader exposes ``set_epoch``."""
     from torch.utils.data import DataLoader
     if getattr(dataset, "widths", None) is not None:     # width buckets: batches of one width each
         sampler = BucketBatchSampler(dataset.widths, batch_size, shuffle, seed, rank, world)
@@ -375,4 +380,14 @@ def make_loader(dataset, batch_size, shuffle, seed=42, rank=0, world=1, drop_las
         loader = DataLoader(dataset, batch_size=batch_size, sampler=sampler, collate_fn=collate, drop_last=drop_last,
                             num_workers=num_workers)
     loader.set_epoch = sampler.set_epoch
-    return DeviceBatchLoader(loader, preprocessor) if preprocessor is not None else loader
+    if preprocessor is not None:
+        loader = DeviceBatchLoader(loader, preprocessor)
+    if augment is not None:
+        if not (shuffle if train is None else train):    # validation and test loaders are never augmented
+            raise ValueError("augment= is for training loaders and this one is " + ("unshuffled: pass train=True to augment it all the same, "
+                             if train is None else "built with train=False: ") + "or leave augment out (validation and test are never augmented)")
+        from .augment import AugmentLoader
+        aug, aug_cfg, aug_seed = augment
+        if aug_cfg.enabled:
+            loader = AugmentLoader(loader, aug, aug_cfg, seed=aug_seed, rank=rank)
+    return loader

@@ -78,6 +78,11 @@ def parse_args(argv=None):
                         "0 = off, the reference's behaviour")
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize / pad / normalise the decoded crops on the GPU (kzv.preprocess; byte-exact with the PIL transform)")
+    p.add_argument("--augment", type=str, default="off", choices=["off", "reference"],
+                   help="training-time augmentation of the crops on the GPU (an extension; kzv.augment): reference = the reference workspace's "
+                        "own numbers (RandomAffine 7 deg / 7 %% / 0.93-1.07 / shear 5, brightness-contrast, noise, blur, stroke thinning and "
+                        "thickening); validation and test batches are never augmented; off = the crops as they lie on disk")
+    p.add_argument("--augment_seed", type=int, default=None, help="seed of the augmentation draws (default: --seed)")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
     p.add_argument("--ema_decay", type=float, default=0.0, help="> 0 attaches kzv.ema.EMACallback (reference: decay 0.9999)")
     # the ResNet34 / BiLSTM / CTC model of ocr_lightning/model.py behind ocr_lightning/train.py's own flags (:161-189)
@@ -195,6 +200,9 @@ def _ocr_epoch_end(args, model, rec, epoch, log, state):
 def main(argv=None):
     args = parse_args(argv)
     if args.model == "ocr":
+        if args.augment != "off":
+            raise SystemExit("--augment applies to the TrOCR line crops only: --model ocr trains on whole pages with box targets, which a "
+                             "warp of the pixels alone would leave behind")
         return main_ocr(args)
     import torch
     from .config import ModelConfig
@@ -272,7 +280,13 @@ def main(argv=None):
         from .preprocess import DevicePreprocessor
         pre = DevicePreprocessor(tuple(args.image_size), device=f"cuda:{local}")
     nw = 0 if args.synthetic else max(0, args.num_workers)      # decode (and, without --device_preprocess, resize) in worker processes
-    train_loader = make_loader(train_ds, args.batch_size, True, args.seed, rank, world, num_workers=nw, preprocessor=pre)
+    aug = None
+    if args.augment != "off":
+        from .augment import DeviceAugment, preset
+        aug = (DeviceAugment(f"cuda:{local}"), preset(args.augment), args.seed if args.augment_seed is None else args.augment_seed)
+    if rank == 0:
+        print(f"augmentation: {args.augment}" + (f" (seed {aug[2]}, training batches only)" if aug else ""))
+    train_loader = make_loader(train_ds, args.batch_size, True, args.seed, rank, world, num_workers=nw, preprocessor=pre, augment=aug)
     val_loader = make_loader(val_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)
     test_loader = make_loader(test_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)   # scripts/train_trocr.py:93
     if rank == 0:
