@@ -396,6 +396,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_kernel(const AttnP p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)      // MODE 1: causal
                     att_bwd_elem<MODE == 1>(r, S[r], dP[r], sc, lq4[r], dq4[r], key <= qb * 32 + t2 * 16 + 4 * g + r, u01, u23, thr_s, pm[r], ds[r]);
+                // causal query 0 sees one key: P = 1 and dS = 0 EXACTLY, whatever dP - delta' computes to (dP comes out of the
+                // MFMAs, delta' out of dot8 sums of the bf16-rounded O: apart by 1e-6, by 0.04 under dropout).  dV keeps its P.
+                if (MODE == 1 && t2 == 0) ds[0] = (qb | g) == 0 ? 0.f : ds[0];
                 pdw[t2 * 2] = pack_bf2(pm[0], pm[1]); pdw[t2 * 2 + 1] = pack_bf2(pm[2], pm[3]);
                 dsw[t2 * 2] = pack_bf2(ds[0], ds[1]); dsw[t2 * 2 + 1] = pack_bf2(ds[2], ds[3]);
                 *(uint2*)(dsrow + (((t2 * 4 + g) ^ dsz) << 3)) = make_uint2(dsw[t2 * 2], dsw[t2 * 2 + 1]);
