@@ -6,6 +6,7 @@
 
 int kzv_fail(int code, const char* fmt, ...);          // records message, returns code
 int kzv_check_launch(const char* what);                // hipGetLastError -> KZV_E_HIP
+#define KZV_TRY_RC(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)   // pass a failed check's code on (KZV_OK: include/kzv.h)
 int kzv_cu_reserve();                                  // CUs left to concurrent collectives (kzv_set_cu_reserve / KZV_CU_RESERVE)
 #define KZV_LOCAL __attribute__((visibility("hidden")))  // shared by the library's units, not part of its dynamic symbol table
 KZV_LOCAL int kzv_device_cus();                        // compute units of the current device (read once; 256 if the query fails)

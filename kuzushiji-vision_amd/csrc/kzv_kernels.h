@@ -76,7 +76,7 @@ int kzv_sqnorm(const float* g, int64_t n, float* out1, float* scratch, hipStream
 
 // attention.hip : see include/kzv.h (kzv_attn_fwd / kzv_attn_bwd)
 
-// decode.hip (KV-cached generation step)
+// decode_attention.hip (KV-cached generation step: attention, row table, cross-attention K/V relayout)
 int kzv_attn_decode(const bf16_t* q, int64_t ldq, const bf16_t* knew, const bf16_t* vnew, int64_t ldnew, bf16_t* K, bf16_t* V, int64_t kb,
                     int64_t kj, const unsigned char* valid, int64_t ldvalid, bf16_t* out, int64_t ldo, int B, int heads, int nkeys,
                     int append_at, hipStream_t s, const int* tptr = nullptr, int group = 1, int* rows = nullptr, int64_t ldrows = 0, int64_t kh = 64);

@@ -14,7 +14,7 @@
 // minimum length, the caller's suppress mask) hold one bit per token, 2 KiB each at the 16,384-token bound, filled with LDS atomics by
 // threads striding over the history -- thread i compares the g - 1 tokens h[i ..] with the history's tail.  Then one dense pass in batches
 // of independent loads (beam_topk_kernel's remedy for a round trip per element).  With `normalise` a first phase takes the row's maximum
-// and sum of exponentials in the order of beam_topk_kernel's first phase (decode.hip): thread tid owns tokens tid + 256 e; the WAVE's
+// and sum of exponentials in the order of beam_topk_kernel's first phase (token_search.hip): thread tid owns tokens tid + 256 e; the WAVE's
 // maximum first (wave_max of the threads' maxima), each thread's exponentials summed against it in ascending e, wave_sum, then the four
 // waves' (max, sum) merged under the row maximum.  The dense pass writes (x - max) - log(sum), that kernel's own expression.
 #include "kzv_common.h"

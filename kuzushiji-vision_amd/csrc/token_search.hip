@@ -1,225 +1,55 @@
-// N1: KV-cached decoder step: one new token per sequence attends over cached keys / values.
-//
-// Replaces, for generation only, the per-step work of HF RobertaSelfAttention / RobertaCrossAttention with `use_cache=True`
-// (modeling_roberta.py:186-326) as driven by `decoder.generate` (src/models/trocr_model.py:306-316).  One wave per
-// (sequence, head), fp32 scores and softmax in registers (see attn_decode_kernel); the self-attention variant also appends this
-// step's key and value to the cache.  The reference's default 1024x64 columns give 256 cross-attention keys.
+// The token search of generation, i.e. what happens between two decoder steps (their attention: decode_attention.hip): greedy selection,
+// beam ranking and update, and their slot-refill forms (kzv_stream_*, kzv_stream_beam_*).  Two rules carry every "stream equals static
+// equals torch statement" test and are written once: the FIRST arg-max of a row (row_first_argmax) and the seating order (seat_rank).
 #include "kzv_common.h"
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "kzv_kernels.h"
+#include "row_scan.h"
 #include <cmath>
-#include <cstdlib>
-
-#define KZV_TRY_RC(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)
+#include <initializer_list>
 
 namespace {
 
-struct DecAttnP {
-    const bf16_t* q; int64_t ldq;                 // [B, ldq], head h at column h*64
-    const bf16_t* knew; const bf16_t* vnew; int64_t ldnew;   // this step's key/value rows [B, ldnew] (self-attention) or null
-    bf16_t* K; bf16_t* V; int64_t kb, kj, kh;     // key j, head h of sequence b: K + b*kb + h*kh + j*kj (same strides for V)
-    const unsigned char* valid; int64_t ldvalid;  // [B, ldvalid]: key j usable (null: all)
-    bf16_t* out; int64_t ldo;
-    int nkeys, append_at, heads;                  // append_at >= 0: write knew/vnew at key index append_at first
-    float scale;
-    const int* tptr;                              // non-null: the step index t lives in device memory (graph replay): nkeys = t + 1, append_at = t
-    int group;                                    // keys / values of sequence b live at batch index b / group (beams sharing one image's cross-attention K/V)
-    int* rows; int64_t ldrows;                    // non-null (beam search): cached key j of sequence b lives in cache row rows[b * ldrows + j]
-};
-
-// One WAVE per (G sequences, head), no LDS and no barrier.  Every global access is a wave-instruction over 8 key (or value) rows x
-// 128 contiguous bytes: lane = (row r = lane >> 3, 16-byte chunk c = lane & 7), iteration i owns key 8 i + r.  Scores: each
-// lane multiplies its chunk of the key by the matching 8 query dimensions (registers), three shuffles sum the 8 chunks, so
-// the 8 lanes of a row all hold that key's score; max and sum run across the wave.  Output: the SAME lanes hold the matching
-// chunk of the value row, weight it by their key's probability, and three shuffles sum the 8 rows of an iteration.
-// The step's own key / value (self-attention) is taken from the projection output directly and stored to the cache on the
-// side.  NI = iterations (8 keys each): 24 -> 192 keys, 40 -> 320 keys.
-// G > 1 (cross-attention of beam search): the G sequences of a wave are beams of ONE image and share its keys / values, which are
-// loaded once and used for G queries (at one wave per beam the four beams re-read the same 41 KB through L2: 31.7 us per call
-// at 1,024 rows against 23 us for the self-attention over a cache that does not fit the Infinity Cache).
-template <int NI, int G>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const DecAttnP p, const int nunits) {
-    const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);          // (G sequences, head) of this wave
-    if (unit >= nunits) return;
-    const int b0 = (unit / p.heads) * G, h = unit - (unit / p.heads) * p.heads, lane = threadIdx.x & 63;
-    const int b = b0;                                              // G == 1: the sequence
-    bf16_t* Kb = p.K + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
-    bf16_t* Vb = p.V + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
-    const int tdev = p.tptr ? *p.tptr : 0;
-    const int nkeys = p.tptr ? min(tdev + 1, 8 * NI) : p.nkeys;
-    const int append_at = (G > 1) ? -1 : (p.tptr ? min(tdev, 8 * NI - 1) : p.append_at);
-    const int r = lane >> 3, c = lane & 7;
-    const bf16_t* knew = append_at >= 0 ? p.knew + (int64_t)b * p.ldnew + h * 64 : nullptr;
-    const bf16_t* vnew = append_at >= 0 ? p.vnew + (int64_t)b * p.ldnew + h * 64 : nullptr;
-    if (append_at >= 0) {                         // lane d copies dimension d of the new key and value into the cache
-        Kb[(int64_t)append_at * p.kj + lane] = knew[lane];
-        Vb[(int64_t)append_at * p.kj + lane] = vnew[lane];
-        // ... and the row table learns where it went (own row): steps that are not followed by a re-parenting leave it complete.
-        // No wave reads entry [b][append_at] during this step (that key comes from the projection output).
-        if (G == 1 && p.rows && lane == 0 && h == 0) p.rows[(int64_t)b * p.ldrows + append_at] = b;
+// The first arg-max (value bv, column bi) of one fp32 logits row by 256 threads, in every thread: torch.argmax's, the smallest column
+// among equal maxima.  Thread tid scans columns tid + 256 e in ascending order (strict >: its first), E per batch of independent loads
+// (clamped index, masked afterwards); the wave's 64 candidates, then the 4 waves' (s_v / s_i [4], one barrier) merge under row_before.
+template <int E>
+__device__ __forceinline__ void row_first_argmax(const float* __restrict__ row, int V, int tid, float* s_v, int* s_i, float& bv, int& bi) {
+    bv = -INFINITY; bi = ROW_NO_COL;
+    for (int v0 = tid; v0 < V; v0 += 256 * E) {
+        float x[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
+#pragma unroll
+        for (int e = 0; e < E; ++e) { const int v = v0 + e * 256; if (v < V && x[e] > bv) { bv = x[e]; bi = v; } }
     }
-    float qc[G][8];
+    wave_first_argmax(bv, bi);
+    if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+    __syncthreads();
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const bf16x8 q8 = *(const bf16x8*)(p.q + (int64_t)(b0 + g) * p.ldq + h * 64 + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qc[g][e] = bf2f((bf16_t)q8[e]) * p.scale;
-    }
-    // Beam search re-parents sequences every step; instead of copying cache rows (113 us per step at 1,024 rows), key j of
-    // sequence b is read from the row of the ancestor that wrote it (rows[b][j], kzv_decode_reorder keeps the table).  This
-    // step's own key is still stored to row b above and read from the projection output.
-    int roff[G > 1 ? 1 : NI];                      // element offset of the ancestor's row relative to row b (checked < 2^31 on the host)
-    if constexpr (G == 1) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) roff[i] = 0;
-        if (p.rows) {                              // wave-uniform; the loads themselves are unconditional (clamped index) so that
-            const int* tr = p.rows + (int64_t)b * p.ldrows;   // they all go out together instead of one round trip each
-            int rj[NI];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) rj[i] = tr[min(8 * i + r, (int)p.ldrows - 1)];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int j = 8 * i + r;
-                roff[i] = (j < nkeys && j != append_at) ? (rj[i] - b) * (int)p.kb : 0;
-            }
-        }
-    }
-    auto row = [&](const bf16_t* base, const bf16_t* fresh, int i) -> bf16x8 {
-        const int j = 8 * i + r;
-        if (j >= nkeys) return (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        return *(const bf16x8*)((j == append_at ? fresh : base + (G > 1 ? 0 : roff[G > 1 ? 0 : i]) + (int64_t)j * p.kj) + c * 8);
-    };
-    // key-usable flags of this lane's keys: loaded up front and unconditionally (clamped index) -- inside the score loop each one
-    // sat in its own branch behind an s_waitcnt vmcnt(0), i.e. 24 serial round trips per self-attention call
-    bool kok[G][NI];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int i = 0; i < NI; ++i) kok[g][i] = true;
-    if (p.valid) {
-        unsigned char vb[G][NI];
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int i = 0; i < NI; ++i) vb[g][i] = p.valid[(int64_t)(b0 + g) * p.ldvalid + min(8 * i + r, (int)p.ldvalid - 1)];
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int i = 0; i < NI; ++i) kok[g][i] = vb[g][i] != 0;
-    }
-    float sc[G][NI];
-    float mx[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) mx[g] = -INFINITY;
-    // rows in flight: 8 wave-instructions = 64 keys.  (Requesting ALL key and value rows before the first score -- 225
-    // registers -- changed nothing for 1,024 waves and cost the 4,096-wave beam step 6 ms per generation: occupancy.)
-    constexpr int CH = 8;
-#pragma unroll
-    for (int i0 = 0; i0 < NI; i0 += CH) {
-        if (i0 * 8 >= nkeys) {                     // wave-uniform: nothing left
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int u = 0; u < CH; ++u) sc[g][i0 + u] = -INFINITY;
-            continue;
-        }
-        bf16x8 kk[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) kk[u] = row(Kb, knew, i0 + u);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = 8 * (i0 + u) + r;
-            float kf[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) kf[e] = bf2f((bf16_t)kk[u][e]);
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a += qc[g][e] * kf[e];
-                a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64);
-                const bool ok = j < nkeys && kok[g][i0 + u];
-                sc[g][i0 + u] = ok ? a : -INFINITY;
-                mx[g] = fmaxf(mx[g], sc[g][i0 + u]);
-            }
-        }
-    }
-    float inv[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        mx[g] = wave_max(mx[g]);
-        const bool dead = mx[g] == -INFINITY;      // no usable key (a finished, all-pad row): output zeros
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) { sc[g][i] = dead ? 0.f : __expf(sc[g][i] - mx[g]); sum += sc[g][i]; }
-        sum = wave_sum(sum) * 0.125f;              // every key is counted by the 8 lanes of its row
-        inv[g] = dead ? 0.f : 1.f / sum;
-    }
-    float o[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
-#pragma unroll
-    for (int i0 = 0; i0 < NI; i0 += CH) {
-        if (i0 * 8 >= nkeys) continue;
-        bf16x8 vv[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) vv[u] = row(Vb, vnew, i0 + u);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            float vf[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vf[e] = bf2f((bf16_t)vv[u][e]);
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[g][e] += sc[g][i0 + u] * vf[e];
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { o[g][e] += __shfl_xor(o[g][e], 8, 64); o[g][e] += __shfl_xor(o[g][e], 16, 64); o[g][e] += __shfl_xor(o[g][e], 32, 64); }
-        if (r == 0) {
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-            const float iv = inv[g];
-            const u32x4 pk = (u32x4){pack_bf2(o[g][0] * iv, o[g][1] * iv), pack_bf2(o[g][2] * iv, o[g][3] * iv), pack_bf2(o[g][4] * iv, o[g][5] * iv), pack_bf2(o[g][6] * iv, o[g][7] * iv)};
-            *(u32x4*)(p.out + (int64_t)(b0 + g) * p.ldo + h * 64 + c * 8) = pk;
-        }
-    }
+    for (int q = 0; q < 4; ++q) if (row_before(s_v[q], s_i[q], bv, bi)) { bv = s_v[q]; bi = s_i[q]; }
 }
 
-// Cross-attention keys / values for the generation steps: [layer][K|V][image][head][key][64] from the projection output
-// [image * keys][layer][K|V][head][64] (one GEMM row per patch token).  There a head's key rows are 128-byte pieces 6 KB
-// apart (17 us per call at 256 images: 2.5 TB/s); here each (image, head) streams one contiguous block.  Once per generation.
-__global__ __launch_bounds__(256) void cross_relayout_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int images, int keys, int heads,
-                                                             int layers2, int64_t total16) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total16) return;
-    int64_t r = t;                                  // dst order: [l2][img][h][key][8 chunks]
-    const int c = r & 7; r >>= 3;
-    const int key = r % keys; r /= keys;
-    const int h = r % heads; r /= heads;
-    const int img = r % images; r /= images;
-    const int l2 = (int)r;
-    dst[t] = src[(((int64_t)img * keys + key) * layers2 + l2) * heads * 8 + h * 8 + c];
+// One pass of the seating prefix sum over 256 slots (thread tid holds one slot's ended flag): the ended slots BELOW this thread's within
+// the pass, `total` = those of the whole pass.  Ballot + popcount per wave, s_w [4], one barrier; the caller's barrier frees s_w again.
+__device__ __forceinline__ int seat_rank(bool ended, int tid, int* s_w, int& total) {
+    const int lane = tid & 63, w = tid >> 6;
+    const unsigned long long mask = __ballot(ended);
+    if (lane == 0) s_w[w] = __popcll(mask);
+    __syncthreads();
+    int below = 0; total = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { below += q < w ? s_w[q] : 0; total += s_w[q]; }
+    return below + __popcll(mask & ((1ull << lane) - 1ull));
 }
 
-// the same copy into a POOL of dst_images images ([layer][K|V][pool image][head][key][64]) at entries first .. first + images - 1:
-// slot-refill decoding keeps the cross-attention K/V of a whole wave of images resident (kzv_stream_encode)
-__global__ __launch_bounds__(256) void cross_relayout_pool_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int images, int keys, int heads,
-                                                                  int layers2, int64_t total16, int dst_images, int first) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total16) return;
-    int64_t r = t;                                  // source-side order: [l2][img][h][key][8 chunks]
-    const int c = r & 7; r >>= 3;
-    const int key = r % keys; r /= keys;
-    const int h = r % heads; r /= heads;
-    const int img = r % images; r /= images;
-    const int l2 = (int)r;
-    dst[((((int64_t)l2 * dst_images + first + img) * heads + h) * keys + key) * 8 + c] = src[(((int64_t)img * keys + key) * layers2 + l2) * heads * 8 + h * 8 + c];
+// the counters after a seating pass over all slots (one thread): next unseated image, lines / searches ended, steps taken
+__device__ __forceinline__ void seat_counters(int* counters, int next, int ended_now, int n_images) {
+    counters[0] = min(next + ended_now, n_images);
+    const int ended = counters[1];
+    counters[1] = ended + ended_now;
+    if (ended < n_images) counters[2] += 1;      // steps issued past the end (the host looks only every few steps) do not count
 }
 
 // ---- slot-refill greedy decoding: selection and seating (kzv/stream.py::select_seat is the readable statement these are pinned against) ----
@@ -247,25 +77,9 @@ __global__ __launch_bounds__(256) void stream_select_kernel(const StreamP p) {
         return;
     }
     const float* row = p.logits + (int64_t)b * p.ld;
-    const int V = p.V;
-    constexpr int E = 8;
-    float bv = -INFINITY; int bi = 0x7fffffff;
-    for (int v0 = tid; v0 < V; v0 += 256 * E) {
-        float x[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
-#pragma unroll
-        for (int e = 0; e < E; ++e) { const int v = v0 + e * 256; if (v < V && x[e] > bv) { bv = x[e]; bi = v; } }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_v[w] = bv; s_i[w] = bi; }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) if (s_v[q] > bv || (s_v[q] == bv && s_i[q] < bi)) { bv = s_v[q]; bi = s_i[q]; }
+    const int V = p.V; constexpr int E = 8;
+    float bv; int bi;
+    row_first_argmax<E>(row, V, tid, s_v, s_i, bv, bi);
     // log-sum-exp against the row maximum (the row is in cache): log p(token) = max - lse = -log(sum)
     float sum = 0.f;
     for (int v0 = tid; v0 < V; v0 += 256 * E) {
@@ -291,27 +105,24 @@ __global__ __launch_bounds__(256) void stream_select_kernel(const StreamP p) {
     }
 }
 
+// a slot at the start of a line: step 0, BOS, the first RoBERTa position
+__device__ __forceinline__ void stream_reset(const StreamP& p, int s) { p.slot_t[s] = 0; p.tokens[s] = p.bos; p.posids[s] = p.pad + 1; }
+
 __global__ __launch_bounds__(256) void stream_seat_kernel(const StreamP p) {
     __shared__ int s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int next = p.counters[0];
+    const int tid = threadIdx.x, next = p.counters[0];
     int carry = 0;                               // lines ended in the slots below this pass
     for (int base = 0; base < p.slots; base += 256) {
         const int s = base + tid;
         const bool in = s < p.slots;
         const int e = in ? p.sel[2 * s] : 0;
-        const unsigned long long mask = __ballot(e != 0);
-        if (lane == 0) s_w[w] = __popcll(mask);
-        __syncthreads();
-        int below = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { below += q < w ? s_w[q] : 0; total += s_w[q]; }
-        const int rank = carry + below + __popcll(mask & ((1ull << lane) - 1ull));      // ended slots below slot s
+        int total;
+        const int rank = carry + seat_rank(e != 0, tid, s_w, total);      // ended slots below slot s
         if (in) {
             if (e) {
                 const int ni = next + rank;
                 p.slot_image[s] = ni < p.n_images ? ni : -1;
-                p.slot_t[s] = 0; p.tokens[s] = p.bos; p.posids[s] = p.pad + 1;
+                stream_reset(p, s);
             } else if (p.slot_image[s] >= 0) {
                 const int t = p.slot_t[s];
                 p.slot_t[s] = t + 1; p.tokens[s] = p.sel[2 * s + 1]; p.posids[s] = t + 2 + p.pad;
@@ -320,12 +131,7 @@ __global__ __launch_bounds__(256) void stream_seat_kernel(const StreamP p) {
         carry += total;
         __syncthreads();
     }
-    if (tid == 0) {
-        p.counters[0] = min(next + carry, p.n_images);
-        const int ended = p.counters[1];
-        p.counters[1] = ended + carry;
-        if (ended < p.n_images) p.counters[2] += 1;      // steps issued past the end (the host looks only every few steps) do not count
-    }
+    if (tid == 0) seat_counters(p.counters, next, carry, p.n_images);
 }
 
 // the first min(slots, n_images) images take the slots in order; the other slots are idle
@@ -333,19 +139,9 @@ __global__ void stream_start_kernel(const StreamP p) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s < p.slots) {
         p.slot_image[s] = s < p.n_images ? s : -1;
-        p.slot_t[s] = 0; p.tokens[s] = p.bos; p.posids[s] = p.pad + 1;
+        stream_reset(p, s);
     }
     if (s == 0) { p.counters[0] = min(p.slots, p.n_images); p.counters[1] = 0; p.counters[2] = 0; }
-}
-
-// beam re-parenting without moving the cache: dst[b][j] = src[parent[b]][j] for the keys written before this step, and the key
-// the parent wrote at this step (index len - 1) sits in the parent's own row.  src == nullptr: the identity table (first step).
-__global__ void kv_rows_kernel(const int* __restrict__ src, int* __restrict__ dst, const int64_t* __restrict__ parent, int B, int ld, int len) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= B * len) return;
-    const int b = t / len, j = t - b * len;
-    const int p = (int)parent[b];
-    dst[(int64_t)b * ld + j] = (j == len - 1 || !src) ? p : src[(int64_t)p * ld + j];
 }
 
 // One beam-search step's ranking for one image (HF GenerationMixin._get_top_k_continuations, transformers generation/utils.py:
@@ -473,7 +269,7 @@ struct BeamUpd {
     int64_t* rows;                                                // [B * nb]: former flat row each running beam continues from
     int* flags;                                                   // [5]: images still unsatisfied, images whose finished list is not full, images with a continuation that did not stop; [3] = stopped, [4] = updates applied
     int nb, K, L, V, cur, eos, early;
-    float div_fin, div_open;                                      // (cur + 1 - prompt) ** length_penalty, (cur + 1 + 1 - prompt - 1) ** length_penalty as fp32
+    float div;                                                    // cur ** length_penalty as fp32: the length divisor of a hypothesis that ends at this step
 };
 
 // One image's step, ranked: what one lane works out between the loads and the row copies.  The inputs are filled by the lanes together
@@ -490,8 +286,16 @@ struct BeamRankOut {                                             // the ranking 
     bool un, done_new, all_hits;                                 // still unsatisfied, finished list full, every continuation stopped
 };
 
-// `lim`: the length at which a continuation stops whatever its token (max_len, or the image's own limit)
-__device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, int K, int V, int eos, int cur, int lim, int early, float div_fin, float div_open) {
+// the co-operative fill from row b (an image, or a slot) of the ranking [.., K] and of the finished state [.., nb]: one load per thread, together
+__device__ __forceinline__ void beam_rank_load(BeamRank& r, int tid, int K, int nb, int b, const float* lp, const int64_t* ix, const float* fsc,
+                                               const unsigned char* fdone, const int64_t* flen, const unsigned char* unsat) {
+    if (tid < K) { r.lp[tid] = lp[(int64_t)b * K + tid]; r.ix[tid] = ix[(int64_t)b * K + tid]; }
+    if (tid >= 16 && tid < 16 + nb) { const int i = tid - 16; r.fsc[i] = fsc[b * nb + i]; r.fdone[i] = fdone[b * nb + i]; r.flen[i] = flen[b * nb + i]; }
+    if (tid == 32) r.unsat = unsat[b];
+}
+
+// `lim`: the length at which a continuation stops whatever its token (max_len, or the image's own limit); `div`: the length divisor at cur
+__device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, int K, int V, int eos, int cur, int lim, int early, float div) {
     constexpr float NEG = -1.0e9f;
     float s2[16], msc[24];
     unsigned char mdone[24];
@@ -508,7 +312,7 @@ __device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, i
         all_hits = all_hits && hit;
         s2[k] = lp + (hit ? NEG : 0.f);
         const bool just = hit && k < nb;
-        float f = lp / div_fin;
+        float f = lp / div;
         f = f + full_neg; f = f + unsat_neg; f = f + (just ? 0.f : NEG);
         msc[nb + k] = f; mdone[nb + k] = just;
     }
@@ -535,7 +339,7 @@ __device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, i
     bool done_new = true;
     for (int i = 0; i < nb; ++i) { fmin = fminf(fmin, o.fsc_new[i]); done_new = done_new && o.fd_new[i]; }
     // can the best open beam still beat the worst finished one?
-    const float best_open = o.run_new[0] / div_open;
+    const float best_open = o.run_new[0] / div;
     bool any = false;
     for (int i = 0; i < nb; ++i) any = any || best_open > (o.fd_new[i] ? fmin : NEG);
     o.un = r.unsat && any; o.done_new = done_new; o.all_hits = all_hits;
@@ -546,17 +350,12 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
     const int img = blockIdx.x, lane = threadIdx.x;
     const int nb = p.nb, K = p.K, L = p.L;
     if (p.flags[3]) return;                      // the search has ended (beam_stop_kernel): steps issued before the host noticed change nothing
-    // the ~40 state words of this image: one load per lane, together
-    if (lane < K) { r.lp[lane] = p.top_lp[(int64_t)img * K + lane]; r.ix[lane] = p.top_ix[(int64_t)img * K + lane]; }
-    if (lane >= 16 && lane < 16 + nb) {
-        const int i = lane - 16;
-        r.fsc[i] = p.fin_sc[img * nb + i]; r.fdone[i] = p.fin_done[img * nb + i]; r.flen[i] = p.fin_len[img * nb + i];
-    }
-    if (lane == 32) r.unsat = p.unsat[img];
+    // the ~40 state words of this image
+    beam_rank_load(r, lane, K, nb, img, p.top_lp, p.top_ix, p.fin_sc, p.fin_done, p.fin_len, p.unsat);
     __syncthreads();
     if (lane == 0) {
         BeamRankOut o;
-        beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, p.div_fin, p.div_open);
+        beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, p.div);
         for (int i = 0; i < nb; ++i) {
             p.rows[img * nb + i] = (int64_t)img * nb + r.src[r.nxt[i]];
             p.run_sc[img * nb + i] = o.run_new[i];
@@ -608,6 +407,11 @@ struct StreamBeamP {
 };
 constexpr int SB_NB = 4, SB_L = 128;                                // what the staging holds: 2 x 4 x 128 token rows (8 KB) + 4 x 128 table entries
 
+// token j of merged finished row mi from the staged rows: an old finished row (mi < nb), or continuation mi - nb = its beam's prefix + the token at cur
+__device__ __forceinline__ int64_t beam_fin_token(const BeamRank& r, int mi, int j, int cur, int nb, int L, const int64_t* s_fin, const int64_t* s_run) {
+    return mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
+}
+
 __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBeamP p) {
     __shared__ BeamRank r;
     __shared__ BeamRankOut o;                    // the ranking lane's results, for every thread
@@ -623,17 +427,12 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
     const int t = min(p.slot_t[s], L - 2), cur = t + 1;
     const int lim = p.limit ? min(p.limit[img], L) : L;
     const float div = p.div[cur];
-    if (tid < K) { r.lp[tid] = p.top_lp[(int64_t)s * K + tid]; r.ix[tid] = p.top_ix[(int64_t)s * K + tid]; }
-    if (tid >= 16 && tid < 16 + nb) {
-        const int i = tid - 16;
-        r.fsc[i] = p.fin_sc[s * nb + i]; r.fdone[i] = p.fin_done[s * nb + i]; r.flen[i] = p.fin_len[s * nb + i];
-    }
-    if (tid == 32) r.unsat = p.unsat[s];
+    beam_rank_load(r, tid, K, nb, s, p.top_lp, p.top_ix, p.fin_sc, p.fin_done, p.fin_len, p.unsat);
     // the slot's old rows: whole rows, as the statement moves them (what lies behind cur may be an earlier image's and is never read)
     for (int e = tid; e < nb * L; e += 256) { s_run[e] = p.run_seq[(int64_t)s * nb * L + e]; s_fin[e] = p.fin_seq[(int64_t)s * nb * L + e]; }
     if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; s_rt[i * L + j] = p.rows[((int64_t)s * nb + i) * p.ld_rows + j]; }
     __syncthreads();
-    if (tid == 0) { BeamRankOut mine; beam_rank(r, mine, nb, K, p.V, p.eos, cur, lim, p.early, div, div); o = mine; }
+    if (tid == 0) { BeamRankOut mine; beam_rank(r, mine, nb, K, p.V, p.eos, cur, lim, p.early, div); o = mine; }
     __syncthreads();
     const bool go_on = o.un && !(o.done_new && p.early) && !o.all_hits;      // beam_search's go_on, for this image
     if (!go_on) {
@@ -641,7 +440,7 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
         const int mi = r.mix[0], n = (int)o.fl_new[0];
         if (img < p.n_images)
             for (int j = tid; j < min(n, L); j += 256)
-                p.out_ids[(int64_t)img * p.ld_ids + j] = mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
+                p.out_ids[(int64_t)img * p.ld_ids + j] = beam_fin_token(r, mi, j, cur, nb, L, s_fin, s_run);
         if (tid == 0) {
             if (p.out_score && img < p.n_images) p.out_score[img] = o.fsc_new[0];
             p.sel[2 * s] = 1; p.sel[2 * s + 1] = 0;
@@ -652,7 +451,7 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
         const int i = e / L, j = e - i * L;
         const int k = r.nxt[i], mi = r.mix[i];
         p.run_seq[(int64_t)s * nb * L + e] = j == cur ? (int64_t)r.tok[k] : s_run[r.src[k] * L + j];
-        p.fin_seq[(int64_t)s * nb * L + e] = mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
+        p.fin_seq[(int64_t)s * nb * L + e] = beam_fin_token(r, mi, j, cur, nb, L, s_fin, s_run);
     }
     // the row table, kv_rows_kernel's rule with len = slot_t + 1: the step kernel has just written old[b][slot_t] = b; nothing of the cache moves
     if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; p.rows[((int64_t)s * nb + i) * p.ld_rows + j] = s_rt[r.src[r.nxt[i]] * L + j]; }
@@ -680,21 +479,15 @@ __device__ __forceinline__ void stream_beam_reset(const StreamBeamP& p, int s) {
 
 __global__ __launch_bounds__(256) void stream_beam_seat_kernel(const StreamBeamP p) {
     __shared__ int s_w[4], s_pad;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int next = p.counters[0];
+    const int tid = threadIdx.x, next = p.counters[0];
     if (tid == 0) s_pad = 0;
     int carry = 0;                               // searches ended in the slots below this pass
     for (int base = 0; base < p.slots; base += 256) {
         const int s = base + tid;
         const bool in = s < p.slots;
         const int e = in ? p.sel[2 * s] : 0;
-        const unsigned long long mask = __ballot(e != 0);
-        if (lane == 0) s_w[w] = __popcll(mask);
-        __syncthreads();
-        int below = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { below += q < w ? s_w[q] : 0; total += s_w[q]; }
-        const int rank = carry + below + __popcll(mask & ((1ull << lane) - 1ull));      // ended slots below slot s
+        int total;
+        const int rank = carry + seat_rank(e != 0, tid, s_w, total);      // ended slots below slot s
         if (in) {
             if (e) {
                 const int ni = next + rank;
@@ -709,10 +502,7 @@ __global__ __launch_bounds__(256) void stream_beam_seat_kernel(const StreamBeamP
         __syncthreads();
     }
     if (tid == 0) {
-        p.counters[0] = min(next + carry, p.n_images);
-        const int ended = p.counters[1];
-        p.counters[1] = ended + carry;
-        if (ended < p.n_images) p.counters[2] += 1;      // steps issued past the end (the host looks only every few steps) do not count
+        seat_counters(p.counters, next, carry, p.n_images);
         p.counters[3] += s_pad;
     }
 }
@@ -723,96 +513,6 @@ __global__ void stream_beam_start_kernel(const StreamBeamP p) {
     if (e < p.slots * p.nb * p.L) { const int64_t v = e % p.L == 0 ? p.bos : p.pad; p.run_seq[e] = v; p.fin_seq[e] = v; }
     if (e < p.slots) { p.slot_image[e] = e < p.n_images ? e : -1; stream_beam_reset(p, e); }
     if (e == 0) { p.counters[0] = min(p.slots, p.n_images); p.counters[1] = 0; p.counters[2] = 0; p.counters[3] = 0; }
-}
-
-// More than 320 keys (cross-attention over long encoder sequences; no cache append, no row table): the lane layout of
-// attn_decode_kernel, but the keys are swept in chunks of 64 (8 wave-instructions of 8 rows) with a running max and sum per
-// sequence, so nothing is held per key.  The output accumulators are rescaled when the max moves.
-template <int G>
-__global__ __launch_bounds__(256) void attn_decode_long_kernel(const DecAttnP p, const int nunits) {
-    const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (unit >= nunits) return;
-    const int b0 = (unit / p.heads) * G, h = unit - (unit / p.heads) * p.heads, lane = threadIdx.x & 63;
-    const bf16_t* Kb = p.K + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
-    const bf16_t* Vb = p.V + (int64_t)(b0 / p.group) * p.kb + h * p.kh;
-    const int nkeys = p.nkeys, r = lane >> 3, c = lane & 7;
-    float qc[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const bf16x8 q8 = *(const bf16x8*)(p.q + (int64_t)(b0 + g) * p.ldq + h * 64 + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qc[g][e] = bf2f((bf16_t)q8[e]) * p.scale;
-    }
-    constexpr int CH = 8;
-    float mx[G], sum[G], o[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        mx[g] = -INFINITY; sum[g] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
-    }
-    for (int j0 = 0; j0 < nkeys; j0 += 8 * CH) {
-        bf16x8 kk[CH], vv[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int j = min(j0 + 8 * u + r, nkeys - 1);          // clamped rows: their scores are masked below
-            kk[u] = *(const bf16x8*)(Kb + (int64_t)j * p.kj + c * 8);
-            vv[u] = *(const bf16x8*)(Vb + (int64_t)j * p.kj + c * 8);
-        }
-        bool kok[G][CH];
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int u = 0; u < CH; ++u) kok[g][u] = j0 + 8 * u + r < nkeys;
-        if (p.valid) {
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int u = 0; u < CH; ++u)
-                    kok[g][u] = kok[g][u] && p.valid[(int64_t)(b0 + g) * p.ldvalid + min(j0 + 8 * u + r, (int)p.ldvalid - 1)] != 0;
-        }
-        float sc[G][CH];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            float cm = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a += qc[g][e] * bf2f((bf16_t)kk[u][e]);
-                a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64);
-                sc[g][u] = kok[g][u] ? a : -INFINITY;
-                cm = fmaxf(cm, sc[g][u]);
-            }
-            cm = wave_max(cm);
-            const float mn = fmaxf(mx[g], cm);
-            if (mn == -INFINITY) continue;                          // nothing usable yet (wave-uniform)
-            const float alpha = __expf(mx[g] - mn);                 // 0 on the first usable chunk (mx = -inf)
-            mx[g] = mn;
-            sum[g] *= alpha;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const float pr = __expf(sc[g][u] - mn);
-                sum[g] += pr;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[g][e] += pr * bf2f((bf16_t)vv[u][e]);
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const bool dead = mx[g] == -INFINITY;                       // no usable key: output zeros
-        const float iv = dead ? 0.f : 1.f / (wave_sum(sum[g]) * 0.125f);   // every key is counted by the 8 lanes of its row
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { o[g][e] += __shfl_xor(o[g][e], 8, 64); o[g][e] += __shfl_xor(o[g][e], 16, 64); o[g][e] += __shfl_xor(o[g][e], 32, 64); }
-        if (r == 0) {
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-            const u32x4 pk = (u32x4){pack_bf2(o[g][0] * iv, o[g][1] * iv), pack_bf2(o[g][2] * iv, o[g][3] * iv), pack_bf2(o[g][4] * iv, o[g][5] * iv), pack_bf2(o[g][6] * iv, o[g][7] * iv)};
-            *(u32x4*)(p.out + (int64_t)(b0 + g) * p.ldo + h * 64 + c * 8) = pk;
-        }
-    }
 }
 
 // inputs of decoder step t from the token table: newest token, its RoBERTa position id (HF modeling_roberta.py:142-155: t + 1 +
@@ -833,27 +533,10 @@ __global__ void decode_prep_kernel(const int64_t* __restrict__ ids, int64_t ld_i
 __global__ __launch_bounds__(256) void greedy_update_kernel(const float* __restrict__ logits, int64_t ld, int V, int64_t* __restrict__ ids, int64_t ld_ids,
                                                             int t, unsigned char* __restrict__ done, int pad, int eos, int* __restrict__ flags) {
     __shared__ float s_v[4]; __shared__ int s_i[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float* row = logits + (int64_t)b * ld;
-    constexpr int E = 8;
-    float bv = -INFINITY; int bi = 0x7fffffff;
-    for (int v0 = tid; v0 < V; v0 += 256 * E) {
-        float x[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
-#pragma unroll
-        for (int e = 0; e < E; ++e) { const int v = v0 + e * 256; if (v < V && x[e] > bv) { bv = x[e]; bi = v; } }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_v[w] = bv; s_i[w] = bi; }
-    __syncthreads();
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float bv; int bi;
+    row_first_argmax<8>(logits + (int64_t)b * ld, V, tid, s_v, s_i, bv, bi);
     if (tid == 0) {
-#pragma unroll
-        for (int q = 1; q < 4; ++q) if (s_v[q] > bv || (s_v[q] == bv && s_i[q] < bi)) { bv = s_v[q]; bi = s_i[q]; }
         const bool was = done[b] != 0;
         const int nxt = was ? pad : bi;
         ids[(int64_t)b * ld_ids + t + 1] = nxt;
@@ -871,69 +554,23 @@ __global__ void beam_stop_kernel(int* flags, int early, int cur) {
     if (!go_on) flags[3] = 1;
 }
 
-__global__ void step_inc_kernel(int* t) { *t += 1; }
-
 }  // namespace
 
-int kzv_step_inc(int* d_t, hipStream_t s) {
-    hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, d_t);
-    return kzv_check_launch("step_inc");
-}
-
-// tptr != nullptr: self-attention of graph-replayed step `*tptr` (nkeys = the cache capacity, which picks the kernel)
-int kzv_attn_decode(const bf16_t* q, int64_t ldq, const bf16_t* knew, const bf16_t* vnew, int64_t ldnew, bf16_t* K, bf16_t* V, int64_t kb,
-                    int64_t kj, const unsigned char* valid, int64_t ldvalid, bf16_t* out, int64_t ldo, int B, int heads, int nkeys,
-                    int append_at, hipStream_t s, const int* tptr, int group, int* rows, int64_t ldrows, int64_t kh) {
-    if (nkeys < 1 || nkeys > 4097) return kzv_fail(KZV_E_ARG, "attn_decode: 1..4097 keys");
-    if (nkeys > 320 && (append_at >= 0 || tptr || rows)) return kzv_fail(KZV_E_ARG, "attn_decode: beyond 320 keys only without a cache append or row table");
-    if (ldq % 8 || ldo % 8 || (knew && ldnew % 8)) return kzv_fail(KZV_E_ARG, "attn_decode: rows must be 16-byte aligned");
-    if (group < 1 || (append_at >= 0 && group != 1)) return kzv_fail(KZV_E_ARG, "attn_decode: shared keys cannot be appended to");
-    if (kj % 8) return kzv_fail(KZV_E_ARG, "attn_decode: key rows must be 16-byte aligned");
-    if (rows && group != 1) return kzv_fail(KZV_E_ARG, "attn_decode: a row table and shared keys exclude each other");
-    if (rows && (int64_t)B * kb >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "attn_decode: cache too large for 32-bit row offsets");
-    if (kh % 8) return kzv_fail(KZV_E_ARG, "attn_decode: head stride must be 16-byte aligned");
-    DecAttnP p{q, ldq, knew, vnew, ldnew, K, V, kb, kj, kh, valid, ldvalid, out, ldo, nkeys, append_at, heads, 0.125f, tptr, group, rows, ldrows};
-    // beams of one image (group > 1, shared keys): G of them per wave, G = the largest of 4, 3, 2 dividing the group
-    const int G = group % 4 == 0 ? 4 : group % 3 == 0 ? 3 : group % 2 == 0 ? 2 : 1;
-    const int nunits = (B / G) * heads;
-#define KZV_AD(NI, GG) hipLaunchKernelGGL((attn_decode_kernel<NI, GG>), dim3((nunits + 3) / 4), dim3(256), 0, s, p, nunits)
-#define KZV_AD_G(NI) do { if (G == 4) KZV_AD(NI, 4); else if (G == 3) KZV_AD(NI, 3); else if (G == 2) KZV_AD(NI, 2); else KZV_AD(NI, 1); } while (0)
-#define KZV_ADL(GG) hipLaunchKernelGGL((attn_decode_long_kernel<GG>), dim3((nunits + 3) / 4), dim3(256), 0, s, p, nunits)
-    if (nkeys <= 192) KZV_AD_G(24);
-    else if (nkeys <= 320) KZV_AD_G(40);
-    else if (G == 4) KZV_ADL(4); else if (G == 3) KZV_ADL(3); else if (G == 2) KZV_ADL(2); else KZV_ADL(1);
-#undef KZV_ADL
-#undef KZV_AD_G
-#undef KZV_AD
-    return kzv_check_launch("attn_decode");
-}
-
-int kzv_kv_rows(const int* src, int* dst, const int64_t* parent, int B, int ld, int len, hipStream_t s) {
-    hipLaunchKernelGGL(kv_rows_kernel, dim3((B * len + 255) / 256), dim3(256), 0, s, src, dst, parent, B, ld, len);
-    return kzv_check_launch("kv_rows");
-}
-
-int kzv_cross_relayout(const bf16_t* src, bf16_t* dst, int images, int keys, int heads, int layers2, hipStream_t s) {
-    const int64_t total16 = (int64_t)layers2 * images * heads * keys * 8;
-    hipLaunchKernelGGL(cross_relayout_kernel, dim3((unsigned)((total16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, images, keys, heads,
-                       layers2, total16);
-    return kzv_check_launch("cross_relayout");
-}
-
-int kzv_cross_relayout_pool(const bf16_t* src, bf16_t* dst, int images, int keys, int heads, int layers2, int dst_images, int first, hipStream_t s) {
-    if (images < 1 || first < 0 || first + images > dst_images) return kzv_fail(KZV_E_ARG, "cross_relayout_pool: entries %d .. %d outside a pool of %d images", first, first + images - 1, dst_images);
-    const int64_t total16 = (int64_t)layers2 * images * heads * keys * 8;
-    hipLaunchKernelGGL(cross_relayout_pool_kernel, dim3((unsigned)((total16 + 255) / 256)), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, images, keys, heads,
-                       layers2, total16, dst_images, first);
-    return kzv_check_launch("cross_relayout_pool");
+// what both slot states owe: their device arrays and out_ids, positive sizes, max_len columns (2 .. cap, 0: no cap) within the shortest output row
+static int slot_state_check(const char* who, int slots, int n_images, int vocab, int max_len, int cap, int64_t ld_out, const void* out_ids,
+                            std::initializer_list<const void*> arrays) {
+    for (const void* a : arrays) if (!a) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
+    if (!out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
+    if (slots < 1 || n_images < 1 || vocab < 1) return kzv_fail(KZV_E_ARG, "%s: slots, images and vocabulary must be positive", who);
+    if (max_len < 2 || (cap && max_len > cap) || ld_out < max_len)
+        return cap ? kzv_fail(KZV_E_ARG, "%s: max_len 2..%d columns within the output rows", who, cap) : kzv_fail(KZV_E_ARG, "%s: max_len >= 2 columns within the output rows", who);
+    return KZV_OK;
 }
 
 static int stream_params(const kzv_stream_state* st, const float* d_logits, int64_t ld, StreamP* p, const char* who) {
     if (!st) return kzv_fail(KZV_E_ARG, "%s: null state", who);
-    if (!st->slot_image || !st->slot_t || !st->tokens || !st->posids || !st->counters || !st->scratch) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
-    if (!st->out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
-    if (st->slots < 1 || st->n_images < 1 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "%s: slots, images and vocabulary must be positive", who);
-    if (st->max_len < 2 || st->ld_ids < st->max_len || (st->out_logprob && st->ld_logprob < st->max_len)) return kzv_fail(KZV_E_ARG, "%s: max_len >= 2 columns within the output rows", who);
+    KZV_TRY_RC(slot_state_check(who, st->slots, st->n_images, st->vocab, st->max_len, 0, st->out_logprob && st->ld_logprob < st->ld_ids ? st->ld_logprob : st->ld_ids,
+                                st->out_ids, {st->slot_image, st->slot_t, st->tokens, st->posids, st->counters, st->scratch}));
     *p = StreamP{d_logits, ld, st->vocab, st->slots, st->n_images, st->max_len, st->bos_id, st->eos_id, st->pad_id, st->slot_image, st->slot_t, st->tokens,
                  st->posids, st->counters, st->scratch, st->out_ids, st->ld_ids, st->out_logprob, st->ld_logprob, st->limit};
     return KZV_OK;
@@ -957,13 +594,11 @@ extern "C" int kzv_stream_update(const kzv_stream_state* st, const float* d_logi
 
 static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_lp, const int64_t* top_ix, StreamBeamP* p, const char* who) {
     if (!st) return kzv_fail(KZV_E_ARG, "%s: null state", who);
-    if (!st->slot_image || !st->slot_t || !st->tokens || !st->posids || !st->run_seq || !st->fin_seq || !st->run_scores || !st->fin_scores ||
-        !st->fin_done || !st->fin_len || !st->unsatisfied || !st->counters || !st->scratch) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
-    if (!st->out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
+    KZV_TRY_RC(slot_state_check(who, st->slots, st->n_images, st->vocab, st->max_len, SB_L, st->ld_ids, st->out_ids,
+                                {st->slot_image, st->slot_t, st->tokens, st->posids, st->run_seq, st->fin_seq, st->run_scores, st->fin_scores, st->fin_done,
+                                 st->fin_len, st->unsatisfied, st->counters, st->scratch}));
     if (!st->divisors) return kzv_fail(KZV_E_ARG, "%s: null divisors (fp32 [max_len + 1] of n ** length_penalty)", who);
     if (st->num_beams != 2 && st->num_beams != 4) return kzv_fail(KZV_E_ARG, "%s: num_beams %d: a slot holds 2 or 4 beams", who, st->num_beams);
-    if (st->slots < 1 || st->n_images < 1 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "%s: slots, images and vocabulary must be positive", who);
-    if (st->max_len < 2 || st->max_len > SB_L || st->ld_ids < st->max_len) return kzv_fail(KZV_E_ARG, "%s: max_len 2..%d columns within the output rows", who, SB_L);
     if ((int64_t)st->slots * st->num_beams * st->max_len >= (1ll << 31) || (int64_t)st->num_beams * st->vocab >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "%s: state beyond 32-bit indices", who);
     if (st->rows && st->ld_rows < st->max_len - 1) return kzv_fail(KZV_E_ARG, "%s: row table rows shorter than the max_len - 1 steps", who);
     *p = StreamBeamP{top_lp, top_ix, st->slots, st->n_images, st->num_beams, st->max_len, st->vocab, st->bos_id, st->eos_id, st->pad_id, st->early_stopping ? 1 : 0,
@@ -1036,8 +671,7 @@ extern "C" int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scor
     if (hipMemsetAsync(d_flags, 0, (cur == 1 ? 5 : 3) * sizeof(int), s) != hipSuccess) return kzv_fail(KZV_E_HIP, "beam_update: memset");
     BeamUpd p{d_top_scores, d_top_index, st->run_seq_in, st->run_seq_out, st->fin_seq_in, st->fin_seq_out, st->run_scores, st->fin_scores,
               st->fin_done, st->fin_len, st->unsatisfied, d_rows, d_flags, st->num_beams, 2 * st->num_beams, st->max_len, st->vocab, cur,
-              st->eos_id, early_stopping ? 1 : 0,
-              (float)pow((double)(cur + 1 - 1), (double)length_penalty), (float)pow((double)(cur + 1 - 1), (double)length_penalty)};
+              st->eos_id, early_stopping ? 1 : 0, (float)pow((double)cur, (double)length_penalty)};
     hipLaunchKernelGGL(beam_update_kernel, dim3(st->batch), dim3(64), 0, s, p);
     hipLaunchKernelGGL(beam_stop_kernel, dim3(1), dim3(1), 0, s, d_flags, early_stopping ? 1 : 0, cur);
     return kzv_check_launch("beam_update");

@@ -16,8 +16,6 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 
-#define KZV_TRY_RC(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)
-
 namespace {
 
 constexpr int TOPK_DEPTH = 8;

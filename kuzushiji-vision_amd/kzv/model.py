@@ -7,6 +7,7 @@ autograd and no fallback path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import itertools
 import os
@@ -465,6 +466,26 @@ class TrOCRModel:
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
                                to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
 
+    @contextlib.contextmanager
+    def _decode_stream(self, use_graph: bool):
+        """The stream a decode loop runs on, as ``(graph, keep)``.  ``graph``: the step is replayed from a hipGraph (``use_graph`` unless
+        KZV_DECODE_GRAPH=0); stream capture needs a non-default stream, so the whole loop then runs on a side stream that starts
+        behind the current one.  The body appends every tensor its kernels touched to ``keep``; on a clean exit the current stream
+        waits for the side stream and the tensors are recorded on it.  After an exception neither happens."""
+        import torch
+        graph = use_graph and os.environ.get("KZV_DECODE_GRAPH", "1") != "0"
+        cur = torch.cuda.current_stream(self.device)
+        side = torch.cuda.Stream(self.device) if graph else cur
+        if graph:
+            side.wait_stream(cur)
+        keep: list = []
+        with torch.cuda.stream(side):
+            yield graph, keep
+        if graph:
+            cur.wait_stream(side)
+            for t_ in keep:
+                t_.record_stream(cur)
+
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True, return_scores: bool = False,
                  no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None):
@@ -524,14 +545,8 @@ class TrOCRModel:
         state = {"valid": torch.zeros(BB, Lh, dtype=torch.uint8, device=self.device)}   # self-attention keys usable (token != pad)
         posids = torch.empty(BB, dtype=torch.int32, device=self.device)
         tok_buf = torch.empty(BB, dtype=torch.int64, device=self.device)
-        # the cached step is ~100 small launches: replayed from a hipGraph (kzv_decode_step_graph) unless KZV_DECODE_GRAPH=0;
-        # stream capture needs a non-default stream, so the whole decode loop runs on a side stream
-        graph = use_cache and os.environ.get("KZV_DECODE_GRAPH", "1") != "0"
-        cur = torch.cuda.current_stream(self.device)
-        side = torch.cuda.Stream(self.device) if graph else cur
-        if graph:
-            side.wait_stream(cur)
-
+        # the cached step is ~100 small launches: replayed from a hipGraph (kzv_decode_step_graph) where _decode_stream says so (`graph`,
+        # bound by the `with` below before any step runs)
         self.last_generate_steps = 0             # decoder steps this call issued (those run past the end before the host looked included)
 
         def step(t, ids):
@@ -586,7 +601,7 @@ class TrOCRModel:
             return controls_hook(raw_step(t, ids), ids, t + 1, normalise=1)
 
         try:
-            with torch.cuda.stream(side):
+            with self._decode_stream(use_cache) as (graph, keep):
                 # the hooks allocate and zero their flag / top-k buffers: on the stream whose kernels read them
                 if nb > 1 and nb <= 8 and self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0":
                     topk, update = BM.make_device_hooks(B, nb, Lh, c.vocab, c.eos_id, early_stopping, length_penalty, self.device,
@@ -611,12 +626,9 @@ class TrOCRModel:
                     out = BM.beam_search(step, reorder, B, nb, Lh, c.vocab, c.pad_id, c.bos_id, c.eos_id, self.device,
                                          early_stopping=early_stopping, length_penalty=length_penalty, topk=topk, update=update,
                                          process=process)
-            if graph:
-                cur.wait_stream(side)
-                for t_ in (out, step_logits, posids, tok_buf, state["valid"], px) + (() if ctl_mask is None else (ctl_mask,)):
-                    t_.record_stream(cur)
+                keep += (out, step_logits, posids, tok_buf, state["valid"], px) + (() if ctl_mask is None else (ctl_mask,))
                 if return_scores:
-                    scores.record_stream(cur)
+                    keep.append(scores)
             return (out, scores) if return_scores else out
         finally:
             self.training = was
@@ -846,14 +858,8 @@ class TrOCRModel:
         limd = None if lim is None else lim.to(dev).contiguous()
         pool = -(-n // rows) * rows
         divisors = [d for d in range(1, rows + 1) if rows % d == 0]
-        graph = os.environ.get("KZV_DECODE_GRAPH", "1") != "0"
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev) if graph else cur
-        if graph:
-            side.wait_stream(cur)
-        keep = []
         try:
-            with torch.cuda.stream(side):
+            with self._decode_stream(True) as (graph, keep):
                 st = L.stream_handle()
                 if beams:
                     L.check(lib.kzv_stream_begin_beams(self._h, nb, 1 if beams[1] else 0, beams[2], score.data_ptr(), pool, n, Lh, c.bos_id, c.eos_id,
@@ -895,10 +901,7 @@ class TrOCRModel:
                         if steps >= bound:
                             raise L.KzvError(f"generate_stream: {fin.value} of {n} lines ended after {steps} steps; {slots} slots bound them by {bound}")
                 self.last_stream_steps += took.value
-            if graph:
-                cur.wait_stream(side)
-                for t_ in [ids] + keep + [x for x in (lp, score, limd, alt_ids, alt_lp) if x is not None]:
-                    t_.record_stream(cur)
+                keep += [ids] + [x for x in (lp, score, limd, alt_ids, alt_lp) if x is not None]
         finally:
             self.training = was
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it

@@ -7,7 +7,7 @@ prefix-consistent and every decoder step is local to a sequence, so per image th
 generation -- in fewer steps.
 
 ``select_seat(logits, state)`` is what happens between two decoder steps; ``greedy_stream`` is the loop around it.  Both run on
-whatever device the tensors live on.  On the GPU the same thing is two kernels (csrc/decode.hip: stream_select_kernel,
+whatever device the tensors live on.  On the GPU the same thing is two kernels (csrc/token_search.hip: stream_select_kernel,
 stream_seat_kernel through kzv_stream_update) which tests/test_stream_gpu.py pins against this module state for state.
 
 State (a dict of tensors; out_ids / out_logprob are written in place, the others replaced):
@@ -151,7 +151,7 @@ def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int,
 # image's search has ended the slot holds the next image that has no slot yet.  Beam search is independent per image, so per image the
 # result is that of beam.beam_search run on it alone.  ``beam_select_seat`` is what happens between two decoder steps once the 2 * nb
 # best continuations of every slot are ranked (kzv_beam_topk); ``beam_stream`` is the loop around it.  On the GPU the same thing is
-# csrc/decode.hip: stream_beam_update_kernel, stream_beam_seat_kernel (kzv_stream_beam_update), pinned against this state for state.
+# csrc/token_search.hip: stream_beam_update_kernel, stream_beam_seat_kernel (kzv_stream_beam_update), pinned against this state for state.
 #
 # State, beyond slot_image / slot_t [slots] as above:
 #   tokens int64, posids int32 [slots * nb]    the next step's input of every beam row

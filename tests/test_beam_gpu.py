@@ -51,11 +51,15 @@ def test_fused_greedy_equals_the_torch_statement(B, V, T, eos_bias):
     got = BM.greedy(_step_fn(V, T, B + V, eos_bias), B, T, PAD, BOS, EOS, DEV, update=BM.make_greedy_hook(B, V, PAD, EOS, DEV, T))
     torch.cuda.synchronize()
     assert torch.equal(got.cpu(), want.cpu())
-    # first maximum on exact ties, like torch.argmax
-    flat = torch.zeros(B, V, device=DEV)
-    ids = torch.full((B, T), PAD, dtype=torch.int64, device=DEV)
-    done = torch.zeros(B, dtype=torch.uint8, device=DEV)
-    flat[:, 7] = 1.0; flat[:, 19] = 1.0
-    BM.make_greedy_hook(B, V, PAD, EOS, DEV, T)(flat, ids, 0, done)
-    torch.cuda.synchronize()
-    assert ids[:, 1].tolist() == [7] * B
+    # first maximum on exact ties, like torch.argmax: two columns of one wave; the smaller column in the HIGHER lane (column 300 is
+    # thread 44's second column, column 45 thread 45's first); different waves and different sweeps of 2,048 columns
+    for lo, hi in [(7, 19), (45, 300), (70, 2100)]:
+        if hi >= V:
+            continue
+        flat = torch.zeros(B, V, device=DEV)
+        ids = torch.full((B, T), PAD, dtype=torch.int64, device=DEV)
+        done = torch.zeros(B, dtype=torch.uint8, device=DEV)
+        flat[:, lo] = 1.0; flat[:, hi] = 1.0
+        BM.make_greedy_hook(B, V, PAD, EOS, DEV, T)(flat, ids, 0, done)
+        torch.cuda.synchronize()
+        assert ids[:, 1].tolist() == [lo] * B, (lo, hi)

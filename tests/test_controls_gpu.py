@@ -1,4 +1,4 @@
-"""Generation controls on the GPU (csrc/logits_process.hip: kzv_logits_process; csrc/decode.hip: kzv_beam_rank_logprobs;
+"""Generation controls on the GPU (csrc/logits_process.hip: kzv_logits_process; csrc/token_search.hip: kzv_beam_rank_logprobs;
 kzv_stream_set_controls; TrOCRModel.generate / generate_stream with no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens):
 
   1. the kernel in raw mode against kzv/controls.py::process_reference, ``torch.equal`` including the -inf positions and the columns

@@ -1,9 +1,10 @@
 """Beam search on device-refilled slots on the GPU (TrOCRModel.generate_stream(num_beams=2 | 4); include/kzv.h: kzv_stream_begin_beams,
-kzv_stream_beam_*; csrc/decode_fused.hip: the slot instances with 2 / 4 rows and the row table; csrc/decode.hip: update and seating):
+kzv_stream_beam_*; csrc/decode_fused.hip: the slot instances with 2 / 4 rows and the row table; csrc/token_search.hip: update and seating):
 
   1. the update and seating kernels alone against their torch statement (kzv/stream.py: beam_select_seat), state for state over 50 steps:
      rankings from kzv_beam_topk on seeded logits with planted ties, planted EOS, planted padding and several searches ending in one
-     step; every integer array equal, every score torch.equal, the row table re-parented in place;
+     step; every integer array equal, every score torch.equal, the row table re-parented in place; 7, 70 and 300 slots (one wave of
+     slots, several, and a second seating pass of 256 with its carry);
   2. generate_stream(num_beams=nb, slots=6) == generate(num_beams=nb), token for token: 8 and 164 patch keys (the one-pass and the
      chunked instances), bf16 and e4m3 weights, 2 and 4 beams; no running beam took padding;
   3. fewer steps than lockstep batches of 6 (generate's own last_generate_steps), and within the list-scheduling bound;
@@ -23,7 +24,7 @@ CROSS_GAIN / EOS_BIAS / PAD_BIAS of the file's model and the end steps observed 
 Also observed there: 40 crops on 6 slots take 197 / 201 / 202 steps (8 keys: bf16 with 2 and 4 beams, e4m3 with 4) and 225 / 228 / 238
 (164 keys) where lockstep batches of 6 issue 259 at 8 keys and the bound is 296; 75 images on 70 slots 41 steps; no running beam took
 padding; sequence scores within 7.1e-4 (8 keys) and 3.4e-4 (164 keys) of the teacher-forced mean; the per-op case 23 steps for 30
-searches on 7 slots with 4 - 7 planted padding continuations counted."""
+searches on 7 slots with 4 - 7 planted padding continuations counted (31 - 73 at 70 slots, 319 at 300)."""
 import ctypes as C
 import dataclasses
 
@@ -122,10 +123,15 @@ def _static(keys, fmt, nb, decoder_dir):
 
 
 # ---- 1. the kernels against the statement --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nb,early,lpen", [(2, True, 1.0), (4, True, 1.0), (4, False, 0.6)])
-def test_update_and_seat_kernels_equal_the_torch_statement(nb, early, lpen):
+# 7 slots: one wave of slots, one seating pass.  70 slots: ended flags in two waves.  300 slots: a second seating pass of 256 slots with
+# its carry (one beam setting: the statement is a Python loop over the slots).  Every live search ends at steps 4, 13, ..., 49 (six
+# times), so N <= 5 slots images are all seated and ended by the last step.
+@pytest.mark.parametrize("nb,early,lpen,slots,N", [
+    pytest.param(2, True, 1.0, 7, 30, id="2-True-1.0"), pytest.param(4, True, 1.0, 7, 30, id="4-True-1.0"), pytest.param(4, False, 0.6, 7, 30, id="4-False-0.6"),
+    (2, True, 1.0, 70, 300), (4, True, 1.0, 70, 300), (4, False, 0.6, 70, 300), (4, True, 1.0, 300, 1500)])
+def test_update_and_seat_kernels_equal_the_torch_statement(nb, early, lpen, slots, N):
     lib = L.load()
-    slots, V, N, ML, pad, bos, eos = 7, 157, 30, 12, 1, 2, 3
+    V, ML, pad, bos, eos = 157, 12, 1, 2, 3
     K, R = 2 * nb, slots * nb
     g = torch.Generator().manual_seed(13 + nb)
     limits = torch.randint(2, ML + 1, (N,), generator=g, dtype=torch.int32)

@@ -1,8 +1,9 @@
 """Proof that a source change left kernels alone: compiles the same .hip units of two trees with the Makefile's flags and compares
 the gfx950 assembly kernel by kernel.
    python tools/isa_diff.py PARENT_CSRC [--new CSRC] [--units attention.hip gemm_nt256p.hip ...] [--cache DIR] [--show] [--strict]
-                            [--rename REGEX REPLACEMENT]
-(--rename rewrites the parent's demangled kernel names before they are matched, for a kernel template that gained a parameter:
+                            [--rename REGEX REPLACEMENT] [--parent-units decode.hip ...]
+(--parent-units: a unit was split, merged or renamed: the kernels of those PARENT units, pooled, are matched by demangled name against
+the pooled kernels of --units; --rename rewrites the parent's demangled kernel names before they are matched, for a kernel template that gained a parameter:
 --rename 'decode_fused_kernel<(\d)>' 'decode_fused_kernel<\1, 1>'; --units takes any .hip units of csrc, default: csrc/attention*.hip; --cache keeps the parent's assembly between runs; --show prints
 the diff of every kernel whose instruction stream differs).  Per kernel it reports
    (a) the resource counts (.vgpr_count, .agpr_count, .sgpr_count, LDS, scratch, spills: equal to the parent's; a count of
@@ -78,6 +79,7 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("--new", default=CSRC)
     ap.add_argument("--units", nargs="*")
+    ap.add_argument("--parent-units", nargs="+")
     ap.add_argument("--cache")
     ap.add_argument("--show", action="store_true")
     ap.add_argument("--strict", action="store_true")
@@ -91,11 +93,18 @@ def main():
             hit = asm_of(u, pdir)
             return hit[0] if hit else compile_unit(os.path.abspath(a.parent), u, pdir)
         with ThreadPoolExecutor(8) as ex:
-            old = list(ex.map(parent_asm, units))
+            old = list(ex.map(parent_asm, a.parent_units or units))
             new = list(ex.map(lambda u: compile_unit(os.path.abspath(a.new), u, os.path.join(tmp, "new")), units))
+
+        def pooled(files):
+            out = {}
+            for f in files:
+                out.update(parse(f))
+            return out
+        # one comparison per unit; with --parent-units one comparison of the two pools
+        pairs = [("+".join(units), pooled(old), pooled(new))] if a.parent_units else [(u, parse(fo), parse(fn)) for u, fo, fn in zip(units, old, new)]
         bad = 0
-        for u, fo, fn in zip(units, old, new):
-            ko, kn = parse(fo), parse(fn)
+        for u, ko, kn in pairs:
             if a.rename:
                 ko = {re.sub(a.rename[0], a.rename[1], k): v for k, v in ko.items()}
             for name in sorted(set(ko) | set(kn)):
