@@ -285,6 +285,15 @@ int kzv_set_dec_chain(int on);
  * hidden 256).  1 (default; KZV_HEAD_CE), 0: head GEMM + ce_kernel, -1: the environment's default.  kzv_forward_loss with d_logits != NULL
  * always takes the GEMM (it returns them).  Same arithmetic up to fp32 summation order. */
 int kzv_set_head_ce(int on);
+/* Label smoothing of the training loss (an extension: the reference's criterion is plain CrossEntropyLoss; the published TrOCR recipe
+ * smooths with 0.1): kzv_forward_loss(train != 0) computes torch.nn.functional.cross_entropy(logits, target, ignore_index = pad,
+ * label_smoothing = eps), mean over the scored rows, V = the real vocabulary:
+ *   loss_row = lse(z) - (1 - eps) z[y] - (eps / V) sum_{v < V} z[v];   dlogits[v] = (softmax(z)[v] - (1 - eps) [v == y] - eps / V) / count
+ * on whichever path runs (the one-launch head or head GEMM + ce_kernel).  kzv_forward_loss(train == 0) keeps the plain NLL whatever eps
+ * is: validation losses rank checkpoints and stay comparable between runs.  Per handle, 0 after kzv_model_create (the kernels as they
+ * were: smoothing is a compile-time variant), in force from the next kzv_forward_loss.  KZV_E_ARG unless 0 <= eps < 1. */
+int kzv_set_label_smoothing(kzv_model* m, float eps);
+float kzv_get_label_smoothing(const kzv_model* m);      /* 0 for a null handle */
 int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, const int32_t* d_posids, const uint8_t* d_valid, int64_t ld_valid,
                           float* d_logits, void* stream);
 
@@ -652,6 +661,11 @@ int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const
  * kzv_copy_logits: out fp32 [rows, V] = logits[row * ldl + col] (drops the padding columns; ldl may also skip rows). */
 int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
                    const float* count, float* loss, void* dlogits_bf16, void* stream);
+/* The same with label smoothing (F.cross_entropy(..., label_smoothing), 0 <= label_smoothing < 1, else KZV_E_ARG): loss row = lse -
+ *   (1 - eps) z[y] - (eps / V) sum_{v < V} z[v], dlogits = (softmax - (1 - eps) onehot - eps / V) / count in columns < V, zero in pad-target
+ *   rows and in columns [V, ldl).  0 is kzv_ce_fwd_bwd itself (the same kernels, the same bits). */
+int kzv_ce_fwd_bwd_ls(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
+                      const float* count, float* loss, void* dlogits_bf16, float label_smoothing, void* stream);
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream);
 /* fp32 masters -> bf16 compute copies, n matrices in one launch (what kzv_model_sync_weights does for the whole table): dst bf16
  *   [rows, cols], dstT bf16 [cols, ldT] = the transpose, or NULL.  `descs` is a HOST array of device pointers; cols % 4 == 0, and

@@ -379,12 +379,21 @@ __global__ __launch_bounds__(512) void dec_chain_b_kernel(const SegB p) {
 //   pass 2: the same chunks again -> (exp(logit - lse) - onehot) / count as bf16 through an LDS tile, whole rows out (dlogits, the
 //           operand of the head's two gradient GEMMs).  Skipped without a gradient buffer (validation).
 // Same arithmetic as gemm_nt + ce_kernel up to fp32 summation order (bf16 operands, fp32 accumulation, fp32 softmax statistics).
+// LS (compile time; label smoothing, F.cross_entropy(label_smoothing = eps), eps in (0, 1)): the target distribution is (1 - eps) onehot +
+// eps / V over the V real columns.  Pass 1 keeps a third running statistic per lane, the plain sum of its logits in columns < V (the -inf
+// fill of the padded columns stays out of it); the 32 partial sums of a row meet in LDS behind the other row arrays and are folded in the
+// same fixed order: loss_row = lse - (1 - eps) logit[target] - (eps / V) sum.  Pass 2 writes (exp(logit - lse) - (1 - eps) onehot - eps / V)
+// / count in columns < V and ZERO in columns [V, Vp) by an explicit guard: without smoothing exp(-inf) = 0 covers them, with it they
+// would hold -eps / (V count) and enter the head's two gradient GEMMs and the fused dh.  LS = false is the kernel as it was.
 struct HeadCE {
     const bf16_t* x; const bf16_t* wp; const float* bias; const int64_t* labels; const float* count; float* loss; bf16_t* dlogits;
     int M, L, T, V, Vp, nch, pad;
     const bf16_t* wpt; bf16_t* dh;      // optional: dh[M, 256] = dlogits . W (the head's input gradient), wpt = W^T [256, 256 nch] in fragment order
+    float eps;                          // label smoothing (read by the LS instantiations only)
 };
-template <bool DH>
+constexpr int LDS_HEAD = 2 * LDS_A1 + RM * 64 * 4 + RM * 4 * 3;           // head_ce_kernel<*, false>
+constexpr int LDS_HEAD_LS = LDS_HEAD + RM * 32 * 4;                        // + the 32 partial logit sums of every row
+template <bool DH, bool LS>
 __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* a1 = (bf16_t*)smem;                                   // [RM][LDH] the rows' operand tile
@@ -393,6 +402,7 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
     float* lse_s = red + RM * 64;                                 // [RM]
     float* tl_s = lse_s + RM;                                     // [RM] the target's logit
     int* tgt_s = (int*)(tl_s + RM);                               // [RM] target class, -1 = ignored row
+    float* zsum = (float*)(tgt_s + RM);                           // LS only: [RM][32] partial plain sums of the row's logits
     const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m0 = blockIdx.x * RM;
     bf16x8 R[WIN];
@@ -414,6 +424,7 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) tg[rt] = tgt_s[rt * 16 + l15];
     const float inv_cnt = 1.f / *p.count;
+    const float unif = LS ? p.eps / (float)p.V : 0.f, hot = LS ? 1.f - p.eps : 1.f;      // the smoothed target: hot at the label + unif everywhere below V
     // the chunk's logits of this lane: v[c][rt][r] at column n0(c) + r, row rt * 16 + l15; columns >= V -> -inf
     auto chunk_logits = [&](int j, const f32x4 (&acc)[2][RT], float (&v)[2][RT][4]) {
 #pragma unroll
@@ -429,9 +440,9 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
         }
     };
     // ---- pass 1 ----
-    float mrun[RT], lrun[RT];
+    float mrun[RT], lrun[RT], zrun[RT];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) { mrun[rt] = -INFINITY; lrun[rt] = 0.f; }
+    for (int rt = 0; rt < RT; ++rt) { mrun[rt] = -INFINITY; lrun[rt] = 0.f; zrun[rt] = 0.f; }
 #pragma unroll 1
     for (int j = 0; j < p.nch; ++j) {
         f32x4 acc[2][RT];
@@ -454,6 +465,12 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
                     for (int r = 0; r < 4; ++r) sacc += __expf(v[c][rt][r] - mx);
                 lrun[rt] = sacc; mrun[rt] = mx;
             }
+            if constexpr (LS) {                                               // plain sum over the columns the vocabulary has (-inf marks the others)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) zrun[rt] += v[c][rt][r] == -INFINITY ? 0.f : v[c][rt][r];
+            }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const int n0 = j * 256 + (w + 8 * c) * 16 + 4 * g;
@@ -466,6 +483,7 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
     for (int rt = 0; rt < RT; ++rt) {
         float* q = red + ((rt * 16 + l15) * 32 + w * 4 + g) * 2;
         q[0] = mrun[rt]; q[1] = lrun[rt];
+        if constexpr (LS) zsum[(rt * 16 + l15) * 32 + w * 4 + g] = zrun[rt];
     }
     wg_barrier();
     if (tid < RM) {                                   // one thread per row folds the 32 pairs in a fixed order
@@ -475,7 +493,14 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
         for (int k = 0; k < 32; ++k) se += red[(tid * 32 + k) * 2 + 1] * __expf(red[(tid * 32 + k) * 2] - mx);
         const float lse = mx + __logf(se);
         lse_s[tid] = lse;
-        float contrib = tgt_s[tid] >= 0 ? (lse - tl_s[tid]) * inv_cnt : 0.f;
+        float contrib;
+        if constexpr (LS) {
+            float zs = 0.f;
+            for (int k = 0; k < 32; ++k) zs += zsum[tid * 32 + k];
+            contrib = tgt_s[tid] >= 0 ? (lse - hot * tl_s[tid] - unif * zs) * inv_cnt : 0.f;
+        } else {
+            contrib = tgt_s[tid] >= 0 ? (lse - tl_s[tid]) * inv_cnt : 0.f;
+        }
         contrib = wave_sum(contrib);
         if (tid == 0) atomicAdd(p.loss, contrib);
     }
@@ -518,7 +543,10 @@ __global__ __launch_bounds__(512) void head_ce_kernel(const HeadCE p) {
             for (int rt = 0; rt < RT; ++rt) {
                 float o[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = tg[rt] >= 0 ? (__expf(v[c][rt][r] - ls[rt]) - (n0 + r == tg[rt] ? 1.f : 0.f)) * inv_cnt : 0.f;      // exp(-inf) = 0: padded columns
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (LS) o[r] = tg[rt] >= 0 && n0 + r < p.V ? (__expf(v[c][rt][r] - ls[rt]) - (n0 + r == tg[rt] ? hot : 0.f) - unif) * inv_cnt : 0.f;      // padded columns: the guard
+                    else o[r] = tg[rt] >= 0 ? (__expf(v[c][rt][r] - ls[rt]) - (n0 + r == tg[rt] ? 1.f : 0.f)) * inv_cnt : 0.f;      // exp(-inf) = 0: padded columns
+                }
                 *(uint2*)(stage + (rt * 16 + l15) * LDH + nl) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
             }
         }
@@ -910,15 +938,24 @@ int kzv_head_ce(const KzvHeadCE& a, hipStream_t s) {
     p.x = a.x; p.wp = a.wp; p.bias = a.bias; p.labels = a.labels; p.count = a.count; p.loss = a.loss; p.dlogits = a.dlogits;
     p.M = a.M; p.L = a.L; p.T = a.T; p.V = a.V; p.Vp = a.Vp; p.nch = (a.V + 255) / 256; p.pad = a.pad;
     p.wpt = (a.dlogits && a.dh) ? a.wpt : nullptr; p.dh = a.dh;
-    constexpr int LDS_H = 2 * LDS_A1 + RM * 64 * 4 + RM * 4 * 3;
+    if (!(a.label_smoothing >= 0.f && a.label_smoothing < 1.f)) return kzv_fail(KZV_E_ARG, "head_ce: label_smoothing %g is not in [0, 1)", (double)a.label_smoothing);
+    p.eps = a.label_smoothing;
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)head_ce_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
-        (void)hipFuncSetAttribute((const void*)head_ce_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
+        (void)hipFuncSetAttribute((const void*)head_ce_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HEAD);
+        (void)hipFuncSetAttribute((const void*)head_ce_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HEAD);
+        (void)hipFuncSetAttribute((const void*)head_ce_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HEAD_LS);
+        (void)hipFuncSetAttribute((const void*)head_ce_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HEAD_LS);
         attr_done = true;
     }
-    if (p.wpt) hipLaunchKernelGGL(head_ce_kernel<true>, dim3((a.M + RM - 1) / RM), dim3(512), LDS_H, s, p);
-    else hipLaunchKernelGGL(head_ce_kernel<false>, dim3((a.M + RM - 1) / RM), dim3(512), LDS_H, s, p);
+    const dim3 grid((a.M + RM - 1) / RM), block(512);
+    if (p.eps > 0.f) {                                // eps = 0: the plain instantiations, the kernel as it was before label smoothing
+        if (p.wpt) hipLaunchKernelGGL((head_ce_kernel<true, true>), grid, block, LDS_HEAD_LS, s, p);
+        else hipLaunchKernelGGL((head_ce_kernel<false, true>), grid, block, LDS_HEAD_LS, s, p);
+    } else {
+        if (p.wpt) hipLaunchKernelGGL((head_ce_kernel<true, false>), grid, block, LDS_HEAD, s, p);
+        else hipLaunchKernelGGL((head_ce_kernel<false, false>), grid, block, LDS_HEAD, s, p);
+    }
     return kzv_check_launch("head_ce");
 }
 

@@ -237,10 +237,16 @@ __global__ __launch_bounds__(256) void embed_scatter_bwd_kernel(const float* __r
 // ------------------------------------------------------------------------------------------ cross entropy
 // one workgroup per token row; target = labels[b][t+1]; rows whose target is pad contribute nothing and
 // get a zero dlogits row.  dlogits = (softmax - onehot) / count, bf16, pad columns [V, ldl) zeroed.
+// LS (compile time; label smoothing eps in (0, 1), F.cross_entropy(label_smoothing = eps)): the target distribution is (1 - eps) onehot +
+// eps / V over the V real columns, so loss_row = lse - (1 - eps) z[y] - (eps / V) sum_{v < V} z[v] and dlogits = (softmax - (1 - eps) onehot
+// - eps / V) / count in columns < V; columns [V, ldl) stay zero by an explicit guard (exp(-inf) = 0 no longer covers them).  One more block
+// reduction (the plain logit sum).  LS = false is the kernel as it was: eps is not read.
+__device__ __forceinline__ float finite_or_zero(float x) { return x == -INFINITY ? 0.f : x; }
+template <bool LS>
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ labels,
                                                  int L, int T, int V, int pad, const float* __restrict__ count,
-                                                 float* loss, bf16_t* __restrict__ dlogits) {
-    __shared__ float red[8];
+                                                 float* loss, bf16_t* __restrict__ dlogits, float eps) {
+    __shared__ float red[LS ? 12 : 8];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = row / T, t = row - b * T;
     const int64_t tgt = labels[(int64_t)b * L + t + 1];
@@ -268,10 +274,18 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
         }
         mx = fmaxf(fmaxf(mx, fmaxf(v[j].x, v[j].y)), fmaxf(v[j].z, v[j].w));
     }
+    float sz = 0.f;                                         // LS: the plain sum of the row's V logits, taken before the registers turn into exponentials
+    if constexpr (LS) {
+#pragma unroll
+        for (int j = 0; j < RV; ++j) sz += (finite_or_zero(v[j].x) + finite_or_zero(v[j].y)) + (finite_or_zero(v[j].z) + finite_or_zero(v[j].w));
+        sz = wave_sum(sz);
+        if (lane == 0) red[8 + w] = sz;
+    }
     mx = wave_max(mx);
     if (lane == 0) red[w] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if constexpr (LS) sz = (red[8] + red[9]) + (red[10] + red[11]);
     float se = 0.f;
 #pragma unroll
     for (int j = 0; j < RV; ++j) {
@@ -284,7 +298,9 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
     se = red[4] + red[5] + red[6] + red[7];
     const float lse = mx + __logf(se);
     const float inv_cnt = 1.f / *count;
-    if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
+    const float unif = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
+    if constexpr (LS) { if (tid == 0) atomicAdd(loss, (lse - hot * lr[tgt] - unif * sz) * inv_cnt); }
+    else if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
     if (dr) {
         const float sc = inv_cnt / se;                     // softmax = exp(x - mx) / se
 #pragma unroll
@@ -293,7 +309,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
             if (i < n4) {
                 float o[4] = {v[j].x * sc, v[j].y * sc, v[j].z * sc, v[j].w * sc};
                 const int64_t d = tgt - 4 * (int64_t)i;
-                if (d >= 0 && d < 4) o[d] -= inv_cnt;
+                if constexpr (LS) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] = 4 * i + r < V ? o[r] - (d == r ? hot : 0.f) * inv_cnt - unif * inv_cnt : 0.f;
+                } else {
+                    if (d >= 0 && d < 4) o[d] -= inv_cnt;
+                }
                 ((uint2*)dr)[i] = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
             }
         }
@@ -303,10 +324,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
 // the same for rows wider than the registers of ce_kernel hold (> 5120 columns): three passes over the (L2-resident) row
 // one workgroup per token row; target = labels[b][t+1]; rows whose target is pad contribute nothing and
 // get a zero dlogits row.  dlogits = (softmax - onehot) / count, bf16, pad columns [V, ldl) zeroed.
+// LS: ce_kernel's label smoothing, the logit sum riding in the first pass.
+template <bool LS>
 __global__ __launch_bounds__(256) void ce_generic_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ labels,
                                                  int L, int T, int V, int pad, const float* __restrict__ count,
-                                                 float* loss, bf16_t* __restrict__ dlogits) {
-    __shared__ float red[8];
+                                                 float* loss, bf16_t* __restrict__ dlogits, float eps) {
+    __shared__ float red[LS ? 12 : 8];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = row / T, t = row - b * T;
     const int64_t tgt = labels[(int64_t)b * L + t + 1];
@@ -317,12 +340,19 @@ __global__ __launch_bounds__(256) void ce_generic_kernel(const float* __restrict
         if (dr) for (int i = tid; i < n4; i += 256) ((uint2*)dr)[i] = make_uint2(0, 0);
         return;
     }
-    float mx = -INFINITY;
-    for (int i = tid; i < V; i += 256) mx = fmaxf(mx, lr[i]);
+    float mx = -INFINITY, sz = 0.f;
+    if constexpr (LS) {
+        for (int i = tid; i < V; i += 256) { const float z = lr[i]; mx = fmaxf(mx, z); sz += z; }
+        sz = wave_sum(sz);
+        if (lane == 0) red[8 + w] = sz;
+    } else {
+        for (int i = tid; i < V; i += 256) mx = fmaxf(mx, lr[i]);
+    }
     mx = wave_max(mx);
     if (lane == 0) red[w] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if constexpr (LS) sz = (red[8] + red[9]) + (red[10] + red[11]);
     float se = 0.f;
     for (int i = tid; i < V; i += 256) se += __expf(lr[i] - mx);
     se = wave_sum(se);
@@ -331,14 +361,17 @@ __global__ __launch_bounds__(256) void ce_generic_kernel(const float* __restrict
     se = red[4] + red[5] + red[6] + red[7];
     const float lse = mx + __logf(se);
     const float inv_cnt = 1.f / *count;
-    if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
+    const float unif = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
+    if constexpr (LS) { if (tid == 0) atomicAdd(loss, (lse - hot * lr[tgt] - unif * sz) * inv_cnt); }
+    else if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
     if (dr) {
         for (int i = tid; i < n4; i += 256) {
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int col = 4 * i + r;
-                v[r] = col < V ? (__expf(lr[col] - lse) - (col == tgt ? 1.f : 0.f)) * inv_cnt : 0.f;
+                if constexpr (LS) v[r] = col < V ? (__expf(lr[col] - lse) - (col == tgt ? hot : 0.f) - unif) * inv_cnt : 0.f;
+                else v[r] = col < V ? (__expf(lr[col] - lse) - (col == tgt ? 1.f : 0.f)) * inv_cnt : 0.f;
             }
             ((uint2*)dr)[i] = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
         }
@@ -545,10 +578,18 @@ int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const
 }
 
 int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                   const float* count, float* loss, bf16_t* dlogits, hipStream_t s) {
+                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s) {
     if (ldl % 4) return kzv_fail(KZV_E_ARG, "ce: ldl %% 4");
-    if (ldl <= 5120) hipLaunchKernelGGL(ce_kernel, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits);
-    else hipLaunchKernelGGL(ce_generic_kernel, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits);
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return kzv_fail(KZV_E_ARG, "ce: label_smoothing %g is not in [0, 1)", (double)label_smoothing);
+    const float eps = label_smoothing;
+    // eps = 0 launches the plain kernels (the LS = false instantiations: the kernels as they were before label smoothing)
+    if (ldl <= 5120) {
+        if (eps > 0.f) hipLaunchKernelGGL(ce_kernel<true>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, eps);
+        else hipLaunchKernelGGL(ce_kernel<false>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, 0.f);
+    } else {
+        if (eps > 0.f) hipLaunchKernelGGL(ce_generic_kernel<true>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, eps);
+        else hipLaunchKernelGGL(ce_generic_kernel<false>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, 0.f);
+    }
     return kzv_check_launch("ce_fwd_bwd");
 }
 
@@ -642,7 +683,12 @@ extern "C" int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, i
 
 extern "C" int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
                               const float* count, float* loss, void* dlogits_bf16, void* stream) {
-    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, (hipStream_t)stream);
+    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int kzv_ce_fwd_bwd_ls(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
+                                 const float* count, float* loss, void* dlogits_bf16, float label_smoothing, void* stream) {
+    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, label_smoothing, (hipStream_t)stream);
 }
 
 extern "C" int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream) {

@@ -46,7 +46,7 @@ int kzv_embed_gather(const int64_t* labels, int L, const int* posids, const floa
 int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int* posids, float* dword, float* dtype0,
                           float* dpostab, int B, int T, int Hd, int pad, hipStream_t s);
 int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                   const float* count, float* loss, bf16_t* dlogits, hipStream_t s);
+                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s);
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, hipStream_t s);
 
 struct KzvCastDesc {         // one 2-D fp32 weight -> bf16 copy (+ optional transposed copy)
@@ -142,7 +142,9 @@ struct KzvPackJob { const bf16_t* src; bf16_t* dst; int N, K; int n_valid = 0; i
 // number of scored rows (device), loss accumulated (+=), dlogits bf16 [M, Vp] or null
 struct KzvHeadCE { const bf16_t* x; const bf16_t* wp; const float* bias; const int64_t* labels; const float* count; float* loss; bf16_t* dlogits; int M, L, T, V, Vp, pad;
                    // optional (with dlogits): dh[M, 256] = dlogits . W, the head's input gradient, from wpt = W^T [256, ceil(V / 256) * 256] in fragment order
-                   const bf16_t* wpt = nullptr; bf16_t* dh = nullptr; };
+                   const bf16_t* wpt = nullptr; bf16_t* dh = nullptr;
+                   // label smoothing eps in [0, 1) (kzv_ce_fwd_bwd's); 0 launches the plain instantiations
+                   float label_smoothing = 0.f; };
 int kzv_head_ce(const KzvHeadCE& a, hipStream_t s);
 #define KZV_PACK_MAX_JOBS (12 * KZV_DECODE_FUSED_MAX_LAYERS + 4)
 // one input-gradient GEMM of the decoder on the row-panel scheme (decoder_chain.hip): out[M, N] = a[M, K] . (packed W^T)  [+ resid | * aux]

@@ -114,6 +114,7 @@ struct kzv_model_plain {
     int dec_weights = KZV_DECODE_WEIGHTS_BF16;
     bool dec_pack8_ok = false;
     bool dhln_fused = false;     // the last training forward's head_ce launch already wrote dhln (the LM head's input gradient)
+    float label_smoothing = 0.f; // kzv_set_label_smoothing: the loss of TRAINING forwards; evaluation forwards keep the plain NLL
     int* d_t = nullptr;          // graph-replayed decode step (kzv_decode_step_graph): device-side step index
     // slot-refill decoding (kzv_stream_*): the images kzv_model::spool holds, the geometry kzv_model::sstate was laid out for, the slots'
     // state and logits inside it, the wave in progress

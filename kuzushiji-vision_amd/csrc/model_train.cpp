@@ -29,6 +29,14 @@ extern "C" int kzv_set_head_ce(int on) {
     g_head_ce = on;
     return KZV_OK;
 }
+// label smoothing of the training loss, per handle (F.cross_entropy(label_smoothing = eps)); evaluation forwards never apply it
+extern "C" int kzv_set_label_smoothing(kzv_model* m, float eps) {
+    if (!m) return kzv_fail(KZV_E_ARG, "set_label_smoothing: null model");
+    if (!(eps >= 0.f && eps < 1.f)) return kzv_fail(KZV_E_ARG, "set_label_smoothing: %g is not in [0, 1)", (double)eps);
+    m->label_smoothing = eps;
+    return KZV_OK;
+}
+extern "C" float kzv_get_label_smoothing(const kzv_model* m) { return m ? m->label_smoothing : 0.f; }
 
 namespace {
 
@@ -277,17 +285,19 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
     KZV_TRY(ln_fwd(m, m->hd_gelu, m->hln_w, m->hln_b, m->hd_ln, nullptr, m->hd_st, Md, Hd, s));
     // no logits asked for (the training / validation step): head GEMM + log-softmax + NLL + dlogits in ONE launch, the [B*T, Vp] fp32
     // logits never written (decoder_chain.hip head_ce_kernel).  Otherwise the GEMM materialises them and ce_kernel follows.
+    const float ls_eps = m->train ? m->label_smoothing : 0.f;          // smoothing is a training criterion: validation logs the plain NLL
     if (fused_head) {
         KzvHeadCE hc{m->hd_ln, m->dec_pack.as<bf16_t>() + pk.head(), P + m->word.b, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
         static int fuse_dh = -1;     // the head's input gradient inside the same launch (KZV_HEAD_DGRAD=0: the separate GEMM)
         if (fuse_dh < 0) fuse_dh = kzv_env_int("KZV_HEAD_DGRAD", 1);
         m->dhln_fused = m->train && fuse_dh && m->word.h.ldt % 8 == 0;
         if (m->dhln_fused) { hc.wpt = m->dec_pack.as<bf16_t>() + pk.head_t(); hc.dh = m->dhln; }
+        hc.label_smoothing = ls_eps;
         KZV_TRY(kzv_head_ce(hc, s));
     } else {
         m->dhln_fused = false;
         KZV_TRY(lin_fwd(m, m->word, m->hd_ln, Hd, Md, m->logits, m->Vp, KZV_EPI_F32, s, {.n = m->Vp}));
-        KZV_TRY(kzv_ce_fwd_bwd(m->logits, m->Vp, labels, m->L, B, T, m->V, c.pad_id, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, s));
+        KZV_TRY(kzv_ce_fwd_bwd(m->logits, m->Vp, labels, m->L, B, T, m->V, c.pad_id, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, ls_eps, s));
     }
     if (d_loss && hipMemcpyAsync(d_loss, m->loss_acc, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return kzv_fail(KZV_E_HIP, "forward: loss copy");

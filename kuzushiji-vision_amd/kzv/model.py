@@ -43,11 +43,12 @@ class TrOCRModel:
     def __init__(self, encoder_config: dict[str, Any], decoder_path: str, learning_rate: float = 1e-4,
                  beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, weight_decay: float = 0,
                  *, device: str = "cuda", init_seed: int = 42, load_tokenizer: bool = True, width_buckets=None,
-                 fp8: bool = False, long_sequences: bool = False, decode_weights: str = "bf16"):
+                 fp8: bool = False, long_sequences: bool = False, decode_weights: str = "bf16", label_smoothing: float = 0.0):
         import torch
+        self._check_label_smoothing(label_smoothing)
         self.hparams = types.SimpleNamespace(encoder_config=encoder_config, decoder_path=decoder_path,
                                              learning_rate=learning_rate, beta1=beta1, beta2=beta2,
-                                             epsilon=epsilon, weight_decay=weight_decay)
+                                             epsilon=epsilon, weight_decay=weight_decay, label_smoothing=float(label_smoothing))
         dec_cfg = load_decoder_config(decoder_path)          # FileNotFoundError like scripts/train_trocr.py:88-89
         self.cfg = ModelConfig.from_reference(encoder_config, dec_cfg)
         # long_sequences (include/kzv.h: KZV_MODEL_LONG_SEQ): encoders with head_dim 64 or 96 take up to 4,097 tokens, attention
@@ -112,6 +113,9 @@ class TrOCRModel:
         # generation from e4m3 decoder weights (an extension; include/kzv.h: kzv_set_decode_weights, kzv/quant.py): opt-in, and only
         # where the one-launch step runs -- decode_weights_impl says what a generate actually read
         self.set_decode_weights(decode_weights)
+        # label smoothing of the TRAINING loss (an extension; include/kzv.h: kzv_set_label_smoothing): F.cross_entropy(label_smoothing=eps)
+        # inside the loss kernels; evaluation forwards (val_loss, test) keep the plain loss.  0 = the reference's criterion.
+        self.label_smoothing = label_smoothing
         self._offsets, total = P.param_offsets(c)
         if lib.kzv_param_total(h) != total:
             raise L.KzvError("parameter table mismatch between kzv/params.py and libkzv")
@@ -250,6 +254,24 @@ class TrOCRModel:
         if rc < 0:
             L.check(rc, "kzv_decode_weights_impl")
         return self._DECODE_WEIGHTS[rc]
+
+    @staticmethod
+    def _check_label_smoothing(eps) -> None:
+        if not 0.0 <= float(eps) < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), not {eps!r}")
+
+    @property
+    def label_smoothing(self) -> float:
+        """eps of the training loss, F.cross_entropy(..., label_smoothing=eps).  Training-mode forwards only: eval-mode forwards return
+        the plain loss whatever it is.  Setting it (kzv_set_label_smoothing) takes effect on the next forward and is recorded in hparams,
+        which is what this returns: the value as given, of which the handle holds the fp32 rounding (kzv_get_label_smoothing)."""
+        return self.hparams.label_smoothing
+
+    @label_smoothing.setter
+    def label_smoothing(self, eps: float) -> None:
+        self._check_label_smoothing(eps)
+        L.check(L.load().kzv_set_label_smoothing(self._h, float(eps)), "kzv_set_label_smoothing")
+        self.hparams.label_smoothing = float(eps)
 
     def train(self, mode: bool = True):
         self.training = mode

@@ -83,6 +83,11 @@ def parse_args(argv=None):
                         "own numbers (RandomAffine 7 deg / 7 %% / 0.93-1.07 / shear 5, brightness-contrast, noise, blur, stroke thinning and "
                         "thickening); validation and test batches are never augmented; off = the crops as they lie on disk")
     p.add_argument("--augment_seed", type=int, default=None, help="seed of the augmentation draws (default: --seed)")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing of the TrOCR training loss (an extension; nn.CrossEntropyLoss(label_smoothing=...), 0 <= value < 1; "
+                        "the published TrOCR recipe uses 0.1): train_loss in the logs is then the SMOOTHED loss, while val_loss and the test "
+                        "losses stay the plain cross-entropy, so checkpoints rank and runs compare as without it; the value is written into "
+                        "the checkpoints' hyper_parameters; 0 = off, the reference's criterion")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
     p.add_argument("--ema_decay", type=float, default=0.0, help="> 0 attaches kzv.ema.EMACallback (reference: decay 0.9999)")
     # the ResNet34 / BiLSTM / CTC model of ocr_lightning/model.py behind ocr_lightning/train.py's own flags (:161-189)
@@ -97,7 +102,13 @@ def parse_args(argv=None):
     p.add_argument("--resume", type=str, default=None,
                    help="--model ocr: continue from a checkpoint this CLI (or Lightning, for the reference) wrote -- weights, Adam moments and "
                         "step count, epoch (pl.Trainer.fit(ckpt_path=...))")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not 0.0 <= args.label_smoothing < 1.0:
+        p.error(f"--label_smoothing must be in [0, 1), not {args.label_smoothing}")
+    if args.label_smoothing and args.model == "ocr":
+        p.error("--label_smoothing applies to the TrOCR cross-entropy only: --model ocr trains with CTC and SmoothL1 losses, which have no "
+                "softmax cross-entropy to smooth")
+    return args
 
 
 def main_ocr(args):
@@ -249,7 +260,8 @@ def main(argv=None):
                       "hidden_dropout_prob": 0.1, "attention_probs_dropout_prob": 0.1}   # :111-121
     model = TrOCRModel(encoder_config, decoder_path, learning_rate=args.learning_rate, beta1=args.beta1, beta2=args.beta2,
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
-                       fp8=args.precision == "fp8-mixed", long_sequences=True, decode_weights=args.decode_weights)
+                       fp8=args.precision == "fp8-mixed", long_sequences=True, decode_weights=args.decode_weights,
+                       label_smoothing=args.label_smoothing)
     model._step_seed = 1_000_003 * rank
     model.decode_controls = {k: v for k, v, off in (("no_repeat_ngram_size", args.no_repeat_ngram_size, 0),
                                                     ("repetition_penalty", args.repetition_penalty, 1.0),
@@ -286,6 +298,8 @@ def main(argv=None):
         aug = (DeviceAugment(f"cuda:{local}"), preset(args.augment), args.seed if args.augment_seed is None else args.augment_seed)
     if rank == 0:
         print(f"augmentation: {args.augment}" + (f" (seed {aug[2]}, training batches only)" if aug else ""))
+        if args.label_smoothing:
+            print(f"label smoothing: {args.label_smoothing} (train_loss is the smoothed loss; val_loss stays the plain cross-entropy)")
     train_loader = make_loader(train_ds, args.batch_size, True, args.seed, rank, world, num_workers=nw, preprocessor=pre, augment=aug)
     val_loader = make_loader(val_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)
     test_loader = make_loader(test_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)   # scripts/train_trocr.py:93

@@ -218,6 +218,9 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     ck = torch.load(path, map_location="cpu", weights_only=False)
     sd, osd = read_checkpoint(ck, model.cfg)
     model.load_state_dict(sd, strict=True)
+    # the training criterion travels with the weights; a checkpoint without the key (every reference checkpoint) means the plain loss
+    hp = ck.get("hyper_parameters") or {}
+    model.label_smoothing = float(hp.get("label_smoothing", 0.0) if isinstance(hp, dict) else getattr(hp, "label_smoothing", 0.0))
     if opt is not None and osd is not None:
         opt.load_state_dict(osd)
     for cb in callbacks:
