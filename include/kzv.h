@@ -281,7 +281,7 @@ int kzv_quant_pack_e4m3(const void* w_bf16, int N, int K, void* q_out, float* sc
 int kzv_set_dec_chain(int on);
 /* Training / validation forward without returned logits: lm_head.decoder (HF modeling_roberta.py:888-893, tied weight) + log-softmax +
  * NLL (src/models/trocr_model.py:256,292) + the bf16 gradient of the logits as ONE launch; the [B*T, vocab] fp32 logits are never written
- * (csrc/decoder_chain.hip head_ce_kernel: 64 rows per workgroup against the whole vocabulary twice, online softmax statistics; decoder
+ * (csrc/cross_entropy.hip head_ce_kernel: 64 rows per workgroup against the whole vocabulary twice, online softmax statistics; decoder
  * hidden 256).  1 (default; KZV_HEAD_CE), 0: head GEMM + ce_kernel, -1: the environment's default.  kzv_forward_loss with d_logits != NULL
  * always takes the GEMM (it returns them).  Same arithmetic up to fp32 summation order. */
 int kzv_set_head_ce(int on);
@@ -625,7 +625,7 @@ typedef struct kzv_ln_bwd_args {
 } kzv_ln_bwd_args;
 int kzv_ln_bwd_ex(const kzv_ln_bwd_args* a, void* stream);
 
-/* The HBM-bound glue kernels of the training step (csrc/elementwise.hip), as the model handle launches them.
+/* The HBM-bound glue kernels of the training step (csrc/elementwise.hip; the cross-entropy entries: csrc/cross_entropy.hip), as the model handle launches them.
  * kzv_im2row: the data movement of nn.Conv2d(kernel = stride = patch) (trocr_model.py:77,89-90): px fp32 [B, C, H, W] -> bf16
  *   [B * (H / ph) * (W / pw), C * ph * pw], column (c * ph + i) * pw + j; pw % 8 == 0. */
 int kzv_im2row(const float* px, void* out_bf16, int B, int C, int H, int W, int ph, int pw, void* stream);

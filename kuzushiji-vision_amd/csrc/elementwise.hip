@@ -4,7 +4,7 @@
 //   cast_drop_colsum  -- backward of "dropout(linear(x))": masked bf16 copy of the upstream grad + bias grad
 //   colsum_bf16       -- bias gradient of a bf16 gradient matrix
 //   dec_prepare / embed_gather / embed_scatter_bwd -- RobertaEmbeddings (HF modeling_roberta.py:75-155)
-//   ce_fwd_bwd        -- nn.CrossEntropyLoss(ignore_index=pad) forward + dlogits (trocr_model.py:256,292)
+//   copy_logits       -- the padded logits buffer -> the caller's dense [rows, V] (training and generation; the loss is cross_entropy.hip)
 //   cast_weights      -- fp32 master -> bf16 W and W^T compute copies (autocast's weight cast)
 #include "kzv_common.h"
 #include "../../include/kzv.h"
@@ -55,12 +55,7 @@ __global__ void embed_assemble_kernel(const float* __restrict__ pe, const float*
     const float4 a = s == 0 ? ((const float4*)cls)[c] : ((const float4*)(pe + ((int64_t)b * np + s - 1) * He))[c];
     const float4 p = ((const float4*)(pos + (int64_t)pos_row(s, gw, gw_max) * He))[c];
     float o0 = a.x + p.x, o1 = a.y + p.y, o2 = a.z + p.z, o3 = a.w + p.w;
-    if (thr16) {
-        const unsigned e = (unsigned)row * (unsigned)He + 4u * c;
-        const unsigned b0 = drop_bits(key, e >> 1), b1 = drop_bits(key, (e >> 1) + 1);
-        o0 *= drop_keep(b0, 0, thr16, inv_keep); o1 *= drop_keep(b0, 1, thr16, inv_keep);
-        o2 *= drop_keep(b1, 0, thr16, inv_keep); o3 *= drop_keep(b1, 1, thr16, inv_keep);
-    }
+    if (thr16) KZV_DROP4(o0, o1, o2, o3, key, (unsigned)row * (unsigned)He + 4u * c, thr16, inv_keep);
     ((float4*)(x0 + row * He))[c] = make_float4(o0, o1, o2, o3);
 }
 
@@ -84,12 +79,7 @@ __global__ void embed_assemble_bwd_part_kernel(const float* __restrict__ dx0, bf
     for (int b = b0; b < b1; ++b) {
         const int64_t row = (int64_t)b * S + s;
         float4 d = ((const float4*)(dx0 + row * He))[c];
-        if (thr16) {
-            const unsigned e = (unsigned)row * (unsigned)He + 4u * c;
-            const unsigned q0 = drop_bits(key, e >> 1), q1 = drop_bits(key, (e >> 1) + 1);
-            d.x *= drop_keep(q0, 0, thr16, inv_keep); d.y *= drop_keep(q0, 1, thr16, inv_keep);
-            d.z *= drop_keep(q1, 0, thr16, inv_keep); d.w *= drop_keep(q1, 1, thr16, inv_keep);
-        }
+        if (thr16) KZV_DROP4(d.x, d.y, d.z, d.w, key, (unsigned)row * (unsigned)He + 4u * c, thr16, inv_keep);
         a0 += d.x; a1 += d.y; a2 += d.z; a3 += d.w;
         if (s > 0) ((uint2*)(dpatch + ((int64_t)b * np + s - 1) * He))[c] = make_uint2(pack_bf2(d.x, d.y), pack_bf2(d.z, d.w));
     }
@@ -149,12 +139,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ gi
                 d = make_float4(bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16));
             }
             if (IN_F32) {
-                if (thr16) {
-                    const unsigned e = (unsigned)r * (unsigned)N + (unsigned)col;
-                    const unsigned b0 = drop_bits(key, e >> 1), b1 = drop_bits(key, (e >> 1) + 1);
-                    d.x *= drop_keep(b0, 0, thr16, inv_keep); d.y *= drop_keep(b0, 1, thr16, inv_keep);
-                    d.z *= drop_keep(b1, 0, thr16, inv_keep); d.w *= drop_keep(b1, 1, thr16, inv_keep);
-                }
+                if (thr16) KZV_DROP4(d.x, d.y, d.z, d.w, key, (unsigned)r * (unsigned)N + (unsigned)col, thr16, inv_keep);
                 if (gelu_pre) {   // backward of GELU: multiply by the derivative the forward epilogue saved
                     const uint2 u = *(const uint2*)(gelu_pre + (int64_t)r * N + col);
                     d.x *= bf2f(u.x & 0xffff); d.y *= bf2f(u.x >> 16);
@@ -231,150 +216,6 @@ __global__ __launch_bounds__(256) void embed_scatter_bwd_kernel(const float* __r
             if (pid != pad) atomicAdd(dpostab + (int64_t)pid * Hd + c, v);
         }
         atomicAdd(dtype0 + c, acc);
-    }
-}
-
-// ------------------------------------------------------------------------------------------ cross entropy
-// one workgroup per token row; target = labels[b][t+1]; rows whose target is pad contribute nothing and
-// get a zero dlogits row.  dlogits = (softmax - onehot) / count, bf16, pad columns [V, ldl) zeroed.
-// LS (compile time; label smoothing eps in (0, 1), F.cross_entropy(label_smoothing = eps)): the target distribution is (1 - eps) onehot +
-// eps / V over the V real columns, so loss_row = lse - (1 - eps) z[y] - (eps / V) sum_{v < V} z[v] and dlogits = (softmax - (1 - eps) onehot
-// - eps / V) / count in columns < V; columns [V, ldl) stay zero by an explicit guard (exp(-inf) = 0 no longer covers them).  One more block
-// reduction (the plain logit sum).  LS = false is the kernel as it was: eps is not read.
-__device__ __forceinline__ float finite_or_zero(float x) { return x == -INFINITY ? 0.f : x; }
-template <bool LS>
-__global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ labels,
-                                                 int L, int T, int V, int pad, const float* __restrict__ count,
-                                                 float* loss, bf16_t* __restrict__ dlogits, float eps) {
-    __shared__ float red[LS ? 12 : 8];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int b = row / T, t = row - b * T;
-    const int64_t tgt = labels[(int64_t)b * L + t + 1];
-    const float* lr = logits + (int64_t)row * ldl;
-    bf16_t* dr = dlogits ? dlogits + (int64_t)row * ldl : nullptr;
-    const int n4 = (int)(ldl / 4);
-    if (tgt == pad) {
-        if (dr) for (int i = tid; i < n4; i += 256) ((uint2*)dr)[i] = make_uint2(0, 0);
-        return;
-    }
-    // the row lives in registers (ldl / 4 <= 256 * RV float4 pieces): read once, 16 bytes per lane
-    constexpr int RV = 5;                                  // 5 * 256 * 4 = 5120 columns
-    float4 v[RV];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < RV; ++j) {
-        const int i = tid + j * 256;
-        v[j] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        if (i < n4) {
-            v[j] = ((const float4*)lr)[i];
-            if (4 * i + 1 > V) v[j].x = -INFINITY;      // pad columns [V, ldl) hold zeros, not logits
-            if (4 * i + 2 > V) v[j].y = -INFINITY;
-            if (4 * i + 3 > V) v[j].z = -INFINITY;
-            if (4 * i + 4 > V) v[j].w = -INFINITY;
-        }
-        mx = fmaxf(fmaxf(mx, fmaxf(v[j].x, v[j].y)), fmaxf(v[j].z, v[j].w));
-    }
-    float sz = 0.f;                                         // LS: the plain sum of the row's V logits, taken before the registers turn into exponentials
-    if constexpr (LS) {
-#pragma unroll
-        for (int j = 0; j < RV; ++j) sz += (finite_or_zero(v[j].x) + finite_or_zero(v[j].y)) + (finite_or_zero(v[j].z) + finite_or_zero(v[j].w));
-        sz = wave_sum(sz);
-        if (lane == 0) red[8 + w] = sz;
-    }
-    mx = wave_max(mx);
-    if (lane == 0) red[w] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if constexpr (LS) sz = (red[8] + red[9]) + (red[10] + red[11]);
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < RV; ++j) {
-        v[j].x = __expf(v[j].x - mx); v[j].y = __expf(v[j].y - mx); v[j].z = __expf(v[j].z - mx); v[j].w = __expf(v[j].w - mx);
-        se += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    }
-    se = wave_sum(se);
-    if (lane == 0) red[4 + w] = se;
-    __syncthreads();
-    se = red[4] + red[5] + red[6] + red[7];
-    const float lse = mx + __logf(se);
-    const float inv_cnt = 1.f / *count;
-    const float unif = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
-    if constexpr (LS) { if (tid == 0) atomicAdd(loss, (lse - hot * lr[tgt] - unif * sz) * inv_cnt); }
-    else if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
-    if (dr) {
-        const float sc = inv_cnt / se;                     // softmax = exp(x - mx) / se
-#pragma unroll
-        for (int j = 0; j < RV; ++j) {
-            const int i = tid + j * 256;
-            if (i < n4) {
-                float o[4] = {v[j].x * sc, v[j].y * sc, v[j].z * sc, v[j].w * sc};
-                const int64_t d = tgt - 4 * (int64_t)i;
-                if constexpr (LS) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = 4 * i + r < V ? o[r] - (d == r ? hot : 0.f) * inv_cnt - unif * inv_cnt : 0.f;
-                } else {
-                    if (d >= 0 && d < 4) o[d] -= inv_cnt;
-                }
-                ((uint2*)dr)[i] = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
-            }
-        }
-    }
-}
-
-// the same for rows wider than the registers of ce_kernel hold (> 5120 columns): three passes over the (L2-resident) row
-// one workgroup per token row; target = labels[b][t+1]; rows whose target is pad contribute nothing and
-// get a zero dlogits row.  dlogits = (softmax - onehot) / count, bf16, pad columns [V, ldl) zeroed.
-// LS: ce_kernel's label smoothing, the logit sum riding in the first pass.
-template <bool LS>
-__global__ __launch_bounds__(256) void ce_generic_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ labels,
-                                                 int L, int T, int V, int pad, const float* __restrict__ count,
-                                                 float* loss, bf16_t* __restrict__ dlogits, float eps) {
-    __shared__ float red[LS ? 12 : 8];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int b = row / T, t = row - b * T;
-    const int64_t tgt = labels[(int64_t)b * L + t + 1];
-    const float* lr = logits + (int64_t)row * ldl;
-    bf16_t* dr = dlogits ? dlogits + (int64_t)row * ldl : nullptr;
-    const int n4 = (int)(ldl / 4);
-    if (tgt == pad) {
-        if (dr) for (int i = tid; i < n4; i += 256) ((uint2*)dr)[i] = make_uint2(0, 0);
-        return;
-    }
-    float mx = -INFINITY, sz = 0.f;
-    if constexpr (LS) {
-        for (int i = tid; i < V; i += 256) { const float z = lr[i]; mx = fmaxf(mx, z); sz += z; }
-        sz = wave_sum(sz);
-        if (lane == 0) red[8 + w] = sz;
-    } else {
-        for (int i = tid; i < V; i += 256) mx = fmaxf(mx, lr[i]);
-    }
-    mx = wave_max(mx);
-    if (lane == 0) red[w] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if constexpr (LS) sz = (red[8] + red[9]) + (red[10] + red[11]);
-    float se = 0.f;
-    for (int i = tid; i < V; i += 256) se += __expf(lr[i] - mx);
-    se = wave_sum(se);
-    if (lane == 0) red[4 + w] = se;
-    __syncthreads();
-    se = red[4] + red[5] + red[6] + red[7];
-    const float lse = mx + __logf(se);
-    const float inv_cnt = 1.f / *count;
-    const float unif = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
-    if constexpr (LS) { if (tid == 0) atomicAdd(loss, (lse - hot * lr[tgt] - unif * sz) * inv_cnt); }
-    else if (tid == 0) atomicAdd(loss, (lse - lr[tgt]) * inv_cnt);
-    if (dr) {
-        for (int i = tid; i < n4; i += 256) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = 4 * i + r;
-                if constexpr (LS) v[r] = col < V ? (__expf(lr[col] - lse) - (col == tgt ? hot : 0.f) - unif) * inv_cnt : 0.f;
-                else v[r] = col < V ? (__expf(lr[col] - lse) - (col == tgt ? 1.f : 0.f)) * inv_cnt : 0.f;
-            }
-            ((uint2*)dr)[i] = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
-        }
     }
 }
 
@@ -577,22 +418,6 @@ int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const
     return kzv_check_launch("embed_scatter_bwd");
 }
 
-int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s) {
-    if (ldl % 4) return kzv_fail(KZV_E_ARG, "ce: ldl %% 4");
-    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return kzv_fail(KZV_E_ARG, "ce: label_smoothing %g is not in [0, 1)", (double)label_smoothing);
-    const float eps = label_smoothing;
-    // eps = 0 launches the plain kernels (the LS = false instantiations: the kernels as they were before label smoothing)
-    if (ldl <= 5120) {
-        if (eps > 0.f) hipLaunchKernelGGL(ce_kernel<true>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, eps);
-        else hipLaunchKernelGGL(ce_kernel<false>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, 0.f);
-    } else {
-        if (eps > 0.f) hipLaunchKernelGGL(ce_generic_kernel<true>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, eps);
-        else hipLaunchKernelGGL(ce_generic_kernel<false>, dim3(B * T), dim3(256), 0, s, logits, ldl, labels, L, T, V, pad, count, loss, dlogits, 0.f);
-    }
-    return kzv_check_launch("ce_fwd_bwd");
-}
-
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, hipStream_t s) {
     const int64_t total = (int64_t)rows * V;
     hipLaunchKernelGGL(copy_logits_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, logits, ldl, out, total, V);
@@ -679,16 +504,6 @@ extern "C" int kzv_embed_gather(const int64_t* labels, int L, const int32_t* pos
 extern "C" int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int32_t* posids, float* dword, float* dtype0,
                                      float* dpostab, int B, int T, int Hd, int pad, void* stream) {
     return kzv_embed_scatter_bwd(dsum, labels, L, posids, dword, dtype0, dpostab, B, T, Hd, pad, (hipStream_t)stream);
-}
-
-extern "C" int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                              const float* count, float* loss, void* dlogits_bf16, void* stream) {
-    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, 0.f, (hipStream_t)stream);
-}
-
-extern "C" int kzv_ce_fwd_bwd_ls(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                                 const float* count, float* loss, void* dlogits_bf16, float label_smoothing, void* stream) {
-    return kzv_ce_fwd_bwd(logits, ldl, labels, L, B, T, V, pad, count, loss, (bf16_t*)dlogits_bf16, label_smoothing, (hipStream_t)stream);
 }
 
 extern "C" int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream) {

@@ -1,7 +1,7 @@
-// The weight stream of the row-panel kernels (decode_fused.hip: the generation step, 4 linear waves; decoder_chain.hip: the training
-// chains, 8 waves), stated once: a weight in MFMA FRAGMENT ORDER, read by each wave as one stream through a window of registers.
+// The weight stream of the row-panel kernels (decode_fused.hip: the generation step, 4 linear waves; dec_rows.h: the training
+// chains and their backward, 8 waves), stated once: a weight in MFMA FRAGMENT ORDER, read by each wave as one stream through a window of registers.
 //
-// Wp = the weight in fragment order (pack_frag_multi_kernel, decoder_chain.hip): the 64 lanes' 16-byte pieces of (16-column block nb,
+// Wp = the weight in fragment order (pack_frag_multi_kernel, frag_pack.hip): the 64 lanes' 16-byte pieces of (16-column block nb,
 // 32-deep k-step ks) are 1 KiB of contiguous memory at ((nb * KS + ks) * 64 + lane) * 16 bytes, lane = (row nb * 16 + (lane & 15),
 // columns ks * 32 + 8 (lane >> 4) .. + 7), so a wave-instruction is one contiguous KiB.  (Read from the row-major [N, K] copy, the 64
 // lanes of a fragment are 64 separate 16-byte requests -- 16 rows x 4 pieces -- and the address coalescer, at one request per cycle,

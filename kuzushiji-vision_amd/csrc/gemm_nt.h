@@ -56,14 +56,7 @@ __device__ __forceinline__ void nt_emit(const NtParams& p, int m, int n0, float 
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = y[r];          // the fp8 kernel quantises the activation once more from here
     } else if (EPI == KZV_EPI_RESID) {
-        if (p.drop_thr16) {
-            const unsigned e = (unsigned)m * (unsigned)p.N + (unsigned)n0;
-            const unsigned b0 = drop_bits(p.drop_key, e >> 1), b1 = drop_bits(p.drop_key, (e >> 1) + 1);
-            v[0] *= drop_keep(b0, 0, p.drop_thr16, p.drop_inv_keep);
-            v[1] *= drop_keep(b0, 1, p.drop_thr16, p.drop_inv_keep);
-            v[2] *= drop_keep(b1, 0, p.drop_thr16, p.drop_inv_keep);
-            v[3] *= drop_keep(b1, 1, p.drop_thr16, p.drop_inv_keep);
-        }
+        if (p.drop_thr16) KZV_DROP4(v[0], v[1], v[2], v[3], p.drop_key, (unsigned)m * (unsigned)p.N + (unsigned)n0, p.drop_thr16, p.drop_inv_keep);
 #ifndef KZV_RESID_NT       // the residual stream is read again at once (the LayerNorm behind this GEMM, then the next residual add): a PLAIN store leaves it in
                            // L2 / the Infinity Cache: step 31.02 -> 30.93 ms, family 0.386 -> 0.388 over four same-box alternations (round 4, tools/dev/ab_build.sh)
         *(float4*)((float*)p.C + (int64_t)m * p.ldc + n0) = make_float4(v[0] + r4.x, v[1] + r4.y, v[2] + r4.z, v[3] + r4.w);

@@ -49,7 +49,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // ---- LayerNorm backward: the per-lane part of one row (4 columns) -----------------------------------------------------------------
 // Explicit roundings (no contraction left to the compiler's choice per context): ln_bwd_fast_kernel (layernorm.hip) and the decoder's
-// backward segments (decoder_chain.hip) carry the same row arithmetic and must produce the same bits.
+// backward segments (decoder_chain_bwd.hip) carry the same row arithmetic and must produce the same bits.
 struct LnBwdTerms { float4 xh, gy; float s1, s2; };
 __device__ __forceinline__ LnBwdTerms ln_bwd_terms(const float4 d, const float4 xv, const float4 gm, float mean, float rstd) {
     LnBwdTerms t;
@@ -85,6 +85,18 @@ __device__ __forceinline__ float drop_keep(unsigned bits, int which, unsigned th
     unsigned r = which ? (bits >> 16) : (bits & 0xffffu);
     return r >= thr16 ? inv_keep : 0.f;
 }
+// The hidden-state mask of the four adjacent elements e .. e + 3 (e even: two pairs, two hashes) applied to the lvalues a, b, c, d.
+// EVERY forward site and the backward site that regenerates its mask state it through here, so the two cannot drift apart.
+// A macro, not a function: as a __forceinline__ function hipcc simplifies the body BEFORE it is inlined (the second hash index becomes
+// "the first + the golden ratio"), the callers' loop-invariant key + ratio is no longer hoisted, and over forty code objects move
+// (layernorm's backward kernels, two GEMM epilogues, the decoder's backward segments): DESIGN 4l.  Expanded in place it is the text the sites had.
+#define KZV_DROP4(a, b, c, d, key, e, thr16, inv_keep)                                                    \
+    do {                                                                                                  \
+        const unsigned e_ = (e);                                                                          \
+        const unsigned b0_ = drop_bits(key, e_ >> 1), b1_ = drop_bits(key, (e_ >> 1) + 1);                \
+        a *= drop_keep(b0_, 0, thr16, inv_keep); b *= drop_keep(b0_, 1, thr16, inv_keep);                 \
+        c *= drop_keep(b1_, 0, thr16, inv_keep); d *= drop_keep(b1_, 1, thr16, inv_keep);                 \
+    } while (0)
 
 // ---- attention-probability dropout: 4 x 4 blocks of one (batch, head)'s [Sq, Sk] matrix ---------------------------
 // The forward kernel holds 4 consecutive KEYS of one query per lane, the backward kernel 4 consecutive QUERIES of one key,

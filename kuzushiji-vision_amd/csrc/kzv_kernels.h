@@ -1,5 +1,5 @@
 // Internal launcher API (C++ linkage) used by the model handle's units (model.cpp, model_train.cpp, model_decode.cpp); the per-op C ABI in include/kzv.h wraps a subset.
-// Where a wrapper carries its launcher's name (kzv_ln_*_ex, the elementwise.hip entries) the two are overloads: the launcher takes a hipStream_t,
+// Where a wrapper carries its launcher's name (kzv_ln_*_ex, the elementwise.hip and cross_entropy.hip entries) the two are overloads: the launcher takes a hipStream_t,
 // the extern "C" wrapper a void* stream (and an args struct or void* buffers), and is defined next to it.  Where the two differ in the stream's
 // type alone (kzv_copy_logits, kzv_dec_prepare, kzv_embed_gather, kzv_embed_scatter_bwd) the wrapper's (hipStream_t) cast is what selects the launcher:
 // without it the wrapper would call itself.  C++ callers pass a hipStream_t, never nullptr (ambiguous between the two).
@@ -25,7 +25,7 @@ int kzv_ln_bwd_ex(const void* dy, int dy_is_f32, const float* x, const float* st
 // folds at once (the per-op C ABI).
 struct KzvLnDeferScope { explicit KzvLnDeferScope(hipStream_t stream); ~KzvLnDeferScope(); hipStream_t s; };
 
-// for kernels that fuse a LayerNorm backward (decoder_chain.hip): see layernorm.hip
+// for kernels that fuse a LayerNorm backward (decoder_chain_bwd.hip): see layernorm.hip
 constexpr int KZV_LN_SLOTS = 32;
 float* kzv_ln_partial_region(float* dgamma, float* dbeta, int H, hipStream_t s, bool* fold_now);
 int kzv_ln_partial_fold(float* partial, float* dgamma, float* dbeta, int H, hipStream_t s);
@@ -46,7 +46,7 @@ int kzv_embed_gather(const int64_t* labels, int L, const int* posids, const floa
 int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int* posids, float* dword, float* dtype0,
                           float* dpostab, int B, int T, int Hd, int pad, hipStream_t s);
 int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s);
+                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s);      // cross_entropy.hip
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, hipStream_t s);
 
 struct KzvCastDesc {         // one 2-D fp32 weight -> bf16 copy (+ optional transposed copy)
@@ -137,7 +137,7 @@ int kzv_dec_chain_supported(int Hd, int Fd);
 int kzv_dec_chain_a(const KzvDecChainA& a, hipStream_t s);
 int kzv_dec_chain_b(const KzvDecChainB& a, hipStream_t s);
 struct KzvPackJob { const bf16_t* src; bf16_t* dst; int N, K; int n_valid = 0; int ld = 0; int k_valid = 0; };      // rows >= n_valid / columns >= k_valid (> 0) pack as zeros; ld: source row stride (0 = K)
-// LM head + cross-entropy in one launch (decoder_chain.hip): x = the head's LayerNorm output [M, 256] bf16, wp = the tied weight in
+// LM head + cross-entropy in one launch (cross_entropy.hip): x = the head's LayerNorm output [M, 256] bf16, wp = the tied weight in
 // fragment order (ceil(V / 256) * 256 rows, zeros beyond V), labels int64 [B, L] (row m = b * T + t scores labels[b][t + 1]), count = the
 // number of scored rows (device), loss accumulated (+=), dlogits bf16 [M, Vp] or null
 struct KzvHeadCE { const bf16_t* x; const bf16_t* wp; const float* bias; const int64_t* labels; const float* count; float* loss; bf16_t* dlogits; int M, L, T, V, Vp, pad;
@@ -147,10 +147,10 @@ struct KzvHeadCE { const bf16_t* x; const bf16_t* wp; const float* bias; const i
                    float label_smoothing = 0.f; };
 int kzv_head_ce(const KzvHeadCE& a, hipStream_t s);
 #define KZV_PACK_MAX_JOBS (12 * KZV_DECODE_FUSED_MAX_LAYERS + 4)
-// one input-gradient GEMM of the decoder on the row-panel scheme (decoder_chain.hip): out[M, N] = a[M, K] . (packed W^T)  [+ resid | * aux]
+// one input-gradient GEMM of the decoder on the row-panel scheme (decoder_chain_bwd.hip): out[M, N] = a[M, K] . (packed W^T)  [+ resid | * aux]
 int kzv_dec_lin(const bf16_t* a, const bf16_t* wp, void* out, const float* resid, const bf16_t* aux, int M, int N, int K, int epi, hipStream_t s);
-int kzv_pack_frag_multi(const KzvPackJob* jobs, int n, hipStream_t s);
-// One row-local segment of a decoder layer's BACKWARD in one launch (decoder_chain.hip, dec_bwd_seg_kernel):
+int kzv_pack_frag_multi(const KzvPackJob* jobs, int n, hipStream_t s);      // frag_pack.hip
+// One row-local segment of a decoder layer's BACKWARD in one launch (decoder_chain_bwd.hip, dec_bwd_seg_kernel):
 //   d = a[M, K1] . (packed W1^T) (+ resid)          the input gradient of the Linear BELOW a LayerNorm (+ the residual gradient)
 //   ds = LayerNorm backward of d (x = the LayerNorm's forward input, st = (mean, rstd), gamma)  -> dsum fp32, dy16 = bf16(dropout mask * ds)
 //   out2 = dy16 . (packed W2^T)  [* aux]            the input gradient of the Linear ABOVE it: bf16 [M, 256] or, with aux, [M, 768] (DGELU)

@@ -70,12 +70,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwd p) {
             const float4 gm = ((const float4*)p.gamma)[i], bt = ((const float4*)p.beta)[i];
             float o0 = (v[c].x - mean) * rstd * gm.x + bt.x, o1 = (v[c].y - mean) * rstd * gm.y + bt.y;
             float o2 = (v[c].z - mean) * rstd * gm.z + bt.z, o3 = (v[c].w - mean) * rstd * gm.w + bt.w;
-            if (p.thr16) {
-                const unsigned e = (unsigned)orow * (unsigned)p.H + 4u * i;
-                const unsigned b0 = drop_bits(p.key, e >> 1), b1 = drop_bits(p.key, (e >> 1) + 1);
-                o0 *= drop_keep(b0, 0, p.thr16, p.inv_keep); o1 *= drop_keep(b0, 1, p.thr16, p.inv_keep);
-                o2 *= drop_keep(b1, 0, p.thr16, p.inv_keep); o3 *= drop_keep(b1, 1, p.thr16, p.inv_keep);
-            }
+            if (p.thr16) KZV_DROP4(o0, o1, o2, o3, p.key, (unsigned)orow * (unsigned)p.H + 4u * i, p.thr16, p.inv_keep);
             if (p.y16) ((uint2*)(p.y16 + (int64_t)orow * p.H))[i] = make_uint2(pack_bf2(o0, o1), pack_bf2(o2, o3));
             if (p.y32) ((float4*)(p.y32 + (int64_t)orow * p.H))[i] = make_float4(o0, o1, o2, o3);
             if (F8) {
@@ -158,12 +153,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
                         const uint2 u = ((const uint2*)((const bf16_t*)p.dy + (int64_t)drow * p.H))[i];
                         d = make_float4(bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16));
                     }
-                    if (p.thr16) {
-                        const unsigned e = (unsigned)drow * (unsigned)p.H + 4u * i;
-                        const unsigned b0 = drop_bits(p.key, e >> 1), b1 = drop_bits(p.key, (e >> 1) + 1);
-                        d.x *= drop_keep(b0, 0, p.thr16, p.inv_keep); d.y *= drop_keep(b0, 1, p.thr16, p.inv_keep);
-                        d.z *= drop_keep(b1, 0, p.thr16, p.inv_keep); d.w *= drop_keep(b1, 1, p.thr16, p.inv_keep);
-                    }
+                    if (p.thr16) KZV_DROP4(d.x, d.y, d.z, d.w, p.key, (unsigned)drow * (unsigned)p.H + 4u * i, p.thr16, p.inv_keep);
                 }
                 const float4 gm = gmr[c];
                 xh[c] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
@@ -184,12 +174,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwd p) {
                 o.x += prev[c].x; o.y += prev[c].y; o.z += prev[c].z; o.w += prev[c].w;
                 dxr[i] = o;
                 if (p.out16) {   // input of the next "dropout(linear)" backward: mask(dx) in bf16 (same indexing as colsum_kernel)
-                    if (p.o_thr16) {
-                        const unsigned e = (unsigned)row * (unsigned)p.H + 4u * i;
-                        const unsigned b0 = drop_bits(p.o_key, e >> 1), b1 = drop_bits(p.o_key, (e >> 1) + 1);
-                        o.x *= drop_keep(b0, 0, p.o_thr16, p.o_inv_keep); o.y *= drop_keep(b0, 1, p.o_thr16, p.o_inv_keep);
-                        o.z *= drop_keep(b1, 0, p.o_thr16, p.o_inv_keep); o.w *= drop_keep(b1, 1, p.o_thr16, p.o_inv_keep);
-                    }
+                    if (p.o_thr16) KZV_DROP4(o.x, o.y, o.z, o.w, p.o_key, (unsigned)row * (unsigned)p.H + 4u * i, p.o_thr16, p.o_inv_keep);
                     ((uint2*)(p.out16 + (int64_t)row * p.H))[i] = make_uint2(pack_bf2(o.x, o.y), pack_bf2(o.z, o.w));
                 }
             }
@@ -262,12 +247,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const LnBwd p) {
             if (DYF32) d = b.d32[c];
             else d = make_float4(bf2f(b.d16[c].x & 0xffff), bf2f(b.d16[c].x >> 16), bf2f(b.d16[c].y & 0xffff), bf2f(b.d16[c].y >> 16));
             if (!has_dy) d = make_float4(0, 0, 0, 0);
-            if (p.thr16) {
-                const unsigned e = (unsigned)drow * (unsigned)p.H + 4u * i;
-                const unsigned b0 = drop_bits(p.key, e >> 1), b1 = drop_bits(p.key, (e >> 1) + 1);
-                d.x *= drop_keep(b0, 0, p.thr16, p.inv_keep); d.y *= drop_keep(b0, 1, p.thr16, p.inv_keep);
-                d.z *= drop_keep(b1, 0, p.thr16, p.inv_keep); d.w *= drop_keep(b1, 1, p.thr16, p.inv_keep);
-            }
+            if (p.thr16) KZV_DROP4(d.x, d.y, d.z, d.w, p.key, (unsigned)drow * (unsigned)p.H + 4u * i, p.thr16, p.inv_keep);
             tm[c] = ln_bwd_terms(d, b.x[c], gmr[c], mean, rstd);      // kzv_common.h: the row arithmetic with explicit roundings
             s1 = __fadd_rn(s1, tm[c].s1); s2 = __fadd_rn(s2, tm[c].s2);
             ln_bwd_accum(dg[c], db[c], d, tm[c]);
@@ -283,12 +263,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const LnBwd p) {
             if (ACC) { o.x += b.prev[c].x; o.y += b.prev[c].y; o.z += b.prev[c].z; o.w += b.prev[c].w; }
             dxr[i] = o;
             if (p.out16) {
-                if (p.o_thr16) {
-                    const unsigned e = (unsigned)row * (unsigned)p.H + 4u * i;
-                    const unsigned b0 = drop_bits(p.o_key, e >> 1), b1 = drop_bits(p.o_key, (e >> 1) + 1);
-                    o.x *= drop_keep(b0, 0, p.o_thr16, p.o_inv_keep); o.y *= drop_keep(b0, 1, p.o_thr16, p.o_inv_keep);
-                    o.z *= drop_keep(b1, 0, p.o_thr16, p.o_inv_keep); o.w *= drop_keep(b1, 1, p.o_thr16, p.o_inv_keep);
-                }
+                if (p.o_thr16) KZV_DROP4(o.x, o.y, o.z, o.w, p.o_key, (unsigned)row * (unsigned)p.H + 4u * i, p.o_thr16, p.o_inv_keep);
                 ((uint2*)(p.out16 + (int64_t)row * p.H))[i] = make_uint2(pack_bf2(o.x, o.y), pack_bf2(o.z, o.w));
                 if (F8) {
                     om[c] = o;
@@ -465,7 +440,7 @@ int kzv_ln_bwd_ex(const void* dy, int dy_is_f32, const float* x, const float* st
     return kzv_check_launch("layernorm_bwd");
 }
 
-// A kernel that fuses a LayerNorm backward (decoder_chain.hip's backward segments) accumulates its gamma / beta partial sums the way
+// A kernel that fuses a LayerNorm backward (decoder_chain_bwd.hip's backward segments) accumulates its gamma / beta partial sums the way
 // ln_bwd_fast_kernel does (one float atomic per column and workgroup into slot blockIdx % LN_SLOTS of a zeroed [LN_SLOTS][2][H]
 // region): this hands out the region, with kzv_ln_bwd_ex's bookkeeping.  Inside a KzvLnDeferScope the fold joins the scope's single
 // launch (*fold_now = false); otherwise the caller launches its kernel and then calls kzv_ln_partial_fold.

@@ -96,7 +96,7 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
     // the tied LM-head weight transposed ([hidden, vocabulary]: the B operand of the head's input gradient inside head_ce_kernel), columns
     // beyond the padded vocabulary as zeros
     jobs.push_back({m->word.h.wt, base + pk.head_t(), Hd, pk.vq, Hd, (int)m->word.h.ldt, (int)m->Vp});
-    KZV_TRY(kzv_pack_frag_multi(jobs.data(), (int)jobs.size(), s));
+    KZV_TRY(kzv_pack_frag_multi(jobs.data(), (int)jobs.size(), s));      // frag_pack.hip: one launch for every matrix
     m->dec_pack_ok = true;
     return KZV_OK;
 }

@@ -43,7 +43,7 @@ struct DecAct {
     bf16_t *g_dy = nullptr, *g_dbig = nullptr, *g_dy2 = nullptr, *g_dq = nullptr, *g_dy3 = nullptr, *g_dqkv = nullptr;
 };
 
-// The decoder's bf16 weights in MFMA fragment order (decode_fused.hip, decoder_chain.hip), element offsets into kzv_model::dec_pack:
+// The decoder's bf16 weights in MFMA fragment order (decode_fused.hip, the dec_rows.h family; packed by frag_pack.hip), element offsets into kzv_model::dec_pack:
 //   [layer 0..Ld-1: qkv | o | cq | co | fc1 | fc2] [head dense] [tied LM head, vq rows] then the same again TRANSPOSED ([in, out]
 //   row-major, the B operands of the input-gradient GEMMs).  vq = the vocabulary in 256-row chunks (zeros beyond it).
 struct DecPack {

@@ -284,7 +284,7 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
     KZV_TRY(lin_fwd(m, m->hd, xh, Hd, Md, m->hd_gelu, Hd, KZV_EPI_GELU_F32, s, {.aux = m->hd_pre, .ldaux = Hd}));
     KZV_TRY(ln_fwd(m, m->hd_gelu, m->hln_w, m->hln_b, m->hd_ln, nullptr, m->hd_st, Md, Hd, s));
     // no logits asked for (the training / validation step): head GEMM + log-softmax + NLL + dlogits in ONE launch, the [B*T, Vp] fp32
-    // logits never written (decoder_chain.hip head_ce_kernel).  Otherwise the GEMM materialises them and ce_kernel follows.
+    // logits never written (cross_entropy.hip head_ce_kernel).  Otherwise the GEMM materialises them and ce_kernel follows.
     const float ls_eps = m->train ? m->label_smoothing : 0.f;          // smoothing is a training criterion: validation logs the plain NLL
     if (fused_head) {
         KzvHeadCE hc{m->hd_ln, m->dec_pack.as<bf16_t>() + pk.head(), P + m->word.b, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
@@ -318,7 +318,7 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
     float* P = m->P; float* G = m->G;
     const int CK = m->Ld * 2 * Hd;
     m->wbatch.clear();
-    // the decoder's input-gradient GEMMs on the row-panel kernel (decoder_chain.hip kzv_dec_lin) where the forward's fragment-ordered
+    // the decoder's input-gradient GEMMs on the row-panel kernel (decoder_chain_bwd.hip kzv_dec_lin) where the forward's fragment-ordered
     // packs exist (the reference decoder's geometry, chains on): transposed packs, same layout as the forward's
     static int dgrad_rows = -1;          // dev A/B: KZV_DEC_DGRAD=0 keeps the 128 x 128 kernel for these
     if (dgrad_rows < 0) dgrad_rows = kzv_env_int("KZV_DEC_DGRAD", 1);
@@ -338,7 +338,7 @@ int backward_decoder(kzv_model* m, hipStream_t s) {
     KZV_TRY(kzv_cast_drop_colsum(m->dsum_d, m->dy_d, G + m->hd.b, Md, Hd, 0.f, 0, s, m->hd_pre));
     const bf16_t* x_last_h = m->Ld ? m->da[m->Ld - 1].x3h : m->xd0h;
     KZV_TRY(lin_wgrad_batch(m, m->hd, CLS_DY, s, m->dy_d, Hd, x_last_h, Hd, Md, {.bias = false}));
-    // the three row-local segments of a layer's backward, one launch each (decoder_chain.hip dec_bwd_seg_kernel): the head dense's input
+    // the three row-local segments of a layer's backward, one launch each (decoder_chain_bwd.hip dec_bwd_seg_kernel): the head dense's input
     // gradient becomes the first GEMM of the top layer's first segment
     const bool segs = rows_dgrad && dec_chain_mode() >= 2 && m->Ld > 0;
     if (!segs) {

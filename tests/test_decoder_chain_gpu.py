@@ -1,4 +1,4 @@
-"""The decoder layer's linear chains as two launches (csrc/decoder_chain.hip) against the launch-per-operation forward they replace
+"""The decoder layer's linear chains as two launches (csrc/decoder_chain.hip; their backward: csrc/decoder_chain_bwd.hip) against the launch-per-operation forward they replace
 (HF RobertaLayer, modeling_roberta.py:421-464, under src/models/trocr_model.py:258-297): same model, same batch, same dropout seed,
 `kzv_set_dec_chain(0 / 1)` -- loss, logits and EVERY gradient (the backward reads the tensors the chains wrote: sums, LayerNorm
 statistics, bf16 operands, the saved GELU derivative, and regenerates their dropout masks).  The oracle-side parity of the chain
@@ -64,7 +64,7 @@ def test_chains_equal_the_launch_per_operation_forward(tmp_path, B, Lh, train):
 @pytest.mark.parametrize("B,Lh,train,vocab", [(5, 30, True, 4300), (3, 12, True, 100), (7, 23, False, 777), (70, 9, True, 4300)])
 def test_one_launch_lm_head_and_cross_entropy_equals_gemm_plus_ce_kernel(tmp_path, B, Lh, train, vocab):
     """kzv_set_head_ce(1) (default): lm_head.decoder + log-softmax + NLL + dlogits in one launch, logits never written (SURVEY K9;
-    csrc/decoder_chain.hip head_ce_kernel) against the head GEMM + ce_kernel it replaces -- same model, batch and dropout seed: the loss
+    csrc/cross_entropy.hip head_ce_kernel) against the head GEMM + ce_kernel it replaces -- same model, batch and dropout seed: the loss
     and EVERY gradient (the head's two gradient GEMMs read the bf16 dlogits the kernel wrote).  Vocabularies that end inside a
     256-column chunk and inside a 64-column pad (100 -> Vp 128, 777 -> 832), rows past M in the last workgroup, ignored (pad) targets,
     and the validation form (no gradient buffer)."""
@@ -111,7 +111,7 @@ def test_chains_with_more_workgroups_than_compute_units(tmp_path):
     round 4's second session: tools/dev/r5_det3.py): the residual epilogue consumed registers whose loads -- issued early, some inside a
     uniform branch -- had not landed, hipcc's own vmcnt wait being too lenient; 2 - 5 % of chain A's workgroups then added `beta` instead
     of the LayerNorm output for 16 rows (logits off by 0.2), only once a launch had more workgroups than CUs (slower loads), and repeated
-    inputs hid nothing.  csrc/decoder_chain.hip now retires such loads by hand (retire_loads + pin)."""
+    inputs hid nothing.  csrc/dec_rows.h now retires such loads by hand (retire_loads + pin)."""
     cfg = dataclasses.replace(tiny_config(), dec_hidden=256, dec_heads=4, dec_ffn=768, dec_layers=4, max_pos=130)
     lib = L.load()
     d = build_decoder_dir(str(tmp_path / "dec"), cfg)

@@ -1,4 +1,4 @@
-"""Per-op references for the glue kernels (csrc/elementwise.hip), LayerNorm in every instantiation and fused form
+"""Per-op references for the glue kernels (csrc/elementwise.hip; cross-entropy: csrc/cross_entropy.hip), LayerNorm in every instantiation and fused form
 (csrc/layernorm.hip) and the hidden-state dropout generator every fused epilogue draws from, through the per-op C ABI.
 
 The whole-step parity tests bound logits by 3e-2 and gradients by a few percent of their largest entry; a fault confined to part

@@ -1,5 +1,5 @@
 """Label smoothing of the training loss (include/kzv.h: kzv_set_label_smoothing, kzv_ce_fwd_bwd_ls): the three loss kernels' LS
-instantiations -- ce_kernel / ce_generic_kernel (csrc/elementwise.hip) and the one-launch head_ce_kernel (csrc/decoder_chain.hip) -- against
+instantiations -- ce_kernel / ce_generic_kernel and the one-launch head_ce_kernel (all three: csrc/cross_entropy.hip) -- against
 torch.nn.functional.cross_entropy(logits, target, ignore_index=pad, label_smoothing=eps), mean over the scored rows, V = the real vocabulary:
 
     loss_row   = lse(z) - (1 - eps) z[y] - (eps / V) sum_{v < V} z[v]

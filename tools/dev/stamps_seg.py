@@ -19,7 +19,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 lib = ctypes.CDLL(_lib.LIB_PATH)
 buf = (ctypes.c_longlong * 32)()
-assert lib.kzv_debug_chain_stamps(buf, 32) == 0
+assert lib.kzv_debug_seg_stamps(buf, 32) == 0      # decoder_chain_bwd.hip's own array (the forward chains': kzv_debug_chain_stamps)
 st = list(buf)
 names = ["window + load rows", "gemm 1", "d tile", "LayerNorm backward", "partials", "gemm 2 (+ gelu')", "rows out"]
 print("dec_bwd_seg, workgroup 0 (cycles of the 100 MHz... s_memtime): " + ", ".join(f"{n} {st[17 + k] - st[16 + k]}" for k, n in enumerate(names)) + f" | total {st[23] - st[16]}")
