@@ -201,6 +201,52 @@ typedef struct kzv_logits_process_args {
     const uint32_t* suppress_mask;
 } kzv_logits_process_args;
 int kzv_logits_process(const kzv_logits_process_args* args, void* stream);
+/* A character n-gram language model on the device (kzv/lm.py: NGramLM fits, loads and lays it out; NGramLM.row is the readable
+ * statement of the evaluation).  order in 1..4, vocab <= 16,384.  All tables are device memory:
+ *   uni [vocab] fp32                      log P_1(v), natural logarithm;
+ *   per context length k = 1 .. order - 1 (index k - 1), n_ctx[k - 1] contexts:
+ *     keys[k - 1] int64, ascending        the context's k tokens as one number in base 16,384, the OLDEST token most significant;
+ *     bo[k - 1]   fp32                    log of the context's back-off weight;
+ *     off[k - 1]  int32 [n_ctx + 1]       CSR offsets into succ_tok / succ_lp (shared by all lengths);
+ *   succ_tok int32, succ_lp fp32          a context's seen successors, ascending by token, with log P_{k+1}(v | context).
+ * The tables of a length with n_ctx == 0 may be null.
+ * Evaluation for a history h[0 .. n), BOS included, all in fp32 and in this order:
+ *   acc = 0;  for k = min(order - 1, n) down to 1:  if h[n - k .. n) is a key of length k:
+ *       lm[v] = acc + lp for each of its successors (v, lp) that no longer context has set;  acc = acc + bo(context)
+ *   lm[v] = acc + uni[v] for every v not set.
+ * A context that holds a token outside [0, vocab) counts as not found. */
+typedef struct kzv_ngram_lm {
+    int32_t order, vocab;
+    int32_t n_ctx[3]; int32_t reserved;
+    const float* uni;
+    const int64_t* keys[3]; const float* bo[3]; const int32_t* off[3];
+    const int32_t* succ_tok; const float* succ_lp;
+} kzv_ngram_lm;
+/* Shallow fusion of the language model into one step's scores, in place: for row r of logits [rows, ld] with history h,
+ *   x[v] = x[v] + weight * lm[v]   for every v < vocab (two fp32 roundings: the multiply, then the add; -inf stays -inf),
+ * columns [vocab, ld) untouched.  Where the history lies, the slot cases, idle slots and the meaning of ids / ld_ids / t / group /
+ * slot_image / slot_t / by_image / n_images: exactly kzv_logits_process's.  `lm` is a HOST pointer to the struct above (read during
+ * the call, passed to the kernel by value); its tables must stay alive until the launch has run.
+ * Where the fusion acts (one rule everywhere; kzv/lm.py): greedy decoding -- raw logits, the controls if any, then + weight * lm, then
+ * arg-max and log-sum-exp of the result; beam search -- log_softmax(logits) (the normalising kzv_logits_process, with neutral controls
+ * when none are set), the controls, + weight * lm, + beam score, ranked by kzv_beam_rank_logprobs without a second normalisation.  The
+ * fusion comes after the controls: the repetition penalty acts on the model's score alone, and a ban's -inf survives the addition.
+ * One workgroup of 256 threads per row; a claim bitmask of one bit per token lives in LDS, hence vocab <= 16,384.
+ * KZV_E_ARG before any launch: null args / logits / ids / lm / tables, rows < 1, vocab outside 1..16,384 or different from the LM's,
+ * ld < vocab, ld_ids < 1, order outside 1..4, a negative context count, a non-finite weight, one of slot_image / slot_t without the
+ * other, rows no multiple of group, t < 0 in the lockstep case. */
+typedef struct kzv_lm_fuse_args {
+    float* logits; int64_t ld;                           /* [rows, ld >= vocab], edited in place */
+    int32_t rows, vocab;
+    const int64_t* ids; int64_t ld_ids;                  /* token histories */
+    int32_t t;                                           /* lockstep: the step index, history length t + 1 */
+    int32_t group;                                       /* slot cases: rows per slot */
+    const int32_t* slot_image; const int32_t* slot_t;    /* slot cases: [rows / group] */
+    int32_t by_image, n_images;
+    float weight; int32_t reserved;
+    const kzv_ngram_lm* lm;                              /* host pointer */
+} kzv_lm_fuse_args;
+int kzv_lm_fuse(const kzv_lm_fuse_args* args, void* stream);
 /* The inputs of decoder step t from the token table d_ids [batch, ld_ids]: d_tokens [batch] = column t, d_posids [batch] = its
  * RoBERTa position id (t + 1 + pad_id, or pad_id for padding), d_valid[:, t] = token != pad. */
 int kzv_decode_prep(const int64_t* d_ids, int64_t ld_ids, int t, int pad_id, int batch, int64_t* d_tokens, uint8_t* d_valid, int64_t ld_valid,
@@ -435,6 +481,14 @@ typedef struct kzv_logits_controls {
     const uint32_t* suppress_mask;                       /* optional, host */
 } kzv_logits_controls;
 int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* controls, void* stream);
+/* Language-model fusion for the wave just begun (greedy or beams): after kzv_stream_begin / kzv_stream_begin_beams and before
+ * kzv_stream_start.  Every kzv_stream_step then runs kzv_lm_fuse as one more kernel node of the same single chain, after the controls'
+ * node (if any) and before kzv_stream_topk / selection; a beam wave takes the normalise (kzv_logits_process, neutral controls when none
+ * are set) -> fuse -> kzv_beam_rank_logprobs route in place of kzv_beam_topk.  The struct is copied; its tables stay the caller's device
+ * memory and must outlive the wave.  The setting belongs to one wave: the next begin clears it.  weight == 0 switches it off: a step then
+ * launches exactly what it launches without this call.  Launches no kernel itself.  KZV_E_STATE outside a begun wave; KZV_E_ARG for a
+ * null struct or tables, a vocabulary different from the model's, an order outside 1..4 and a non-finite weight. */
+int kzv_stream_set_lm(kzv_model* m, const kzv_ngram_lm* lm, float weight, void* stream);
 
 /* loss.backward() for the step above: fills the bound fp32 grad buffer (which must be zero on entry;
  * kzv_zero_grads does that).  Backward is split in `kzv_backward_segments()` segments so the host can

@@ -410,7 +410,9 @@ static int stream_begin(kzv_model* m, const char* who, int nb, int early, float 
     m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
     m->sbeams = nb > 1 ? nb : 0;
     m->stopk = 0;                                // kzv_stream_set_topk belongs to one wave
-    m->sctl_on = false; m->smask_on = false;     // and so does kzv_stream_set_controls
+    m->sctl_on = false; m->smask_on = false;     // and so does kzv_stream_set_controls (neutral until it is called)
+    m->sctl = kzv_logits_controls{}; m->sctl.repetition_penalty = 1.f;
+    m->slm_on = false;                           // and kzv_stream_set_lm
     if (nb == 1) {
         kzv_stream_state& st = m->sst;
         st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
@@ -514,6 +516,19 @@ extern "C" int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* 
     return KZV_OK;
 }
 
+const char* kzv_ngram_lm_problem(const kzv_ngram_lm* lm, int vocab);      // lm_fusion.hip
+
+extern "C" int kzv_stream_set_lm(kzv_model* m, const kzv_ngram_lm* lm, float weight, void* stream) {
+    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_lm: call kzv_stream_begin / kzv_stream_begin_beams first");
+    if (const char* why = kzv_ngram_lm_problem(lm, m->V)) return kzv_fail(KZV_E_ARG, "stream_set_lm: %s", why);
+    if (!std::isfinite(weight)) return kzv_fail(KZV_E_ARG, "stream_set_lm: the weight must be finite (got %g)", (double)weight);
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
+    m->slm = *lm; m->slm_weight = weight;
+    m->slm_on = weight != 0.f;
+    return KZV_OK;
+}
+
 // the wave's controls on the step's logits: one more node between the vocabulary GEMM and what reads the rows (order: repetition penalty,
 // n-gram ban, minimum length, suppression -- immaterial, see logits_process.hip)
 static int stream_process(kzv_model* m, hipStream_t s) {
@@ -527,6 +542,18 @@ static int stream_process(kzv_model* m, hipStream_t s) {
     a.suppress_mask = m->smask_on ? m->smask.as<uint32_t>() : nullptr;
     a.normalise = nb ? 1 : 0;
     return kzv_logits_process(&a, s);
+}
+
+// the wave's language model on the step's (processed) scores: the next node, on the same histories
+static int stream_lm_fuse(kzv_model* m, hipStream_t s) {
+    const int nb = m->sbeams;
+    kzv_lm_fuse_args a;
+    memset(&a, 0, sizeof(a));
+    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
+    if (!nb) { a.ids = m->sst.out_ids; a.ld_ids = m->sst.ld_ids; a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; }
+    else { a.ids = m->sbst.run_seq; a.ld_ids = m->sbst.max_len; a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; }
+    a.weight = m->slm_weight; a.lm = &m->slm;
+    return kzv_lm_fuse(&a, s);
 }
 
 extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
@@ -557,8 +584,12 @@ static int stream_step_body(kzv_model* m, hipStream_t s) {
     }
     KZV_TRY(kzv_decode_fused_launch(a, s));
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
-    if (m->sctl_on) {                            // neutral controls: nothing is added to the chain
-        KZV_TRY(stream_process(m, s));
+    // neutral controls and no language model: nothing is added to the chain.  A beam wave with the language model on normalises through
+    // the controls' node even when the controls are neutral: the fusion acts on log-probabilities
+    const bool lm = m->slm_on;
+    if (m->sctl_on || (lm && nb)) KZV_TRY(stream_process(m, s));
+    if (lm) KZV_TRY(stream_lm_fuse(m, s));
+    if (m->sctl_on || lm) {
         if (nb) {                                // the rows are processed log-probabilities now: ranked without a second normalisation
             KZV_TRY(kzv_beam_rank_logprobs(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
             return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);

@@ -132,6 +132,10 @@ struct kzv_model_plain {
     bool sctl_on = false, smask_on = false;
     kzv_logits_controls sctl = {};
     std::vector<uint32_t> smask_h;
+    // language-model fusion of the wave (kzv_stream_set_lm): on only while the weight is not zero; the struct is a copy, its tables
+    // are the caller's device memory
+    bool slm_on = false; float slm_weight = 0.f;
+    kzv_ngram_lm slm = {};
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU

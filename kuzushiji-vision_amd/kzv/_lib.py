@@ -89,6 +89,17 @@ class kzv_logits_controls(C.Structure):
                 ("suppress_mask", C.c_void_p)]
 
 
+class kzv_ngram_lm(C.Structure):
+    _fields_ = [("order", C.c_int32), ("vocab", C.c_int32), ("n_ctx", C.c_int32 * 3), ("reserved", C.c_int32), ("uni", C.c_void_p),
+                ("keys", C.c_void_p * 3), ("bo", C.c_void_p * 3), ("off", C.c_void_p * 3), ("succ_tok", C.c_void_p), ("succ_lp", C.c_void_p)]
+
+
+class kzv_lm_fuse_args(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("vocab", C.c_int32), ("ids", C.c_void_p), ("ld_ids", C.c_int64),
+                ("t", C.c_int32), ("group", C.c_int32), ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("by_image", C.c_int32),
+                ("n_images", C.c_int32), ("weight", C.c_float), ("reserved", C.c_int32), ("lm", C.POINTER(kzv_ngram_lm))]
+
+
 class kzv_edit_args(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("ld_pred", C.c_int64), ("ref", C.c_void_p), ("ld_ref", C.c_int64),
                 ("n", C.c_int32), ("width_pred", C.c_int32), ("width_ref", C.c_int32), ("vocab", C.c_int32), ("n_special", C.c_int32),
@@ -291,6 +302,9 @@ SYMBOLS = {
     "kzv_logits_process": (C.c_int, [C.POINTER(kzv_logits_process_args), C.c_void_p]),
     "kzv_test_logits_process_calls": (C.c_int64, []),      # test hook (csrc/logits_process.hip), not declared in include/kzv.h
     "kzv_stream_set_controls": (C.c_int, [C.c_void_p, C.POINTER(kzv_logits_controls), C.c_void_p]),
+    "kzv_lm_fuse": (C.c_int, [C.POINTER(kzv_lm_fuse_args), C.c_void_p]),
+    "kzv_test_lm_fuse_calls": (C.c_int64, []),             # test hook (csrc/lm_fusion.hip), not declared in include/kzv.h
+    "kzv_stream_set_lm": (C.c_int, [C.c_void_p, C.POINTER(kzv_ngram_lm), C.c_float, C.c_void_p]),
     "kzv_stream_seat_first": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p]),
     "kzv_stream_update": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_void_p]),
     "kzv_stream_topk": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -78,6 +78,8 @@ class TrOCRModel:
         # what lockstep ``generate`` runs for its generation controls: "device" (kzv_logits_process) or "reference" (the torch statement
         # kzv/controls.py::process_reference on the same step scores; the tests' cross-check, far slower)
         self.controls_impl = "device"
+        # the same switch for the language-model fusion of lockstep ``generate``: "device" (kzv_lm_fuse) or "reference" (kzv/lm.py::fuse_reference)
+        self.lm_impl = "device"
         # generation controls of the validation / test decodes (``forward`` without labels): generate's keywords; empty = the reference's
         self.decode_controls = {}
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
@@ -463,20 +465,21 @@ class TrOCRModel:
 
     def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0,
                   no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None,
-                  allowed_tokens=None) -> list[dict]:
+                  allowed_tokens=None, lm=None, lm_weight: float = 0.0) -> list[dict]:
         """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
         ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
         ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
         pixels) and ``peak_patches`` (kzv/align.py: build_records).  ``top_k`` in 1..8 adds ``alternatives`` (per token the k best
         candidates of the teacher-forced pass with their log-probabilities) and ``margins``; after a beam search the chosen token
         need not be the first alternative.  The generation controls are ``generate``'s and steer the decode only: the align-based
-        values (log-probabilities, confidence, alternatives) stay the model's own, so a token the controls forced may carry a low one."""
+        values (log-probabilities, confidence, alternatives) stay the model's own, so a token the controls forced may carry a low one.
+        ``lm`` / ``lm_weight`` (``generate``'s language-model fusion) do the same: they steer the decode only."""
         import torch
         from . import align as A
         c = self.cfg
         gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
                             no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
-                            suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens)
+                            suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight)
         if gen.shape[1] < 2:                                  # labels need a target column
             gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
         out = self.align(pixel_values, gen, layer=layer, top_k=top_k)
@@ -510,7 +513,8 @@ class TrOCRModel:
 
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True, return_scores: bool = False,
-                 no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None):
+                 no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
+                 lm=None, lm_weight: float = 0.0):
         """Decode from BOS.  The encoder (and the cross-attention K/V of every decoder layer) runs ONCE.
         ``return_scores`` (beam search on the device hooks only, i.e. 2..8 beams on the GPU): returns ``(ids, scores)``, scores fp32 [B] =
         the winners' sum of log-probabilities / generated length ** length_penalty (HF's ``sequences_scores``), read off the search's own
@@ -529,12 +533,19 @@ class TrOCRModel:
         p > 0 (the scores of tokens already emitted are divided by p, or multiplied where negative), ``min_length`` (no EOS before the
         line holds that many tokens, BOS included; ``max_length`` still ends it), ``suppress_tokens`` (ids never chosen) or its
         complement ``allowed_tokens`` (EOS is always kept).  They act on every step's scores on the device (kzv_logits_process): on the
-        raw logits for greedy decoding, on log_softmax(logits) before the beam score is added for beam search, as HF does."""
+        raw logits for greedy decoding, on log_softmax(logits) before the beam score is added for beam search, as HF does.
+
+        ``lm`` (a kzv.lm.NGramLM or its device form) with ``lm_weight`` != 0: shallow fusion of a character n-gram language model, every
+        step's scores + lm_weight * log p_lm(token | the last order - 1 tokens), on the device (kzv_lm_fuse) AFTER the controls: greedy
+        decoding takes arg-max of the fused logits; beam search adds it to the (processed) log-probabilities before the beam score and
+        does not normalise again (kzv/lm.py states the rule).  ``lm=None`` or ``lm_weight=0``: off, nothing is built or launched."""
         import torch
         from . import beam as BM
         from . import controls as CT
+        from . import lm as LM
         c = self.cfg
         ctl = CT.from_kwargs(c.eos_id, no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens, allowed_tokens)
+        lmr = LM.resolve(lm, lm_weight, c.vocab, self.device)          # (host model, device tables, weight) or None
         ctl_mask = None
         if ctl is not None:
             ctl.check(c.vocab, c.eos_id, num_beams)
@@ -601,36 +612,57 @@ class TrOCRModel:
         def controls_hook(scores, ids, n, normalise=0):
             """The controls on ``scores`` [BB, V] in place, histories ids[:, :n] (kzv_logits_process; ``controls_impl`` = "reference"
             substitutes the torch statement on the same scores: the whole-decode tests compare the two)."""
-            if self.controls_impl == "reference":
+            if self.controls_impl == "reference" and ctl is not None:
                 x = torch.log_softmax(scores, dim=-1) if normalise else scores
                 scores.copy_(CT.process_reference(x, ids[:, :n], ctl, c.eos_id))
                 return scores
             if scores.stride(1) != 1 or ids.stride(1) != 1:
                 raise ValueError("controls: scores and ids must be dense along their rows")
+            k = ctl if ctl is not None else neutral      # the language model alone in a beam search: the kernel only normalises
             a = L.kzv_logits_process_args(logits=scores.data_ptr(), ld=scores.stride(0), rows=scores.shape[0], vocab=c.vocab, ids=ids.data_ptr(),
                                           ld_ids=ids.stride(0), t=n - 1, group=1, slot_image=None, slot_t=None, by_image=0, n_images=0,
-                                          no_repeat_ngram_size=ctl.no_repeat_ngram_size, min_length=ctl.min_length, eos_id=c.eos_id,
-                                          normalise=1 if normalise else 0, repetition_penalty=ctl.repetition_penalty, reserved=0,
+                                          no_repeat_ngram_size=k.no_repeat_ngram_size, min_length=k.min_length, eos_id=c.eos_id,
+                                          normalise=1 if normalise else 0, repetition_penalty=k.repetition_penalty, reserved=0,
                                           suppress_mask=L.ptr(ctl_mask))
             L.check(lib.kzv_logits_process(C.byref(a), L.stream_handle()), "logits_process")
             return scores
 
+        def lm_hook(scores, ids, n):
+            """+ lm_weight * lm on ``scores`` [BB, V] in place, histories ids[:, :n] (kzv_lm_fuse; ``lm_impl`` = "reference" substitutes
+            kzv/lm.py::fuse_reference on the same scores)."""
+            host, dlm, w = lmr
+            if self.lm_impl == "reference":
+                scores.copy_(LM.fuse_reference(scores, ids[:, :n], host, w))
+                return scores
+            if scores.stride(1) != 1 or ids.stride(1) != 1:
+                raise ValueError("lm: scores and ids must be dense along their rows")
+            a = L.kzv_lm_fuse_args(logits=scores.data_ptr(), ld=scores.stride(0), rows=scores.shape[0], vocab=c.vocab, ids=ids.data_ptr(),
+                                   ld_ids=ids.stride(0), t=n - 1, group=1, slot_image=None, slot_t=None, by_image=0, n_images=0, weight=w,
+                                   reserved=0, lm=C.pointer(dlm.struct))
+            L.check(lib.kzv_lm_fuse(C.byref(a), L.stream_handle()), "lm_fuse")
+            return scores
+
+        def both_hook(scores, ids, n):           # the one order everywhere: controls first, then the language model
+            return lm_hook(controls_hook(scores, ids, n), ids, n)
+
+        neutral = CT.GenerationControls()
         topk = update = None
-        process = controls_hook if ctl is not None else None
+        process = (both_hook if lmr else controls_hook) if ctl is not None else (lm_hook if lmr else None)
         raw_step = step
 
         def step_logprobs(t, ids):               # beams on the device ranking: normalise + process here, rank log-probabilities after
-            return controls_hook(raw_step(t, ids), ids, t + 1, normalise=1)
+            x = controls_hook(raw_step(t, ids), ids, t + 1, normalise=1)
+            return lm_hook(x, ids, t + 1) if lmr else x
 
         try:
             with self._decode_stream(use_cache) as (graph, keep):
                 # the hooks allocate and zero their flag / top-k buffers: on the stream whose kernels read them
                 if nb > 1 and nb <= 8 and self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0":
                     topk, update = BM.make_device_hooks(B, nb, Lh, c.vocab, c.eos_id, early_stopping, length_penalty, self.device,
-                                                        logprobs=ctl is not None)
+                                                        logprobs=ctl is not None or lmr is not None)
                     if os.environ.get("KZV_BEAM_UPDATE", "1") == "0":
                         update = None
-                    if ctl is not None:
+                    if ctl is not None or lmr is not None:
                         step, process = step_logprobs, None
                 if use_cache:
                     L.check(lib.kzv_set_active_length(self._h, 1), "set_active_length")
@@ -649,6 +681,8 @@ class TrOCRModel:
                                          early_stopping=early_stopping, length_penalty=length_penalty, topk=topk, update=update,
                                          process=process)
                 keep += (out, step_logits, posids, tok_buf, state["valid"], px) + (() if ctl_mask is None else (ctl_mask,))
+                if lmr:
+                    keep += lmr[1].keep()
                 if return_scores:
                     keep.append(scores)
             return (out, scores) if return_scores else out
@@ -700,7 +734,8 @@ class TrOCRModel:
     def generate_stream(self, pixel_values, max_length: int = 128, slots: int | None = None, limits=None, return_logprobs: bool = False,
                         pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
                         return_scores: bool = False, top_k: int = 0,
-                        no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None):
+                        no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
+                        lm=None, lm_weight: float = 0.0):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -737,11 +772,19 @@ class TrOCRModel:
         controls on, ``return_logprobs`` and the ``top_k`` alternatives are those of the PROCESSED row (HF's
         ``scores[t].log_softmax(-1)``): a banned token never appears among the alternatives (it ranks last at -inf).  On the static path
         the log-probabilities stay the model's own (``align``).  Tip: ``suppress_tokens=[pad_id]`` removes the cause of the beam
-        stream's re-decode -- no running beam can take padding."""
+        stream's re-decode -- no running beam can take padding.
+
+        Language-model fusion (``lm``, ``lm_weight``: ``generate``'s keywords and rule; off by default): every step of a wave runs
+        kzv_lm_fuse as one more node of its captured chain, after the controls' node (kzv_stream_set_lm), on each slot's own history; a
+        beam wave then normalises through the controls' kernel even when the controls are neutral.  Every row still equals the matching
+        row of ``generate`` called with the same keywords, both fallbacks carry them, and ``return_logprobs`` / ``top_k`` are those of
+        the FUSED row."""
         import torch
         from . import controls as CT
+        from . import lm as LM
         c = self.cfg
         ctl = CT.from_kwargs(c.eos_id, no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens, allowed_tokens)
+        lmr = LM.resolve(lm, lm_weight, c.vocab, self.device)          # before any wave runs; None: off
         if ctl is not None:
             ctl.check(c.vocab, c.eos_id, num_beams)   # before any wave runs
         nb = int(num_beams)
@@ -784,10 +827,10 @@ class TrOCRModel:
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
             if top_k:
-                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl)
+                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl, lmr)
                 alt_out.append(alts)
             else:
-                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl)
+                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl, lmr)
             ids_out.append(ids); lp_out.append(lp); done += n
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
@@ -801,14 +844,15 @@ class TrOCRModel:
         return ids[:, :width]
 
     @staticmethod
-    def _controls_kw(ctl) -> dict:
-        """``generate``'s keywords for the controls of a wave (none when they are off)."""
+    def _controls_kw(ctl, lmr=None) -> dict:
+        """``generate``'s keywords for the controls and the language model of a wave (none when they are off)."""
+        kw = {} if lmr is None else {"lm": lmr[1], "lm_weight": lmr[2]}
         if ctl is None:
-            return {}
-        return {"no_repeat_ngram_size": ctl.no_repeat_ngram_size, "repetition_penalty": ctl.repetition_penalty, "min_length": ctl.min_length,
-                "suppress_tokens": ctl.suppress_tokens, "allowed_tokens": ctl.allowed_tokens}
+            return kw
+        return dict(kw, no_repeat_ngram_size=ctl.no_repeat_ngram_size, repetition_penalty=ctl.repetition_penalty, min_length=ctl.min_length,
+                    suppress_tokens=ctl.suppress_tokens, allowed_tokens=ctl.allowed_tokens)
 
-    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams, ctl=None):
+    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams, ctl=None, lmr=None):
         """``generate(num_beams=nb)`` over batches of ``slots``: ids [n, Lh] and the winners' scores [n] (from a teacher-forced pass).  With
         limits, the images of every distinct limit are decoded with it as their max_length."""
         import torch
@@ -823,7 +867,7 @@ class TrOCRModel:
             for a in range(0, idx.numel(), slots):
                 sel = idx[a:a + slots]
                 sub = px[sel.to(px.device)]
-                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen, **self._controls_kw(ctl))
+                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen, **self._controls_kw(ctl, lmr))
                 rows = torch.full((sel.numel(), Lh), c.pad_id, dtype=torch.int64, device=dev)
                 rows[:, :g.shape[1]] = g
                 sc = self.align(sub, rows)
@@ -832,10 +876,10 @@ class TrOCRModel:
                 score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
         return ids, score
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None):
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None, lmr=None):
         """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
         length_penalty): ids [n, Lh] and the winners' scores [n]; with ``top_k`` (greedy) a third result, (alt_ids int32, alt_logprob)
-        [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off)."""
+        [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off); ``lmr``: its language model (kzv/lm.py: resolve; None: off)."""
         import torch
         from . import stream as ST
         c = self.cfg
@@ -845,18 +889,18 @@ class TrOCRModel:
         self._check_inputs(px[:1])                                # geometry checks + the active crop width
         nb = beams[0] if beams else 1
         if beams and nb not in (2, 4):
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
         rows = slots * nb                                         # decoder rows: a slot holds one sequence, or an image's beam group
         self._bind(rows, Lh)
         if beams and self.stream_beam_impl_for(nb) == "static":
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
         if not beams and self.stream_decode_impl == "static":
             ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
             lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
             alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
             alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
             for a in range(0, n, slots):
-                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1, **self._controls_kw(ctl))
+                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1, **self._controls_kw(ctl, lmr))
                 ids[a:a + g.shape[0], :g.shape[1]] = g
             if lim is not None:
                 ids = torch.where(torch.arange(Lh, device=dev).view(1, Lh) >= lim.to(dev).view(n, 1), torch.full_like(ids, c.pad_id), ids)
@@ -895,6 +939,9 @@ class TrOCRModel:
                     cc = L.kzv_logits_controls(no_repeat_ngram_size=ctl.no_repeat_ngram_size, repetition_penalty=ctl.repetition_penalty,
                                                min_length=ctl.min_length, reserved=0, suppress_mask=None if mk is None else mk.data_ptr())
                     L.check(lib.kzv_stream_set_controls(self._h, C.byref(cc), st), "stream_set_controls")
+                if lmr is not None:                               # and one more after it; the tables stay ours for the wave
+                    L.check(lib.kzv_stream_set_lm(self._h, C.byref(lmr[1].struct), lmr[2], st), "stream_set_lm")
+                    keep += lmr[1].keep()
                 a = 0
                 while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
                     k = min(rows, n - a)                          # is filled by repeating its last image
@@ -928,7 +975,7 @@ class TrOCRModel:
             self.training = was
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
             self.last_stream_pad_fallbacks += pads.value
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl)
+            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
         if top_k:
             return ids, lp, (alt_ids, alt_lp)
         return ids, (score if beams else lp)
@@ -940,7 +987,8 @@ class TrOCRModel:
         from the cross-attention maps of a teacher-forced pass, which ``recognize`` runs.  ``kw``: generate_stream's arguments; with
         ``top_k`` in 1..8 every record also holds ``alternatives`` and ``margins`` (build_records), taken from the stream's own steps.
         The generation controls (``no_repeat_ngram_size``, ``repetition_penalty``, ``min_length``, ``suppress_tokens``, ``allowed_tokens``)
-        go through ``kw``; log-probabilities, confidence and alternatives are then those of the processed rows (generate_stream)."""
+        go through ``kw``; log-probabilities, confidence and alternatives are then those of the processed rows (generate_stream).
+        So do ``lm`` / ``lm_weight`` (language-model fusion): the values are then those of the fused rows."""
         import numpy as np
         from . import align as A
         c = self.cfg
@@ -996,7 +1044,8 @@ class TrOCRModel:
         ``insertions`` / ``ref_chars`` (totals), ``per_line`` (numpy arrays ``cer``, ``dist``, ``ref_len``, ``pred_len``, ``ops``),
         ``characters`` (metrics.character_table: the ``top`` characters with the most errors) and ``ids`` (the generated rows).  The
         same call serves geometries where generate_stream runs ``generate``: it needs only the ids.  The generation controls of
-        generate_stream (``no_repeat_ngram_size=3`` is what the stock TrOCR generation configs ship with) pass through its keywords."""
+        generate_stream (``no_repeat_ngram_size=3`` is what the stock TrOCR generation configs ship with) pass through its keywords, and
+        so do ``lm`` / ``lm_weight`` (kzv.lm.sweep_weight picks the weight with this call)."""
         import numpy as np
         import torch
         from . import metrics as M

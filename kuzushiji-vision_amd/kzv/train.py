@@ -76,6 +76,15 @@ def parse_args(argv=None):
     p.add_argument("--min_length", type=int, default=0,
                    help="generation control of the validation / test decodes: no EOS before a line holds this many tokens, BOS included; "
                         "0 = off, the reference's behaviour")
+    p.add_argument("--lm_path", type=str, default=None,
+                   help="character n-gram language model fused into the validation / test decodes (an extension; kzv.lm): an .npz written by "
+                        "kzv.lm, or an ARPA file by its .arpa extension (KenLM / SRILM)")
+    p.add_argument("--lm_order", type=int, default=0,
+                   help="with N > 0 and no --lm_path: fit an order-N model (1..4) on the training split's label ids at start-up and save it as "
+                        "lm.npz beside the checkpoints; 0 = off")
+    p.add_argument("--lm_weight", type=float, default=0.0,
+                   help="weight of the language model's log-probability in every decode step's scores (shallow fusion, after the generation "
+                        "controls); 0.0 = off, the reference's behaviour")
     p.add_argument("--device_preprocess", action="store_true",
                    help="resize / pad / normalise the decoded crops on the GPU (kzv.preprocess; byte-exact with the PIL transform)")
     p.add_argument("--augment", type=str, default="off", choices=["off", "reference"],
@@ -108,7 +117,46 @@ def parse_args(argv=None):
     if args.label_smoothing and args.model == "ocr":
         p.error("--label_smoothing applies to the TrOCR cross-entropy only: --model ocr trains with CTC and SmoothL1 losses, which have no "
                 "softmax cross-entropy to smooth")
+    if args.model == "ocr" and (args.lm_path or args.lm_order or args.lm_weight):
+        p.error("--lm_path / --lm_order / --lm_weight act on the TrOCR decodes only: --model ocr decodes with CTC, which has no "
+                "step-wise scores to fuse a language model into")
+    if not 0 <= args.lm_order <= 4:
+        p.error(f"--lm_order must be in 0..4, not {args.lm_order}")
+    if args.lm_weight != args.lm_weight or args.lm_weight in (float("inf"), float("-inf")):
+        p.error("--lm_weight must be finite")
     return args
+
+
+def _decode_lm(args, model, train_ds, out_dir, rank, world=1):
+    """The language model of the validation / test decodes from --lm_path / --lm_order, said once.  With --lm_order N > 0 and no
+    --lm_path the model is fitted on the training split's label ids -- by rank 0, which saves it as lm.npz beside the checkpoints; the
+    other ranks load that file -- whatever the weight.  Returns None where --lm_weight is 0 (off) or no model was asked for.
+    The tokenizer adds no BOS / EOS on encode and a decode's history starts with BOS, so every label row is wrapped as BOS ... EOS."""
+    from . import lm as LM
+    c = model.cfg
+    if not (args.lm_path or args.lm_order):
+        return None
+    if args.lm_path:
+        lm = LM.load_any(args.lm_path, model.tokenizer, c.bos_id, c.eos_id, c.vocab)
+    else:
+        path = os.path.join(out_dir, "checkpoints", "lm.npz")
+        if rank == 0:
+            if hasattr(train_ds, "data") and getattr(train_ds, "tokenizer", None) is not None:      # the texts, no image is opened
+                rows = [train_ds.tokenizer(t, max_length=train_ds.max_length, truncation=True)["input_ids"] for t in train_ds.data["text"]]
+            else:
+                rows = [train_ds[i]["labels"].numpy() for i in range(len(train_ds))]
+            seqs = LM.sequences_from_labels(rows, c.pad_id, c.eos_id, bos_id=c.bos_id)
+            lm = LM.NGramLM.fit(seqs, args.lm_order, c.vocab)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            lm.save(path)
+        if world > 1:
+            import torch
+            torch.distributed.barrier()              # rank 0 has written the file the others load
+        if rank != 0:
+            lm = LM.NGramLM.load(path)
+    if rank == 0:
+        print(f"language model: order {lm.order}, contexts {lm.n_contexts()}, weight {args.lm_weight}" + ("" if args.lm_weight else " (off)"))
+    return lm if args.lm_weight else None
 
 
 def main_ocr(args):
@@ -287,6 +335,9 @@ def main(argv=None):
                   max_length=args.max_length, train_ratio=args.train_ratio, val_ratio=args.val_ratio, test_ratio=args.test_ratio)
         kw["device_preprocess"] = args.device_preprocess
         train_ds, val_ds, test_ds = LineCsvDataset(split="train", **kw), LineCsvDataset(split="val", **kw), LineCsvDataset(split="test", **kw)
+    decode_lm = _decode_lm(args, model, train_ds, out_dir, rank, world)
+    if decode_lm is not None:
+        model.decode_controls.update(lm=decode_lm, lm_weight=args.lm_weight)
     pre = None
     if args.device_preprocess and not args.synthetic:
         from .preprocess import DevicePreprocessor
