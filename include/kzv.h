@@ -340,6 +340,29 @@ int kzv_set_head_ce(int on);
  * were: smoothing is a compile-time variant), in force from the next kzv_forward_loss.  KZV_E_ARG unless 0 <= eps < 1. */
 int kzv_set_label_smoothing(kzv_model* m, float eps);
 float kzv_get_label_smoothing(const kzv_model* m);      /* 0 for a null handle */
+/* Class weights and the focal term of the training loss (extensions, for a vocabulary with a long tail; off after kzv_model_create, and off
+ * launches the kernels that run without them).  Over the scored rows i (target y_i = labels[b][t + 1] != pad), with p_ic = softmax(z_i)[c],
+ * p_i = p_i,y_i, nll_i = lse_i - z_i[y_i], w fp32 [vocab] finite and > 0 (none: w = 1), W = sum_i w[y_i], S_w = sum_c w[c], eps the label
+ * smoothing, V the real vocabulary:
+ *   gamma = 0: F.cross_entropy(z, y, weight = w, ignore_index = pad, label_smoothing = eps)
+ *     loss          = sum_i [ (1 - eps) w[y_i] nll_i + (eps / V) (S_w lse_i - sum_c w[c] z_ic) ] / W
+ *     dlogits[i][c] = [ ((1 - eps) w[y_i] + (eps / V) S_w) p_ic - (1 - eps) w[y_i] [c == y_i] - (eps / V) w[c] ] / W
+ *   gamma > 0 (focal; eps must be 0):
+ *     loss          = sum_i w[y_i] (1 - p_i)^gamma nll_i / W
+ *     dlogits[i][c] = w[y_i] g_i (p_ic - [c == y_i]) / W,   g_i = (1 - p_i)^gamma + gamma (1 - p_i)^(gamma - 1) p_i nll_i
+ *     with nll_i clamped at 0, 1 - p_i = -expm1(-nll_i), and g_i = 0 where 1 - p_i = 0.
+ * dlogits is exactly zero in pad-target rows and in the padded columns.  W and S_w are summed on the device in a fixed order
+ * (kzv_target_weight_sum): 1 / W scales every gradient of the step.  kzv_forward_loss(train == 0) keeps the plain NLL whatever is set, as
+ * with label smoothing.  Under data parallelism every rank normalises by its own W.
+ * kzv_set_class_weights: n == vocabulary, the values are copied into device memory the handle owns (it waits for the device first);
+ *   (NULL, 0) clears them.  A wrong n or a value that is not finite and > 0: KZV_E_ARG, nothing changes.
+ * kzv_get_class_weights: the number of weights written to host_out (room for n), 0 when none are set.
+ * kzv_set_focal_gamma: 0 <= gamma <= 5, else KZV_E_ARG; KZV_E_ARG too when gamma > 0 meets a label smoothing > 0, and
+ *   kzv_set_label_smoothing refuses the reverse order. */
+int kzv_set_class_weights(kzv_model* m, const float* host_weights, int n);
+int kzv_get_class_weights(const kzv_model* m, float* host_out, int n);
+int kzv_set_focal_gamma(kzv_model* m, float gamma);
+float kzv_get_focal_gamma(const kzv_model* m);          /* 0 for a null handle */
 int kzv_decode_step_graph(kzv_model* m, const int64_t* d_tokens, const int32_t* d_posids, const uint8_t* d_valid, int64_t ld_valid,
                           float* d_logits, void* stream);
 
@@ -720,6 +743,15 @@ int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int 
  *   rows and in columns [V, ldl).  0 is kzv_ce_fwd_bwd itself (the same kernels, the same bits). */
 int kzv_ce_fwd_bwd_ls(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
                       const float* count, float* loss, void* dlogits_bf16, float label_smoothing, void* stream);
+/* The same under class weights and / or the focal exponent (kzv_set_class_weights above states both losses): norm2 = {W, S_w} on the
+ *   device, from kzv_target_weight_sum; d_class_weights fp32 [V] on the device or NULL (w = 1); 0 <= focal_gamma <= 5, and > 0 only with
+ *   label_smoothing 0, else KZV_E_ARG.  With NULL and 0 it is kzv_ce_fwd_bwd_ls (the same kernels, the same bits), norm2[0] acting as count.
+ * kzv_target_weight_sum: d_out2[0] = W = sum of w[labels[b][t + 1]] over the scored rows (t < T; not pad, inside [0, V)), d_out2[1] = S_w =
+ *   sum_{c < V} w[c]; one workgroup, a fixed order of additions: two calls give the same bits.  NULL weights: {number of scored rows, V}. */
+int kzv_ce_fwd_bwd_w(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
+                     const float* norm2, float* loss, void* dlogits_bf16, float label_smoothing, const float* d_class_weights,
+                     float focal_gamma, void* stream);
+int kzv_target_weight_sum(const int64_t* labels, int L, int B, int T, int V, int pad, const float* d_class_weights, float* d_out2, void* stream);
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, void* stream);
 /* fp32 masters -> bf16 compute copies, n matrices in one launch (what kzv_model_sync_weights does for the whole table): dst bf16
  *   [rows, cols], dstT bf16 [cols, ldT] = the transpose, or NULL.  `descs` is a HOST array of device pointers; cols % 4 == 0, and

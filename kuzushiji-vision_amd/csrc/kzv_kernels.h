@@ -46,7 +46,12 @@ int kzv_embed_gather(const int64_t* labels, int L, const int* posids, const floa
 int kzv_embed_scatter_bwd(const float* dsum, const int64_t* labels, int L, const int* posids, float* dword, float* dtype0,
                           float* dpostab, int B, int T, int Hd, int pad, hipStream_t s);
 int kzv_ce_fwd_bwd(const float* logits, int64_t ldl, const int64_t* labels, int L, int B, int T, int V, int pad,
-                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s);      // cross_entropy.hip
+                   const float* count, float* loss, bf16_t* dlogits, float label_smoothing, hipStream_t s,      // cross_entropy.hip
+                   // class weights [V] (device) and / or the focal exponent: count is then {W, S_w}, kzv_target_weight_sum's two floats
+                   const float* class_weights = nullptr, float focal_gamma = 0.f);
+int kzv_target_weight_sum(const int64_t* labels, int L, int B, int T, int V, int pad, const float* d_class_weights, float* d_out2, hipStream_t s);
+// the focal exponent's range, and no loss that nobody has stated: gamma > 0 only without label smoothing (NaN fails both tests)
+inline bool kzv_focal_ok(float gamma, float label_smoothing) { return gamma >= 0.f && gamma <= 5.f && !(gamma > 0.f && label_smoothing > 0.f); }
 int kzv_copy_logits(const float* logits, int64_t ldl, float* out, int rows, int V, hipStream_t s);
 
 struct KzvCastDesc {         // one 2-D fp32 weight -> bf16 copy (+ optional transposed copy)
@@ -144,7 +149,10 @@ struct KzvHeadCE { const bf16_t* x; const bf16_t* wp; const float* bias; const i
                    // optional (with dlogits): dh[M, 256] = dlogits . W, the head's input gradient, from wpt = W^T [256, ceil(V / 256) * 256] in fragment order
                    const bf16_t* wpt = nullptr; bf16_t* dh = nullptr;
                    // label smoothing eps in [0, 1) (kzv_ce_fwd_bwd's); 0 launches the plain instantiations
-                   float label_smoothing = 0.f; };
+                   float label_smoothing = 0.f;
+                   // class weights [V] (device) or null, and the focal exponent in [0, 5] (> 0 only with label_smoothing 0): with either,
+                   // count holds {W, S_w} (kzv_target_weight_sum) and the W instantiations run
+                   const float* class_weights = nullptr; float focal_gamma = 0.f; };
 int kzv_head_ce(const KzvHeadCE& a, hipStream_t s);
 #define KZV_PACK_MAX_JOBS (12 * KZV_DECODE_FUSED_MAX_LAYERS + 4)
 // one input-gradient GEMM of the decoder on the row-panel scheme (decoder_chain_bwd.hip): out[M, N] = a[M, K] . (packed W^T)  [+ resid | * aux]

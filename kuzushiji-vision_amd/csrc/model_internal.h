@@ -115,6 +115,11 @@ struct kzv_model_plain {
     bool dec_pack8_ok = false;
     bool dhln_fused = false;     // the last training forward's head_ce launch already wrote dhln (the LM head's input gradient)
     float label_smoothing = 0.f; // kzv_set_label_smoothing: the loss of TRAINING forwards; evaluation forwards keep the plain NLL
+    // kzv_set_focal_gamma / kzv_set_class_weights, TRAINING forwards only like label_smoothing: the focal exponent, and whether
+    // kzv_model::class_w holds weights (the host copy is what kzv_get_class_weights returns); {W, S_w} of a step live at count + 4
+    float focal_gamma = 0.f;
+    bool class_w_on = false;
+    std::vector<float> class_w_h;
     int* d_t = nullptr;          // graph-replayed decode step (kzv_decode_step_graph): device-side step index
     // slot-refill decoding (kzv_stream_*): the images kzv_model::spool holds, the geometry kzv_model::sstate was laid out for, the slots'
     // state and logits inside it, the wave in progress
@@ -174,6 +179,8 @@ struct kzv_model : kzv_model_plain {
     KzvDevBuf spool, sstate;
     // the device copy of a wave's suppress mask ((vocab + 31) / 32 words)
     KzvDevBuf smask;
+    // the class weights of the training loss, fp32 [vocab] (kzv_set_class_weights)
+    KzvDevBuf class_w;
     hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]
     const void* dg_key[3][6] = {};
     int64_t dg_ld[3] = {0, 0, 0};

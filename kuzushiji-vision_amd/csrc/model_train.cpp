@@ -6,6 +6,8 @@
 // backward = what loss.backward() does for that graph, hand-derived (no autograd), every matmul on the
 //            MFMA GEMMs of gemm.hip, everything else fused into their epilogues or the HBM-bound kernels.
 #include "model_internal.h"
+#include <algorithm>
+#include <cmath>
 
 // decoder_chain.hip: the linear chains of a decoder layer as two launches (KZV_DEC_CHAIN, kzv_set_dec_chain): 0 = off, 1 = the forward
 // chains (+ the 256 x 256 input gradients on the row-panel kernel), 2 (default) = also the backward's row-local segments, one launch each
@@ -33,10 +35,44 @@ extern "C" int kzv_set_head_ce(int on) {
 extern "C" int kzv_set_label_smoothing(kzv_model* m, float eps) {
     if (!m) return kzv_fail(KZV_E_ARG, "set_label_smoothing: null model");
     if (!(eps >= 0.f && eps < 1.f)) return kzv_fail(KZV_E_ARG, "set_label_smoothing: %g is not in [0, 1)", (double)eps);
+    if (eps > 0.f && m->focal_gamma > 0.f) return kzv_fail(KZV_E_ARG, "set_label_smoothing: %g with focal_gamma %g: no such loss is stated", (double)eps, (double)m->focal_gamma);
     m->label_smoothing = eps;
     return KZV_OK;
 }
 extern "C" float kzv_get_label_smoothing(const kzv_model* m) { return m ? m->label_smoothing : 0.f; }
+// class weights and the focal exponent of the training loss, per handle (include/kzv.h); evaluation forwards never apply them
+extern "C" int kzv_set_focal_gamma(kzv_model* m, float gamma) {
+    if (!m) return kzv_fail(KZV_E_ARG, "set_focal_gamma: null model");
+    if (!(gamma >= 0.f && gamma <= 5.f)) return kzv_fail(KZV_E_ARG, "set_focal_gamma: %g is not in [0, 5]", (double)gamma);
+    if (gamma > 0.f && m->label_smoothing > 0.f) return kzv_fail(KZV_E_ARG, "set_focal_gamma: %g with label smoothing %g: no such loss is stated", (double)gamma, (double)m->label_smoothing);
+    m->focal_gamma = gamma;
+    return KZV_OK;
+}
+extern "C" float kzv_get_focal_gamma(const kzv_model* m) { return m ? m->focal_gamma : 0.f; }
+extern "C" int kzv_set_class_weights(kzv_model* m, const float* host_weights, int n) {
+    if (!m) return kzv_fail(KZV_E_ARG, "set_class_weights: null model");
+    if (!host_weights && n == 0) { m->class_w_on = false; m->class_w_h.clear(); return KZV_OK; }
+    if (!host_weights || n != m->c.vocab) return kzv_fail(KZV_E_ARG, "set_class_weights: %d weights, the vocabulary has %d", n, m->c.vocab);
+    for (int i = 0; i < n; ++i)
+        if (!(host_weights[i] > 0.f) || std::isinf(host_weights[i])) return kzv_fail(KZV_E_ARG, "set_class_weights: weight %d is %g (finite and > 0 wanted)", i, (double)host_weights[i]);
+    // a forward in flight may still read the previous weights: wait for it, then copy (the caller's array may go away afterwards)
+    if (hipDeviceSynchronize() != hipSuccess) return kzv_fail(KZV_E_HIP, "set_class_weights: synchronise");
+    if (m->class_w.reserve(sizeof(float) * (size_t)n) == KzvDevBuf::FAILED) { m->class_w_on = false; m->class_w_h.clear(); return kzv_fail(KZV_E_HIP, "set_class_weights: allocation"); }
+    if (hipMemcpy(m->class_w.as<float>(), host_weights, sizeof(float) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+        m->class_w_on = false; m->class_w_h.clear();
+        return kzv_fail(KZV_E_HIP, "set_class_weights: copy");
+    }
+    m->class_w_h.assign(host_weights, host_weights + n);
+    m->class_w_on = true;
+    return KZV_OK;
+}
+extern "C" int kzv_get_class_weights(const kzv_model* m, float* host_out, int n) {
+    if (!m || !m->class_w_on) return 0;
+    const int have = (int)m->class_w_h.size();
+    if (!host_out || n < have) return kzv_fail(KZV_E_ARG, "get_class_weights: room for %d weights, %d are set", n, have);
+    std::copy(m->class_w_h.begin(), m->class_w_h.end(), host_out);
+    return have;
+}
 
 namespace {
 
@@ -286,18 +322,26 @@ int forward(kzv_model* m, const float* px, const int64_t* labels, float* d_loss,
     // no logits asked for (the training / validation step): head GEMM + log-softmax + NLL + dlogits in ONE launch, the [B*T, Vp] fp32
     // logits never written (cross_entropy.hip head_ce_kernel).  Otherwise the GEMM materialises them and ce_kernel follows.
     const float ls_eps = m->train ? m->label_smoothing : 0.f;          // smoothing is a training criterion: validation logs the plain NLL
+    // so are class weights and the focal term.  With either the normaliser is {W, S_w} at count + 4, summed in a fixed order
+    const float* cls_w = m->train && m->class_w_on ? m->class_w.as<float>() : nullptr;
+    const float focal = m->train ? m->focal_gamma : 0.f;
+    const float* norm = m->count;
+    if (cls_w || focal > 0.f) {
+        KZV_TRY(kzv_target_weight_sum(labels, m->L, B, T, m->V, c.pad_id, cls_w, m->count + 4, s));
+        norm = m->count + 4;
+    }
     if (fused_head) {
-        KzvHeadCE hc{m->hd_ln, m->dec_pack.as<bf16_t>() + pk.head(), P + m->word.b, labels, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
+        KzvHeadCE hc{m->hd_ln, m->dec_pack.as<bf16_t>() + pk.head(), P + m->word.b, labels, norm, m->loss_acc, m->train ? m->dlogits : nullptr, Md, m->L, T, m->V, (int)m->Vp, c.pad_id};
         static int fuse_dh = -1;     // the head's input gradient inside the same launch (KZV_HEAD_DGRAD=0: the separate GEMM)
         if (fuse_dh < 0) fuse_dh = kzv_env_int("KZV_HEAD_DGRAD", 1);
         m->dhln_fused = m->train && fuse_dh && m->word.h.ldt % 8 == 0;
         if (m->dhln_fused) { hc.wpt = m->dec_pack.as<bf16_t>() + pk.head_t(); hc.dh = m->dhln; }
-        hc.label_smoothing = ls_eps;
+        hc.label_smoothing = ls_eps; hc.class_weights = cls_w; hc.focal_gamma = focal;
         KZV_TRY(kzv_head_ce(hc, s));
     } else {
         m->dhln_fused = false;
         KZV_TRY(lin_fwd(m, m->word, m->hd_ln, Hd, Md, m->logits, m->Vp, KZV_EPI_F32, s, {.n = m->Vp}));
-        KZV_TRY(kzv_ce_fwd_bwd(m->logits, m->Vp, labels, m->L, B, T, m->V, c.pad_id, m->count, m->loss_acc, m->train ? m->dlogits : nullptr, ls_eps, s));
+        KZV_TRY(kzv_ce_fwd_bwd(m->logits, m->Vp, labels, m->L, B, T, m->V, c.pad_id, norm, m->loss_acc, m->train ? m->dlogits : nullptr, ls_eps, s, cls_w, focal));
     }
     if (d_loss && hipMemcpyAsync(d_loss, m->loss_acc, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return kzv_fail(KZV_E_HIP, "forward: loss copy");

@@ -225,6 +225,8 @@ SYMBOLS = {
     "kzv_embed_scatter_bwd": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "kzv_ce_fwd_bwd": (C.c_int, [_P, C.c_int64, _P] + [C.c_int] * 5 + [_P, _P, _P, _P]),
     "kzv_ce_fwd_bwd_ls": (C.c_int, [_P, C.c_int64, _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_float, _P]),
+    "kzv_ce_fwd_bwd_w": (C.c_int, [_P, C.c_int64, _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_float, _P, C.c_float, _P]),
+    "kzv_target_weight_sum": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P]),
     "kzv_copy_logits": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P]),
     "kzv_cast_weights": (C.c_int, [C.POINTER(kzv_cast_desc), C.c_int, _P]),
     "kzv_attn_fwd": (C.c_int, [C.POINTER(kzv_attn_args), _P]),
@@ -291,6 +293,10 @@ SYMBOLS = {
     "kzv_set_head_ce": (C.c_int, [C.c_int]),
     "kzv_set_label_smoothing": (C.c_int, [C.c_void_p, C.c_float]),
     "kzv_get_label_smoothing": (C.c_float, [C.c_void_p]),
+    "kzv_set_class_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "kzv_get_class_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "kzv_set_focal_gamma": (C.c_int, [C.c_void_p, C.c_float]),
+    "kzv_get_focal_gamma": (C.c_float, [C.c_void_p]),
     "kzv_decode_step_graph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "kzv_decode_reorder": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "kzv_decode_prep": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -43,12 +43,15 @@ class TrOCRModel:
     def __init__(self, encoder_config: dict[str, Any], decoder_path: str, learning_rate: float = 1e-4,
                  beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, weight_decay: float = 0,
                  *, device: str = "cuda", init_seed: int = 42, load_tokenizer: bool = True, width_buckets=None,
-                 fp8: bool = False, long_sequences: bool = False, decode_weights: str = "bf16", label_smoothing: float = 0.0):
+                 fp8: bool = False, long_sequences: bool = False, decode_weights: str = "bf16", label_smoothing: float = 0.0,
+                 class_weights=None, focal_gamma: float = 0.0):
         import torch
         self._check_label_smoothing(label_smoothing)
+        self._check_focal_gamma(focal_gamma, label_smoothing)
         self.hparams = types.SimpleNamespace(encoder_config=encoder_config, decoder_path=decoder_path,
                                              learning_rate=learning_rate, beta1=beta1, beta2=beta2,
-                                             epsilon=epsilon, weight_decay=weight_decay, label_smoothing=float(label_smoothing))
+                                             epsilon=epsilon, weight_decay=weight_decay, label_smoothing=float(label_smoothing),
+                                             class_weights=None, focal_gamma=0.0)
         dec_cfg = load_decoder_config(decoder_path)          # FileNotFoundError like scripts/train_trocr.py:88-89
         self.cfg = ModelConfig.from_reference(encoder_config, dec_cfg)
         # long_sequences (include/kzv.h: KZV_MODEL_LONG_SEQ): encoders with head_dim 64 or 96 take up to 4,097 tokens, attention
@@ -118,6 +121,10 @@ class TrOCRModel:
         # label smoothing of the TRAINING loss (an extension; include/kzv.h: kzv_set_label_smoothing): F.cross_entropy(label_smoothing=eps)
         # inside the loss kernels; evaluation forwards (val_loss, test) keep the plain loss.  0 = the reference's criterion.
         self.label_smoothing = label_smoothing
+        # class weights and the focal term of the TRAINING loss (extensions; include/kzv.h: kzv_set_class_weights states both losses):
+        # F.cross_entropy(weight=w) and (1 - p_t)^gamma inside the loss kernels; evaluation forwards keep the plain loss.  None / 0 = off.
+        self.class_weights = class_weights
+        self.focal_gamma = focal_gamma
         self._offsets, total = P.param_offsets(c)
         if lib.kzv_param_total(h) != total:
             raise L.KzvError("parameter table mismatch between kzv/params.py and libkzv")
@@ -272,8 +279,52 @@ class TrOCRModel:
     @label_smoothing.setter
     def label_smoothing(self, eps: float) -> None:
         self._check_label_smoothing(eps)
+        if float(eps) > 0.0 and self.hparams.focal_gamma > 0.0:
+            raise ValueError(f"label_smoothing {eps!r} with focal_gamma {self.hparams.focal_gamma!r}: no such loss is stated; set one of them to 0")
         L.check(L.load().kzv_set_label_smoothing(self._h, float(eps)), "kzv_set_label_smoothing")
         self.hparams.label_smoothing = float(eps)
+
+    @staticmethod
+    def _check_focal_gamma(gamma, eps) -> None:
+        if not 0.0 <= float(gamma) <= 5.0:
+            raise ValueError(f"focal_gamma must be in [0, 5], not {gamma!r}")
+        if float(gamma) > 0.0 and float(eps) > 0.0:
+            raise ValueError(f"focal_gamma {gamma!r} with label_smoothing {eps!r}: no such loss is stated; set one of them to 0")
+
+    @property
+    def focal_gamma(self) -> float:
+        """gamma of the focal modulation (1 - p_t)^gamma of the training loss, 0 <= gamma <= 5 (0: off), only with label_smoothing 0.
+        Training-mode forwards only, like label_smoothing; recorded in hparams (kzv_set_focal_gamma)."""
+        return self.hparams.focal_gamma
+
+    @focal_gamma.setter
+    def focal_gamma(self, gamma: float) -> None:
+        self._check_focal_gamma(gamma, self.hparams.label_smoothing)
+        L.check(L.load().kzv_set_focal_gamma(self._h, float(gamma)), "kzv_set_focal_gamma")
+        self.hparams.focal_gamma = float(gamma)
+
+    @property
+    def class_weights(self):
+        """Per-class weights of the training loss, F.cross_entropy(weight=w): a float32 CPU tensor [vocab], or None (off).  Accepts a tensor,
+        an ndarray or a list of length vocab, every value finite and > 0.  Training-mode forwards only; the loss and every gradient are
+        normalised by the sum of the targets' weights, as torch does.  Recorded in hparams (kzv_set_class_weights copies the values)."""
+        return self.hparams.class_weights
+
+    @class_weights.setter
+    def class_weights(self, w) -> None:
+        import torch
+        lib = L.load()
+        if w is None:
+            L.check(lib.kzv_set_class_weights(self._h, None, 0), "kzv_set_class_weights")
+            self.hparams.class_weights = None
+            return
+        t = torch.as_tensor(w).detach().to(device="cpu", dtype=torch.float32).contiguous().clone()
+        if t.dim() != 1 or t.numel() != self.cfg.vocab:
+            raise ValueError(f"class_weights must hold {self.cfg.vocab} values (the vocabulary), not shape {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+            raise ValueError("class_weights must be finite and > 0")
+        L.check(lib.kzv_set_class_weights(self._h, t.data_ptr(), t.numel()), "kzv_set_class_weights")
+        self.hparams.class_weights = t
 
     def train(self, mode: bool = True):
         self.training = mode

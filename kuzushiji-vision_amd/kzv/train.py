@@ -97,6 +97,22 @@ def parse_args(argv=None):
                         "the published TrOCR recipe uses 0.1): train_loss in the logs is then the SMOOTHED loss, while val_loss and the test "
                         "losses stay the plain cross-entropy, so checkpoints rank and runs compare as without it; the value is written into "
                         "the checkpoints' hyper_parameters; 0 = off, the reference's criterion")
+    p.add_argument("--class_weights", type=str, default="none", metavar="{none,inv_sqrt,effective,PATH.npy}",
+                   help="per-class weights of the TrOCR training loss (an extension; nn.CrossEntropyLoss(weight=...)) for the long tail of the "
+                        "vocabulary, from how often each character is a target in the training split: inv_sqrt = count ** -0.5, effective = "
+                        "(1 - beta) / (1 - beta ** count) (class-balanced loss), both clamped to --class_weight_cap and scaled so that an "
+                        "average training token weighs 1; PATH.npy = float32 weights [vocab] of your own (kzv.classweights builds them); "
+                        "train_loss in the logs is then the WEIGHTED loss, while val_loss and the test losses stay the plain "
+                        "cross-entropy, so checkpoints rank and runs compare as without it; the weights are written into the checkpoints' "
+                        "hyper_parameters; none = off, the reference's criterion")
+    p.add_argument("--class_weight_beta", type=float, default=0.999, help="beta of --class_weights effective, in (0, 1)")
+    p.add_argument("--class_weight_cap", type=float, default=10.0,
+                   help="largest ratio between two weights of --class_weights inv_sqrt / effective (>= 1): rarer classes are clamped to it")
+    p.add_argument("--focal_gamma", type=float, default=0.0,
+                   help="focal modulation of the TrOCR training loss (an extension): every target's loss is scaled by (1 - p_target) ** gamma, "
+                        "0 <= gamma <= 5, so characters the model already gets right count less; combines with --class_weights, not with "
+                        "--label_smoothing; train_loss in the logs is then the FOCAL loss, while val_loss and the test losses stay the "
+                        "plain cross-entropy; 0 = off, the reference's criterion")
     p.add_argument("--skip_test", action="store_true", help="do not run the reference's post-fit test phase (scripts/train_trocr.py:193-195)")
     p.add_argument("--ema_decay", type=float, default=0.0, help="> 0 attaches kzv.ema.EMACallback (reference: decay 0.9999)")
     # the ResNet34 / BiLSTM / CTC model of ocr_lightning/model.py behind ocr_lightning/train.py's own flags (:161-189)
@@ -117,6 +133,19 @@ def parse_args(argv=None):
     if args.label_smoothing and args.model == "ocr":
         p.error("--label_smoothing applies to the TrOCR cross-entropy only: --model ocr trains with CTC and SmoothL1 losses, which have no "
                 "softmax cross-entropy to smooth")
+    if not 0.0 <= args.focal_gamma <= 5.0:
+        p.error(f"--focal_gamma must be in [0, 5], not {args.focal_gamma}")
+    if args.focal_gamma > 0 and args.label_smoothing > 0:
+        p.error("--focal_gamma and --label_smoothing do not combine: nobody has stated that loss; set one of them to 0")
+    if args.class_weights not in ("none", "inv_sqrt", "effective") and not args.class_weights.endswith(".npy"):
+        p.error(f"--class_weights must be none, inv_sqrt, effective or a .npy file, not {args.class_weights}")
+    if not 0.0 < args.class_weight_beta < 1.0:
+        p.error(f"--class_weight_beta must be in (0, 1), not {args.class_weight_beta}")
+    if not args.class_weight_cap >= 1.0:
+        p.error(f"--class_weight_cap must be >= 1, not {args.class_weight_cap}")
+    if args.model == "ocr" and (args.class_weights != "none" or args.focal_gamma > 0 or args.class_weight_beta != 0.999 or args.class_weight_cap != 10.0):
+        p.error("--class_weights / --class_weight_beta / --class_weight_cap / --focal_gamma apply to the TrOCR cross-entropy only: "
+                "--model ocr trains with CTC and SmoothL1 losses")
     if args.model == "ocr" and (args.lm_path or args.lm_order or args.lm_weight):
         p.error("--lm_path / --lm_order / --lm_weight act on the TrOCR decodes only: --model ocr decodes with CTC, which has no "
                 "step-wise scores to fuse a language model into")
@@ -157,6 +186,35 @@ def _decode_lm(args, model, train_ds, out_dir, rank, world=1):
     if rank == 0:
         print(f"language model: order {lm.order}, contexts {lm.n_contexts()}, weight {args.lm_weight}" + ("" if args.lm_weight else " (off)"))
     return lm if args.lm_weight else None
+
+
+def _label_rows(train_ds):
+    """The training split's label ids, row by row, without opening an image where the dataset keeps its texts."""
+    if hasattr(train_ds, "data") and getattr(train_ds, "tokenizer", None) is not None:
+        return [train_ds.tokenizer(t, max_length=train_ds.max_length, truncation=True)["input_ids"] for t in train_ds.data["text"]]
+    return [train_ds[i]["labels"].numpy() for i in range(len(train_ds))]
+
+
+def _class_weights(args, model, train_ds, rank):
+    """The weights --class_weights asks for (None: off), said once.  Every rank derives the same weights from the same split."""
+    import numpy as np
+    from . import classweights as CW
+    if args.class_weights == "none":
+        return None
+    c = model.cfg
+    if args.class_weights.endswith(".npy"):
+        w = np.load(args.class_weights).astype(np.float32).reshape(-1)
+        what, cap = args.class_weights, None
+    else:
+        counts = CW.count_targets(_label_rows(train_ds), c.vocab, c.pad_id)
+        if args.class_weights == "inv_sqrt":
+            w = CW.from_counts(counts, "inv_pow", power=0.5, cap=args.class_weight_cap)
+        else:
+            w = CW.from_counts(counts, "effective", beta=args.class_weight_beta, cap=args.class_weight_cap)
+        what, cap = f"{args.class_weights} over {int(counts.sum())} targets, {int((counts > 0).sum())} of {c.vocab} classes seen", args.class_weight_cap
+    if rank == 0:
+        print(f"class weights: {what}: {CW.describe(w, cap)} (train_loss is the weighted loss; val_loss stays the plain cross-entropy)")
+    return w
 
 
 def main_ocr(args):
@@ -309,7 +367,7 @@ def main(argv=None):
     model = TrOCRModel(encoder_config, decoder_path, learning_rate=args.learning_rate, beta1=args.beta1, beta2=args.beta2,
                        epsilon=args.epsilon, weight_decay=args.weight_decay, device=f"cuda:{local}", init_seed=args.seed,
                        fp8=args.precision == "fp8-mixed", long_sequences=True, decode_weights=args.decode_weights,
-                       label_smoothing=args.label_smoothing)
+                       label_smoothing=args.label_smoothing, focal_gamma=args.focal_gamma)
     model._step_seed = 1_000_003 * rank
     model.decode_controls = {k: v for k, v, off in (("no_repeat_ngram_size", args.no_repeat_ngram_size, 0),
                                                     ("repetition_penalty", args.repetition_penalty, 1.0),
@@ -335,6 +393,7 @@ def main(argv=None):
                   max_length=args.max_length, train_ratio=args.train_ratio, val_ratio=args.val_ratio, test_ratio=args.test_ratio)
         kw["device_preprocess"] = args.device_preprocess
         train_ds, val_ds, test_ds = LineCsvDataset(split="train", **kw), LineCsvDataset(split="val", **kw), LineCsvDataset(split="test", **kw)
+    model.class_weights = _class_weights(args, model, train_ds, rank)
     decode_lm = _decode_lm(args, model, train_ds, out_dir, rank, world)
     if decode_lm is not None:
         model.decode_controls.update(lm=decode_lm, lm_weight=args.lm_weight)
@@ -351,6 +410,8 @@ def main(argv=None):
         print(f"augmentation: {args.augment}" + (f" (seed {aug[2]}, training batches only)" if aug else ""))
         if args.label_smoothing:
             print(f"label smoothing: {args.label_smoothing} (train_loss is the smoothed loss; val_loss stays the plain cross-entropy)")
+        if args.focal_gamma:
+            print(f"focal loss: gamma {args.focal_gamma} (train_loss is the focal loss; val_loss stays the plain cross-entropy)")
     train_loader = make_loader(train_ds, args.batch_size, True, args.seed, rank, world, num_workers=nw, preprocessor=pre, augment=aug)
     val_loader = make_loader(val_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)
     test_loader = make_loader(test_ds, args.batch_size, False, args.seed, rank, world, num_workers=nw, preprocessor=pre)   # scripts/train_trocr.py:93

@@ -220,7 +220,12 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     model.load_state_dict(sd, strict=True)
     # the training criterion travels with the weights; a checkpoint without the key (every reference checkpoint) means the plain loss
     hp = ck.get("hyper_parameters") or {}
-    model.label_smoothing = float(hp.get("label_smoothing", 0.0) if isinstance(hp, dict) else getattr(hp, "label_smoothing", 0.0))
+    def hparam(name, default):
+        return hp.get(name, default) if isinstance(hp, dict) else getattr(hp, name, default)
+    model.focal_gamma = 0.0                     # (first: the two setters refuse a gamma > 0 beside an eps > 0, in either order)
+    model.label_smoothing = float(hparam("label_smoothing", 0.0))
+    model.focal_gamma = float(hparam("focal_gamma", 0.0))
+    model.class_weights = hparam("class_weights", None)
     if opt is not None and osd is not None:
         opt.load_state_dict(osd)
     for cb in callbacks:
