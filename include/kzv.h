@@ -523,6 +523,15 @@ int kzv_backward_segments(const kzv_model* m);
 int kzv_backward_segment(kzv_model* m, int seg, void* stream);
 int kzv_backward_segment_range(const kzv_model* m, int seg, int64_t* lo, int64_t* hi);
 int kzv_backward(kzv_model* m, void* stream);               /* all segments */
+/* Frozen bottom of the encoder (fine-tuning), 0 <= n <= encoder layers, 0 (the default) = everything trains.  n > 0 freezes the patch
+ * embedding, the CLS token, the position table and encoder layers 0 .. n-1: kzv_backward and kzv_backward_segment launch NOTHING for
+ * segments > Le - n and return KZV_OK, so those gradients stay what kzv_zero_grads left; the last segment that runs joins the side
+ * stream as the embedding segment does otherwise.  The encoder's final LayerNorm, proj and the decoder (segment 0) always train.  The
+ * forward is unchanged (dropout stays on in frozen layers in train mode); kzv_backward_segment_range is unchanged.  The optimizer must
+ * be told separately (lr_scale 0 over the same range in kzv_clip_and_step_groups), or weight decay and the z iterate still move the
+ * frozen parameters.  KZV_E_ARG: null model, n out of range; get returns 0 for a null handle. */
+int kzv_set_frozen_encoder_layers(kzv_model* m, int n);
+int kzv_get_frozen_encoder_layers(const kzv_model* m);
 
 /* gradient_clip_val (scripts/train_trocr.py:175) + RAdamScheduleFree.step (trocr_model.py:412-421),
  * fused over the flat buffers.  d_z, d_v: optimizer state (z iterate, second moment), same layout.
@@ -545,6 +554,26 @@ int kzv_clip_and_step(float* d_params, float* d_z, float* d_v, const float* d_gr
  * after every batch) updated in the same pass from the freshly stepped parameters; d_ema NULL = no EMA. */
 int kzv_clip_and_step_ema(float* d_params, float* d_z, float* d_v, const float* d_grads, int64_t n,
                           const float* d_sqnorm, const kzv_opt_step* s, float* d_ema, float ema_decay, void* stream);
+/* Parameter groups (fine-tuning): the same norm and the same step over a table of ranges of the flat buffer, each with a factor on
+ * the learning rate and one on the weight decay.  The table is DEVICE memory: sorted, contiguous, covering [0, n) exactly, every
+ * boundary a multiple of 64 floats (the parameter table guarantees it), 1 <= n_groups <= KZV_OPT_MAX_GROUPS.  Its contents cannot be
+ * checked here without reading the device: kzv.optim.check_groups does it on the host before the upload; a table that breaks these
+ * rules gives wrong scales, never an access outside the buffers.
+ *   per element of a group: kzv_clip_and_step's arithmetic with lr_t * lr_scale (both places lr_t enters) and weight_decay * wd_scale;
+ *     ckp1 is shared by all groups (a scale constant in time cancels in schedulefree's weight / weight_sum).
+ *   lr_scale == 0: FROZEN.  p, z, v and the EMA shadow of the range are neither read nor written (v does not decay), its gradients do not
+ *     enter the norm (torch's clip_grad_norm_ sees only parameters that have a gradient), so the clip coefficient is the trainable
+ *     groups' own.
+ *   one group (1, 1): the bits of kzv_grad_sqnorm / kzv_clip_and_step_ema.  The norm's sum order is fixed: the same bits from run to run.
+ * One launch whatever n_groups is, the plain kernels' bytes per trainable parameter.  KZV_E_ARG: a null pointer (d_ema and, without
+ * clipping, d_sqnorm may be null), n % 4 != 0, n_groups outside its range, an EMA decay outside [0, 1]. */
+#define KZV_OPT_MAX_GROUPS 4096
+typedef struct kzv_opt_group { int64_t lo, hi; float lr_scale, wd_scale; } kzv_opt_group;   /* floats [lo, hi) */
+int kzv_grad_sqnorm_groups(const float* d_grads, int64_t n, const kzv_opt_group* d_groups, int n_groups,
+                           float* d_out1, float* d_scratch, void* stream);
+int kzv_clip_and_step_groups(float* d_params, float* d_z, float* d_v, const float* d_grads, int64_t n,
+                             const float* d_sqnorm, const kzv_opt_step* s, const kzv_opt_group* d_groups, int n_groups,
+                             float* d_ema, float ema_decay, void* stream);
 /* optimizer.eval()/train() parameter swap (trocr_model.py:423-451): p <- p + w*(z - p) */
 int kzv_lerp_params(float* d_params, const float* d_z, int64_t n, float w, void* stream);
 

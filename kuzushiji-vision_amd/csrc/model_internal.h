@@ -118,6 +118,7 @@ struct kzv_model_plain {
     // kzv_set_focal_gamma / kzv_set_class_weights, TRAINING forwards only like label_smoothing: the focal exponent, and whether
     // kzv_model::class_w holds weights (the host copy is what kzv_get_class_weights returns); {W, S_w} of a step live at count + 4
     float focal_gamma = 0.f;
+    int frozen_enc = 0;          // kzv_set_frozen_encoder_layers: backward segments > Le - frozen_enc launch nothing
     bool class_w_on = false;
     std::vector<float> class_w_h;
     int* d_t = nullptr;          // graph-replayed decode step (kzv_decode_step_graph): device-side step index

@@ -40,6 +40,15 @@ extern "C" int kzv_set_label_smoothing(kzv_model* m, float eps) {
     return KZV_OK;
 }
 extern "C" float kzv_get_label_smoothing(const kzv_model* m) { return m ? m->label_smoothing : 0.f; }
+
+// frozen bottom of the encoder, per handle: kzv_backward_segment skips the segments below the cut (embeddings and layers 0 .. n-1)
+extern "C" int kzv_set_frozen_encoder_layers(kzv_model* m, int n) {
+    if (!m) return kzv_fail(KZV_E_ARG, "set_frozen_encoder_layers: null model");
+    if (n < 0 || n > m->Le) return kzv_fail(KZV_E_ARG, "set_frozen_encoder_layers: %d is not in 0..%d", n, m->Le);
+    m->frozen_enc = n;
+    return KZV_OK;
+}
+extern "C" int kzv_get_frozen_encoder_layers(const kzv_model* m) { return m ? m->frozen_enc : 0; }
 // class weights and the focal exponent of the training loss, per handle (include/kzv.h); evaluation forwards never apply them
 extern "C" int kzv_set_focal_gamma(kzv_model* m, float gamma) {
     if (!m) return kzv_fail(KZV_E_ARG, "set_focal_gamma: null model");
@@ -651,6 +660,9 @@ extern "C" int kzv_backward_segment(kzv_model* m, int seg, void* stream) {
     if (!m || !m->bound || !m->G) return kzv_fail(KZV_E_STATE, "backward: no gradient buffer bound");
     if (!m->have_fwd) return kzv_fail(KZV_E_STATE, "backward: call kzv_forward_loss(train=1) first");
     if (seg < 0 || seg >= m->Le + 2) return kzv_fail(KZV_E_ARG, "backward: bad segment");
+    // frozen bottom of the encoder: the segments below the cut launch nothing, the last one above it does the final join
+    const int last_seg = m->frozen_enc > 0 ? m->Le - m->frozen_enc : m->Le + 1;
+    if (seg > last_seg) return KZV_OK;
     hipStream_t s = (hipStream_t)stream;
     int rc;
     {
@@ -662,7 +674,7 @@ extern "C" int kzv_backward_segment(kzv_model* m, int seg, void* stream) {
     if (rc != KZV_OK) return rc;
     // contract: in `stream` order, this segment's gradient range is final -> the side stream must be joined
     // (kzv_backward, which has no consumer between segments, joins once at the end instead)
-    if (m->join_each_segment || seg == m->Le + 1) return join_side(m, s);
+    if (m->join_each_segment || seg == last_seg) return join_side(m, s);
     return KZV_OK;
 }
 

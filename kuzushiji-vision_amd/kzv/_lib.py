@@ -28,6 +28,13 @@ class kzv_opt_step(C.Structure):
                 ("adaptive", C.c_int32), ("max_grad_norm", C.c_float), ("grad_scale", C.c_float), ("one_minus_beta2", C.c_float)]
 
 
+class kzv_opt_group(C.Structure):
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("lr_scale", C.c_float), ("wd_scale", C.c_float)]
+
+
+OPT_MAX_GROUPS = 4096
+
+
 class kzv_gemm_nt_args(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64),
                 ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p),
@@ -196,6 +203,8 @@ SYMBOLS = {
     "kzv_grad_sqnorm": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "kzv_clip_and_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.POINTER(kzv_opt_step), _P]),
     "kzv_clip_and_step_ema": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.POINTER(kzv_opt_step), _P, C.c_float, _P]),
+    "kzv_grad_sqnorm_groups": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    "kzv_clip_and_step_groups": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.POINTER(kzv_opt_step), _P, C.c_int, _P, C.c_float, _P]),
     "kzv_lerp_params": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
     "kzv_gemm_nt": (C.c_int, [C.POINTER(kzv_gemm_nt_args), C.c_int, _P]),
     "kzv_set_rows_max_m": (C.c_int, [C.c_int]),
@@ -293,6 +302,8 @@ SYMBOLS = {
     "kzv_set_head_ce": (C.c_int, [C.c_int]),
     "kzv_set_label_smoothing": (C.c_int, [C.c_void_p, C.c_float]),
     "kzv_get_label_smoothing": (C.c_float, [C.c_void_p]),
+    "kzv_set_frozen_encoder_layers": (C.c_int, [C.c_void_p, C.c_int]),
+    "kzv_get_frozen_encoder_layers": (C.c_int, [C.c_void_p]),
     "kzv_set_class_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "kzv_get_class_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "kzv_set_focal_gamma": (C.c_int, [C.c_void_p, C.c_float]),

@@ -51,7 +51,9 @@ class TrOCRModel:
         self.hparams = types.SimpleNamespace(encoder_config=encoder_config, decoder_path=decoder_path,
                                              learning_rate=learning_rate, beta1=beta1, beta2=beta2,
                                              epsilon=epsilon, weight_decay=weight_decay, label_smoothing=float(label_smoothing),
-                                             class_weights=None, focal_gamma=0.0)
+                                             class_weights=None, focal_gamma=0.0,
+                                             # fine-tuning (kzv/finetune.py); the defaults are "off", and a checkpoint without the keys loads as such
+                                             frozen_encoder_layers=0, layer_decay=1.0, decay_exempt="none", accumulate_grad_batches=1)
         dec_cfg = load_decoder_config(decoder_path)          # FileNotFoundError like scripts/train_trocr.py:88-89
         self.cfg = ModelConfig.from_reference(encoder_config, dec_cfg)
         # long_sequences (include/kzv.h: KZV_MODEL_LONG_SEQ): encoders with head_dim 64 or 96 take up to 4,097 tokens, attention
@@ -284,6 +286,20 @@ class TrOCRModel:
         L.check(L.load().kzv_set_label_smoothing(self._h, float(eps)), "kzv_set_label_smoothing")
         self.hparams.label_smoothing = float(eps)
 
+    @property
+    def frozen_encoder_layers(self) -> int:
+        """Frozen bottom of the encoder, 0 <= n <= encoder layers (0: everything trains).  n > 0 freezes the patch embedding, the CLS token, the
+        position table and encoder layers 0 .. n-1: the backward launches nothing for them (kzv_set_frozen_encoder_layers) and their
+        gradients stay zero.  The optimizer is told separately (kzv.finetune.apply gives the same ranges lr_scale 0).  Recorded in hparams."""
+        return self.hparams.frozen_encoder_layers
+
+    @frozen_encoder_layers.setter
+    def frozen_encoder_layers(self, n: int) -> None:
+        if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= self.cfg.enc_layers:
+            raise ValueError(f"frozen_encoder_layers must be an integer in 0..{self.cfg.enc_layers}, not {n!r}")
+        L.check(L.load().kzv_set_frozen_encoder_layers(self._h, int(n)), "kzv_set_frozen_encoder_layers")
+        self.hparams.frozen_encoder_layers = int(n)
+
     @staticmethod
     def _check_focal_gamma(gamma, eps) -> None:
         if not 0.0 <= float(gamma) <= 5.0:
@@ -419,11 +435,13 @@ class TrOCRModel:
         return {"generated_ids": self.generate(pixel_values, max_length=128, num_beams=4, early_stopping=True, **self.decode_controls),
                 "logits": None}
 
-    def backward(self) -> None:
-        """loss.backward() of the last training-mode forward: fills flat_grads (zeroed first)."""
+    def backward(self, accumulate: bool = False) -> None:
+        """loss.backward() of the last training-mode forward: fills flat_grads (zeroed first).  ``accumulate`` skips the zeroing, so the
+        pass adds to what the buffer holds (every gradient kernel adds: DESIGN.md section 7)."""
         lib = L.load()
         st = L.stream_handle()
-        L.check(lib.kzv_zero_grads(self._h, st), "zero_grads")
+        if not accumulate:
+            L.check(lib.kzv_zero_grads(self._h, st), "zero_grads")
         L.check(lib.kzv_backward(self._h, st), "kzv_backward")
 
     # ------------------------------------------------------------------ per-character confidence and position

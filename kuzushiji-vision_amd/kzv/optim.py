@@ -18,6 +18,27 @@ import math
 from . import _lib as L
 
 
+def check_groups(groups, n: int):
+    """The host-side check of a group table for kzv_clip_and_step_groups (the library cannot read the device copy): a sequence of
+    (lo, hi, lr_scale, wd_scale), sorted, contiguous, covering [0, n) exactly, every boundary a multiple of 64 floats, 1..4096 entries,
+    finite scales >= 0.  Returns the table as a list of tuples; ValueError otherwise."""
+    out = [(int(lo), int(hi), float(ls), float(ws)) for lo, hi, ls, ws in groups]
+    if not 1 <= len(out) <= L.OPT_MAX_GROUPS:
+        raise ValueError(f"{len(out)} parameter groups: 1..{L.OPT_MAX_GROUPS} are served")
+    at = 0
+    for lo, hi, ls, ws in out:
+        if lo != at or hi <= lo:
+            raise ValueError(f"parameter groups must be sorted, contiguous and non-empty: [{lo}, {hi}) follows {at}")
+        if lo % 64 or hi % 64:
+            raise ValueError(f"group boundary [{lo}, {hi}) is not a multiple of 64 floats")
+        if not (math.isfinite(ls) and math.isfinite(ws) and ls >= 0.0 and ws >= 0.0):
+            raise ValueError(f"group scales must be finite and >= 0, not ({ls}, {ws})")
+        at = hi
+    if at != n:
+        raise ValueError(f"parameter groups cover [0, {at}), the buffer has {n} floats")
+    return out
+
+
 class RAdamScheduleFree:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  r=0.0, weight_lr_power=2.0, silent_sgd_phase=True):
@@ -37,6 +58,24 @@ class RAdamScheduleFree:
         self._scratch = torch.zeros(2048, dtype=torch.float32, device=flat.device)
         self._ema = None            # (shadow tensor, decay): kzv.ema.EMACallback attaches itself so that step() fuses its update
         self.param_groups = [{"lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
+        self.groups = None          # set_groups: the host table [(lo, hi, lr_scale, wd_scale)], or None = today's single-group kernels
+        self._d_groups = None
+
+    def set_groups(self, groups):
+        """Parameter groups over the flat buffer (kzv.finetune.build_groups): [(lo, hi, lr_scale, wd_scale)] checked by check_groups and
+        uploaded once; step() then runs kzv_grad_sqnorm_groups / kzv_clip_and_step_groups.  lr_scale 0 freezes a range.  None (the default)
+        = the plain entry points.  The state keeps its single-group layout either way (z and v of a frozen range simply stay put)."""
+        import numpy as np
+        import torch
+        if groups is None:
+            self.groups = self._d_groups = None
+            return
+        table = check_groups(groups, self.model.flat_params.numel())
+        arr = np.zeros(len(table), dtype=np.dtype([("lo", "<i8"), ("hi", "<i8"), ("lr_scale", "<f4"), ("wd_scale", "<f4")]))
+        for i, row in enumerate(table):
+            arr[i] = row
+        self.groups = table
+        self._d_groups = torch.from_numpy(arr.view(np.uint8).copy()).to(self.model.flat_params.device)
 
     # ---- per-step scalars (identical to oracle.RAdamScheduleFreeState.next_scalars) ----
     def _next_scalars(self):
@@ -68,14 +107,24 @@ class RAdamScheduleFree:
         self._last_scale = abs(grad_scale)
         st = L.stream_handle()
         n = m.flat_params.numel()
+        grouped = self._d_groups is not None
         if max_grad_norm > 0:
-            L.check(lib.kzv_grad_sqnorm(m.flat_grads.data_ptr(), n, self._sq.data_ptr(), self._scratch.data_ptr(), st), "grad_sqnorm")
+            if grouped:
+                L.check(lib.kzv_grad_sqnorm_groups(m.flat_grads.data_ptr(), n, self._d_groups.data_ptr(), len(self.groups),
+                                                   self._sq.data_ptr(), self._scratch.data_ptr(), st), "grad_sqnorm_groups")
+            else:
+                L.check(lib.kzv_grad_sqnorm(m.flat_grads.data_ptr(), n, self._sq.data_ptr(), self._scratch.data_ptr(), st), "grad_sqnorm")
         s = L.kzv_opt_step(lr_t=lr, ckp1=ckp1, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
                            weight_decay=self.weight_decay, bias_correction2=bc2, adaptive=int(adaptive),
                            max_grad_norm=max_grad_norm, grad_scale=grad_scale, one_minus_beta2=1.0 - self.beta2)
         ema, decay = self._ema if self._ema is not None else (None, 0.0)
-        L.check(lib.kzv_clip_and_step_ema(m.flat_params.data_ptr(), self.z.data_ptr(), self.v.data_ptr(),
-                                          m.flat_grads.data_ptr(), n, self._sq.data_ptr(), C.byref(s), L.ptr(ema), decay, st), "clip_and_step")
+        if grouped:
+            L.check(lib.kzv_clip_and_step_groups(m.flat_params.data_ptr(), self.z.data_ptr(), self.v.data_ptr(), m.flat_grads.data_ptr(), n,
+                                                 self._sq.data_ptr(), C.byref(s), self._d_groups.data_ptr(), len(self.groups),
+                                                 L.ptr(ema), decay, st), "clip_and_step_groups")
+        else:
+            L.check(lib.kzv_clip_and_step_ema(m.flat_params.data_ptr(), self.z.data_ptr(), self.v.data_ptr(),
+                                              m.flat_grads.data_ptr(), n, self._sq.data_ptr(), C.byref(s), L.ptr(ema), decay, st), "clip_and_step")
         self.ema_fused_steps = getattr(self, "ema_fused_steps", 0) + (1 if ema is not None else 0)
         m.sync_weights()
 

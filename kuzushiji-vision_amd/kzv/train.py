@@ -125,9 +125,40 @@ def parse_args(argv=None):
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--patience", type=int, default=3)
     p.add_argument("--resume", type=str, default=None,
-                   help="--model ocr: continue from a checkpoint this CLI (or Lightning, for the reference) wrote -- weights, Adam moments and "
-                        "step count, epoch (pl.Trainer.fit(ckpt_path=...))")
+                   help="continue from a checkpoint this CLI (or Lightning, for the reference) wrote (pl.Trainer.fit(ckpt_path=...)): "
+                        "--model ocr: weights, Adam moments and step count, epoch; TrOCR: weights, optimizer state, epoch and global step, and "
+                        "the checkpoint's fine-tuning settings where the flags below are left at their defaults")
+    # fine-tuning (extensions; kzv/finetune.py), TrOCR only
+    p.add_argument("--init_from", type=str, default=None,
+                   help="start from the WEIGHTS of a checkpoint (strict: every key, no other); the optimizer starts fresh, epoch and step at 0")
+    p.add_argument("--freeze_encoder_layers", type=int, default=0,
+                   help="freeze the patch embedding, the CLS token, the position table and encoder layers 0 .. N-1 (0 <= N <= "
+                        "--encoder_num_layers): no backward, no optimizer traffic, no all-reduce for them; 0 = off")
+    p.add_argument("--layer_decay", type=float, default=1.0,
+                   help="layer-wise learning-rate decay (BEiT's): a parameter of encoder layer i trains with lr * D ** (layers - i), the "
+                        "embeddings with D ** (layers + 1), the decoder with lr; 0 < D <= 1, 1 = off")
+    p.add_argument("--decay_exempt", type=str, default="none", choices=["none", "bias_norm"],
+                   help="bias_norm: no weight decay on biases, LayerNorm gains and the encoder's CLS and position tables")
+    p.add_argument("--accumulate_grad_batches", type=int, default=1,
+                   help="one optimizer step per K batches (Lightning's): gradients add up over K forward + backward passes and are divided by "
+                        "K; --max_steps counts optimizer steps; 1 = off")
     args = p.parse_args(argv)
+    if not 0.0 < args.layer_decay <= 1.0:
+        p.error(f"--layer_decay must be in (0, 1], not {args.layer_decay}")
+    if not 0 <= args.freeze_encoder_layers <= args.encoder_num_layers:
+        p.error(f"--freeze_encoder_layers must be in 0..{args.encoder_num_layers} (--encoder_num_layers), not {args.freeze_encoder_layers}")
+    if args.accumulate_grad_batches < 1:
+        p.error(f"--accumulate_grad_batches must be >= 1, not {args.accumulate_grad_batches}")
+    if args.init_from and args.resume:
+        p.error("--init_from and --resume do not combine: one starts the optimizer fresh, the other continues it")
+    if args.model == "ocr":
+        for flag, on, why in (("--init_from", args.init_from, "--model ocr loads weights together with its Adam state: use --resume"),
+                              ("--freeze_encoder_layers", args.freeze_encoder_layers, "--model ocr has no ViT encoder layers to freeze"),
+                              ("--layer_decay", args.layer_decay != 1.0, "--model ocr has no ViT encoder whose layers a decay could follow"),
+                              ("--decay_exempt", args.decay_exempt != "none", "--model ocr trains with torch's Adam, which has no parameter-range table"),
+                              ("--accumulate_grad_batches", args.accumulate_grad_batches != 1, "--model ocr's step has no accumulation window")):
+            if on:
+                p.error(f"{flag} applies to the TrOCR model only: {why}")
     if not 0.0 <= args.label_smoothing < 1.0:
         p.error(f"--label_smoothing must be in [0, 1), not {args.label_smoothing}")
     if args.label_smoothing and args.model == "ocr":
@@ -421,9 +452,39 @@ def main(argv=None):
     if args.ema_decay > 0:
         from .ema import EMACallback
         cbs.append(EMACallback(args.ema_decay))
+    # fine-tuning: where the run starts (--init_from: weights; --resume: weights, optimizer state, epoch, step and the checkpoint's
+    # fine-tuning settings) and what trains how (frozen layers on the model, the range table on the optimizer)
+    from . import finetune
+    from .trainer import load_checkpoint
+    opt = model.configure_optimizers()
+    start_epoch = start_step = 0
+    ft = dict(layer_decay=args.layer_decay, freeze_encoder_layers=args.freeze_encoder_layers, decay_exempt=args.decay_exempt)
+    accumulate = args.accumulate_grad_batches
+    if args.init_from:
+        from .checkpoint import read_checkpoint
+        sd, _ = read_checkpoint(torch.load(args.init_from, map_location="cpu", weights_only=False), model.cfg)
+        model.load_state_dict(sd, strict=True)
+        opt.z.copy_(model.flat_params)              # a fresh optimizer: its z iterate starts at the loaded weights
+        if rank == 0:
+            print(f"Initialised the weights from {args.init_from}; the optimizer starts fresh")
+    if args.resume:
+        ck = load_checkpoint(model, opt, args.resume)
+        start_epoch, start_step = int(ck.get("epoch", 0)), int(ck.get("global_step", 0))
+        if finetune.is_default(**ft):               # flags left alone: the checkpoint's settings (load_checkpoint has applied them)
+            ft = dict(layer_decay=model.hparams.layer_decay, freeze_encoder_layers=model.hparams.frozen_encoder_layers,
+                      decay_exempt=model.hparams.decay_exempt)
+        if accumulate == 1:
+            accumulate = int(model.hparams.accumulate_grad_batches)
+        if rank == 0:
+            print(f"Resumed from {args.resume}: epoch {start_epoch}, global step {start_step}")
+    groups = finetune.apply(model, opt, **ft)
+    if rank == 0 and (groups is not None or accumulate != 1):
+        print(finetune.summary(groups if groups is not None else [(0, model.flat_params.numel(), 1.0, 1.0)])
+              + f"; accumulate_grad_batches {accumulate}")
+    main.start = (start_epoch, start_step)
     hist = fit(model, train_loader, val_loader, max_epochs=args.max_epochs, max_steps=args.max_steps, log_every=50,
                val_check_interval=0.5, ckpt_dir=os.path.join(out_dir, "checkpoints"), world=world, rank=rank,
-               callbacks=cbs)
+               callbacks=cbs, accumulate_grad_batches=accumulate, optimizer=opt, start_epoch=start_epoch, start_step=start_step)
     if rank == 0:
         print(f"Training completed! Checkpoints saved to: {os.path.join(out_dir, 'checkpoints')}")
     # scripts/train_trocr.py:193-195: if test_loader is not None: trainer.test(model, test_loader, ckpt_path="best")

@@ -79,15 +79,27 @@ def bucket_plan(seg_ranges, bucket_elems: int):
 
 class Stepper:
     """One training step of the hot path: forward+loss, segmented backward with overlapped bucketed
-    all-reduce, clip, RAdamScheduleFree step, bf16 weight refresh."""
+    all-reduce, clip, RAdamScheduleFree step, bf16 weight refresh.
+
+    ``accumulate_grad_batches = k > 1`` (Lightning's): ``step`` is then called once per micro-batch.  The gradient buffer is zeroed
+    before a window's first micro-batch, every backward adds into it, the all-reduce runs only during the window's last backward
+    (Lightning's no_sync) and ONE optimizer step closes the window with grad_scale = 1 / (k * world) -- also for the short window
+    at the end of an epoch (``last_batch=True``), as Lightning divides every micro-batch loss by k.  ``stepped`` says whether the
+    call ended in an optimizer step; the loss returned is then the mean of the window's micro-batch losses (summed on the device).
+    With k = 1 (the default) a step launches exactly what it always launched."""
 
     def __init__(self, model, optimizer, world: int = 1, max_grad_norm: float = 1.0, bucket_mb: float = 64.0,
-                 dp_path: bool | None = None):
+                 dp_path: bool | None = None, accumulate_grad_batches: int = 1):
         self.model, self.opt, self.world, self.max_grad_norm = model, optimizer, world, max_grad_norm
         # the data-parallel branch of step(); with one rank it is a rehearsal (a 1-rank all-reduce is the identity)
         self.dp_path = (world > 1 or dp_forced()) if dp_path is None else bool(dp_path)
+        self._init_window(accumulate_grad_batches)
         lib = L.load()
         n = lib.kzv_backward_segments(model._h)
+        # a frozen bottom of the encoder: the segments below the cut launch nothing, their ranges are never all-reduced
+        frozen = lib.kzv_get_frozen_encoder_layers(model._h)
+        if frozen > 0:
+            n = n - 1 - frozen
         self.seg_ranges = []
         for s in range(n):
             lo, hi = C.c_int64(), C.c_int64()
@@ -97,17 +109,34 @@ class Stepper:
         # count low; 64 MB fp32 buckets -> ~7 collectives per 393 MB gradient set.
         self.buckets = bucket_plan(self.seg_ranges, int(bucket_mb * 1024 * 1024 / 4))
 
-    def step(self, batch, batch_idx: int = 0):
-        m, lib = self.model, L.load()
-        loss, _ = m.forward_loss(batch["pixel_values"], batch["labels"], want_logits=False)
-        st = L.stream_handle()
-        L.check(lib.kzv_zero_grads(m._h, st), "zero_grads")
-        works = []
+    def _init_window(self, k) -> None:
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, not {k!r}")
+        self.accumulate_grad_batches = int(k)
+        self._micro = 0              # micro-batches of the open window that have run
+        self._loss_sum = None        # their losses, added up on the device
+        self.stepped = False
+
+    # ---- the four device operations of a micro-batch (a test replaces them to record the schedule) ----
+    def _forward(self, batch):
+        loss, _ = self.model.forward_loss(batch["pixel_values"], batch["labels"], want_logits=False)
+        return loss
+
+    def _zero(self) -> None:
+        L.check(L.load().kzv_zero_grads(self.model._h, L.stream_handle()), "zero_grads")
+
+    def _backward(self, sync: bool) -> None:
+        """The backward of the last forward, adding into the gradient buffer; ``sync``: all-reduce the buckets as their segments finish."""
+        m, lib, st = self.model, L.load(), L.stream_handle()
         if not self.dp_path:     # no consumer between segments: let the engine overlap across them
             L.check(lib.kzv_backward(m._h, st), "backward")
-            self.opt.step(max_grad_norm=self.max_grad_norm, grad_scale=1.0)
-            return loss
+            return
+        if not sync:             # no_sync: the same segmented launches, no collective
+            for s in range(len(self.seg_ranges)):
+                L.check(lib.kzv_backward_segment(m._h, s, st), "backward_segment")
+            return
         import torch.distributed as dist
+        works = []
         bi = 0
         for s in range(len(self.seg_ranges)):
             L.check(lib.kzv_backward_segment(m._h, s, st), "backward_segment")
@@ -119,38 +148,70 @@ class Stepper:
                 bi += 1
         for w in works:
             w.wait()
-        self.opt.step(max_grad_norm=self.max_grad_norm, grad_scale=1.0 / self.world)
-        return loss
+
+    def _opt_step(self, grad_scale: float) -> None:
+        self.opt.step(max_grad_norm=self.max_grad_norm, grad_scale=grad_scale)
+
+    def step(self, batch, batch_idx: int = 0, last_batch: bool = False):
+        k = self.accumulate_grad_batches
+        if k == 1:
+            loss = self._forward(batch)
+            self._zero()
+            self._backward(True)
+            self._opt_step(1.0 / self.world if self.dp_path else 1.0)
+            self.stepped = True
+            return loss
+        loss = self._forward(batch)
+        if self._micro == 0:
+            self._zero()
+            self._loss_sum = loss.clone()
+        else:
+            self._loss_sum += loss           # _loss is one device scalar overwritten per forward
+        self._micro += 1
+        closing = self._micro == k or last_batch
+        self._backward(closing)
+        self.stepped = closing
+        if not closing:
+            return None
+        self._opt_step(1.0 / (k * self.world))
+        mean = self._loss_sum / self._micro
+        self._micro = 0
+        return mean
 
 
 def fit(model, train_loader, val_loader=None, max_epochs: int = 1, max_steps: int = -1, log_every: int = 50,
         val_check_interval: float = 0.5, ckpt_dir: str | None = None, world: int = 1, rank: int = 0, log=print,
-        callbacks=()):
+        callbacks=(), accumulate_grad_batches: int = 1, optimizer=None, start_epoch: int = 0, start_step: int = 0):
     """Minimal Trainer.fit: epochs over the loader, validation every ``val_check_interval`` of an epoch
-    (scripts/train_trocr.py:174), rank-0 checkpoints named like the reference (:138)."""
+    (scripts/train_trocr.py:174), rank-0 checkpoints named like the reference (:138).
+    ``accumulate_grad_batches`` (Lightning's): one optimizer step per that many batches (``Stepper``); the global step, ``max_steps``
+    and ``log_every`` count optimizer steps, validation intervals count batches.  ``optimizer``: the model's optimizer when the caller
+    has already configured it (parameter groups, a resumed state); ``start_epoch`` / ``start_step``: where a resumed run continues."""
     import torch
-    opt = model.configure_optimizers()
-    stepper = Stepper(model, opt, world=world)
+    opt = optimizer if optimizer is not None else model.configure_optimizers()
+    stepper = Stepper(model, opt, world=world, accumulate_grad_batches=accumulate_grad_batches)
+    model.hparams.accumulate_grad_batches = stepper.accumulate_grad_batches
     for cb in callbacks:          # e.g. kzv.ema.EMACallback (scripts/train_trocr.py:154,182)
         cb.on_fit_start(model)
-    gstep = 0
+    gstep = int(start_step)
     history = []
     best, save_top_k = [], 3          # (val_loss, path) of the kept checkpoints
     fit.best_model_path = None
     n_batches = len(train_loader)
     val_every = max(1, int(n_batches * val_check_interval)) if val_loader is not None else 0
-    for epoch in range(max_epochs):
+    for epoch in range(int(start_epoch), max_epochs):
         if hasattr(train_loader, "set_epoch"):
             train_loader.set_epoch(epoch)          # DataLoader(shuffle=True) / DistributedSampler.set_epoch: a new order per epoch
         model.train()
         model.on_train_epoch_start()
         t0 = time.time()
         for i, batch in enumerate(train_loader):
-            loss = stepper.step(batch, i)
-            gstep += 1
-            for cb in callbacks:
-                cb.on_train_batch_end(model)
-            if gstep % log_every == 0 or gstep == 1:
+            loss = stepper.step(batch, i, last_batch=i == n_batches - 1)
+            if stepper.stepped:
+                gstep += 1
+                for cb in callbacks:
+                    cb.on_train_batch_end(model)
+            if stepper.stepped and (gstep % log_every == 0 or gstep == 1):
                 lv = float(loss.item())
                 history.append((gstep, lv))
                 if rank == 0:
@@ -226,6 +287,11 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     model.label_smoothing = float(hparam("label_smoothing", 0.0))
     model.focal_gamma = float(hparam("focal_gamma", 0.0))
     model.class_weights = hparam("class_weights", None)
+    # so do the fine-tuning settings (kzv/finetune.py): frozen layers on the model, the group table on the optimizer; no keys = off
+    from . import finetune
+    ft = finetune.settings_from_hparams(hp)
+    model.hparams.accumulate_grad_batches = ft.pop("accumulate_grad_batches")
+    finetune.apply(model, opt, **ft)
     if opt is not None and osd is not None:
         opt.load_state_dict(osd)
     for cb in callbacks:
