@@ -273,6 +273,12 @@ typedef struct kzv_beam_state {
     float* run_scores; float* fin_scores;                /* [batch, num_beams] */
     uint8_t* fin_done; int64_t* fin_len;                 /* [batch, num_beams] */
     uint8_t* unsatisfied;                                /* [batch] */
+    /* optional, all four or none (null = off: the launch is the one without them): the per-token log-probabilities of the token rows,
+     * fp32 [batch, num_beams, max_len], double-buffered and swapped like them.  The lanes that copy a token row copy its log-probability
+     * row the same way: the parent's row, plus top_scores[k] - run_scores[parent of k] (the scores BEFORE this call) at `cur` -- one fp32
+     * subtraction, HF compute_transition_scores.  The caller zeroes both buffers before the first call. */
+    const float* run_lp_in; float* run_lp_out;
+    const float* fin_lp_in; float* fin_lp_out;
 } kzv_beam_state;
 int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
                     float length_penalty, int64_t* d_rows, int32_t* d_flags, void* stream);
@@ -427,8 +433,8 @@ int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* strea
  * kzv_stream_topk between the vocabulary GEMM and selection -- one more kernel node of the same single chain -- into d_alt_ids /
  * d_alt_logprob [n_images, ld_alt >= max_len * k], which the caller has filled (-1 / 0) and keeps alive for the wave.  k = 0 switches it
  * off again; the next kzv_stream_begin clears it; when not set a step launches exactly what it launches without this call.  Launches
- * nothing itself.  KZV_E_STATE outside a begun greedy wave and for beam waves (a beam winner's per-token values are not produced on the
- * slots); KZV_E_ARG for k outside 0..8, null arrays, ld_alt < max_len * k. */
+ * nothing itself.  KZV_E_STATE outside a begun greedy wave and for beam waves (a beam search's per-token candidates are not produced on the
+ * slots; its per-token log-probabilities leave through kzv_stream_set_nbest); KZV_E_ARG for k outside 0..8, null arrays, ld_alt < max_len * k. */
 int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, float* d_alt_logprob, int64_t ld_alt, void* stream);
 
 /* ---- Beam search on the same slots (opt-in; kzv/stream.py: beam_select_seat / beam_stream state the bookkeeping in torch ops) ------------
@@ -453,7 +459,8 @@ int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, float* d_alt_lo
  * KZV_E_ARG: a null array other than out_score / limit / rows, num_beams other than 2 or 4, max_len outside 2..128, output rows shorter
  * than max_len, row table rows shorter than max_len - 1. */
 typedef struct kzv_stream_beam_state {
-    int32_t slots, n_images, num_beams, max_len, vocab, bos_id, eos_id, pad_id, early_stopping, reserved;
+    int32_t slots, n_images, num_beams, max_len, vocab, bos_id, eos_id, pad_id, early_stopping;
+    int32_t n_best;                                      /* 0 = off, else 1..num_beams: see the n-best fields below */
     int32_t* slot_image; int32_t* slot_t;                /* [slots] */
     int64_t* tokens; int32_t* posids;                    /* [slots * num_beams]: the next step's inputs */
     int64_t* run_seq; int64_t* fin_seq;                  /* [slots, num_beams, max_len] */
@@ -467,6 +474,18 @@ typedef struct kzv_stream_beam_state {
     const int32_t* limit;                                /* optional [n_images] */
     const float* divisors;                               /* [max_len + 1] */
     int32_t* rows; int64_t ld_rows;                      /* optional beam row table [slots * num_beams, ld_rows >= max_len - 1] */
+    /* N-best (n_best in 1..num_beams; HF generate(num_return_sequences = n_best)): when image i's search ends, finished rows r = 0 ..
+     * n_best - 1 go to row i * n_best + r of nbest_ids (only fin_len[r] tokens: the caller fills BOS / padding), nbest_scores and
+     * nbest_len (tokens, BOS included).  A finished entry that never received a hypothesis writes no tokens, score -1e9 and length 0.
+     * Row 0 is what out_ids / out_score get, which are written as before.
+     * run_lp / fin_lp (optional, both or none, need n_best): fp32 [slots, num_beams, max_len], the per-token log-probabilities of the
+     * token rows, carried as kzv_beam_state's (seat_first zeroes them); with them nbest_logprob (optional) gets the rows' values, column
+     * t = the log-probability of the token in column t, 0 in column 0 (the caller fills zeros).
+     * KZV_E_ARG: n_best outside 0..num_beams, null ids / scores / lengths, rows shorter than max_len, any of these fields with n_best 0. */
+    float* run_lp; float* fin_lp;
+    int64_t* nbest_ids; int64_t ld_nbest;                /* [n_images * n_best, ld_nbest >= max_len] */
+    float* nbest_scores; int32_t* nbest_len;             /* [n_images * n_best] */
+    float* nbest_logprob; int64_t ld_nbest_logprob;      /* optional [n_images * n_best, ld_nbest_logprob >= max_len] */
 } kzv_stream_beam_state;
 int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void* stream);
 int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream);
@@ -476,7 +495,7 @@ int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_s
  * else 0; launches nothing; KZV_E_STATE before kzv_model_bind.
  * kzv_stream_begin_beams: kzv_stream_begin for a wave of beam searches (generate's num_beams, early_stopping, length_penalty): lays the
  * beam state out in the handle's slot state, builds the divisor table, uses the handle's first beam row table.  d_out_scores: optional
- * fp32 [n_images].  d_out_logprob must be null (per-token log-probabilities of a beam winner are not produced).  Argument errors as
+ * fp32 [n_images].  d_out_logprob must be null (per-token log-probabilities of a beam search leave through kzv_stream_set_nbest).  Argument errors as
  * kzv_stream_begin's, before any launch; the pool must hold at least bound batch / num_beams images.
  * kzv_stream_encode / kzv_stream_start / kzv_stream_step / kzv_stream_poll then serve the wave as they serve a greedy one; a step is the
  * one-launch step (slot instances with 2 / 4 rows and the row table), the vocabulary GEMM, kzv_beam_topk and kzv_stream_beam_update, in
@@ -486,6 +505,17 @@ int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_stopping, floa
                            int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob, int64_t ld_logprob,
                            const int32_t* d_limit, void* stream);
 int kzv_stream_poll_beams(kzv_model* m, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream);
+/* N-best lists and per-token log-probabilities for the beam wave just begun: after kzv_stream_begin_beams and before kzv_stream_start
+ * (as kzv_stream_set_topk for a greedy wave).  Every search that ends then also writes rows 0 .. n_best - 1 of its finished list to
+ * d_ids [n_images * n_best, ld_ids] int64 (the caller has filled BOS / padding), d_scores fp32 and d_lengths int32 [n_images * n_best],
+ * image-major, best first (kzv_stream_beam_state's n-best fields); row 0 is the wave's d_out_ids / d_out_scores row.  d_logprob:
+ * optional fp32 [n_images * n_best, ld_logprob] (the caller has filled zeros): the handle then allocates the log-probability rows
+ * beside its token rows and every step carries them (the LP instance of the update kernel); without it the step moves what it moves
+ * without this call and only the end of a search writes more.  One captured graph still serves every step.  The setting belongs to
+ * one wave: the next begin clears it.  Launches no kernel itself.  KZV_E_STATE outside a begun wave; KZV_E_ARG for a greedy wave, n_best
+ * outside 1..num_beams, null ids / scores / lengths, a leading dimension shorter than max_len -- before any launch. */
+int kzv_stream_set_nbest(kzv_model* m, int n_best, int64_t* d_ids, int64_t ld_ids, float* d_scores, int32_t* d_lengths, float* d_logprob,
+                         int64_t ld_logprob, void* stream);
 /* Generation controls for the wave just begun (greedy or beams): after kzv_stream_begin / kzv_stream_begin_beams and before
  * kzv_stream_start.  Every kzv_stream_step then runs kzv_logits_process as one more kernel node of the same single chain, between the
  * vocabulary GEMM and kzv_stream_topk / selection in a greedy wave (histories: the wave's out_ids); in a beam wave the normalising

@@ -426,7 +426,9 @@ static int stream_begin(kzv_model* m, const char* who, int nb, int early, float 
     } else {
         kzv_stream_beam_state& st = m->sbst;
         st.slots = slots; st.n_images = n_images; st.num_beams = nb; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id;
-        st.eos_id = eos_id; st.early_stopping = early ? 1 : 0; st.reserved = 0;
+        st.eos_id = eos_id; st.early_stopping = early ? 1 : 0;
+        st.n_best = 0; st.run_lp = st.fin_lp = nullptr;      // kzv_stream_set_nbest belongs to one wave
+        st.nbest_ids = nullptr; st.ld_nbest = 0; st.nbest_scores = nullptr; st.nbest_len = nullptr; st.nbest_logprob = nullptr; st.ld_nbest_logprob = 0;
         st.tokens = (int64_t*)q; q += (size_t)B * 8;                       // 8-byte words first
         st.run_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
         st.fin_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
@@ -483,6 +485,27 @@ extern "C" int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, floa
     if (k && ld_alt < (int64_t)m->sst.max_len * k) return kzv_fail(KZV_E_ARG, "stream_set_topk: ld_alt %lld < max_len * k = %lld", (long long)ld_alt, (long long)m->sst.max_len * k);
     if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
     m->stopk = k; m->salt_ids = k ? d_alt_ids : nullptr; m->salt_lp = k ? d_alt_logprob : nullptr; m->sld_alt = k ? ld_alt : 0;
+    return KZV_OK;
+}
+
+extern "C" int kzv_stream_set_nbest(kzv_model* m, int n_best, int64_t* d_ids, int64_t ld_ids, float* d_scores, int32_t* d_lengths, float* d_logprob,
+                                    int64_t ld_logprob, void* stream) {
+    (void)stream;                                // nothing is launched: kzv_stream_start zeroes the log-probability rows with the token rows
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_nbest: call kzv_stream_begin_beams first");
+    if (!m->sbeams) return kzv_fail(KZV_E_ARG, "stream_set_nbest: the wave is greedy (an n-best list needs a beam search: kzv_stream_begin_beams)");
+    kzv_stream_beam_state& st = m->sbst;
+    if (n_best < 1 || n_best > st.num_beams) return kzv_fail(KZV_E_ARG, "stream_set_nbest: n_best %d outside 1..num_beams = %d", n_best, st.num_beams);
+    if (!d_ids || !d_scores || !d_lengths) return kzv_fail(KZV_E_ARG, "stream_set_nbest: null ids / scores / lengths");
+    if (ld_ids < st.max_len || (d_logprob && ld_logprob < st.max_len)) return kzv_fail(KZV_E_ARG, "stream_set_nbest: output rows shorter than max_len = %d", st.max_len);
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
+    st.run_lp = st.fin_lp = nullptr;
+    if (d_logprob) {                             // the log-probability rows, laid out as the token rows are: [slots, num_beams, max_len]
+        const size_t rows = (size_t)m->B * st.max_len;
+        if (!reserve(m, m->snbest, 2 * rows * sizeof(float))) return kzv_fail(KZV_E_HIP, "stream_set_nbest: log-probability rows allocation");
+        st.run_lp = m->snbest.as<float>(); st.fin_lp = st.run_lp + rows;
+    }
+    st.n_best = n_best; st.nbest_ids = d_ids; st.ld_nbest = ld_ids; st.nbest_scores = d_scores; st.nbest_len = d_lengths;
+    st.nbest_logprob = d_logprob; st.ld_nbest_logprob = d_logprob ? ld_logprob : 0;
     return KZV_OK;
 }
 

@@ -180,6 +180,8 @@ struct kzv_model : kzv_model_plain {
     KzvDevBuf spool, sstate;
     // the device copy of a wave's suppress mask ((vocab + 31) / 32 words)
     KzvDevBuf smask;
+    // the log-probability rows of a beam wave (kzv_stream_set_nbest with d_logprob): run_lp | fin_lp, fp32 [bound batch, max_len] each
+    KzvDevBuf snbest;
     // the class weights of the training loss, fp32 [vocab] (kzv_set_class_weights)
     KzvDevBuf class_w;
     hipGraphExec_t dgraph[3] = {nullptr, nullptr, nullptr};          // one per row table in use: none, rowtab[0], rowtab[1]

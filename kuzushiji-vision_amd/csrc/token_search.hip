@@ -270,6 +270,8 @@ struct BeamUpd {
     int* flags;                                                   // [5]: images still unsatisfied, images whose finished list is not full, images with a continuation that did not stop; [3] = stopped, [4] = updates applied
     int nb, K, L, V, cur, eos, early;
     float div;                                                    // cur ** length_penalty as fp32: the length divisor of a hypothesis that ends at this step
+    const float* run_lp_in; float* run_lp_out;                    // [B, nb, L] fp32 or null: the token rows' per-token log-probabilities (LP instance)
+    const float* fin_lp_in; float* fin_lp_out;
 };
 
 // One image's step, ranked: what one lane works out between the loads and the row copies.  The inputs are filled by the lanes together
@@ -345,17 +347,29 @@ __device__ __forceinline__ void beam_rank(BeamRank& r, BeamRankOut& o, int nb, i
     o.un = r.unsat && any; o.done_new = done_new; o.all_hits = all_hits;
 }
 
+// the log-probability of continuation k's own token: its accumulated score minus its parent beam's OLD running score, one fp32 subtraction
+// (kzv/beam.py: top_lp[k] - run_sc[src[k]]; HF compute_transition_scores).  s_old: the nb running scores read before they are replaced.
+__device__ __forceinline__ void beam_token_lp(const BeamRank& r, int K, const float* s_old, float* s_tlp) {
+    for (int k = 0; k < K; ++k) s_tlp[k] = r.lp[k] - s_old[r.src[k]];
+}
+
+// LP: the token rows' log-probability rows go through the same copies (run_lp / fin_lp, double-buffered alike).  The off instance holds
+// none of it: no extra LDS, loads or stores.
+template <bool LP>
 __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
     __shared__ BeamRank r;
+    __shared__ float s_old[LP ? 8 : 1], s_tlp[LP ? 16 : 1];
     const int img = blockIdx.x, lane = threadIdx.x;
     const int nb = p.nb, K = p.K, L = p.L;
     if (p.flags[3]) return;                      // the search has ended (beam_stop_kernel): steps issued before the host noticed change nothing
     // the ~40 state words of this image
     beam_rank_load(r, lane, K, nb, img, p.top_lp, p.top_ix, p.fin_sc, p.fin_done, p.fin_len, p.unsat);
+    if constexpr (LP) { if (lane >= 40 && lane < 40 + nb) s_old[lane - 40] = p.run_sc[img * nb + lane - 40]; }      // before lane 0 replaces them
     __syncthreads();
     if (lane == 0) {
         BeamRankOut o;
         beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, p.div);
+        if constexpr (LP) beam_token_lp(r, K, s_old, s_tlp);
         for (int i = 0; i < nb; ++i) {
             p.rows[img * nb + i] = (int64_t)img * nb + r.src[r.nxt[i]];
             p.run_sc[img * nb + i] = o.run_new[i];
@@ -383,6 +397,20 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
             const int64_t* csrc = p.run_seq_in + ((int64_t)img * nb + r.src[kk]) * L;
             for (int j = lane; j < L; j += 64) fdst[j] = j == p.cur ? (int64_t)r.tok[kk] : csrc[j];
         }
+        if constexpr (LP) {                      // the same rows of run_lp / fin_lp, the token's own value at cur
+            const float* lsrc = p.run_lp_in + ((int64_t)img * nb + r.src[k]) * L;
+            float* ldst = p.run_lp_out + ((int64_t)img * nb + i) * L;
+            for (int j = lane; j < L; j += 64) ldst[j] = j == p.cur ? s_tlp[k] : lsrc[j];
+            float* lfdst = p.fin_lp_out + ((int64_t)img * nb + i) * L;
+            if (mi < nb) {
+                const float* lfsrc = p.fin_lp_in + ((int64_t)img * nb + mi) * L;
+                for (int j = lane; j < L; j += 64) lfdst[j] = lfsrc[j];
+            } else {
+                const int kk = mi - nb;
+                const float* lcsrc = p.run_lp_in + ((int64_t)img * nb + r.src[kk]) * L;
+                for (int j = lane; j < L; j += 64) lfdst[j] = j == p.cur ? s_tlp[kk] : lcsrc[j];
+            }
+        }
     }
 }
 
@@ -391,7 +419,8 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
 // beam_topk_kernel has ranked every slot's 2 nb continuations: (1) stream_beam_update_kernel, one workgroup per slot: beam_rank at
 // cur = slot_t + 1 with the slot's own divisor, then the token rows, the beam row table and the scores in place -- the slot's old rows
 // are staged in LDS first, since ONE captured graph serves every step and there is no even / odd buffer to alternate; when the image's
-// search has ended, its best finished row and score go to the outputs; (2) stream_beam_seat_kernel, ONE workgroup over all slots:
+// search has ended, its best finished row and score go to the outputs (NBEST: its n_best best rows, LP: with their per-token
+// log-probabilities); (2) stream_beam_seat_kernel, ONE workgroup over all slots:
 // stream_seat_kernel's prefix sum, the reset of every reseated slot's beam state, the counters.
 struct StreamBeamP {
     const float* top_lp; const int64_t* top_ix;                     // [slots, 2 nb]
@@ -405,18 +434,35 @@ struct StreamBeamP {
     const float* div;                                               // [L + 1]: fp32 of n ** length_penalty
     int* rows; int64_t ld_rows;                                     // beam row table [slots * nb, ld_rows] or null
 };
-constexpr int SB_NB = 4, SB_L = 128;                                // what the staging holds: 2 x 4 x 128 token rows (8 KB) + 4 x 128 table entries
+// what the NBEST / LP instances of stream_beam_update_kernel take beside it (all null / 0 for the plain instance, which reads none of it)
+struct StreamNBestP {
+    float* run_lp; float* fin_lp;                                   // [slots, nb, L] fp32: the token rows' log-probability rows (LP)
+    int n_best;                                                     // rows 0 .. n_best - 1 of the finished list leave when a search ends
+    int64_t* ids; int64_t ld_ids; float* score; int* len;           // [n_images * n_best, ld_ids], [n_images * n_best]
+    float* lp; int64_t ld_lp;                                       // optional [n_images * n_best, ld_lp] (LP)
+};
+constexpr int SB_NB = 4, SB_L = 128;                                // what the staging holds: 2 x 4 x 128 token rows (8 KB) + 4 x 128 table entries; LP: 2 x 4 x 128 fp32 (4 KB) more
 
 // token j of merged finished row mi from the staged rows: an old finished row (mi < nb), or continuation mi - nb = its beam's prefix + the token at cur
 __device__ __forceinline__ int64_t beam_fin_token(const BeamRank& r, int mi, int j, int cur, int nb, int L, const int64_t* s_fin, const int64_t* s_run) {
     return mi < nb ? s_fin[mi * L + j] : (j == cur ? (int64_t)r.tok[mi - nb] : s_run[r.src[mi - nb] * L + j]);
 }
 
-__global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBeamP p) {
+// its log-probability, from the staged log-probability rows in the same way (s_tlp: the continuations' own values at cur)
+__device__ __forceinline__ float beam_fin_lp(const BeamRank& r, int mi, int j, int cur, int nb, int L, const float* s_flp, const float* s_rlp, const float* s_tlp) {
+    return mi < nb ? s_flp[mi * L + j] : (j == cur ? s_tlp[mi - nb] : s_rlp[r.src[mi - nb] * L + j]);
+}
+
+// NBEST: at the end of a search rows 0 .. n_best - 1 of the finished list leave, not only row 0.  LP (needs NBEST): the log-probability
+// rows are staged and moved beside the token rows.  The plain instance <false, false> holds none of either: its LDS and its code are
+// those of the kernel without them.
+template <bool NBEST, bool LP>
+__global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBeamP p, const StreamNBestP q) {
     __shared__ BeamRank r;
     __shared__ BeamRankOut o;                    // the ranking lane's results, for every thread
     __shared__ int64_t s_run[SB_NB * SB_L], s_fin[SB_NB * SB_L];
     __shared__ int s_rt[SB_NB * SB_L];
+    __shared__ float s_rlp[LP ? SB_NB * SB_L : 1], s_flp[LP ? SB_NB * SB_L : 1], s_old[LP ? 8 : 1], s_tlp[LP ? 16 : 1];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int nb = p.nb, K = 2 * nb, L = p.L;
     const int img = p.slot_image[s];
@@ -430,9 +476,16 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
     beam_rank_load(r, tid, K, nb, s, p.top_lp, p.top_ix, p.fin_sc, p.fin_done, p.fin_len, p.unsat);
     // the slot's old rows: whole rows, as the statement moves them (what lies behind cur may be an earlier image's and is never read)
     for (int e = tid; e < nb * L; e += 256) { s_run[e] = p.run_seq[(int64_t)s * nb * L + e]; s_fin[e] = p.fin_seq[(int64_t)s * nb * L + e]; }
+    if constexpr (LP) {
+        for (int e = tid; e < nb * L; e += 256) { s_rlp[e] = q.run_lp[(int64_t)s * nb * L + e]; s_flp[e] = q.fin_lp[(int64_t)s * nb * L + e]; }
+        if (tid >= 40 && tid < 40 + nb) s_old[tid - 40] = p.run_sc[s * nb + tid - 40];      // the old running scores, before they are replaced below
+    }
     if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; s_rt[i * L + j] = p.rows[((int64_t)s * nb + i) * p.ld_rows + j]; }
     __syncthreads();
-    if (tid == 0) { BeamRankOut mine; beam_rank(r, mine, nb, K, p.V, p.eos, cur, lim, p.early, div); o = mine; }
+    if (tid == 0) {
+        BeamRankOut mine; beam_rank(r, mine, nb, K, p.V, p.eos, cur, lim, p.early, div); o = mine;
+        if constexpr (LP) beam_token_lp(r, K, s_old, s_tlp);
+    }
     __syncthreads();
     const bool go_on = o.un && !(o.done_new && p.early) && !o.all_hits;      // beam_search's go_on, for this image
     if (!go_on) {
@@ -441,6 +494,20 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
         if (img < p.n_images)
             for (int j = tid; j < min(n, L); j += 256)
                 p.out_ids[(int64_t)img * p.ld_ids + j] = beam_fin_token(r, mi, j, cur, nb, L, s_fin, s_run);
+        if constexpr (NBEST) {
+            // rows 0 .. n_best - 1 of the finished list, each over its own length only; an entry that never received a hypothesis
+            // writes no tokens, score -1e9 and length 0 (the host checks for it)
+            if (img < p.n_images)
+                for (int rr = 0; rr < q.n_best; ++rr) {
+                    const int mr = r.mix[rr], nr = o.fd_new[rr] ? min((int)o.fl_new[rr], L) : 0;
+                    const int64_t row = (int64_t)img * q.n_best + rr;
+                    for (int j = tid; j < nr; j += 256) {
+                        q.ids[row * q.ld_ids + j] = beam_fin_token(r, mr, j, cur, nb, L, s_fin, s_run);
+                        if constexpr (LP) { if (q.lp) q.lp[row * q.ld_lp + j] = beam_fin_lp(r, mr, j, cur, nb, L, s_flp, s_rlp, s_tlp); }
+                    }
+                    if (tid == 0) { q.score[row] = o.fd_new[rr] ? o.fsc_new[rr] : -1.0e9f; q.len[row] = nr; }
+                }
+        }
         if (tid == 0) {
             if (p.out_score && img < p.n_images) p.out_score[img] = o.fsc_new[0];
             p.sel[2 * s] = 1; p.sel[2 * s + 1] = 0;
@@ -452,6 +519,10 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
         const int k = r.nxt[i], mi = r.mix[i];
         p.run_seq[(int64_t)s * nb * L + e] = j == cur ? (int64_t)r.tok[k] : s_run[r.src[k] * L + j];
         p.fin_seq[(int64_t)s * nb * L + e] = beam_fin_token(r, mi, j, cur, nb, L, s_fin, s_run);
+        if constexpr (LP) {
+            q.run_lp[(int64_t)s * nb * L + e] = j == cur ? s_tlp[k] : s_rlp[r.src[k] * L + j];
+            q.fin_lp[(int64_t)s * nb * L + e] = beam_fin_lp(r, mi, j, cur, nb, L, s_flp, s_rlp, s_tlp);
+        }
     }
     // the row table, kv_rows_kernel's rule with len = slot_t + 1: the step kernel has just written old[b][slot_t] = b; nothing of the cache moves
     if (p.rows) for (int e = tid; e < nb * cur; e += 256) { const int i = e / cur, j = e - i * cur; p.rows[((int64_t)s * nb + i) * p.ld_rows + j] = s_rt[r.src[r.nxt[i]] * L + j]; }
@@ -508,9 +579,10 @@ __global__ __launch_bounds__(256) void stream_beam_seat_kernel(const StreamBeamP
 }
 
 // the first min(slots, n_images) images take the slots in order, every slot's beam state at the start, the token rows BOS + padding
-__global__ void stream_beam_start_kernel(const StreamBeamP p) {
+__global__ void stream_beam_start_kernel(const StreamBeamP p, const StreamNBestP q) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < p.slots * p.nb * p.L) { const int64_t v = e % p.L == 0 ? p.bos : p.pad; p.run_seq[e] = v; p.fin_seq[e] = v; }
+    if (q.run_lp && e < p.slots * p.nb * p.L) { q.run_lp[e] = 0.f; q.fin_lp[e] = 0.f; }      // column 0 is never written again: it stays 0
     if (e < p.slots) { p.slot_image[e] = e < p.n_images ? e : -1; stream_beam_reset(p, e); }
     if (e == 0) { p.counters[0] = min(p.slots, p.n_images); p.counters[1] = 0; p.counters[2] = 0; p.counters[3] = 0; }
 }
@@ -592,7 +664,7 @@ extern "C" int kzv_stream_update(const kzv_stream_state* st, const float* d_logi
     return kzv_check_launch("stream_update");
 }
 
-static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_lp, const int64_t* top_ix, StreamBeamP* p, const char* who) {
+static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_lp, const int64_t* top_ix, StreamBeamP* p, StreamNBestP* q, const char* who) {
     if (!st) return kzv_fail(KZV_E_ARG, "%s: null state", who);
     KZV_TRY_RC(slot_state_check(who, st->slots, st->n_images, st->vocab, st->max_len, SB_L, st->ld_ids, st->out_ids,
                                 {st->slot_image, st->slot_t, st->tokens, st->posids, st->run_seq, st->fin_seq, st->run_scores, st->fin_scores, st->fin_done,
@@ -604,21 +676,38 @@ static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_
     *p = StreamBeamP{top_lp, top_ix, st->slots, st->n_images, st->num_beams, st->max_len, st->vocab, st->bos_id, st->eos_id, st->pad_id, st->early_stopping ? 1 : 0,
                      st->slot_image, st->slot_t, st->tokens, st->posids, st->run_seq, st->fin_seq, st->run_scores, st->fin_scores, st->fin_done, st->fin_len,
                      st->unsatisfied, st->counters, st->scratch, st->out_ids, st->ld_ids, st->out_score, st->limit, st->divisors, st->rows, st->ld_rows};
+    // the n-best outputs and the log-probability rows: n_best == 0 and every pointer null is the state without them
+    const bool lp_rows = st->run_lp || st->fin_lp;
+    if (st->n_best == 0) {
+        if (lp_rows || st->nbest_ids || st->nbest_scores || st->nbest_len || st->nbest_logprob)
+            return kzv_fail(KZV_E_ARG, "%s: n-best arrays or log-probability rows with n_best == 0", who);
+    } else {
+        if (st->n_best < 1 || st->n_best > st->num_beams) return kzv_fail(KZV_E_ARG, "%s: n_best %d outside 1..num_beams = %d", who, st->n_best, st->num_beams);
+        if (!st->nbest_ids || !st->nbest_scores || !st->nbest_len) return kzv_fail(KZV_E_ARG, "%s: null n-best ids / scores / lengths", who);
+        if (st->ld_nbest < st->max_len) return kzv_fail(KZV_E_ARG, "%s: n-best rows shorter than max_len", who);
+        if (lp_rows && (!st->run_lp || !st->fin_lp)) return kzv_fail(KZV_E_ARG, "%s: run_lp and fin_lp come together", who);
+        if (st->nbest_logprob && !lp_rows) return kzv_fail(KZV_E_ARG, "%s: nbest_logprob needs the log-probability rows run_lp / fin_lp", who);
+        if (st->nbest_logprob && st->ld_nbest_logprob < st->max_len) return kzv_fail(KZV_E_ARG, "%s: n-best log-probability rows shorter than max_len", who);
+        if ((int64_t)st->n_images * st->n_best >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "%s: n-best rows beyond 32-bit indices", who);
+    }
+    *q = StreamNBestP{st->run_lp, st->fin_lp, st->n_best, st->nbest_ids, st->ld_nbest, st->nbest_scores, st->nbest_len, st->nbest_logprob, st->ld_nbest_logprob};
     return KZV_OK;
 }
 
 extern "C" int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void* stream) {
-    StreamBeamP p;
-    KZV_TRY_RC(stream_beam_params(st, nullptr, nullptr, &p, "stream_beam_seat_first"));
-    hipLaunchKernelGGL(stream_beam_start_kernel, dim3((st->slots * st->num_beams * st->max_len + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
+    StreamBeamP p; StreamNBestP q;
+    KZV_TRY_RC(stream_beam_params(st, nullptr, nullptr, &p, &q, "stream_beam_seat_first"));
+    hipLaunchKernelGGL(stream_beam_start_kernel, dim3((st->slots * st->num_beams * st->max_len + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, q);
     return kzv_check_launch("stream_beam_seat_first");
 }
 
 extern "C" int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream) {
-    StreamBeamP p;
-    KZV_TRY_RC(stream_beam_params(st, d_top_scores, d_top_index, &p, "stream_beam_update"));
+    StreamBeamP p; StreamNBestP q;
+    KZV_TRY_RC(stream_beam_params(st, d_top_scores, d_top_index, &p, &q, "stream_beam_update"));
     if (!d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "stream_beam_update: null ranking [slots, 2 * num_beams]");
-    hipLaunchKernelGGL(stream_beam_update_kernel, dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p);
+    if (q.run_lp) hipLaunchKernelGGL((stream_beam_update_kernel<true, true>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
+    else if (q.n_best) hipLaunchKernelGGL((stream_beam_update_kernel<true, false>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
+    else hipLaunchKernelGGL((stream_beam_update_kernel<false, false>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
     hipLaunchKernelGGL(stream_beam_seat_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
     return kzv_check_launch("stream_beam_update");
 }
@@ -667,12 +756,17 @@ extern "C" int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scor
     if (st->batch < 1 || st->num_beams < 1 || st->num_beams > 8 || st->max_len < 2 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "beam_update: 1..8 beams");
     if (cur < 1 || cur >= st->max_len) return kzv_fail(KZV_E_ARG, "beam_update: position outside 1..max_len-1");
     if (st->run_seq_in == st->run_seq_out || st->fin_seq_in == st->fin_seq_out) return kzv_fail(KZV_E_ARG, "beam_update: in and out token rows must differ");
+    const bool lp_rows = st->run_lp_in || st->run_lp_out || st->fin_lp_in || st->fin_lp_out;
+    if (lp_rows && (!st->run_lp_in || !st->run_lp_out || !st->fin_lp_in || !st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "beam_update: the four log-probability row arrays come together");
+    if (lp_rows && (st->run_lp_in == st->run_lp_out || st->fin_lp_in == st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "beam_update: in and out log-probability rows must differ");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_flags, 0, (cur == 1 ? 5 : 3) * sizeof(int), s) != hipSuccess) return kzv_fail(KZV_E_HIP, "beam_update: memset");
     BeamUpd p{d_top_scores, d_top_index, st->run_seq_in, st->run_seq_out, st->fin_seq_in, st->fin_seq_out, st->run_scores, st->fin_scores,
               st->fin_done, st->fin_len, st->unsatisfied, d_rows, d_flags, st->num_beams, 2 * st->num_beams, st->max_len, st->vocab, cur,
-              st->eos_id, early_stopping ? 1 : 0, (float)pow((double)cur, (double)length_penalty)};
-    hipLaunchKernelGGL(beam_update_kernel, dim3(st->batch), dim3(64), 0, s, p);
+              st->eos_id, early_stopping ? 1 : 0, (float)pow((double)cur, (double)length_penalty),
+              st->run_lp_in, st->run_lp_out, st->fin_lp_in, st->fin_lp_out};
+    if (lp_rows) hipLaunchKernelGGL(beam_update_kernel<true>, dim3(st->batch), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL(beam_update_kernel<false>, dim3(st->batch), dim3(64), 0, s, p);
     hipLaunchKernelGGL(beam_stop_kernel, dim3(1), dim3(1), 0, s, d_flags, early_stopping ? 1 : 0, cur);
     return kzv_check_launch("beam_update");
 }

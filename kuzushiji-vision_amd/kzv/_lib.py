@@ -65,7 +65,8 @@ class kzv_beam_state(C.Structure):
     _fields_ = [("batch", C.c_int32), ("num_beams", C.c_int32), ("max_len", C.c_int32), ("vocab", C.c_int32), ("eos_id", C.c_int32),
                 ("run_seq_in", C.c_void_p), ("run_seq_out", C.c_void_p), ("fin_seq_in", C.c_void_p), ("fin_seq_out", C.c_void_p),
                 ("run_scores", C.c_void_p), ("fin_scores", C.c_void_p), ("fin_done", C.c_void_p), ("fin_len", C.c_void_p),
-                ("unsatisfied", C.c_void_p)]
+                ("unsatisfied", C.c_void_p),
+                ("run_lp_in", C.c_void_p), ("run_lp_out", C.c_void_p), ("fin_lp_in", C.c_void_p), ("fin_lp_out", C.c_void_p)]
 
 
 class kzv_stream_state(C.Structure):
@@ -77,11 +78,13 @@ class kzv_stream_state(C.Structure):
 
 class kzv_stream_beam_state(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("slots", "n_images", "num_beams", "max_len", "vocab", "bos_id", "eos_id", "pad_id", "early_stopping",
-                                         "reserved")] + [
+                                         "n_best")] + [
         ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("tokens", C.c_void_p), ("posids", C.c_void_p), ("run_seq", C.c_void_p),
         ("fin_seq", C.c_void_p), ("run_scores", C.c_void_p), ("fin_scores", C.c_void_p), ("fin_done", C.c_void_p), ("fin_len", C.c_void_p),
         ("unsatisfied", C.c_void_p), ("counters", C.c_void_p), ("scratch", C.c_void_p), ("out_ids", C.c_void_p), ("ld_ids", C.c_int64),
-        ("out_score", C.c_void_p), ("limit", C.c_void_p), ("divisors", C.c_void_p), ("rows", C.c_void_p), ("ld_rows", C.c_int64)]
+        ("out_score", C.c_void_p), ("limit", C.c_void_p), ("divisors", C.c_void_p), ("rows", C.c_void_p), ("ld_rows", C.c_int64),
+        ("run_lp", C.c_void_p), ("fin_lp", C.c_void_p), ("nbest_ids", C.c_void_p), ("ld_nbest", C.c_int64), ("nbest_scores", C.c_void_p),
+        ("nbest_len", C.c_void_p), ("nbest_logprob", C.c_void_p), ("ld_nbest_logprob", C.c_int64)]
 
 
 class kzv_logits_process_args(C.Structure):
@@ -330,6 +333,7 @@ SYMBOLS = {
     "kzv_stream_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "kzv_stream_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "kzv_stream_start": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kzv_stream_set_nbest": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "kzv_stream_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "kzv_stream_poll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "kzv_stream_beam_seat_first": (C.c_int, [C.POINTER(kzv_stream_beam_state), C.c_void_p]),

@@ -66,21 +66,60 @@ def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int
     return ids[:, :n]
 
 
+def nbest_result(fin_seq, fin_sc, fin_done, fin_len, fin_lp, n: int, bos_id: int, pad_id: int):
+    """The first ``n`` rows of every image's finished list in HF's ``num_return_sequences`` layout (image-major, best first): a dict of
+    ``ids`` int64 [B * n, width], width = the longest of those rows; ``scores`` fp32 [B * n] (HF ``sequences_scores``); ``lengths`` int64
+    [B * n], tokens with BOS included; and, where ``fin_lp`` is given, ``logprobs`` fp32 [B * n, width]: column t holds the
+    log-probability of the token in column t, 0 in column 0 and from the row's length on (generate_stream's conventions for greedy).
+    A finished entry that never received a hypothesis (fin_done == 0) comes out as BOS + padding, score -1e9, length 0: what the slot
+    kernel writes for it."""
+    import torch
+    B, _, L = fin_seq.shape
+    done = fin_done[:, :n].bool()
+    lengths = torch.where(done, fin_len[:, :n], torch.zeros_like(fin_len[:, :n]))
+    width = max(2, int(lengths.max()))
+    col = torch.arange(width, device=fin_seq.device).view(1, 1, width)
+    keep = col < lengths.unsqueeze(-1)
+    blank = torch.full_like(fin_seq[:, :n, :width], pad_id)
+    blank[:, :, 0] = bos_id
+    out = {"ids": torch.where(keep, fin_seq[:, :n, :width], blank).reshape(B * n, width),
+           "scores": torch.where(done, fin_sc[:, :n], torch.full_like(fin_sc[:, :n], NEG)).reshape(B * n),
+           "lengths": lengths.reshape(B * n)}
+    if fin_lp is not None:
+        lp = fin_lp[:, :n, :width]
+        out["logprobs"] = torch.where(keep & (col >= 1), lp, torch.zeros_like(lp)).reshape(B * n, width)
+    return out
+
+
+def _check_nbest(num_return_sequences, num_beams):
+    n = int(num_return_sequences)
+    if not 1 <= n <= int(num_beams):
+        raise ValueError(f"num_return_sequences must be in 1..num_beams = {int(num_beams)} (got {n})")
+    return n
+
+
 def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int,
-                device, early_stopping=True, length_penalty: float = 1.0, topk=None, update=None, process=None):
+                device, early_stopping=True, length_penalty: float = 1.0, topk=None, update=None, process=None,
+                num_return_sequences: int = 1, return_logprobs: bool = False):
     """``topk(logits [B * nb, vocab] fp32, run_sc [B, nb]) -> (top_lp [B, 2 nb], top_ix [B, 2 nb])``: optional fused ranking
     (kzv_beam_topk on the GPU); None = the torch expression of the same thing below.
     ``update``: optional fused bookkeeping (kzv_beam_update); with it the loop below is replaced by beam_search_fused.
     ``process(logp, ids, n) -> logp`` (optional; GenerationControls.hook): generation controls on ``log_softmax(logits)`` given the
     histories ids[:, :n], before the beam score is added and with no second normalisation -- where HF's beam search applies its logits
     processors.  It belongs to the torch expression: a caller that passes ``topk`` processes inside ``step`` and passes a ranking over
-    log-probabilities (make_device_hooks(logprobs=True)).  None: what this computed before."""
+    log-probabilities (make_device_hooks(logprobs=True)).  None: what this computed before.
+    ``num_return_sequences`` n in 1..num_beams / ``return_logprobs``: with n > 1 or log-probabilities asked for, the result is
+    nbest_result's dict of the first n rows of the finished list instead of the winner's ids (HF ``generate(num_return_sequences=n)``).
+    A token's log-probability is the fp32 difference ``top_lp[k] - run_sc[src[k]]``, the continuation's accumulated score minus its
+    parent beam's, carried in run_lp / fin_lp [B, nb, max_len] through exactly the gathers of run_seq / fin_seq (HF
+    ``compute_transition_scores``); under ``process`` it is therefore the processed row's value."""
     import torch
     if process is not None and topk is not None:
         raise ValueError("beam_search: `process` belongs to the torch ranking; with `topk` process inside `step` and rank log-probabilities")
     if update is not None and topk is not None:
         return beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, bos_id, eos_id, device, early_stopping,
-                                 length_penalty, topk, update)
+                                 length_penalty, topk, update, num_return_sequences=num_return_sequences, return_logprobs=return_logprobs)
+    n_ret = _check_nbest(num_return_sequences, num_beams)
     B, nb, K = batch, num_beams, 2 * num_beams
     prompt = 1                                                    # decoder prompt = [BOS]
     run_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=device)
@@ -91,6 +130,10 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
     fin_sc = torch.full((B, nb), NEG, device=device)
     fin_done = torch.zeros(B, nb, dtype=torch.bool, device=device)
     fin_len = torch.full((B, nb), prompt, dtype=torch.int64, device=device)
+    run_lp = fin_lp = None
+    if return_logprobs:
+        run_lp = torch.zeros(B, nb, max_len, dtype=torch.float32, device=device)
+        fin_lp = run_lp.clone()
     unsat = torch.ones(B, 1, dtype=torch.bool, device=device)     # "the open beams may still improve the finished ones"
     top_mask = (torch.arange(K, device=device) < nb).view(1, K)
     base = (torch.arange(B, device=device) * nb).view(B, 1)
@@ -120,6 +163,10 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
         hits = (tok == eos_id) | (cur + 1 >= max_len)
         # running beams of the next step: the best nb continuations that did not stop
         nxt_ix = (top_lp + hits.float() * NEG).topk(nb, dim=1)[1]
+        if run_lp is not None:                                    # the token's own log-probability, from the OLD running scores
+            cand_lp = run_lp.gather(1, src.unsqueeze(-1).expand(B, K, max_len)).clone()
+            cand_lp[:, :, cur] = top_lp.float() - run_sc.gather(1, src)
+            run_lp = cand_lp.gather(1, nxt_ix.unsqueeze(-1).expand(B, nb, max_len))
         run_seq = cand.gather(1, nxt_ix.unsqueeze(-1).expand(B, nb, max_len))
         run_sc = (top_lp + hits.float() * NEG).gather(1, nxt_ix)
         rows = (base + src.gather(1, nxt_ix)).reshape(-1)
@@ -131,6 +178,8 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
         m_sc = torch.cat((fin_sc, fsc), dim=1)
         m_ix = m_sc.topk(nb, dim=1)[1]
         fin_seq = torch.cat((fin_seq, cand), dim=1).gather(1, m_ix.unsqueeze(-1).expand(B, nb, max_len))
+        if fin_lp is not None:
+            fin_lp = torch.cat((fin_lp, cand_lp), dim=1).gather(1, m_ix.unsqueeze(-1).expand(B, nb, max_len))
         fin_sc = m_sc.gather(1, m_ix)
         fin_done = torch.cat((fin_done, just), dim=1).gather(1, m_ix)
         fin_len = torch.cat((fin_len, torch.full((B, K), cur + 1, dtype=torch.int64, device=device)), dim=1).gather(1, m_ix)
@@ -143,16 +192,20 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
         if not bool(go_on):
             break
         reorder(rows, cur - 1)
+    if n_ret > 1 or return_logprobs:
+        return nbest_result(fin_seq, fin_sc, fin_done, fin_len, fin_lp, n_ret, bos_id, pad_id)
     width = int(fin_len[:, 0].max())
     return fin_seq[:, 0, :width]
 
 
 def beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, bos_id, eos_id, device, early_stopping, length_penalty,
-                      topk, update, return_state=False):
+                      topk, update, return_state=False, num_return_sequences: int = 1, return_logprobs: bool = False):
     """The same loop with the two device kernels: ``topk`` ranks the continuations, ``update(state, top_lp, top_ix, cur) -> (rows,
     flags)`` does everything beam_search does between two steps (state: dict of the tensors below; token rows double-buffered).
-    One host synchronisation per step (the three counters of ``flags``)."""
+    One host synchronisation per step (the three counters of ``flags``).  ``num_return_sequences`` / ``return_logprobs``: as
+    beam_search's; the log-probability rows run_lp / fin_lp join the state (double-buffered like the token rows) only when asked for."""
     import torch
+    n_ret = _check_nbest(num_return_sequences, num_beams)
     B, nb = batch, num_beams
     st = {"run_seq": [torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=device) for _ in range(2)],
           "fin_seq": [torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=device) for _ in range(2)],
@@ -163,6 +216,9 @@ def beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, b
     for t in st["run_seq"] + st["fin_seq"]:
         t[:, :, 0] = bos_id
     st["run_sc"][:, 1:] = NEG
+    if return_logprobs:
+        st["run_lp"] = [torch.zeros(B, nb, max_len, dtype=torch.float32, device=device) for _ in range(2)]
+        st["fin_lp"] = [torch.zeros(B, nb, max_len, dtype=torch.float32, device=device) for _ in range(2)]
     cur = 1
     while True:
         raw = step(cur - 1, st["run_seq"][st["cur_buf"]].view(B * nb, max_len))
@@ -178,6 +234,10 @@ def beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, b
                 break
         reorder(rows, cur - 1)
     fin_seq = st["fin_seq"][st["cur_buf"]]
+    if n_ret > 1 or return_logprobs:
+        out = nbest_result(fin_seq, st["fin_sc"], st["fin_done"], st["fin_len"], st["fin_lp"][st["cur_buf"]] if return_logprobs else None,
+                           n_ret, bos_id, pad_id)
+        return (out, st) if return_state else out
     width = int(st["fin_len"][:, 0].max())
     out = fin_seq[:, 0, :width]
     return (out, st) if return_state else out
@@ -208,11 +268,13 @@ def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, 
 
     def update(st, lp, ix, cur):          # everything between two decoder steps in one launch
         a = st["cur_buf"]
+        lp_rows = {} if "run_lp" not in st else dict(run_lp_in=st["run_lp"][a].data_ptr(), run_lp_out=st["run_lp"][a ^ 1].data_ptr(),
+                                                     fin_lp_in=st["fin_lp"][a].data_ptr(), fin_lp_out=st["fin_lp"][a ^ 1].data_ptr())
         bs = L.kzv_beam_state(batch=B, num_beams=nb, max_len=max_len, vocab=vocab, eos_id=eos_id,
                               run_seq_in=st["run_seq"][a].data_ptr(), run_seq_out=st["run_seq"][a ^ 1].data_ptr(),
                               fin_seq_in=st["fin_seq"][a].data_ptr(), fin_seq_out=st["fin_seq"][a ^ 1].data_ptr(),
                               run_scores=st["run_sc"].data_ptr(), fin_scores=st["fin_sc"].data_ptr(), fin_done=st["fin_done"].data_ptr(),
-                              fin_len=st["fin_len"].data_ptr(), unsatisfied=st["unsat"].data_ptr())
+                              fin_len=st["fin_len"].data_ptr(), unsatisfied=st["unsat"].data_ptr(), **lp_rows)
         L.check(lib.kzv_beam_update(C.byref(bs), lp.data_ptr(), ix.data_ptr(), cur, 1 if early_stopping is True else 0, float(length_penalty),
                                     rows_buf.data_ptr(), flags_buf.data_ptr(), L.stream_handle()), "beam_update")
         return rows_buf, flags_buf

@@ -534,7 +534,7 @@ class TrOCRModel:
 
     def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0,
                   no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None,
-                  allowed_tokens=None, lm=None, lm_weight: float = 0.0) -> list[dict]:
+                  allowed_tokens=None, lm=None, lm_weight: float = 0.0, n_best: int = 0) -> list[dict]:
         """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
         ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
         ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
@@ -542,23 +542,42 @@ class TrOCRModel:
         candidates of the teacher-forced pass with their log-probabilities) and ``margins``; after a beam search the chosen token
         need not be the first alternative.  The generation controls are ``generate``'s and steer the decode only: the align-based
         values (log-probabilities, confidence, alternatives) stay the model's own, so a token the controls forced may carry a low one.
-        ``lm`` / ``lm_weight`` (``generate``'s language-model fusion) do the same: they steer the decode only."""
+        ``lm`` / ``lm_weight`` (``generate``'s language-model fusion) do the same: they steer the decode only.
+        ``n_best`` n in 1..num_beams: every record also holds ``score`` (HF ``sequences_scores``) and ``hypotheses``, the n best readings
+        of the line as ``recognize_many``'s records (the search's own log-probabilities, best first, entry 0 the winner's reading); the
+        align pass still supplies centroids, log-probabilities and confidence of the winner only."""
         import torch
         from . import align as A
         c = self.cfg
-        gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
-                            no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
-                            suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight)
+        hyps = None
+        if n_best:
+            from . import nbest as NB
+            n = NB.check_request(num_beams, n_best, True, "recognize")
+            gen_all, h_sc, h_lp = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
+                                                no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
+                                                suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight,
+                                                num_return_sequences=n, return_scores=True, return_logprobs=True)
+            hyps = NB.records(self, gen_all, h_sc, h_lp, n)
+            gen = gen_all[0::n]
+            gen = gen[:, :max(1, int((gen != c.pad_id).sum(dim=1).max()))]
+        else:
+            gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
+                                no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
+                                suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight)
         if gen.shape[1] < 2:                                  # labels need a target column
             gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
         out = self.align(pixel_values, gen, layer=layer, top_k=top_k)
         ids = gen.cpu().numpy()
         tok = self.tokenizer
         alts = (out["alt_ids"].cpu().numpy(), out["alt_logprob"].cpu().numpy()) if top_k else None
-        return A.build_records(ids, out["logprob"].cpu().numpy(), out["centroid"].cpu().numpy(), out["peak_patch"].cpu().numpy(),
+        recs = A.build_records(ids, out["logprob"].cpu().numpy(), out["centroid"].cpu().numpy(), out["peak_patch"].cpu().numpy(),
                                pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
                                to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
+        if hyps is not None:
+            for r, h in zip(recs, hyps):
+                r["score"], r["hypotheses"] = h["score"], h["hypotheses"]
+        return recs
 
     @contextlib.contextmanager
     def _decode_stream(self, use_graph: bool):
@@ -583,8 +602,14 @@ class TrOCRModel:
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True, return_scores: bool = False,
                  no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
-                 lm=None, lm_weight: float = 0.0):
+                 lm=None, lm_weight: float = 0.0, num_return_sequences: int = 1, return_logprobs: bool = False):
         """Decode from BOS.  The encoder (and the cross-attention K/V of every decoder layer) runs ONCE.
+        ``num_return_sequences`` n in 1..num_beams / ``return_logprobs`` (the device hooks, as ``return_scores``; kzv/nbest.py): with
+        n > 1 the ids are [B * n, W], HF's layout (image-major, best first) -- rows 0 .. n - 1 of every image's finished list, read off
+        the search's own state -- and ``return_scores`` gives [B * n]; ``return_logprobs`` adds fp32 [B * n, W]: column t holds the
+        log-probability of the token in column t, 0 in column 0 and from the row's length on (the search's own fp32 difference of
+        accumulated scores: HF ``compute_transition_scores``; under controls or fusion the processed / fused row's value).  The results
+        come in the order ids, scores, log-probabilities.
         ``return_scores`` (beam search on the device hooks only, i.e. 2..8 beams on the GPU): returns ``(ids, scores)``, scores fp32 [B] =
         the winners' sum of log-probabilities / generated length ** length_penalty (HF's ``sequences_scores``), read off the search's own
         state -- under generation controls the sum of the PROCESSED log-probabilities, which a teacher-forced pass cannot give.
@@ -629,6 +654,11 @@ class TrOCRModel:
         nb = max(1, int(num_beams))
         if return_scores and nb == 1:
             raise ValueError("return_scores needs num_beams > 1")
+        from . import nbest as NB
+        n_ret = NB.check_request(nb, num_return_sequences, return_logprobs, "generate")
+        if return_logprobs and nb == 1:
+            raise ValueError("generate: return_logprobs needs num_beams > 1 (greedy decoding returns them from generate_stream)")
+        nbest = n_ret > 1 or bool(return_logprobs)
         BB = B * nb
         # cached decoding runs the encoder and the cross-attention K/V once per IMAGE (kzv_encode_images): beams share them, and no
         # teacher-forced decoder pass is spent on the BOS-only prompt
@@ -739,6 +769,16 @@ class TrOCRModel:
                 if nb == 1:
                     gupd = BM.make_greedy_hook(B, c.vocab, c.pad_id, c.eos_id, self.device, Lh) if self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0" else None
                     out = BM.greedy(step, B, Lh, c.pad_id, c.bos_id, c.eos_id, self.device, update=gupd, process=process)
+                elif nbest:                                       # rows 0 .. n - 1 of the finished lists, off the search's own state
+                    if topk is None or update is None:
+                        raise ValueError("num_return_sequences / return_logprobs need the device beam hooks (2..8 beams on the GPU, KZV_BEAM_TOPK / KZV_BEAM_UPDATE on)")
+                    res, bst = BM.beam_search_fused(step, reorder, B, nb, Lh, c.vocab, c.pad_id, c.bos_id, c.eos_id, self.device, early_stopping,
+                                                    length_penalty, topk, update, return_state=True, num_return_sequences=n_ret,
+                                                    return_logprobs=bool(return_logprobs))
+                    NB.check_done(res["lengths"], "generate")
+                    self.last_generate_lengths = res["lengths"]      # tokens per returned row, BOS included (a row may END in padding at max_length)
+                    out, scores, lps = res["ids"], res["scores"], res.get("logprobs")
+                    keep += [t for t in (scores, lps) if t is not None]
                 elif return_scores:                               # (what beam_search runs with both hooks; the state holds the scores)
                     if topk is None or update is None:
                         raise ValueError("return_scores needs the device beam hooks (2..8 beams on the GPU, KZV_BEAM_TOPK / KZV_BEAM_UPDATE on)")
@@ -754,6 +794,9 @@ class TrOCRModel:
                     keep += lmr[1].keep()
                 if return_scores:
                     keep.append(scores)
+            if nbest:
+                got = (out,) + ((scores,) if return_scores else ()) + ((lps,) if return_logprobs else ())
+                return got if len(got) > 1 else out
             return (out, scores) if return_scores else out
         finally:
             self.training = was
@@ -804,7 +847,7 @@ class TrOCRModel:
                         pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
                         return_scores: bool = False, top_k: int = 0,
                         no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
-                        lm=None, lm_weight: float = 0.0):
+                        lm=None, lm_weight: float = 0.0, num_return_sequences: int | None = None):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -825,8 +868,8 @@ class TrOCRModel:
         the matching row of ``generate(num_beams=num_beams)``, with ``limits`` that of ``generate(max_length=limit)``.  Other beam
         counts, or ``stream_beam_impl_for(num_beams) == "static"``, run ``generate`` over batches of ``slots``: the same rows.
         ``return_scores``: also fp32 [N], the winner's sum of log-probabilities / generated length ** length_penalty (HF's
-        ``sequences_scores``; on the static path from ``align``).  ``return_logprobs`` is greedy only: per-token log-probabilities of
-        a beam winner are not produced.  The slots assume that no running beam holds padding; a wave in which one took ``pad_id`` is
+        ``sequences_scores``; on the static path from ``align``).  ``return_logprobs`` with beams needs ``num_return_sequences`` stated
+        (below); without it the call refuses, as it did.  The slots assume that no running beam holds padding; a wave in which one took ``pad_id`` is
         decoded again by ``generate`` and counted in ``last_stream_pad_fallbacks``.
 
         ``top_k`` in 1..8 (greedy only): the call returns ``(ids, logprobs, alt_ids, alt_logprob)``, the last two int64 / fp32
@@ -847,11 +890,21 @@ class TrOCRModel:
         kzv_lm_fuse as one more node of its captured chain, after the controls' node (kzv_stream_set_lm), on each slot's own history; a
         beam wave then normalises through the controls' kernel even when the controls are neutral.  Every row still equals the matching
         row of ``generate`` called with the same keywords, both fallbacks carry them, and ``return_logprobs`` / ``top_k`` are those of
-        the FUSED row."""
+        the FUSED row.
+
+        ``num_return_sequences`` n in 1..num_beams (beams only; kzv/nbest.py): the n best readings of every line, ids [N * n, width] in
+        HF's layout (image-major, best first; rows 0::n are the rows without it), ``return_scores`` then fp32 [N * n]; stating it --
+        ``num_return_sequences=1`` serves a winner -- also admits ``return_logprobs`` for a beam search: fp32 [N * n, width], column
+        t the log-probability of the token in column t, 0 in column 0 and from the row's length on, the search's own values
+        (kzv_stream_set_nbest; one more staged row copy per step).  The results come in the order ids, scores, log-probabilities.  Both
+        fallbacks call ``generate`` with the same keywords and return the same rows."""
         import torch
         from . import controls as CT
         from . import lm as LM
+        from . import nbest as NB
         c = self.cfg
+        n_ret = NB.check_request(num_beams, 1 if num_return_sequences is None else num_return_sequences, return_logprobs, "generate_stream")
+        nbest = n_ret if num_return_sequences is not None and int(num_beams) > 1 and (n_ret > 1 or return_logprobs) else 0
         ctl = CT.from_kwargs(c.eos_id, no_repeat_ngram_size, repetition_penalty, min_length, suppress_tokens, allowed_tokens)
         lmr = LM.resolve(lm, lm_weight, c.vocab, self.device)          # before any wave runs; None: off
         if ctl is not None:
@@ -866,8 +919,9 @@ class TrOCRModel:
             raise ValueError("top_k is greedy only: a beam winner's per-token candidates are not produced on the slots (recognize(top_k=...) scores them in a teacher-forced pass)")
         if top_k:
             return_logprobs = True
-        if nb > 1 and return_logprobs:
-            raise ValueError("return_logprobs is greedy only: a beam search returns sequence scores (return_scores)")
+        if nb > 1 and return_logprobs and not nbest:
+            raise ValueError("return_logprobs is greedy only: a beam search returns sequence scores (return_scores), and its per-token "
+                             "log-probabilities where num_return_sequences is stated")
         if nb == 1 and return_scores:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding returns per-token log-probabilities: return_logprobs)")
         beams = None if nb == 1 else (nb, bool(early_stopping), float(length_penalty))
@@ -883,7 +937,7 @@ class TrOCRModel:
         if slots < 1:
             raise ValueError("slots must be positive")
         lim_all = None if limits is None else torch.as_tensor(limits, dtype=torch.int32).reshape(-1).clamp(min=2)
-        ids_out, lp_out, alt_out, done = [], [], [], 0
+        ids_out, lp_out, alt_out, nb_out, done = [], [], [], [], 0
         self.last_stream_steps = 0               # decoder steps the last call took (every wave; the static path leaves 0)
         src = iter((pixel_values,) if torch.is_tensor(pixel_values) else pixel_values)
         first_batch = next(src)
@@ -895,12 +949,24 @@ class TrOCRModel:
             lim = None if lim_all is None else lim_all[done:done + n]
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
+            if nbest:
+                nb_out.append(self._stream_wave(px, Lh, slots, lim, bool(return_logprobs), beams, 0, ctl, lmr, nbest=nbest))
+                done += n
+                continue
             if top_k:
                 ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl, lmr)
                 alt_out.append(alts)
             else:
                 ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl, lmr)
             ids_out.append(ids); lp_out.append(lp); done += n
+        if nbest:                                 # waves concatenate image-major
+            lengths = torch.cat([w["lengths"] for w in nb_out])
+            NB.check_done(lengths, "generate_stream")
+            width = max(2, int(lengths.max()))
+            got = (torch.cat([w["ids"] for w in nb_out])[:, :width],)
+            got += (torch.cat([w["scores"] for w in nb_out]),) if return_scores else ()
+            got += (torch.cat([w["logprobs"] for w in nb_out])[:, :width],) if return_logprobs else ()
+            return got if len(got) > 1 else got[0]
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
         if top_k:
@@ -945,11 +1011,13 @@ class TrOCRModel:
                 score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
         return ids, score
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None, lmr=None):
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None, lmr=None, nbest: int = 0):
         """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
         length_penalty): ids [n, Lh] and the winners' scores [n]; with ``top_k`` (greedy) a third result, (alt_ids int32, alt_logprob)
-        [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off); ``lmr``: its language model (kzv/lm.py: resolve; None: off)."""
+        [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off); ``lmr``: its language model (kzv/lm.py: resolve; None: off).
+        ``nbest`` n >= 1 (beams): the result is kzv/nbest.py's dict of the n best rows per image instead (``want_lp``: with log-probabilities)."""
         import torch
+        from . import nbest as NB
         from . import stream as ST
         c = self.cfg
         lib = L.load()
@@ -957,12 +1025,14 @@ class TrOCRModel:
         dev = self.device
         self._check_inputs(px[:1])                                # geometry checks + the active crop width
         nb = beams[0] if beams else 1
+        static_beams = self._static_beam_wave if not nbest else (
+            lambda px_, Lh_, slots_, lim_, beams_, ctl_, lmr_: NB.static_wave(self, px_, Lh_, slots_, lim_, beams_, nbest, want_lp, self._controls_kw(ctl_, lmr_)))
         if beams and nb not in (2, 4):
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
+            return static_beams(px, Lh, slots, lim, beams, ctl, lmr)
         rows = slots * nb                                         # decoder rows: a slot holds one sequence, or an image's beam group
         self._bind(rows, Lh)
         if beams and self.stream_beam_impl_for(nb) == "static":
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
+            return static_beams(px, Lh, slots, lim, beams, ctl, lmr)
         if not beams and self.stream_decode_impl == "static":
             ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
             lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
@@ -986,8 +1056,9 @@ class TrOCRModel:
         self.training = False
         ids = torch.full((n, Lh), c.pad_id, dtype=torch.int64, device=dev)
         ids[:, 0] = c.bos_id
-        lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp else None
+        lp = torch.zeros(n, Lh, dtype=torch.float32, device=dev) if want_lp and not nbest else None
         score = torch.zeros(n, dtype=torch.float32, device=dev) if beams else None
+        nbo = NB.WaveOutputs(n, nbest, Lh, c.pad_id, c.bos_id, dev, want_lp) if nbest else None
         alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
         alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
         limd = None if lim is None else lim.to(dev).contiguous()
@@ -999,6 +1070,8 @@ class TrOCRModel:
                 if beams:
                     L.check(lib.kzv_stream_begin_beams(self._h, nb, 1 if beams[1] else 0, beams[2], score.data_ptr(), pool, n, Lh, c.bos_id, c.eos_id,
                                                        ids.data_ptr(), Lh, None, 0, L.ptr(limd), st), "stream_begin_beams")
+                    if nbo is not None:
+                        nbo.arm(lib, self._h, st, L.check)
                 else:
                     L.check(lib.kzv_stream_begin(self._h, pool, n, Lh, c.bos_id, c.eos_id, ids.data_ptr(), Lh, L.ptr(lp), Lh, L.ptr(limd), st), "stream_begin")
                     if top_k:
@@ -1039,17 +1112,19 @@ class TrOCRModel:
                         if steps >= bound:
                             raise L.KzvError(f"generate_stream: {fin.value} of {n} lines ended after {steps} steps; {slots} slots bound them by {bound}")
                 self.last_stream_steps += took.value
-                keep += [ids] + [x for x in (lp, score, limd, alt_ids, alt_lp) if x is not None]
+                keep += [ids] + [x for x in (lp, score, limd, alt_ids, alt_lp) if x is not None] + (nbo.tensors() if nbo is not None else [])
         finally:
             self.training = was
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
             self.last_stream_pad_fallbacks += pads.value
-            return self._static_beam_wave(px, Lh, slots, lim, beams, ctl, lmr)
+            return static_beams(px, Lh, slots, lim, beams, ctl, lmr)
+        if nbo is not None:
+            return nbo.result()
         if top_k:
             return ids, lp, (alt_ids, alt_lp)
         return ids, (score if beams else lp)
 
-    def recognize_many(self, pixel_values, top_k: int = 0, **kw) -> list[dict]:
+    def recognize_many(self, pixel_values, top_k: int = 0, n_best: int = 0, **kw) -> list[dict]:
         """``generate_stream`` with its own log-probabilities: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD),
         ``token_strings``, ``logprobs`` and ``confidence`` = exp(mean log-probability over the tokens, EOS included) -- ``recognize``'s
         definitions, for greedy decoding, with no teacher-forced second pass.  It returns NO centroids or peak patches: those come
@@ -1057,11 +1132,22 @@ class TrOCRModel:
         ``top_k`` in 1..8 every record also holds ``alternatives`` and ``margins`` (build_records), taken from the stream's own steps.
         The generation controls (``no_repeat_ngram_size``, ``repetition_penalty``, ``min_length``, ``suppress_tokens``, ``allowed_tokens``)
         go through ``kw``; log-probabilities, confidence and alternatives are then those of the processed rows (generate_stream).
-        So do ``lm`` / ``lm_weight`` (language-model fusion): the values are then those of the fused rows."""
+        So do ``lm`` / ``lm_weight`` (language-model fusion): the values are then those of the fused rows.
+        ``num_beams`` > 1 (through ``kw``) with ``n_best`` n in 1..num_beams (default 1): the records of a beam search, from the winner's
+        own search log-probabilities with no second pass, plus ``score`` (HF ``sequences_scores``) and ``hypotheses``: the n best
+        readings of the line as such records, best first, the winner included as entry 0 (kzv/nbest.py)."""
         import numpy as np
         from . import align as A
+        from . import nbest as NB
         c = self.cfg
         top_k = int(top_k)
+        nb = int(kw.get("num_beams", 1))
+        if nb > 1 or n_best:
+            n = NB.check_request(nb, n_best or 1, True, "recognize_many")
+            if nb == 1:
+                raise ValueError("recognize_many: n_best needs a beam search (num_beams > 1)")
+            gen, score, lp = self.generate_stream(pixel_values, return_logprobs=True, return_scores=True, top_k=top_k, num_return_sequences=n, **kw)
+            return NB.records(self, gen, score, lp, n)
         alts = None
         if top_k:
             gen, lp, a_ids, a_lp = self.generate_stream(pixel_values, return_logprobs=True, top_k=top_k, **kw)
@@ -1106,7 +1192,7 @@ class TrOCRModel:
         st = M.edit_stats(gen, torch.as_tensor(labels).to(self.device), self._edit_special_ids(), self.cfg.vocab, ops=False)
         return M.cer_values(st["dist"], st["ref_len"], st["pred_len"])
 
-    def evaluate_many(self, pixel_values, labels, num_beams: int = 1, top: int = 20, **generate_stream_kw) -> dict:
+    def evaluate_many(self, pixel_values, labels, num_beams: int = 1, top: int = 20, n_best: int = 0, **generate_stream_kw) -> dict:
         """``generate_stream`` over the images followed by ONE kzv_edit_distance against ``labels`` ([N, <= 128] ids, or an iterable of
         such batches in the images' order).  Returns ``cer`` (the mean of the per-line CER: the reference's test_cer), ``cer_corpus``
         (sum of distances / sum of label lengths), ``exact`` (share of lines with distance 0), ``substitutions`` / ``deletions`` /
@@ -1114,26 +1200,48 @@ class TrOCRModel:
         ``characters`` (metrics.character_table: the ``top`` characters with the most errors) and ``ids`` (the generated rows).  The
         same call serves geometries where generate_stream runs ``generate``: it needs only the ids.  The generation controls of
         generate_stream (``no_repeat_ngram_size=3`` is what the stock TrOCR generation configs ship with) pass through its keywords, and
-        so do ``lm`` / ``lm_weight`` (kzv.lm.sweep_weight picks the weight with this call)."""
+        so do ``lm`` / ``lm_weight`` (kzv.lm.sweep_weight picks the weight with this call).
+        ``n_best`` n in 1..num_beams (beams only): the decode returns the n best readings of every line and ONE more kzv_edit_distance
+        (distance only) scores them all; every key above stays the winner's, and the call adds ``cer_oracle`` (the mean over lines of the
+        best reading's CER: what a rescoring of the candidates could reach at most), ``cer_oracle_corpus``, ``oracle_rank`` (how often
+        rank r held the best reading, ties to the lower rank), ``per_line["dist_nbest"]`` [N, n] and ``per_line["cer_oracle"]`` [N] (kzv/nbest.py:
+        oracle_stats)."""
         import numpy as np
         import torch
         from . import metrics as M
+        from . import nbest as NB
+        n_best = int(n_best)
+        if n_best:
+            NB.check_request(num_beams, n_best, False, "evaluate_many")
+            if int(num_beams) == 1:
+                raise ValueError("evaluate_many: n_best needs a beam search (num_beams > 1)")
         special = self._edit_special_ids()
         for k in ("return_logprobs", "return_scores", "top_k"):
             if generate_stream_kw.get(k):
                 raise ValueError(f"evaluate_many scores the ids only: {k} is not served")
-        gen = self.generate_stream(pixel_values, num_beams=num_beams, **generate_stream_kw)
+        gen_all = None
+        if n_best:
+            gen_all = self.generate_stream(pixel_values, num_beams=num_beams, num_return_sequences=n_best, **generate_stream_kw)
+            gen = gen_all[0::n_best]
+            gen = gen[:, :max(2, int((gen != self.cfg.pad_id).sum(dim=1).max()))]      # the winners at the width the call without n_best gives them
+        else:
+            gen = self.generate_stream(pixel_values, num_beams=num_beams, **generate_stream_kw)
         lab = labels if torch.is_tensor(labels) else torch.cat([torch.as_tensor(b) for b in labels])
         st = M.edit_stats(gen, lab.to(gen.device), special, self.cfg.vocab, char_stats=True)
         dist, ref_len, pred_len, ops = (st[k].cpu().numpy() for k in ("dist", "ref_len", "pred_len", "ops"))
         cers = M.cer_values(dist, ref_len, pred_len)
         tot = ops.astype(np.int64).sum(axis=0)
         chars = int(ref_len.astype(np.int64).sum())
-        return {"cer": sum(cers) / len(cers) if cers else 0.0,
+        oracle, extra = {}, {}
+        if gen_all is not None:
+            oracle = NB.oracle_of_ids(self, gen_all, lab, n_best)
+            extra = {"dist_nbest": oracle.pop("dist_nbest"), "cer_oracle": np.asarray(oracle.pop("cer_oracle_lines"), dtype=np.float64)}
+        return {**oracle,
+                "cer": sum(cers) / len(cers) if cers else 0.0,
                 "cer_corpus": int(dist.astype(np.int64).sum()) / chars if chars else 0.0,
                 "exact": float((dist == 0).mean()) if len(cers) else 0.0,
                 "substitutions": int(tot[1]), "deletions": int(tot[2]), "insertions": int(tot[3]), "ref_chars": chars,
-                "per_line": {"cer": np.asarray(cers, dtype=np.float64), "dist": dist, "ref_len": ref_len, "pred_len": pred_len, "ops": ops},
+                "per_line": {"cer": np.asarray(cers, dtype=np.float64), "dist": dist, "ref_len": ref_len, "pred_len": pred_len, "ops": ops, **extra},
                 "characters": M.character_table(st["char_stats"], self.tokenizer, top=top), "ids": gen}
 
     # ------------------------------------------------------------------ Lightning-shaped steps (:323-398)

@@ -162,6 +162,11 @@ def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int,
 #                         took pad_id (a prefix with padding breaks "position = step + 1 + pad_id, every cached key usable")
 #   out_ids int64 [N, L]  BOS, the best finished hypothesis, then padding;  out_score fp32 [N]: its score (HF sequences_scores)
 #   rowtab int32 [slots * nb, ld] (optional): the beam row table the step kernel reads; re-parented in place
+#   run_lp, fin_lp fp32 [slots, nb, L] (optional, ``want_logprobs``): the per-token log-probabilities of the token rows, the fp32 difference
+#                         top_lp[k] - run_sc[src[k]] at cur, moved through exactly the gathers of run_seq / fin_seq (beam.beam_search)
+#   nbest_ids int64 [N * n, L], nbest_score fp32 [N * n], nbest_len int32 [N * n], nbest_logprob fp32 [N * n, L] (optional, ``n_best`` = n):
+#                         rows 0 .. n - 1 of an image's finished list when its search ends, image-major, best first; only the row's
+#                         length is written over BOS + padding / zeros; an entry that is not done: nothing, score -1e9, length 0
 NEG = -1.0e9
 
 
@@ -173,10 +178,17 @@ def divisor_table(max_len: int, length_penalty: float, device="cpu"):
 
 
 def new_beam_state(n_images: int, slots: int, num_beams: int, max_len: int, pad_id: int, bos_id: int, device, want_scores: bool = True,
-                   rowtab_ld: int = 0):
-    """The state with the first min(slots, n_images) images seated in slot order (kzv_stream_beam_seat_first)."""
+                   rowtab_ld: int = 0, n_best: int = 0, want_logprobs: bool = False):
+    """The state with the first min(slots, n_images) images seated in slot order (kzv_stream_beam_seat_first).  ``n_best`` in
+    1..num_beams adds the n-best outputs, ``want_logprobs`` (needs n_best) the log-probability rows and their output; the keys exist
+    only when asked for."""
     import torch
     nb = num_beams
+    n_best = int(n_best)
+    if not 0 <= n_best <= nb:
+        raise ValueError(f"n_best must be in 1..num_beams = {nb} (got {n_best})")
+    if want_logprobs and not n_best:
+        raise ValueError("want_logprobs needs n_best >= 1 (the log-probability rows leave through the n-best outputs)")
     s = torch.arange(slots, dtype=torch.int32, device=device)
     out_ids = torch.full((n_images, max_len), pad_id, dtype=torch.int64, device=device)
     out_ids[:, 0] = bos_id
@@ -184,7 +196,18 @@ def new_beam_state(n_images: int, slots: int, num_beams: int, max_len: int, pad_
     run_seq[:, :, 0] = bos_id
     run_sc = torch.zeros(slots, nb, device=device)
     run_sc[:, 1:] = NEG
+    extra = {}
+    if n_best:
+        nbest_ids = torch.full((n_images * n_best, max_len), pad_id, dtype=torch.int64, device=device)
+        nbest_ids[:, 0] = bos_id
+        extra = {"nbest_ids": nbest_ids, "nbest_score": torch.zeros(n_images * n_best, dtype=torch.float32, device=device),
+                 "nbest_len": torch.zeros(n_images * n_best, dtype=torch.int32, device=device)}
+        if want_logprobs:
+            extra["run_lp"] = torch.zeros(slots, nb, max_len, dtype=torch.float32, device=device)
+            extra["fin_lp"] = torch.zeros(slots, nb, max_len, dtype=torch.float32, device=device)
+            extra["nbest_logprob"] = torch.zeros(n_images * n_best, max_len, dtype=torch.float32, device=device)
     return {
+        **extra,
         "slot_image": torch.where(s < n_images, s, torch.full_like(s, -1)),
         "slot_t": torch.zeros(slots, dtype=torch.int32, device=device),
         "tokens": torch.full((slots * nb,), bos_id, dtype=torch.int64, device=device),
@@ -231,6 +254,11 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
     s2 = top_lp + hits.float() * NEG
     nxt_ix = torch.sort(s2, dim=1, descending=True, stable=True)[1][:, :nb]
     n_run_seq = cand.gather(1, nxt_ix.unsqueeze(-1).expand(S, nb, L))
+    run_lp, fin_lp = st.get("run_lp"), st.get("fin_lp")
+    if run_lp is not None:                                                                 # the token's own log-probability, from the OLD running scores
+        cand_lp = run_lp.gather(1, src.unsqueeze(-1).expand(S, K, L)).clone()
+        cand_lp.scatter_(2, cur.view(S, 1, 1).expand(S, K, 1), (top_lp - run_sc.gather(1, src)).unsqueeze(-1))
+        n_run_lp = cand_lp.gather(1, nxt_ix.unsqueeze(-1).expand(S, nb, L))
     n_run_sc = s2.gather(1, nxt_ix)
     parent = src.gather(1, nxt_ix)                                                         # [S, nb]: the beam of the slot each one continues
     n_tok = tok.gather(1, nxt_ix)
@@ -244,6 +272,8 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
     m_sc = torch.cat((fin_sc, fsc), dim=1)
     m_ix = torch.sort(m_sc, dim=1, descending=True, stable=True)[1][:, :nb]
     n_fin_seq = torch.cat((fin_seq, cand), dim=1).gather(1, m_ix.unsqueeze(-1).expand(S, nb, L))
+    if run_lp is not None:
+        n_fin_lp = torch.cat((fin_lp, cand_lp), dim=1).gather(1, m_ix.unsqueeze(-1).expand(S, nb, L))
     n_fin_sc = m_sc.gather(1, m_ix)
     n_fin_done = torch.cat((fin_done, just), dim=1).gather(1, m_ix)
     n_fin_len = torch.cat((fin_len, (cur + 1).view(S, 1).expand(S, K)), dim=1).gather(1, m_ix)
@@ -261,6 +291,17 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
         st["out_ids"][rows] = torch.where(keep, n_fin_seq[ended][:, 0], torch.full_like(n_fin_seq[ended][:, 0], pad_id))
         if st.get("out_score") is not None:
             st["out_score"][rows] = n_fin_sc[ended][:, 0]
+        if st.get("nbest_ids") is not None:            # rows 0 .. n - 1 of the finished list, each over its own length only
+            n = st["nbest_ids"].shape[0] // n_images
+            e_done = n_fin_done[ended][:, :n]
+            e_len = torch.where(e_done, n_fin_len[ended][:, :n], torch.zeros_like(n_fin_len[ended][:, :n]))              # [E, n]
+            keep_n = (col.view(1, 1, L) < e_len.unsqueeze(-1)).reshape(-1, L)
+            dst = (rows.view(-1, 1) * n + torch.arange(n, device=dev).view(1, n)).reshape(-1)
+            st["nbest_ids"][dst] = torch.where(keep_n, n_fin_seq[ended][:, :n].reshape(-1, L), st["nbest_ids"][dst])
+            st["nbest_score"][dst] = torch.where(e_done, n_fin_sc[ended][:, :n], torch.full_like(n_fin_sc[ended][:, :n], NEG)).reshape(-1)
+            st["nbest_len"][dst] = e_len.reshape(-1).to(torch.int32)
+            if st.get("nbest_logprob") is not None:
+                st["nbest_logprob"][dst] = torch.where(keep_n, n_fin_lp[ended][:, :n].reshape(-1, L), st["nbest_logprob"][dst])
     # seats: the slots whose searches ended take the next images in ascending slot order
     e32 = ended.to(torch.int32)
     n_ended = e32.sum().to(torch.int32)
@@ -271,6 +312,9 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
     first = (torch.arange(nb, device=dev) == 0).view(1, nb)
     st["run_seq"] = torch.where(g2, n_run_seq, run_seq)
     st["fin_seq"] = torch.where(g2, n_fin_seq, fin_seq)
+    if run_lp is not None:
+        st["run_lp"] = torch.where(g2, n_run_lp, run_lp)
+        st["fin_lp"] = torch.where(g2, n_fin_lp, fin_lp)
     st["run_sc"] = torch.where(g3, torch.where(first, torch.zeros_like(run_sc), torch.full_like(run_sc, NEG)), torch.where(g1, n_run_sc, run_sc))
     st["fin_sc"] = torch.where(g3, torch.full_like(fin_sc, NEG), torch.where(g1, n_fin_sc, fin_sc))
     st["fin_done"] = torch.where(g3, torch.zeros_like(fin_done), torch.where(g1, n_fin_done, fin_done)).to(torch.uint8)
@@ -295,7 +339,7 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
 
 def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int, device,
                 early_stopping=True, length_penalty: float = 1.0, limits=None, topk=None, poll: int = 8, return_state: bool = False,
-                process=None):
+                process=None, num_return_sequences: int = 1, return_logprobs: bool = False):
     """Beam search of ``n_images`` images over ``slots`` slots of ``num_beams`` decoder rows.  ``step_fn(state) -> logits [slots * nb, V]``
     runs one decoder step for every row: row slot * nb + i feeds state["tokens"][row] at step state["slot_t"][slot] for image
     state["slot_image"][slot], its prefix state["run_seq"][slot][i][:slot_t + 1] (idle slots may return anything finite).
@@ -304,12 +348,19 @@ def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int
     ``process(logp, hist [slots * nb, L], lens [slots * nb], live [slots * nb]) -> logp`` (optional; GenerationControls.rows_hook):
     generation controls on ``log_softmax(logits)``, row slot * nb + i with the history run_seq[slot][i][:slot_t[slot] + 1], before the
     beam score is added and with no second normalisation.  It belongs to the torch ranking (not combined with ``topk``).  None: what
-    this computed before."""
+    this computed before.
+    ``num_return_sequences`` n in 1..num_beams / ``return_logprobs``: with n > 1 or log-probabilities asked for, the result is
+    beam.nbest_result's dict instead (ids [N * n, width], scores, lengths, logprobs: image-major, best first), read off the n-best
+    outputs that every ended search wrote; per image it equals beam.beam_search's with the same two keywords."""
     import torch
     if process is not None and topk is not None:
         raise ValueError("beam_stream: `process` belongs to the torch ranking")
     nb, K = num_beams, 2 * num_beams
-    st = new_beam_state(n_images, slots, nb, max_len, pad_id, bos_id, device)
+    n_ret = int(num_return_sequences)
+    if not 1 <= n_ret <= nb:
+        raise ValueError(f"num_return_sequences must be in 1..num_beams = {nb} (got {n_ret})")
+    n_best = n_ret if (n_ret > 1 or return_logprobs) else 0
+    st = new_beam_state(n_images, slots, nb, max_len, pad_id, bos_id, device, n_best=n_best, want_logprobs=bool(return_logprobs))
     lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
     div = divisor_table(max_len, length_penalty, device)
     bound = step_bound(n_images, slots, max_len)
@@ -334,4 +385,15 @@ def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int
             if steps >= bound:
                 raise RuntimeError(f"beam_stream: {steps} steps for {n_images} images over {slots} slots exceed the bound {bound}")
     out = (st["out_ids"], st["out_score"])
+    if n_best:
+        out = nbest_outputs(st["nbest_ids"], st["nbest_score"], st["nbest_len"], st.get("nbest_logprob"))
     return (out, st) if return_state else out
+
+
+def nbest_outputs(nbest_ids, nbest_score, nbest_len, nbest_logprob=None):
+    """The n-best outputs of a wave as beam.nbest_result's dict: cropped to the longest row (at least 2 columns)."""
+    width = max(2, int(nbest_len.max()))
+    out = {"ids": nbest_ids[:, :width], "scores": nbest_score, "lengths": nbest_len.long()}
+    if nbest_logprob is not None:
+        out["logprobs"] = nbest_logprob[:, :width]
+    return out

@@ -67,6 +67,11 @@ def parse_args(argv=None):
                         "loader (TrOCRModel.generate_stream); stream-beam (an extension): it also logs test_cer_stream_beam from ONE "
                         "generate_stream(num_beams=4) over it, the test step's own beam search on refilled slots; beam = the reference's test "
                         "phase alone")
+    p.add_argument("--test_n_best", type=int, default=0,
+                   help="with --test_decode stream-beam (an extension): that decode returns the N best readings of every line (1..4, "
+                        "generate_stream(num_return_sequences=N)) and the test phase also logs test_cer_oracle, the mean CER of each line's "
+                        "best reading -- what a language model or lexicon rescoring of the candidates could reach at most -- and how often "
+                        "each rank held it; 0 = off")
     p.add_argument("--no_repeat_ngram_size", type=int, default=0,
                    help="generation control of the validation / test decodes (an extension; transformers.generate's name and rule): no "
                         "n-gram of this size occurs twice in a decoded line; 0 = off, the reference's behaviour")
@@ -159,6 +164,13 @@ def parse_args(argv=None):
                               ("--accumulate_grad_batches", args.accumulate_grad_batches != 1, "--model ocr's step has no accumulation window")):
             if on:
                 p.error(f"{flag} applies to the TrOCR model only: {why}")
+    if args.test_n_best:
+        if args.model == "ocr":
+            p.error("--test_n_best acts on the TrOCR beam search only: --model ocr decodes with CTC, which keeps no list of hypotheses")
+        if args.test_decode != "stream-beam":
+            p.error("--test_n_best needs --test_decode stream-beam: the n-best list comes from the beam search on refilled slots")
+        if not 1 <= args.test_n_best <= 4:
+            p.error(f"--test_n_best must be in 1..4 (the test decode runs 4 beams), not {args.test_n_best}")
     if not 0.0 <= args.label_smoothing < 1.0:
         p.error(f"--label_smoothing must be in [0, 1), not {args.label_smoothing}")
     if args.label_smoothing and args.model == "ocr":
@@ -497,7 +509,8 @@ def main(argv=None):
             box = [path]
             torch.distributed.broadcast_object_list(box, src=0)
             path = box[0]
-        main.test_metrics = run_test(model, test_loader, ckpt_path=path, rank=rank, stream_decode={"stream": True, "stream-beam": "stream-beam"}.get(args.test_decode, False))
+        main.test_metrics = run_test(model, test_loader, ckpt_path=path, rank=rank, stream_decode={"stream": True, "stream-beam": "stream-beam"}.get(args.test_decode, False),
+                                     **({"n_best": args.test_n_best} if args.test_n_best else {}))
     if world > 1:
         torch.distributed.destroy_process_group()
     if tmp is not None:

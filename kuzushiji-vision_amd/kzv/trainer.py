@@ -299,7 +299,7 @@ def load_checkpoint(model, opt, path: str, callbacks=()):
     return ck
 
 
-def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0, stream_decode: bool | str = False):
+def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int = 0, stream_decode: bool | str = False, n_best: int = 0):
     """``trainer.test(model, test_loader, ckpt_path="best")`` (scripts/train_trocr.py:193-195): load the best checkpoint,
     switch the optimizer to its eval parameters (on_test_epoch_start, trocr_model.py:441-445), run test_step over the
     loader, report the epoch means of test_loss / test_cer.  ``stream_decode`` (an extension): True also reports ``test_cer_greedy``,
@@ -308,7 +308,12 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
     itself is untouched.  In the stream modes, where the tokenizer is one character per token (``model.one_char_tokenizer``), the
     per-line values are computed from the ids on the device (kzv.metrics.edit_stats: the same values, ==) and rank 0 logs one more
     line: substitutions / deletions / insertions, corpus CER and the ten characters with the most errors; other tokenizers keep
-    batch_decode + calculate_cer."""
+    batch_decode + calculate_cer.  ``n_best`` n in 1..4 (with "stream-beam"; an extension): that decode returns the n best readings of every
+    line (``generate_stream(num_return_sequences=n)``), ``test_cer_stream_beam`` stays the winners', and the call also reports
+    ``test_cer_oracle`` -- the mean CER of each line's best reading, what a rescoring of the candidates could reach at most -- and rank 0
+    logs how often each rank held it (kzv.nbest.oracle_stats)."""
+    if n_best and stream_decode != "stream-beam":
+        raise ValueError("trainer.test: n_best needs stream_decode=\"stream-beam\" (an n-best list comes from the beam search on refilled slots)")
     if ckpt_path:
         load_checkpoint(model, model.optimizers(), ckpt_path)
     model.eval()
@@ -322,7 +327,13 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
         import torch
         key, kw = ("test_cer_stream_beam", {"num_beams": 4, "early_stopping": True}) if stream_decode == "stream-beam" else ("test_cer_greedy", {})
         model.logged.pop(key, None)
-        gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw, **getattr(model, "decode_controls", {}))
+        gen_all = None
+        if n_best:
+            model.logged.pop("test_cer_oracle", None)
+            gen_all = model.generate_stream((b["pixel_values"] for b in test_loader), **kw, num_return_sequences=int(n_best), **getattr(model, "decode_controls", {}))
+            gen = gen_all[0::int(n_best)]
+        else:
+            gen = model.generate_stream((b["pixel_values"] for b in test_loader), **kw, **getattr(model, "decode_controls", {}))
         labels = torch.cat([b["labels"] for b in test_loader])
         from . import metrics as M
         if model.one_char_tokenizer and gen.shape[1] <= M.MAX_WIDTH and labels.shape[1] <= M.MAX_WIDTH:
@@ -337,6 +348,25 @@ def test(model, test_loader, ckpt_path: str | None = None, log=print, rank: int 
             for p, t in zip(preds, tgts):
                 model.log(key, model.calculate_cer(p, t))
         keys += (key,)
+        if gen_all is not None:
+            import numpy as np
+            from . import nbest as NB
+            n = int(n_best)
+            if model.one_char_tokenizer and gen_all.shape[1] <= M.MAX_WIDTH and labels.shape[1] <= M.MAX_WIDTH:
+                st2 = M.edit_stats(gen_all, labels.to(gen_all.device).repeat_interleave(n, dim=0), model.tokenizer.all_special_ids, model.cfg.vocab, ops=False)
+                d, r, q = (st2[k].view(-1, n).cpu().numpy() for k in ("dist", "ref_len", "pred_len"))
+            else:
+                hyps = model.tokenizer.batch_decode(gen_all, skip_special_tokens=True)
+                tgts = [t for t in model.tokenizer.batch_decode(labels, skip_special_tokens=True) for _ in range(n)]
+                from .model import _levenshtein
+                d = np.asarray([_levenshtein(h, t) for h, t in zip(hyps, tgts)]).reshape(-1, n)
+                r = np.asarray([len(t) for t in tgts]).reshape(-1, n)
+                q = np.asarray([len(h) for h in hyps]).reshape(-1, n)
+            oracle = NB.oracle_stats(d, r[:, 0], q)
+            for v in oracle["cer_oracle_lines"]:
+                model.log("test_cer_oracle", v)
+            keys += ("test_cer_oracle",)
+            detail = (detail + "\n" if detail else "") + "best reading at rank (0 = the winner): " + " ".join(f"{k}:{c}" for k, c in enumerate(oracle["oracle_rank"]))
     if model.optimizers() is not None:
         model.optimizers().train()
     out = {k: (sum(model.logged[k]) / len(model.logged[k]) if model.logged.get(k) else float("nan")) for k in keys}
