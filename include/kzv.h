@@ -247,6 +247,37 @@ typedef struct kzv_lm_fuse_args {
     const kzv_ngram_lm* lm;                              /* host pointer */
 } kzv_lm_fuse_args;
 int kzv_lm_fuse(const kzv_lm_fuse_args* args, void* stream);
+/* Forced prefixes (kzv/prefix.py: force_reference is the torch statement): decoding continues a line from given tokens.  A prefix is 0 or
+ * more token ids per image, without BOS, in prefix [n, ld_prefix] int64 with its length in prefix_len [n] int32 (clamped to ld_prefix);
+ * both are device memory indexed by IMAGE: r / group in the lockstep case, slot_image[r / group] in the slot cases.  At a step whose
+ * chosen index cur = t + 1 satisfies 1 <= cur <= prefix_len[image], row r of logits [rows, ld] becomes -inf in every column below vocab
+ * and 0 at the forced token prefix[image][cur - 1] (HF's ForceTokensLogitsProcessor); rows past their prefix, rows of an idle slot and
+ * columns [vocab, ld) are not written.  A forced token outside [0, vocab) leaves the row alone (the callers refuse such a prefix).  It
+ * is the LAST node of the logits chain, after kzv_logits_process and kzv_lm_fuse: the prompt is subject to neither.  Selection does not
+ * change: arg-max picks the forced token with log-probability exactly 0; a beam step (normalise -> fuse -> force ->
+ * kzv_beam_rank_logprobs) carries the prefix in all beams at scores 0, -1e9, -1e9, .. -- HF's state after a prompt.  One decoder step per
+ * forced token: there is no prefill pass.
+ * t / group / slot_image / slot_t / n_images and the idle-slot rule: kzv_logits_process's (group >= 1 also in the lockstep case, where it
+ * is the rows per image; by_image is accepted and ignored, since no history is read).
+ * forced_logprob (optional, fp32 [n, ld_forced_logprob > ld_prefix]): the model's own opinion of the forced token, written to
+ * forced_logprob[image][cur] BEFORE the overwrite by the first row of the group only: x[f] when `normalised` != 0 (the row holds
+ * log-probabilities already), x[f] - logsumexp(x) otherwise.
+ * One workgroup of 256 threads per row.  KZV_E_ARG before any launch: null args / logits / prefix / prefix_len, rows < 1, vocab outside
+ * 1..16,384, ld < vocab, ld_prefix < 1, group < 1 or rows no multiple of it, forced_logprob rows not longer than ld_prefix, one of
+ * slot_image / slot_t without the other, n_images < 1 in the slot cases, t < 0 in the lockstep case. */
+typedef struct kzv_force_prefix_args {
+    float* logits; int64_t ld;                           /* [rows, ld >= vocab], edited in place */
+    int32_t rows, vocab;
+    int32_t t;                                           /* lockstep: the step index */
+    int32_t group;                                       /* rows per image / slot */
+    const int32_t* slot_image; const int32_t* slot_t;    /* slot cases: [rows / group] */
+    int32_t by_image, n_images;
+    const int64_t* prefix; int64_t ld_prefix;            /* [n, ld_prefix] */
+    const int32_t* prefix_len;                           /* [n] */
+    int32_t normalised, reserved;
+    float* forced_logprob; int64_t ld_forced_logprob;    /* optional [n, ld_forced_logprob] */
+} kzv_force_prefix_args;
+int kzv_force_prefix(const kzv_force_prefix_args* args, void* stream);
 /* The inputs of decoder step t from the token table d_ids [batch, ld_ids]: d_tokens [batch] = column t, d_posids [batch] = its
  * RoBERTa position id (t + 1 + pad_id, or pad_id for padding), d_valid[:, t] = token != pad. */
 int kzv_decode_prep(const int64_t* d_ids, int64_t ld_ids, int t, int pad_id, int batch, int64_t* d_tokens, uint8_t* d_valid, int64_t ld_valid,
@@ -282,6 +313,15 @@ typedef struct kzv_beam_state {
 } kzv_beam_state;
 int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
                     float length_penalty, int64_t* d_rows, int32_t* d_flags, void* stream);
+/* kzv_beam_update for images that carry forced prefixes (kzv_force_prefix): d_prefix_len int32 [batch] holds every image's prefix length
+ * and d_divisors fp32 [max_len + 1] the table n -> (float)pow(n, length_penalty) (entry 0 unused), since the generated length now differs
+ * per image: g = max(cur - prefix_len[i], 1) is the divisor's index both for a hypothesis that ends at this step (cur + 1 - (1 + prefix_len))
+ * and for the early-stop heuristic after it (the same number, as in kzv_beam_update).  The clamp to 1 is the rule for forced steps: there
+ * g would be <= 0, nothing can finish (a prefix holds no EOS and ends before max_len - 1), so only the running-beam part of the update
+ * has an effect and the image stays unsatisfied (0 / 1 > -1e9).  A null d_prefix_len is kzv_beam_update itself (today's kernel instance; d_divisors is
+ * then not read).  The length table is an argument of its own, not a field of kzv_beam_state, whose layout stays what it was. */
+int kzv_beam_update_prefix(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
+                           float length_penalty, const float* d_divisors, const int32_t* d_prefix_len, int64_t* d_rows, int32_t* d_flags, void* stream);
 /* The same step replayed from a hipGraph (the eager step is ~100 small launches and host-bound at ~0.85 ms per token):
  * the step index lives in device memory -- kzv_decode_begin resets it to 0, every kzv_decode_step_graph runs step t and
  * leaves t + 1 -- so one instantiated graph serves every step of a generation.  The graph is captured on the first call
@@ -489,6 +529,11 @@ typedef struct kzv_stream_beam_state {
 } kzv_stream_beam_state;
 int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void* stream);
 int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream);
+/* kzv_stream_beam_update for a wave with forced prefixes: d_prefix_len int32 [n_images], indexed by IMAGE.  A slot holding image i at
+ * cur = slot_t + 1 divides by divisors[max(cur - prefix_len[i], 1)] -- kzv_beam_update_prefix's rule, clamp included (forced steps do
+ * the running-beam part only and stay unsatisfied).  Null: kzv_stream_beam_update itself, today's kernel instances. */
+int kzv_stream_beam_update_prefix(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, const int32_t* d_prefix_len,
+                                  void* stream);
 /* On the model handle: the bound batch = slots * num_beams decoder rows.
  * kzv_stream_beam_impl: 1 where the bound geometry gets beam search on slots -- where kzv_stream_decode_impl's conditions hold for
  * num_beams (2 or 4) rows per image, the bound batch is a multiple of num_beams and the vocabulary is within kzv_beam_topk's 16,384 --
@@ -542,6 +587,20 @@ int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* controls, v
  * launches exactly what it launches without this call.  Launches no kernel itself.  KZV_E_STATE outside a begun wave; KZV_E_ARG for a
  * null struct or tables, a vocabulary different from the model's, an order outside 1..4 and a non-finite weight. */
 int kzv_stream_set_lm(kzv_model* m, const kzv_ngram_lm* lm, float weight, void* stream);
+/* Forced prefixes for the wave just begun (greedy or beams): after kzv_stream_begin / kzv_stream_begin_beams and before kzv_stream_start.
+ * d_prefix int64 [n_images, ld_prefix] and d_prefix_len int32 [n_images] are kzv_force_prefix's tables, indexed by the wave's image
+ * numbers; d_forced_logprob (optional) fp32 [n_images, ld_forced_logprob > ld_prefix] receives the model's own log-probability of every
+ * forced token at column cur (the caller has filled zeros).  All three are caller-owned device memory that must outlive the wave.  Every
+ * kzv_stream_step then runs kzv_force_prefix as one more kernel node of the same single chain, after the language model's node (if any)
+ * and before kzv_stream_topk / selection, on each slot's own image and step: a slot that is reseated reads the new image's prefix from
+ * step 0.  A beam wave takes the normalise -> (fuse) -> force -> kzv_beam_rank_logprobs route, as kzv_stream_set_lm's, and updates through
+ * kzv_stream_beam_update_prefix.  The lengths live on the device, so the library cannot see them: ld_prefix (the longest prefix) is what
+ * it checks against max_len, and ld_prefix == 0 -- every prefix empty -- switches the setting off: a step then launches exactly what it
+ * launches without this call.  The setting belongs to one wave: the next begin clears it.  Launches no kernel itself.  KZV_E_STATE outside
+ * a begun wave; KZV_E_ARG for a null prefix or length table (with ld_prefix > 0), ld_prefix < 0, 1 + ld_prefix > max_len - 1 (a prefix that
+ * reaches max_len - 1 leaves no token to generate), a vocabulary beyond 16,384 and forced_logprob rows not longer than ld_prefix. */
+int kzv_stream_set_prefix(kzv_model* m, const int64_t* d_prefix, int64_t ld_prefix, const int32_t* d_prefix_len, float* d_forced_logprob,
+                          int64_t ld_forced_logprob, void* stream);
 
 /* loss.backward() for the step above: fills the bound fp32 grad buffer (which must be zero on entry;
  * kzv_zero_grads does that).  Backward is split in `kzv_backward_segments()` segments so the host can

@@ -413,6 +413,7 @@ static int stream_begin(kzv_model* m, const char* who, int nb, int early, float 
     m->sctl_on = false; m->smask_on = false;     // and so does kzv_stream_set_controls (neutral until it is called)
     m->sctl = kzv_logits_controls{}; m->sctl.repetition_penalty = 1.f;
     m->slm_on = false;                           // and kzv_stream_set_lm
+    m->spfx_on = false; m->spfx = nullptr; m->spfx_len = nullptr; m->spfx_lp = nullptr; m->spfx_ld = m->spfx_lp_ld = 0;      // and kzv_stream_set_prefix
     if (nb == 1) {
         kzv_stream_state& st = m->sst;
         st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
@@ -552,6 +553,25 @@ extern "C" int kzv_stream_set_lm(kzv_model* m, const kzv_ngram_lm* lm, float wei
     return KZV_OK;
 }
 
+extern "C" int kzv_stream_set_prefix(kzv_model* m, const int64_t* d_prefix, int64_t ld_prefix, const int32_t* d_prefix_len, float* d_forced_logprob,
+                                     int64_t ld_forced_logprob, void* stream) {
+    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
+    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_prefix: call kzv_stream_begin / kzv_stream_begin_beams first");
+    const int max_len = m->sbeams ? m->sbst.max_len : m->sst.max_len;
+    if (ld_prefix < 0) return kzv_fail(KZV_E_ARG, "stream_set_prefix: ld_prefix must not be negative");
+    if (ld_prefix > 0 && (!d_prefix || !d_prefix_len)) return kzv_fail(KZV_E_ARG, "stream_set_prefix: null prefix / prefix_len table");
+    if (1 + ld_prefix > (int64_t)max_len - 1)
+        return kzv_fail(KZV_E_ARG, "stream_set_prefix: BOS + %lld forced tokens reach max_len - 1 = %d: no token would be generated", (long long)ld_prefix, max_len - 1);
+    if (m->V > 64 * 256) return kzv_fail(KZV_E_ARG, "stream_set_prefix: vocabulary %d beyond 16,384", m->V);
+    if (ld_prefix > 0 && d_forced_logprob && ld_forced_logprob < ld_prefix + 1)
+        return kzv_fail(KZV_E_ARG, "stream_set_prefix: forced_logprob rows of %lld columns are shorter than BOS + the %lld prefix columns", (long long)ld_forced_logprob, (long long)ld_prefix);
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
+    m->spfx_on = ld_prefix > 0;
+    m->spfx = m->spfx_on ? d_prefix : nullptr; m->spfx_ld = ld_prefix; m->spfx_len = m->spfx_on ? d_prefix_len : nullptr;
+    m->spfx_lp = m->spfx_on ? d_forced_logprob : nullptr; m->spfx_lp_ld = m->spfx_lp ? ld_forced_logprob : 0;
+    return KZV_OK;
+}
+
 // the wave's controls on the step's logits: one more node between the vocabulary GEMM and what reads the rows (order: repetition penalty,
 // n-gram ban, minimum length, suppression -- immaterial, see logits_process.hip)
 static int stream_process(kzv_model* m, hipStream_t s) {
@@ -577,6 +597,20 @@ static int stream_lm_fuse(kzv_model* m, hipStream_t s) {
     else { a.ids = m->sbst.run_seq; a.ld_ids = m->sbst.max_len; a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; }
     a.weight = m->slm_weight; a.lm = &m->slm;
     return kzv_lm_fuse(&a, s);
+}
+
+// the wave's forced prefixes on the step's scores: the chain's last node before selection, on every slot's own image and step
+static int stream_force_prefix(kzv_model* m, hipStream_t s, bool normalised) {
+    const int nb = m->sbeams;
+    kzv_force_prefix_args a;
+    memset(&a, 0, sizeof(a));
+    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
+    if (!nb) { a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; }
+    else { a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; }
+    a.prefix = m->spfx; a.ld_prefix = m->spfx_ld; a.prefix_len = m->spfx_len;
+    a.normalised = normalised ? 1 : 0;
+    a.forced_logprob = m->spfx_lp; a.ld_forced_logprob = m->spfx_lp_ld;
+    return kzv_force_prefix(&a, s);
 }
 
 extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
@@ -609,13 +643,15 @@ static int stream_step_body(kzv_model* m, hipStream_t s) {
     KZV_TRY(vocab_logits(m, true, m->slogits, s));
     // neutral controls and no language model: nothing is added to the chain.  A beam wave with the language model on normalises through
     // the controls' node even when the controls are neutral: the fusion acts on log-probabilities
-    const bool lm = m->slm_on;
-    if (m->sctl_on || (lm && nb)) KZV_TRY(stream_process(m, s));
+    // Forced prefixes come last (the prompt is subject to neither) and take the same route in a beam wave: a forced row is no logits row.
+    const bool lm = m->slm_on, pfx = m->spfx_on;
+    if (m->sctl_on || ((lm || pfx) && nb)) KZV_TRY(stream_process(m, s));
     if (lm) KZV_TRY(stream_lm_fuse(m, s));
-    if (m->sctl_on || lm) {
+    if (pfx) KZV_TRY(stream_force_prefix(m, s, nb != 0));
+    if (m->sctl_on || lm || pfx) {
         if (nb) {                                // the rows are processed log-probabilities now: ranked without a second normalisation
             KZV_TRY(kzv_beam_rank_logprobs(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
-            return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);
+            return kzv_stream_beam_update_prefix(&m->sbst, m->stop_lp, m->stop_ix, pfx ? m->spfx_len : nullptr, s);
         }
     }
     if (!nb) {                                   // the alternatives read slot_image / slot_t before seating replaces them

@@ -142,6 +142,10 @@ struct kzv_model_plain {
     // are the caller's device memory
     bool slm_on = false; float slm_weight = 0.f;
     kzv_ngram_lm slm = {};
+    // forced prefixes of the wave (kzv_stream_set_prefix): on only while ld_prefix > 0; the tables are the caller's device memory
+    bool spfx_on = false;
+    const int64_t* spfx = nullptr; int64_t spfx_ld = 0; const int32_t* spfx_len = nullptr;
+    float* spfx_lp = nullptr; int64_t spfx_lp_ld = 0;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU

@@ -272,6 +272,7 @@ struct BeamUpd {
     float div;                                                    // cur ** length_penalty as fp32: the length divisor of a hypothesis that ends at this step
     const float* run_lp_in; float* run_lp_out;                    // [B, nb, L] fp32 or null: the token rows' per-token log-probabilities (LP instance)
     const float* fin_lp_in; float* fin_lp_out;
+    const int* prefix_len; const float* divtab;                   // PFX instance: [B] prefix lengths, [L + 1] fp32 of n ** length_penalty
 };
 
 // One image's step, ranked: what one lane works out between the loads and the row copies.  The inputs are filled by the lanes together
@@ -355,7 +356,10 @@ __device__ __forceinline__ void beam_token_lp(const BeamRank& r, int K, const fl
 
 // LP: the token rows' log-probability rows go through the same copies (run_lp / fin_lp, double-buffered alike).  The off instance holds
 // none of it: no extra LDS, loads or stores.
-template <bool LP>
+// PFX (kzv_beam_update_prefix): the image carries a forced prefix, so the generated length is its own: the divisor comes from the table at
+// max(cur - prefix_len, 1).  The clamp serves the forced steps, where nothing can finish: they do the running-beam part only and stay
+// unsatisfied.  The off instances read neither field.
+template <bool LP, bool PFX>
 __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
     __shared__ BeamRank r;
     __shared__ float s_old[LP ? 8 : 1], s_tlp[LP ? 16 : 1];
@@ -368,7 +372,9 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const BeamUpd p) {
     __syncthreads();
     if (lane == 0) {
         BeamRankOut o;
-        beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, p.div);
+        float div = p.div;
+        if constexpr (PFX) div = p.divtab[min(max(p.cur - p.prefix_len[img], 1), L)];
+        beam_rank(r, o, nb, K, p.V, p.eos, p.cur, L, p.early, div);
         if constexpr (LP) beam_token_lp(r, K, s_old, s_tlp);
         for (int i = 0; i < nb; ++i) {
             p.rows[img * nb + i] = (int64_t)img * nb + r.src[r.nxt[i]];
@@ -440,6 +446,7 @@ struct StreamNBestP {
     int n_best;                                                     // rows 0 .. n_best - 1 of the finished list leave when a search ends
     int64_t* ids; int64_t ld_ids; float* score; int* len;           // [n_images * n_best, ld_ids], [n_images * n_best]
     float* lp; int64_t ld_lp;                                       // optional [n_images * n_best, ld_lp] (LP)
+    const int* prefix_len;                                          // [n_images] forced-prefix lengths (PFX), else null
 };
 constexpr int SB_NB = 4, SB_L = 128;                                // what the staging holds: 2 x 4 x 128 token rows (8 KB) + 4 x 128 table entries; LP: 2 x 4 x 128 fp32 (4 KB) more
 
@@ -456,7 +463,9 @@ __device__ __forceinline__ float beam_fin_lp(const BeamRank& r, int mi, int j, i
 // NBEST: at the end of a search rows 0 .. n_best - 1 of the finished list leave, not only row 0.  LP (needs NBEST): the log-probability
 // rows are staged and moved beside the token rows.  The plain instance <false, false> holds none of either: its LDS and its code are
 // those of the kernel without them.
-template <bool NBEST, bool LP>
+// PFX (kzv_stream_beam_update_prefix): the divisor's index is the image's own generated length max(cur - prefix_len[img], 1), as in
+// beam_update_kernel; the off instances do not read the table.
+template <bool NBEST, bool LP, bool PFX>
 __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBeamP p, const StreamNBestP q) {
     __shared__ BeamRank r;
     __shared__ BeamRankOut o;                    // the ranking lane's results, for every thread
@@ -472,7 +481,7 @@ __global__ __launch_bounds__(256) void stream_beam_update_kernel(const StreamBea
     }
     const int t = min(p.slot_t[s], L - 2), cur = t + 1;
     const int lim = p.limit ? min(p.limit[img], L) : L;
-    const float div = p.div[cur];
+    const float div = p.div[PFX ? min(max(cur - q.prefix_len[min(img, p.n_images - 1)], 1), L) : cur];
     beam_rank_load(r, tid, K, nb, s, p.top_lp, p.top_ix, p.fin_sc, p.fin_done, p.fin_len, p.unsat);
     // the slot's old rows: whole rows, as the statement moves them (what lies behind cur may be an earlier image's and is never read)
     for (int e = tid; e < nb * L; e += 256) { s_run[e] = p.run_seq[(int64_t)s * nb * L + e]; s_fin[e] = p.fin_seq[(int64_t)s * nb * L + e]; }
@@ -690,7 +699,7 @@ static int stream_beam_params(const kzv_stream_beam_state* st, const float* top_
         if (st->nbest_logprob && st->ld_nbest_logprob < st->max_len) return kzv_fail(KZV_E_ARG, "%s: n-best log-probability rows shorter than max_len", who);
         if ((int64_t)st->n_images * st->n_best >= (1ll << 31)) return kzv_fail(KZV_E_ARG, "%s: n-best rows beyond 32-bit indices", who);
     }
-    *q = StreamNBestP{st->run_lp, st->fin_lp, st->n_best, st->nbest_ids, st->ld_nbest, st->nbest_scores, st->nbest_len, st->nbest_logprob, st->ld_nbest_logprob};
+    *q = StreamNBestP{st->run_lp, st->fin_lp, st->n_best, st->nbest_ids, st->ld_nbest, st->nbest_scores, st->nbest_len, st->nbest_logprob, st->ld_nbest_logprob, nullptr};
     return KZV_OK;
 }
 
@@ -701,15 +710,28 @@ extern "C" int kzv_stream_beam_seat_first(const kzv_stream_beam_state* st, void*
     return kzv_check_launch("stream_beam_seat_first");
 }
 
-extern "C" int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream) {
+template <bool PFX>
+static int stream_beam_update_launch(const char* who, const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index,
+                                     const int32_t* d_prefix_len, void* stream) {
     StreamBeamP p; StreamNBestP q;
-    KZV_TRY_RC(stream_beam_params(st, d_top_scores, d_top_index, &p, &q, "stream_beam_update"));
-    if (!d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "stream_beam_update: null ranking [slots, 2 * num_beams]");
-    if (q.run_lp) hipLaunchKernelGGL((stream_beam_update_kernel<true, true>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
-    else if (q.n_best) hipLaunchKernelGGL((stream_beam_update_kernel<true, false>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
-    else hipLaunchKernelGGL((stream_beam_update_kernel<false, false>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
+    KZV_TRY_RC(stream_beam_params(st, d_top_scores, d_top_index, &p, &q, who));
+    if (!d_top_scores || !d_top_index) return kzv_fail(KZV_E_ARG, "%s: null ranking [slots, 2 * num_beams]", who);
+    q.prefix_len = PFX ? d_prefix_len : nullptr;
+    if (q.run_lp) hipLaunchKernelGGL((stream_beam_update_kernel<true, true, PFX>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
+    else if (q.n_best) hipLaunchKernelGGL((stream_beam_update_kernel<true, false, PFX>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
+    else hipLaunchKernelGGL((stream_beam_update_kernel<false, false, PFX>), dim3(st->slots), dim3(256), 0, (hipStream_t)stream, p, q);
     hipLaunchKernelGGL(stream_beam_seat_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
-    return kzv_check_launch("stream_beam_update");
+    return kzv_check_launch(who);
+}
+
+extern "C" int kzv_stream_beam_update(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, void* stream) {
+    return stream_beam_update_launch<false>("stream_beam_update", st, d_top_scores, d_top_index, nullptr, stream);
+}
+
+extern "C" int kzv_stream_beam_update_prefix(const kzv_stream_beam_state* st, const float* d_top_scores, const int64_t* d_top_index,
+                                             const int32_t* d_prefix_len, void* stream) {
+    if (!d_prefix_len) return stream_beam_update_launch<false>("stream_beam_update_prefix", st, d_top_scores, d_top_index, nullptr, stream);
+    return stream_beam_update_launch<true>("stream_beam_update_prefix", st, d_top_scores, d_top_index, d_prefix_len, stream);
 }
 
 static int beam_topk_args(const char* who, const float* d_logits, int64_t ld, const float* d_beam_scores, int batch, int num_beams, int vocab, int k,
@@ -748,27 +770,43 @@ extern "C" int kzv_beam_rank_logprobs(const float* d_logprobs, int64_t ld, const
     return beam_topk_launch<false>("beam_rank_logprobs", d_logprobs, ld, d_beam_scores, batch, num_beams, vocab, k, d_top_scores, d_top_index, stream);
 }
 
-extern "C" int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
-                               float length_penalty, int64_t* d_rows, int* d_flags, void* stream) {
-    if (!st || !d_top_scores || !d_top_index || !d_rows || !d_flags) return kzv_fail(KZV_E_ARG, "beam_update: null operand");
+static int beam_update_launch(const char* who, const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
+                              float length_penalty, const float* d_divisors, const int32_t* d_prefix_len, int64_t* d_rows, int* d_flags, void* stream) {
+    if (!st || !d_top_scores || !d_top_index || !d_rows || !d_flags) return kzv_fail(KZV_E_ARG, "%s: null operand", who);
     if (!st->run_seq_in || !st->run_seq_out || !st->fin_seq_in || !st->fin_seq_out || !st->run_scores || !st->fin_scores || !st->fin_done ||
-        !st->fin_len || !st->unsatisfied) return kzv_fail(KZV_E_ARG, "beam_update: null state array");
-    if (st->batch < 1 || st->num_beams < 1 || st->num_beams > 8 || st->max_len < 2 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "beam_update: 1..8 beams");
-    if (cur < 1 || cur >= st->max_len) return kzv_fail(KZV_E_ARG, "beam_update: position outside 1..max_len-1");
-    if (st->run_seq_in == st->run_seq_out || st->fin_seq_in == st->fin_seq_out) return kzv_fail(KZV_E_ARG, "beam_update: in and out token rows must differ");
+        !st->fin_len || !st->unsatisfied) return kzv_fail(KZV_E_ARG, "%s: null state array", who);
+    if (st->batch < 1 || st->num_beams < 1 || st->num_beams > 8 || st->max_len < 2 || st->vocab < 1) return kzv_fail(KZV_E_ARG, "%s: 1..8 beams", who);
+    if (cur < 1 || cur >= st->max_len) return kzv_fail(KZV_E_ARG, "%s: position outside 1..max_len-1", who);
+    if (st->run_seq_in == st->run_seq_out || st->fin_seq_in == st->fin_seq_out) return kzv_fail(KZV_E_ARG, "%s: in and out token rows must differ", who);
     const bool lp_rows = st->run_lp_in || st->run_lp_out || st->fin_lp_in || st->fin_lp_out;
-    if (lp_rows && (!st->run_lp_in || !st->run_lp_out || !st->fin_lp_in || !st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "beam_update: the four log-probability row arrays come together");
-    if (lp_rows && (st->run_lp_in == st->run_lp_out || st->fin_lp_in == st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "beam_update: in and out log-probability rows must differ");
+    if (lp_rows && (!st->run_lp_in || !st->run_lp_out || !st->fin_lp_in || !st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "%s: the four log-probability row arrays come together", who);
+    if (lp_rows && (st->run_lp_in == st->run_lp_out || st->fin_lp_in == st->fin_lp_out)) return kzv_fail(KZV_E_ARG, "%s: in and out log-probability rows must differ", who);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(d_flags, 0, (cur == 1 ? 5 : 3) * sizeof(int), s) != hipSuccess) return kzv_fail(KZV_E_HIP, "beam_update: memset");
+    if (hipMemsetAsync(d_flags, 0, (cur == 1 ? 5 : 3) * sizeof(int), s) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: memset", who);
     BeamUpd p{d_top_scores, d_top_index, st->run_seq_in, st->run_seq_out, st->fin_seq_in, st->fin_seq_out, st->run_scores, st->fin_scores,
               st->fin_done, st->fin_len, st->unsatisfied, d_rows, d_flags, st->num_beams, 2 * st->num_beams, st->max_len, st->vocab, cur,
               st->eos_id, early_stopping ? 1 : 0, (float)pow((double)cur, (double)length_penalty),
-              st->run_lp_in, st->run_lp_out, st->fin_lp_in, st->fin_lp_out};
-    if (lp_rows) hipLaunchKernelGGL(beam_update_kernel<true>, dim3(st->batch), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(beam_update_kernel<false>, dim3(st->batch), dim3(64), 0, s, p);
+              st->run_lp_in, st->run_lp_out, st->fin_lp_in, st->fin_lp_out, d_prefix_len, d_divisors};
+    if (d_prefix_len) {
+        if (lp_rows) hipLaunchKernelGGL((beam_update_kernel<true, true>), dim3(st->batch), dim3(64), 0, s, p);
+        else hipLaunchKernelGGL((beam_update_kernel<false, true>), dim3(st->batch), dim3(64), 0, s, p);
+    } else {
+        if (lp_rows) hipLaunchKernelGGL((beam_update_kernel<true, false>), dim3(st->batch), dim3(64), 0, s, p);
+        else hipLaunchKernelGGL((beam_update_kernel<false, false>), dim3(st->batch), dim3(64), 0, s, p);
+    }
     hipLaunchKernelGGL(beam_stop_kernel, dim3(1), dim3(1), 0, s, d_flags, early_stopping ? 1 : 0, cur);
-    return kzv_check_launch("beam_update");
+    return kzv_check_launch(who);
+}
+
+extern "C" int kzv_beam_update(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
+                               float length_penalty, int64_t* d_rows, int* d_flags, void* stream) {
+    return beam_update_launch("beam_update", st, d_top_scores, d_top_index, cur, early_stopping, length_penalty, nullptr, nullptr, d_rows, d_flags, stream);
+}
+
+extern "C" int kzv_beam_update_prefix(const kzv_beam_state* st, const float* d_top_scores, const int64_t* d_top_index, int cur, int early_stopping,
+                                      float length_penalty, const float* d_divisors, const int32_t* d_prefix_len, int64_t* d_rows, int* d_flags, void* stream) {
+    if (d_prefix_len && !d_divisors) return kzv_fail(KZV_E_ARG, "beam_update_prefix: prefix lengths need the divisor table (fp32 [max_len + 1] of n ** length_penalty)");
+    return beam_update_launch("beam_update_prefix", st, d_top_scores, d_top_index, cur, early_stopping, length_penalty, d_divisors, d_prefix_len, d_rows, d_flags, stream);
 }
 
 extern "C" int kzv_decode_prep(const int64_t* d_ids, int64_t ld_ids, int t, int pad_id, int batch, int64_t* d_tokens, uint8_t* d_valid, int64_t ld_valid,

@@ -110,6 +110,13 @@ class kzv_lm_fuse_args(C.Structure):
                 ("n_images", C.c_int32), ("weight", C.c_float), ("reserved", C.c_int32), ("lm", C.POINTER(kzv_ngram_lm))]
 
 
+class kzv_force_prefix_args(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("vocab", C.c_int32), ("t", C.c_int32), ("group", C.c_int32),
+                ("slot_image", C.c_void_p), ("slot_t", C.c_void_p), ("by_image", C.c_int32), ("n_images", C.c_int32),
+                ("prefix", C.c_void_p), ("ld_prefix", C.c_int64), ("prefix_len", C.c_void_p), ("normalised", C.c_int32), ("reserved", C.c_int32),
+                ("forced_logprob", C.c_void_p), ("ld_forced_logprob", C.c_int64)]
+
+
 class kzv_edit_args(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("ld_pred", C.c_int64), ("ref", C.c_void_p), ("ld_ref", C.c_int64),
                 ("n", C.c_int32), ("width_pred", C.c_int32), ("width_ref", C.c_int32), ("vocab", C.c_int32), ("n_special", C.c_int32),
@@ -325,6 +332,12 @@ SYMBOLS = {
     "kzv_lm_fuse": (C.c_int, [C.POINTER(kzv_lm_fuse_args), C.c_void_p]),
     "kzv_test_lm_fuse_calls": (C.c_int64, []),             # test hook (csrc/lm_fusion.hip), not declared in include/kzv.h
     "kzv_stream_set_lm": (C.c_int, [C.c_void_p, C.POINTER(kzv_ngram_lm), C.c_float, C.c_void_p]),
+    "kzv_force_prefix": (C.c_int, [C.POINTER(kzv_force_prefix_args), C.c_void_p]),
+    "kzv_test_force_prefix_calls": (C.c_int64, []),        # test hook (csrc/force_prefix.hip), not declared in include/kzv.h
+    "kzv_stream_set_prefix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "kzv_beam_update_prefix": (C.c_int, [C.POINTER(kzv_beam_state), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kzv_stream_beam_update_prefix": (C.c_int, [C.POINTER(kzv_stream_beam_state), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kzv_stream_seat_first": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p]),
     "kzv_stream_update": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_void_p]),
     "kzv_stream_topk": (C.c_int, [C.POINTER(kzv_stream_state), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

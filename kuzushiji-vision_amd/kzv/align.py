@@ -56,7 +56,7 @@ def pad_rows(x, width: int, fill=0):
 
 
 def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: int, eos_id: int, texts=None, to_strings=None,
-                  alternatives=None) -> list[dict]:
+                  alternatives=None, forced=None, prefix_logprobs=None) -> list[dict]:
     """One record per image from ids [B, L] (BOS first, PAD after the end) and the per-position arrays [B, L - 1] (centroid
     [B, L - 1, 2] in pixels, (y, x)):
 
@@ -76,7 +76,13 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
 
       alternatives  per token of ``tokens`` a list of up to k dicts {"token", "string", "logprob"} in rank order (entries with
                     id -1 dropped; ``string`` from ``to_strings``, else None)
-      margins       per token the first alternative's log-probability minus the second's; inf with a single candidate"""
+      margins       per token the first alternative's log-probability minus the second's; inf with a single candidate
+
+    ``forced`` = [B] ints (forced prefixes, kzv/prefix.py: the first forced[b] tokens after BOS were given, not read) adds ``forced``
+    (the count) to every record; ``confidence`` is then taken over the FREE tokens only (EOS included), and the ``alternatives`` /
+    ``margins`` of forced positions are emptied ([] / inf).  ``prefix_logprobs`` [B, >= forced + 1] (column t + 1 = the model's own
+    log-probability of the token forced at row t; generate_stream(return_prefix_logprobs=True)) adds ``prefix_logprobs``, one value
+    per forced token.  None: the records as they were."""
     ids = np.asarray(ids)
     logprob = np.asarray(logprob, dtype=np.float64)
     centroid = np.asarray(centroid, dtype=np.float64)
@@ -96,7 +102,9 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
             tok = int(ids[b, t + 1])
             if tok == pad_id or int(ids[b, t]) == pad_id:
                 break
-            scored.append(float(logprob[b, t]))
+            is_forced = forced is not None and t < int(forced[b])
+            if not is_forced:
+                scored.append(float(logprob[b, t]))
             if tok == eos_id:
                 break
             if tok == bos_id:            # a BOS past column 0 is a special token like any other: scored, not reported
@@ -108,6 +116,10 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
             if alternatives is not None:
                 cand = [(int(i), float(p)) for i, p in zip(alt_ids[b, t], alt_lp[b, t]) if int(i) >= 0]
                 strs = [None] * len(cand) if to_strings is None else list(to_strings([i for i, _ in cand]))
+                if is_forced:            # the row was overwritten: its candidates say nothing about the model
+                    alts.append([])
+                    margins.append(math.inf)
+                    continue
                 alts.append([{"token": i, "string": s, "logprob": p} for (i, p), s in zip(cand, strs)])
                 margins.append(cand[0][1] - cand[1][1] if len(cand) > 1 and cand[1][1] > -math.inf else math.inf)
         records.append({
@@ -122,4 +134,8 @@ def build_records(ids, logprob, centroid, peak_patch, *, pad_id: int, bos_id: in
         if alternatives is not None:
             records[-1]["alternatives"] = alts
             records[-1]["margins"] = margins
+        if forced is not None:
+            records[-1]["forced"] = int(forced[b])
+            if prefix_logprobs is not None:
+                records[-1]["prefix_logprobs"] = [float(prefix_logprobs[b][t + 1]) for t in range(int(forced[b]))]
     return records

@@ -29,18 +29,37 @@ from __future__ import annotations
 NEG = -1.0e9
 
 
-def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, update=None, process=None):
+def _prefix_rows(prefix, batch: int, group: int, device):
+    """``prefix`` = (ids int64 [batch, P], lengths [batch]) (kzv/prefix.py: normalise) on ``device``, expanded to ``group`` rows per
+    image: (ids [batch * group, P], lengths int64 [batch * group], lengths per image int64 [batch, 1])."""
+    pfx, plen = prefix
+    pfx, plen = pfx.to(device).long(), plen.to(device).long().reshape(-1)
+    if pfx.dim() != 2 or pfx.shape[0] != batch or plen.numel() != batch:
+        raise ValueError(f"prefix: ids [batch, P] and lengths [batch] for batch = {batch}")
+    return pfx.repeat_interleave(group, dim=0), plen.repeat_interleave(group), plen.view(batch, 1)
+
+
+def greedy(step, batch: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, update=None, process=None, prefix=None):
     """``num_beams=1``: argmax per step; finished rows emit padding; stops when every row has emitted EOS.
     ``update(logits, ids, t, done) -> running`` (optional, kzv_greedy_update): the selection in one launch; running[t] = rows
     still running after step t.
     ``process(logits, ids, n) -> logits`` (optional; kzv/controls.py: GenerationControls.hook): generation controls on the step's raw
-    logits given the histories ids[:, :n] -- where HF's greedy loop applies its logits processors.  None: what this computed before."""
+    logits given the histories ids[:, :n] -- where HF's greedy loop applies its logits processors.  None: what this computed before.
+    ``prefix`` = (ids [batch, P], lengths [batch]) (optional; kzv/prefix.py): every row's forced prefix, the prompt [BOS] + prefix of HF's
+    ``generate(input_ids=...)``.  While the chosen index t + 1 lies inside a row's prefix its scores are replaced by force_reference's
+    row AFTER ``process``, so arg-max takes the forced token; nothing else changes (a prefix holds no EOS).  A caller that forces inside
+    ``step`` / ``process`` itself (the device kernel) passes None."""
     import torch
     ids = torch.full((batch, max_len), pad_id, dtype=torch.int64, device=device)
     ids[:, 0] = bos_id
     if process is not None:
         raw_step = step
         step = lambda t, ids_: process(raw_step(t, ids_), ids_, t + 1)      # noqa: E731
+    if prefix is not None:
+        from . import prefix as PF
+        pfx_rows, plen_rows, _ = _prefix_rows(prefix, batch, 1, device)
+        free_step = step
+        step = lambda t, ids_: PF.force_reference(free_step(t, ids_).float(), t + 1, pfx_rows, plen_rows)      # noqa: E731
     if update is not None:
         # the stop test costs a host round trip: taken every 4th step; the steps run past the end only write padding, and the
         # per-step counters say where the end was
@@ -100,7 +119,7 @@ def _check_nbest(num_return_sequences, num_beams):
 
 def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int,
                 device, early_stopping=True, length_penalty: float = 1.0, topk=None, update=None, process=None,
-                num_return_sequences: int = 1, return_logprobs: bool = False):
+                num_return_sequences: int = 1, return_logprobs: bool = False, prefix=None):
     """``topk(logits [B * nb, vocab] fp32, run_sc [B, nb]) -> (top_lp [B, 2 nb], top_ix [B, 2 nb])``: optional fused ranking
     (kzv_beam_topk on the GPU); None = the torch expression of the same thing below.
     ``update``: optional fused bookkeeping (kzv_beam_update); with it the loop below is replaced by beam_search_fused.
@@ -112,7 +131,16 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
     nbest_result's dict of the first n rows of the finished list instead of the winner's ids (HF ``generate(num_return_sequences=n)``).
     A token's log-probability is the fp32 difference ``top_lp[k] - run_sc[src[k]]``, the continuation's accumulated score minus its
     parent beam's, carried in run_lp / fin_lp [B, nb, max_len] through exactly the gathers of run_seq / fin_seq (HF
-    ``compute_transition_scores``); under ``process`` it is therefore the processed row's value."""
+    ``compute_transition_scores``); under ``process`` it is therefore the processed row's value.
+    ``prefix`` = (ids [B, P], lengths [B]) (optional; kzv/prefix.py): every image's forced prefix, so that its prompt is [BOS] + prefix
+    and ``prompt`` below becomes 1 + lengths PER IMAGE.  While cur lies inside an image's prefix the processed log-probabilities of its
+    rows are replaced by force_reference's rows (the torch ranking; with ``topk`` the caller forces inside ``step``), so all beams carry
+    the prefix at scores 0, -1e9, -1e9, .. -- HF's state after a prompt.  Scores sum the generated tokens only (a forced token adds 0);
+    a hypothesis is normalised by its generated length cur + 1 - prompt and the heuristic uses cur - prompt, both clamped to >= 1: inside
+    a prefix nothing can finish (it holds no EOS and ends before max_len - 1), so a forced step only moves the running beams and the
+    image stays unsatisfied, where 0 / 0 ** p would end the search.  The divisors are fp32 of n ** length_penalty computed in double
+    (stream.divisor_table): what HF's tensor / Python float divides by.  With the device ``update`` the lengths live in that hook
+    (make_device_hooks(prefix_len=...))."""
     import torch
     if process is not None and topk is not None:
         raise ValueError("beam_search: `process` belongs to the torch ranking; with `topk` process inside `step` and rank log-probabilities")
@@ -122,6 +150,12 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
     n_ret = _check_nbest(num_return_sequences, num_beams)
     B, nb, K = batch, num_beams, 2 * num_beams
     prompt = 1                                                    # decoder prompt = [BOS]
+    pfx_rows = plen_rows = plen_img = div_tab = None
+    if prefix is not None:                                        # per image: prompt = [BOS] + prefix
+        from . import prefix as PF
+        from .stream import divisor_table
+        pfx_rows, plen_rows, plen_img = _prefix_rows(prefix, B, nb, device)
+        div_tab = divisor_table(max_len, length_penalty, device)
     run_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=device)
     run_seq[:, :, 0] = bos_id
     fin_seq = run_seq.clone()
@@ -146,6 +180,8 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
             logp = torch.log_softmax(raw.float(), dim=-1)
             if process is not None:
                 logp = process(logp, run_seq.view(B * nb, max_len), cur)
+            if pfx_rows is not None:
+                logp = PF.force_reference(logp, cur, pfx_rows, plen_rows)
             acc = logp.view(B, nb, vocab) + run_sc.unsqueeze(-1)
         # top K of the nb * vocab continuations in two stages (the K best overall are among each beam's K best): one
         # single-block top-k per beam row instead of a multi-pass radix select over nb * vocab entries per batch element
@@ -172,7 +208,10 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
         rows = (base + src.gather(1, nxt_ix)).reshape(-1)
         # finished list: stopped continuations of rank < nb, normalised by the generated length
         just = hits & top_mask
-        fsc = top_lp / float((cur + 1 - prompt) ** length_penalty)
+        if plen_img is None:
+            fsc = top_lp / float((cur + 1 - prompt) ** length_penalty)
+        else:                                                     # the image's own generated length, >= 1 (a forced step finishes nothing)
+            fsc = top_lp / div_tab[(cur - plen_img).clamp(min=1)]
         full = fin_done.all(dim=1, keepdim=True) & (early_stopping is True)
         fsc = fsc + full.float() * NEG + (~unsat).float() * NEG + (~just).float() * NEG
         m_sc = torch.cat((fin_sc, fsc), dim=1)
@@ -185,7 +224,10 @@ def beam_search(step, reorder, batch: int, num_beams: int, max_len: int, vocab: 
         fin_len = torch.cat((fin_len, torch.full((B, K), cur + 1, dtype=torch.int64, device=device)), dim=1).gather(1, m_ix)
         cur += 1
         # stop test (one host synchronisation per step)
-        best_open = run_sc[:, :1] / float((cur - prompt) ** length_penalty)
+        if plen_img is None:
+            best_open = run_sc[:, :1] / float((cur - prompt) ** length_penalty)
+        else:
+            best_open = run_sc[:, :1] / div_tab[(cur - 1 - plen_img).clamp(min=1)]
         worst_fin = torch.where(fin_done, fin_sc.min(dim=1, keepdim=True)[0], torch.full_like(fin_sc, NEG))
         unsat = unsat & (best_open > worst_fin).any(dim=-1, keepdim=True)
         go_on = unsat.any() & ~(fin_done.all() & (early_stopping is True)) & ~hits.all()
@@ -243,10 +285,12 @@ def beam_search_fused(step, reorder, batch, num_beams, max_len, vocab, pad_id, b
     return (out, st) if return_state else out
 
 
-def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, length_penalty, device, logprobs: bool = False):
+def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, length_penalty, device, logprobs: bool = False, prefix_len=None):
     """(topk, update) for beam_search on the GPU: kzv_beam_topk and kzv_beam_update through the C ABI, on the current stream,
     writing into buffers allocated here once.  ``logprobs``: the step hands over processed log-probabilities (the normalising
-    kzv_logits_process has run on them), so ``topk`` is kzv_beam_rank_logprobs, which does not normalise again."""
+    kzv_logits_process has run on them), so ``topk`` is kzv_beam_rank_logprobs, which does not normalise again.
+    ``prefix_len`` (int32 [batch] on the device, or None): the images carry forced prefixes (the step forces them: kzv_force_prefix), so
+    ``update`` is kzv_beam_update_prefix -- every image's own generated length, beam_search's rule."""
     import ctypes as C
     import torch
     from . import _lib as L
@@ -257,6 +301,11 @@ def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, 
     rows_buf = torch.empty(B * nb, dtype=torch.int64, device=device)
     flags_buf = torch.zeros(5, dtype=torch.int32, device=device)
     keep = {}
+    if prefix_len is not None:
+        from .stream import divisor_table
+        if prefix_len.dtype != torch.int32 or prefix_len.numel() != B or not prefix_len.is_contiguous():
+            raise ValueError("prefix_len: a contiguous int32 tensor [batch]")
+        div_tab = divisor_table(max_len, length_penalty, device).contiguous()
 
     def topk(raw, run_sc):                # log_softmax + beam score + top 2 * nb per image in one launch
         sc = run_sc.contiguous()
@@ -275,6 +324,11 @@ def make_device_hooks(batch, num_beams, max_len, vocab, eos_id, early_stopping, 
                               fin_seq_in=st["fin_seq"][a].data_ptr(), fin_seq_out=st["fin_seq"][a ^ 1].data_ptr(),
                               run_scores=st["run_sc"].data_ptr(), fin_scores=st["fin_sc"].data_ptr(), fin_done=st["fin_done"].data_ptr(),
                               fin_len=st["fin_len"].data_ptr(), unsatisfied=st["unsat"].data_ptr(), **lp_rows)
+        if prefix_len is not None:
+            L.check(lib.kzv_beam_update_prefix(C.byref(bs), lp.data_ptr(), ix.data_ptr(), cur, 1 if early_stopping is True else 0, float(length_penalty),
+                                               div_tab.data_ptr(), prefix_len.data_ptr(), rows_buf.data_ptr(), flags_buf.data_ptr(),
+                                               L.stream_handle()), "beam_update_prefix")
+            return rows_buf, flags_buf
         L.check(lib.kzv_beam_update(C.byref(bs), lp.data_ptr(), ix.data_ptr(), cur, 1 if early_stopping is True else 0, float(length_penalty),
                                     rows_buf.data_ptr(), flags_buf.data_ptr(), L.stream_handle()), "beam_update")
         return rows_buf, flags_buf

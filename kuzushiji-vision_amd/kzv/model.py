@@ -85,6 +85,8 @@ class TrOCRModel:
         self.controls_impl = "device"
         # the same switch for the language-model fusion of lockstep ``generate``: "device" (kzv_lm_fuse) or "reference" (kzv/lm.py::fuse_reference)
         self.lm_impl = "device"
+        # and for the forced prefixes of lockstep ``generate``: "device" (kzv_force_prefix) or "reference" (kzv/prefix.py::force_reference)
+        self.prefix_impl = "device"
         # generation controls of the validation / test decodes (``forward`` without labels): generate's keywords; empty = the reference's
         self.decode_controls = {}
         # Width buckets (BASELINE.json configs[4]; an extension -- a reference model has one image size): encoder_config's
@@ -534,7 +536,7 @@ class TrOCRModel:
 
     def recognize(self, pixel_values, num_beams: int = 4, max_length: int = 128, layer=-1, top_k: int = 0,
                   no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None,
-                  allowed_tokens=None, lm=None, lm_weight: float = 0.0, n_best: int = 0) -> list[dict]:
+                  allowed_tokens=None, lm=None, lm_weight: float = 0.0, n_best: int = 0, prefix_ids=None, prefix_texts=None) -> list[dict]:
         """``generate`` (the reference's settings: beam 4, max_length 128, early stopping), then ``align`` with the generated
         ids as labels: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD), ``token_strings``,
         ``logprobs``, ``confidence`` = exp(mean log-probability over the tokens, EOS included), ``centroids`` ((y, x) in
@@ -545,10 +547,24 @@ class TrOCRModel:
         ``lm`` / ``lm_weight`` (``generate``'s language-model fusion) do the same: they steer the decode only.
         ``n_best`` n in 1..num_beams: every record also holds ``score`` (HF ``sequences_scores``) and ``hypotheses``, the n best readings
         of the line as ``recognize_many``'s records (the search's own log-probabilities, best first, entry 0 the winner's reading); the
-        align pass still supplies centroids, log-probabilities and confidence of the winner only."""
+        align pass still supplies centroids, log-probabilities and confidence of the winner only.
+        ``prefix_ids`` (``generate``'s forced prefixes) or ``prefix_texts`` (a list of strings, through the tokenizer; one-character
+        tokenizers only): the first characters of every line are given and the model reads the rest.  Every record then holds
+        ``forced`` (how many tokens were given); ``confidence`` is taken over the free tokens only, and the ``alternatives`` of forced
+        positions are empty.  ``logprobs`` stay the model's own opinion of every token, forced ones included (the align pass)."""
         import torch
         from . import align as A
+        from . import prefix as PF
         c = self.cfg
+        if prefix_texts is not None:
+            if prefix_ids is not None:
+                raise ValueError("recognize: prefix_ids or prefix_texts, not both")
+            prefix_ids = PF.texts_to_ids(self.tokenizer, prefix_texts)
+        forced = None
+        if prefix_ids is not None:
+            got = PF.normalise(prefix_ids, len(prefix_ids), vocab=c.vocab, pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
+                               max_length=min(max_length, c.max_pos - c.pad_id - 1))
+            forced = [0] * len(prefix_ids) if got is None else got[1].tolist()
         hyps = None
         if n_best:
             from . import nbest as NB
@@ -556,14 +572,14 @@ class TrOCRModel:
             gen_all, h_sc, h_lp = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
                                                 no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
                                                 suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight,
-                                                num_return_sequences=n, return_scores=True, return_logprobs=True)
+                                                num_return_sequences=n, return_scores=True, return_logprobs=True, prefix_ids=prefix_ids)
             hyps = NB.records(self, gen_all, h_sc, h_lp, n)
             gen = gen_all[0::n]
             gen = gen[:, :max(1, int((gen != c.pad_id).sum(dim=1).max()))]
         else:
             gen = self.generate(pixel_values, max_length=max_length, num_beams=num_beams, early_stopping=True,
                                 no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_length=min_length,
-                                suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight)
+                                suppress_tokens=suppress_tokens, allowed_tokens=allowed_tokens, lm=lm, lm_weight=lm_weight, prefix_ids=prefix_ids)
         if gen.shape[1] < 2:                                  # labels need a target column
             gen = torch.nn.functional.pad(gen, (0, 2 - gen.shape[1]), value=c.pad_id)
         out = self.align(pixel_values, gen, layer=layer, top_k=top_k)
@@ -573,7 +589,7 @@ class TrOCRModel:
         recs = A.build_records(ids, out["logprob"].cpu().numpy(), out["centroid"].cpu().numpy(), out["peak_patch"].cpu().numpy(),
                                pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
-                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts, forced=forced)
         if hyps is not None:
             for r, h in zip(recs, hyps):
                 r["score"], r["hypotheses"] = h["score"], h["hypotheses"]
@@ -602,7 +618,7 @@ class TrOCRModel:
     def generate(self, pixel_values, max_length: int = 128, num_beams: int = 1, early_stopping: bool = True,
                  length_penalty: float = 1.0, use_cache: bool = True, return_scores: bool = False,
                  no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
-                 lm=None, lm_weight: float = 0.0, num_return_sequences: int = 1, return_logprobs: bool = False):
+                 lm=None, lm_weight: float = 0.0, num_return_sequences: int = 1, return_logprobs: bool = False, prefix_ids=None):
         """Decode from BOS.  The encoder (and the cross-attention K/V of every decoder layer) runs ONCE.
         ``num_return_sequences`` n in 1..num_beams / ``return_logprobs`` (the device hooks, as ``return_scores``; kzv/nbest.py): with
         n > 1 the ids are [B * n, W], HF's layout (image-major, best first) -- rows 0 .. n - 1 of every image's finished list, read off
@@ -632,9 +648,20 @@ class TrOCRModel:
         ``lm`` (a kzv.lm.NGramLM or its device form) with ``lm_weight`` != 0: shallow fusion of a character n-gram language model, every
         step's scores + lm_weight * log p_lm(token | the last order - 1 tokens), on the device (kzv_lm_fuse) AFTER the controls: greedy
         decoding takes arg-max of the fused logits; beam search adds it to the (processed) log-probabilities before the beam score and
-        does not normalise again (kzv/lm.py states the rule).  ``lm=None`` or ``lm_weight=0``: off, nothing is built or launched."""
+        does not normalise again (kzv/lm.py states the rule).  ``lm=None`` or ``lm_weight=0``: off, nothing is built or launched.
+
+        ``prefix_ids`` (a list of B id sequences, or a [B, P] tensor padded with pad_id; kzv/prefix.py): continue every line from given
+        tokens -- HF's ``generate(input_ids=[BOS] + prefix)``, with lengths that may differ inside the batch.  The prefix holds no BOS /
+        EOS / padding and 1 + len(prefix) <= max_length - 1, or the call refuses before any launch.  Every output row holds [BOS] +
+        prefix + the generated tokens.  One decoder step per forced token (no prefill pass): while the chosen index lies inside an
+        image's prefix its scores become -inf with 0 at the forced token (kzv_force_prefix), AFTER the controls and the language model,
+        which do not act on the prompt but read it as history; ``max_length`` and ``min_length`` count it.  Beam scores sum the
+        generated tokens only, and the length normalisation and the early-stop heuristic use the generated length.  A beam search
+        with prefixes takes the normalise -> (fuse) -> force -> rank-log-probabilities route.  None or all empty: off, nothing is
+        launched."""
         import torch
         from . import beam as BM
+        from . import prefix as PF
         from . import controls as CT
         from . import lm as LM
         c = self.cfg
@@ -648,6 +675,7 @@ class TrOCRModel:
         px = self._check_inputs(pixel_values)
         B = px.shape[0]
         Lh = min(max_length, c.max_pos - c.pad_id - 1)
+        pfx = PF.resolve(prefix_ids, B, c, Lh, self.device)            # the tables on the device, or None: off (refusals before any launch)
         lib = L.load()
         was = self.training
         self.training = False
@@ -741,28 +769,58 @@ class TrOCRModel:
             L.check(lib.kzv_lm_fuse(C.byref(a), L.stream_handle()), "lm_fuse")
             return scores
 
-        def both_hook(scores, ids, n):           # the one order everywhere: controls first, then the language model
-            return lm_hook(controls_hook(scores, ids, n), ids, n)
+        def prefix_hook(scores, ids, n, normalised=0):
+            """The forced prefixes on ``scores`` [BB, V] in place, nb rows per image, the token chosen being column n (kzv_force_prefix;
+            ``prefix_impl`` = "reference" substitutes kzv/prefix.py::force_reference on the same scores)."""
+            if self.prefix_impl == "reference":
+                scores.copy_(PF.force_reference(scores, n, *pfx.rows(nb)))
+                return scores
+            if scores.stride(1) != 1:
+                raise ValueError("prefix: scores must be dense along their rows")
+            a = L.kzv_force_prefix_args(logits=scores.data_ptr(), ld=scores.stride(0), rows=scores.shape[0], vocab=c.vocab, t=n - 1, group=nb,
+                                        slot_image=None, slot_t=None, by_image=0, n_images=B, prefix=pfx.prefix.data_ptr(), ld_prefix=pfx.width,
+                                        prefix_len=pfx.prefix_len.data_ptr(), normalised=1 if normalised else 0, reserved=0,
+                                        forced_logprob=None, ld_forced_logprob=0)
+            L.check(lib.kzv_force_prefix(C.byref(a), L.stream_handle()), "force_prefix")
+            return scores
+
+        def chain_hook(scores, ids, n):          # the one order everywhere: controls first, then the language model, then the prefix
+            if ctl is not None:
+                scores = controls_hook(scores, ids, n)
+            if lmr:
+                scores = lm_hook(scores, ids, n)
+            return prefix_hook(scores, ids, n) if pfx is not None else scores
 
         neutral = CT.GenerationControls()
         topk = update = None
-        process = (both_hook if lmr else controls_hook) if ctl is not None else (lm_hook if lmr else None)
+        process = chain_hook if (ctl is not None or lmr or pfx is not None) else None
         raw_step = step
 
         def step_logprobs(t, ids):               # beams on the device ranking: normalise + process here, rank log-probabilities after
             x = controls_hook(raw_step(t, ids), ids, t + 1, normalise=1)
-            return lm_hook(x, ids, t + 1) if lmr else x
+            x = lm_hook(x, ids, t + 1) if lmr else x
+            return prefix_hook(x, ids, t + 1, normalised=1) if pfx is not None else x
+
+        def torch_beam_hook(scores, ids, n):     # the torch ranking forces the rows itself (beam_search's ``prefix``): controls and the language model only
+            if ctl is not None:
+                scores = controls_hook(scores, ids, n)
+            return lm_hook(scores, ids, n) if lmr else scores
+
+        bprefix = None if pfx is None else (pfx.prefix, pfx.prefix_len)
 
         try:
             with self._decode_stream(use_cache) as (graph, keep):
                 # the hooks allocate and zero their flag / top-k buffers: on the stream whose kernels read them
                 if nb > 1 and nb <= 8 and self.device.type == "cuda" and os.environ.get("KZV_BEAM_TOPK", "1") != "0":
                     topk, update = BM.make_device_hooks(B, nb, Lh, c.vocab, c.eos_id, early_stopping, length_penalty, self.device,
-                                                        logprobs=ctl is not None or lmr is not None)
+                                                        logprobs=ctl is not None or lmr is not None or pfx is not None,
+                                                        prefix_len=None if pfx is None else pfx.prefix_len)
                     if os.environ.get("KZV_BEAM_UPDATE", "1") == "0":
                         update = None
-                    if ctl is not None or lmr is not None:
+                    if ctl is not None or lmr is not None or pfx is not None:
                         step, process = step_logprobs, None
+                if nb > 1 and process is not None:
+                    process = torch_beam_hook if (ctl is not None or lmr) else None
                 if use_cache:
                     L.check(lib.kzv_set_active_length(self._h, 1), "set_active_length")
                     L.check(lib.kzv_decode_begin(self._h, L.stream_handle()), "decode_begin")
@@ -788,10 +846,12 @@ class TrOCRModel:
                 else:
                     out = BM.beam_search(step, reorder, B, nb, Lh, c.vocab, c.pad_id, c.bos_id, c.eos_id, self.device,
                                          early_stopping=early_stopping, length_penalty=length_penalty, topk=topk, update=update,
-                                         process=process)
+                                         process=process, prefix=bprefix)
                 keep += (out, step_logits, posids, tok_buf, state["valid"], px) + (() if ctl_mask is None else (ctl_mask,))
                 if lmr:
                     keep += lmr[1].keep()
+                if pfx is not None:
+                    keep += pfx.keep()
                 if return_scores:
                     keep.append(scores)
             if nbest:
@@ -847,7 +907,8 @@ class TrOCRModel:
                         pool_bytes: int = 4 << 30, num_beams: int = 1, early_stopping: bool = True, length_penalty: float = 1.0,
                         return_scores: bool = False, top_k: int = 0,
                         no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, min_length: int = 0, suppress_tokens=None, allowed_tokens=None,
-                        lm=None, lm_weight: float = 0.0, num_return_sequences: int | None = None):
+                        lm=None, lm_weight: float = 0.0, num_return_sequences: int | None = None, prefix_ids=None,
+                        return_prefix_logprobs: bool = False):
         """Greedy decoding of N images, N much larger than a batch, over a fixed set of ``slots`` decoder rows that the DEVICE keeps
         full: a slot whose line has ended takes the next waiting image and restarts at BOS in the very next step (kzv/stream.py states
         the bookkeeping; include/kzv.h: kzv_stream_*), where ``generate`` would run every batch until its longest line has ended.
@@ -897,11 +958,21 @@ class TrOCRModel:
         ``num_return_sequences=1`` serves a winner -- also admits ``return_logprobs`` for a beam search: fp32 [N * n, width], column
         t the log-probability of the token in column t, 0 in column 0 and from the row's length on, the search's own values
         (kzv_stream_set_nbest; one more staged row copy per step).  The results come in the order ids, scores, log-probabilities.  Both
-        fallbacks call ``generate`` with the same keywords and return the same rows."""
+        fallbacks call ``generate`` with the same keywords and return the same rows.
+
+        Forced prefixes (``prefix_ids``: ``generate``'s keyword and rule, one entry per image of the whole call; off by default): every
+        step of a wave runs kzv_force_prefix as the LAST node of its captured chain before selection (kzv_stream_set_prefix), on each
+        slot's own image and step, so a slot that is reseated in the middle of another image's prefix reads its new image's from step 0;
+        a beam wave takes the rank-log-probabilities route and its update the images' own generated lengths.  ``limits`` count the
+        prefix (1 + len(prefix) <= limit - 1).  Every row still equals the matching row of ``generate(prefix_ids=...)``; both fallbacks
+        pass the prefixes on; ``return_logprobs`` holds exactly 0 at forced columns.  ``return_prefix_logprobs``: one more result at the
+        end, fp32 [N, width]: at every forced column the MODEL's log-probability of the forced token -- taken off the row before it is
+        overwritten, after controls and fusion -- and 0 elsewhere (slot-refill waves only; refused on the fallbacks' geometries)."""
         import torch
         from . import controls as CT
         from . import lm as LM
         from . import nbest as NB
+        from . import prefix as PF
         c = self.cfg
         n_ret = NB.check_request(num_beams, 1 if num_return_sequences is None else num_return_sequences, return_logprobs, "generate_stream")
         nbest = n_ret if num_return_sequences is not None and int(num_beams) > 1 and (n_ret > 1 or return_logprobs) else 0
@@ -937,6 +1008,17 @@ class TrOCRModel:
         if slots < 1:
             raise ValueError("slots must be positive")
         lim_all = None if limits is None else torch.as_tensor(limits, dtype=torch.int32).reshape(-1).clamp(min=2)
+        pfx_all = None                            # the whole call's prefixes, checked before any wave runs; None: off
+        if prefix_ids is not None:
+            n_pfx = prefix_ids.n if isinstance(prefix_ids, PF.Prefixes) else len(prefix_ids)
+            if lim_all is not None and lim_all.numel() != n_pfx:
+                raise ValueError("limits and prefix_ids must both hold one entry per image")
+            pfx_all = PF.resolve(prefix_ids, n_pfx, c, Lh, self.device, limits=lim_all)
+        if return_prefix_logprobs and pfx_all is None:
+            raise ValueError("return_prefix_logprobs needs prefix_ids with at least one forced token")
+        if return_prefix_logprobs and nbest:
+            raise ValueError("return_prefix_logprobs is not combined with num_return_sequences")
+        pl_out = []
         ids_out, lp_out, alt_out, nb_out, done = [], [], [], [], 0
         self.last_stream_steps = 0               # decoder steps the last call took (every wave; the static path leaves 0)
         src = iter((pixel_values,) if torch.is_tensor(pixel_values) else pixel_values)
@@ -949,16 +1031,33 @@ class TrOCRModel:
             lim = None if lim_all is None else lim_all[done:done + n]
             if lim is not None and lim.numel() != n:
                 raise ValueError("limits must hold one entry per image")
+            pfx = None
+            if pfx_all is not None:               # the wave's own tables (None when all of its prefixes are empty: the wave runs as today)
+                if done + n > pfx_all.n:
+                    raise ValueError("prefix_ids must hold one entry per image")
+                pfx = pfx_all.slice(done, done + n, want_logprobs=bool(return_prefix_logprobs))
+            if return_prefix_logprobs:
+                self._wave_forced_lp = None
             if nbest:
-                nb_out.append(self._stream_wave(px, Lh, slots, lim, bool(return_logprobs), beams, 0, ctl, lmr, nbest=nbest))
+                nb_out.append(self._stream_wave(px, Lh, slots, lim, bool(return_logprobs), beams, 0, ctl, lmr, nbest, pfx))
                 done += n
                 continue
             if top_k:
-                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl, lmr)
+                ids, lp, alts = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, top_k, ctl, lmr, 0, pfx)
                 alt_out.append(alts)
             else:
-                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl, lmr)
+                ids, lp = self._stream_wave(px, Lh, slots, lim, return_logprobs, beams, 0, ctl, lmr, 0, pfx)
+            if return_prefix_logprobs:
+                fl = torch.zeros(n, Lh, dtype=torch.float32, device=self.device)
+                if pfx is not None:
+                    if self._wave_forced_lp is None:
+                        raise ValueError("return_prefix_logprobs: this wave ran on lockstep generate (a geometry without slot-refill decoding, or "
+                                         "a beam wave decoded again), which does not record them")
+                    fl[:, :pfx.width + 1] = self._wave_forced_lp
+                pl_out.append(fl)
             ids_out.append(ids); lp_out.append(lp); done += n
+        if pfx_all is not None and done != pfx_all.n:
+            raise ValueError(f"prefix_ids holds {pfx_all.n} prefixes for {done} images")
         if nbest:                                 # waves concatenate image-major
             lengths = torch.cat([w["lengths"] for w in nb_out])
             NB.check_done(lengths, "generate_stream")
@@ -969,14 +1068,15 @@ class TrOCRModel:
             return got if len(got) > 1 else got[0]
         ids = torch.cat(ids_out)
         width = max(2, int((ids != c.pad_id).sum(dim=1).max()))
+        tail = (torch.cat(pl_out)[:, :width],) if return_prefix_logprobs else ()
         if top_k:
             return (ids[:, :width], torch.cat(lp_out)[:, :width], torch.cat([a[0] for a in alt_out])[:, :width].long(),
-                    torch.cat([a[1] for a in alt_out])[:, :width])
+                    torch.cat([a[1] for a in alt_out])[:, :width]) + tail
         if return_logprobs:
-            return ids[:, :width], torch.cat(lp_out)[:, :width]
+            return (ids[:, :width], torch.cat(lp_out)[:, :width]) + tail
         if return_scores:
-            return ids[:, :width], torch.cat(lp_out)
-        return ids[:, :width]
+            return (ids[:, :width], torch.cat(lp_out)) + tail
+        return (ids[:, :width],) + tail if tail else ids[:, :width]
 
     @staticmethod
     def _controls_kw(ctl, lmr=None) -> dict:
@@ -987,9 +1087,10 @@ class TrOCRModel:
         return dict(kw, no_repeat_ngram_size=ctl.no_repeat_ngram_size, repetition_penalty=ctl.repetition_penalty, min_length=ctl.min_length,
                     suppress_tokens=ctl.suppress_tokens, allowed_tokens=ctl.allowed_tokens)
 
-    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams, ctl=None, lmr=None):
+    def _static_beam_wave(self, px, Lh: int, slots: int, lim, beams, ctl=None, lmr=None, pfx=None):
         """``generate(num_beams=nb)`` over batches of ``slots``: ids [n, Lh] and the winners' scores [n] (from a teacher-forced pass).  With
-        limits, the images of every distinct limit are decoded with it as their max_length."""
+        limits, the images of every distinct limit are decoded with it as their max_length.  ``pfx``: the wave's forced prefixes
+        (kzv/prefix.py: Prefixes) or None; they go to ``generate`` with their images, and the score sums the generated tokens only."""
         import torch
         c = self.cfg
         nb, early, lpen = beams
@@ -1002,20 +1103,26 @@ class TrOCRModel:
             for a in range(0, idx.numel(), slots):
                 sel = idx[a:a + slots]
                 sub = px[sel.to(px.device)]
-                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen, **self._controls_kw(ctl, lmr))
+                sub_pfx = None if pfx is None else pfx.select(sel)
+                g = self.generate(sub, max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen, prefix_ids=sub_pfx,
+                                  **self._controls_kw(ctl, lmr))
                 rows = torch.full((sel.numel(), Lh), c.pad_id, dtype=torch.int64, device=dev)
                 rows[:, :g.shape[1]] = g
                 sc = self.align(sub, rows)
                 live = sc["live"].float()
+                if sub_pfx is not None:               # row t of align belongs to column t + 1: the forced columns 1 .. len do not count
+                    live = live * (torch.arange(live.shape[1], device=dev).view(1, -1) >= sub_pfx.prefix_len.view(-1, 1)).float()
                 ids[sel.to(dev)] = rows
                 score[sel.to(dev)] = (sc["logprob"] * live).sum(1) / live.sum(1).clamp(min=1).pow(lpen)
         return ids, score
 
-    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None, lmr=None, nbest: int = 0):
+    def _stream_wave(self, px, Lh: int, slots: int, lim, want_lp: bool, beams=None, top_k: int = 0, ctl=None, lmr=None, nbest: int = 0, pfx=None):
         """One wave of generate_stream: ids [n, Lh] and log-probabilities [n, Lh] or None; with ``beams`` = (num_beams, early_stopping,
         length_penalty): ids [n, Lh] and the winners' scores [n]; with ``top_k`` (greedy) a third result, (alt_ids int32, alt_logprob)
         [n, Lh, top_k].  ``ctl``: the wave's GenerationControls (None: off); ``lmr``: its language model (kzv/lm.py: resolve; None: off).
-        ``nbest`` n >= 1 (beams): the result is kzv/nbest.py's dict of the n best rows per image instead (``want_lp``: with log-probabilities)."""
+        ``nbest`` n >= 1 (beams): the result is kzv/nbest.py's dict of the n best rows per image instead (``want_lp``: with log-probabilities).
+        ``pfx``: the wave's forced prefixes (kzv/prefix.py: Prefixes; None: off), indexed by the wave's images; where it holds a
+        forced_logprob table, a slot-refill wave leaves it in ``self._wave_forced_lp``."""
         import torch
         from . import nbest as NB
         from . import stream as ST
@@ -1025,8 +1132,9 @@ class TrOCRModel:
         dev = self.device
         self._check_inputs(px[:1])                                # geometry checks + the active crop width
         nb = beams[0] if beams else 1
-        static_beams = self._static_beam_wave if not nbest else (
-            lambda px_, Lh_, slots_, lim_, beams_, ctl_, lmr_: NB.static_wave(self, px_, Lh_, slots_, lim_, beams_, nbest, want_lp, self._controls_kw(ctl_, lmr_)))
+        static_beams = (lambda px_, Lh_, slots_, lim_, beams_, ctl_, lmr_: self._static_beam_wave(px_, Lh_, slots_, lim_, beams_, ctl_, lmr_, pfx)) if not nbest else (
+            lambda px_, Lh_, slots_, lim_, beams_, ctl_, lmr_: NB.static_wave(self, px_, Lh_, slots_, lim_, beams_, nbest, want_lp, self._controls_kw(ctl_, lmr_),
+                                                                              prefixes=pfx))
         if beams and nb not in (2, 4):
             return static_beams(px, Lh, slots, lim, beams, ctl, lmr)
         rows = slots * nb                                         # decoder rows: a slot holds one sequence, or an image's beam group
@@ -1039,7 +1147,8 @@ class TrOCRModel:
             alt_ids = torch.full((n, Lh, top_k), -1, dtype=torch.int32, device=dev) if top_k else None
             alt_lp = torch.zeros(n, Lh, top_k, dtype=torch.float32, device=dev) if top_k else None
             for a in range(0, n, slots):
-                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1, **self._controls_kw(ctl, lmr))
+                g = self.generate(px[a:a + slots], max_length=Lh, num_beams=1, prefix_ids=None if pfx is None else pfx.slice(a, a + slots),
+                                  **self._controls_kw(ctl, lmr))
                 ids[a:a + g.shape[0], :g.shape[1]] = g
             if lim is not None:
                 ids = torch.where(torch.arange(Lh, device=dev).view(1, Lh) >= lim.to(dev).view(n, 1), torch.full_like(ids, c.pad_id), ids)
@@ -1084,6 +1193,10 @@ class TrOCRModel:
                 if lmr is not None:                               # and one more after it; the tables stay ours for the wave
                     L.check(lib.kzv_stream_set_lm(self._h, C.byref(lmr[1].struct), lmr[2], st), "stream_set_lm")
                     keep += lmr[1].keep()
+                if pfx is not None:                               # the chain's last node before selection; the tables stay ours for the wave
+                    L.check(lib.kzv_stream_set_prefix(self._h, pfx.prefix.data_ptr(), pfx.width, pfx.prefix_len.data_ptr(), L.ptr(pfx.forced_logprob),
+                                                      pfx.width + 1, st), "stream_set_prefix")
+                    keep += pfx.keep()
                 a = 0
                 while a < n:                                      # the encoder runs on divisors of the bound batch; a short last batch
                     k = min(rows, n - a)                          # is filled by repeating its last image
@@ -1118,13 +1231,16 @@ class TrOCRModel:
         if beams and pads.value:                                  # a running beam held padding: the slots' positions and key flags were wrong for it
             self.last_stream_pad_fallbacks += pads.value
             return static_beams(px, Lh, slots, lim, beams, ctl, lmr)
+        if pfx is not None and pfx.forced_logprob is not None:
+            self._wave_forced_lp = pfx.forced_logprob
         if nbo is not None:
             return nbo.result()
         if top_k:
             return ids, lp, (alt_ids, alt_lp)
         return ids, (score if beams else lp)
 
-    def recognize_many(self, pixel_values, top_k: int = 0, n_best: int = 0, **kw) -> list[dict]:
+    def recognize_many(self, pixel_values, top_k: int = 0, n_best: int = 0, prefix_ids=None, prefix_texts=None, prefix_logprobs: bool = False,
+                       **kw) -> list[dict]:
         """``generate_stream`` with its own log-probabilities: per image a dict of ``text``, ``tokens`` (ids without BOS / EOS / PAD),
         ``token_strings``, ``logprobs`` and ``confidence`` = exp(mean log-probability over the tokens, EOS included) -- ``recognize``'s
         definitions, for greedy decoding, with no teacher-forced second pass.  It returns NO centroids or peak patches: those come
@@ -1135,32 +1251,57 @@ class TrOCRModel:
         So do ``lm`` / ``lm_weight`` (language-model fusion): the values are then those of the fused rows.
         ``num_beams`` > 1 (through ``kw``) with ``n_best`` n in 1..num_beams (default 1): the records of a beam search, from the winner's
         own search log-probabilities with no second pass, plus ``score`` (HF ``sequences_scores``) and ``hypotheses``: the n best
-        readings of the line as such records, best first, the winner included as entry 0 (kzv/nbest.py)."""
+        readings of the line as such records, best first, the winner included as entry 0 (kzv/nbest.py).
+        ``prefix_ids`` / ``prefix_texts`` (``recognize``'s; one entry per image of the whole call): forced prefixes.  The greedy records
+        then hold ``forced``; their ``logprobs`` are exactly 0 at forced tokens (the forced row's), ``confidence`` is taken over the
+        free tokens only and the ``alternatives`` of forced positions are empty; ``prefix_logprobs=True`` adds ``prefix_logprobs``, the
+        model's own log-probability of every forced token (generate_stream(return_prefix_logprobs=True))."""
         import numpy as np
         from . import align as A
         from . import nbest as NB
+        from . import prefix as PF
         c = self.cfg
         top_k = int(top_k)
         nb = int(kw.get("num_beams", 1))
+        if prefix_texts is not None:
+            if prefix_ids is not None:
+                raise ValueError("recognize_many: prefix_ids or prefix_texts, not both")
+            prefix_ids = PF.texts_to_ids(self.tokenizer, prefix_texts)
+        forced = None
+        if prefix_ids is not None:
+            got = PF.normalise(prefix_ids, len(prefix_ids), vocab=c.vocab, pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
+                               max_length=min(int(kw.get("max_length", 128)), c.max_pos - c.pad_id - 1), limits=kw.get("limits"))
+            forced = [0] * len(prefix_ids) if got is None else got[1].tolist()
+            kw = dict(kw, prefix_ids=prefix_ids)
+        want_pl = bool(prefix_logprobs) and forced is not None and any(forced)
+        if prefix_logprobs and (nb > 1 or n_best):
+            raise ValueError("recognize_many: prefix_logprobs is served for greedy decoding")
         if nb > 1 or n_best:
             n = NB.check_request(nb, n_best or 1, True, "recognize_many")
             if nb == 1:
                 raise ValueError("recognize_many: n_best needs a beam search (num_beams > 1)")
             gen, score, lp = self.generate_stream(pixel_values, return_logprobs=True, return_scores=True, top_k=top_k, num_return_sequences=n, **kw)
-            return NB.records(self, gen, score, lp, n)
-        alts = None
+            recs = NB.records(self, gen, score, lp, n)
+            if forced is not None:                # (a beam record's confidence still averages the forced tokens' exact zeros in)
+                for r, f in zip(recs, forced):
+                    r["forced"] = int(f)
+            return recs
+        alts = pl = None
         if top_k:
-            gen, lp, a_ids, a_lp = self.generate_stream(pixel_values, return_logprobs=True, top_k=top_k, **kw)
+            gen, lp, a_ids, a_lp, *rest = self.generate_stream(pixel_values, return_logprobs=True, top_k=top_k, return_prefix_logprobs=want_pl, **kw)
             alts = (a_ids[:, 1:].cpu().numpy(), a_lp[:, 1:].cpu().numpy())
         else:
-            gen, lp = self.generate_stream(pixel_values, return_logprobs=True, **kw)
+            gen, lp, *rest = self.generate_stream(pixel_values, return_logprobs=True, return_prefix_logprobs=want_pl, **kw)
+        if want_pl:
+            pl = rest[0].cpu().numpy()
         ids = gen.cpu().numpy()
         B, W = ids.shape
         tok = self.tokenizer
         recs = A.build_records(ids, lp[:, 1:].cpu().numpy(), np.zeros((B, W - 1, 2)), np.zeros((B, W - 1), dtype=np.int64),
                                pad_id=c.pad_id, bos_id=c.bos_id, eos_id=c.eos_id,
                                texts=None if tok is None else tok.batch_decode(gen, skip_special_tokens=True),
-                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts)
+                               to_strings=None if tok is None else tok.convert_ids_to_tokens, alternatives=alts, forced=forced,
+                               prefix_logprobs=pl)
         for r in recs:
             del r["centroids"], r["peak_patches"]
         return recs
@@ -1200,7 +1341,9 @@ class TrOCRModel:
         ``characters`` (metrics.character_table: the ``top`` characters with the most errors) and ``ids`` (the generated rows).  The
         same call serves geometries where generate_stream runs ``generate``: it needs only the ids.  The generation controls of
         generate_stream (``no_repeat_ngram_size=3`` is what the stock TrOCR generation configs ship with) pass through its keywords, and
-        so do ``lm`` / ``lm_weight`` (kzv.lm.sweep_weight picks the weight with this call).
+        so do ``lm`` / ``lm_weight`` (kzv.lm.sweep_weight picks the weight with this call) and ``prefix_ids`` (forced prefixes: with the
+        first k label characters of every line forced, the CER of the rest separates early-error propagation from plain misreading;
+        the forced characters are part of the scored rows).
         ``n_best`` n in 1..num_beams (beams only): the decode returns the n best readings of every line and ONE more kzv_edit_distance
         (distance only) scores them all; every key above stays the winner's, and the call adds ``cer_oracle`` (the mean over lines of the
         best reading's CER: what a rescoring of the candidates could reach at most), ``cer_oracle_corpus``, ``oracle_rank`` (how often

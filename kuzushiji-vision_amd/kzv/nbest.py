@@ -67,10 +67,11 @@ class WaveOutputs:
         return out
 
 
-def static_wave(model, px, Lh: int, slots: int, lim, beams, n: int, want_lp: bool, generate_kw: dict) -> dict:
+def static_wave(model, px, Lh: int, slots: int, lim, beams, n: int, want_lp: bool, generate_kw: dict, prefixes=None) -> dict:
     """The rows of a wave from lockstep ``generate(num_return_sequences=n, return_scores=True, return_logprobs=want_lp)`` over batches of
     ``slots`` (generate_stream's two fallbacks): the same dict as ``WaveOutputs.result``.  With limits, the images of every distinct limit
-    are decoded with it as their max_length."""
+    are decoded with it as their max_length.  ``prefixes``: the wave's forced prefixes (kzv/prefix.py: Prefixes) or None; every batch gets
+    those of its images."""
     import torch
     c = model.cfg
     nb, early, lpen = beams
@@ -83,7 +84,8 @@ def static_wave(model, px, Lh: int, slots: int, lim, beams, n: int, want_lp: boo
         for a in range(0, idx.numel(), slots):
             sel = idx[a:a + slots]
             got = model.generate(px[sel.to(px.device)], max_length=width, num_beams=nb, early_stopping=early, length_penalty=lpen,
-                                 num_return_sequences=n, return_scores=True, return_logprobs=want_lp, **generate_kw)
+                                 num_return_sequences=n, return_scores=True, return_logprobs=want_lp,
+                                 prefix_ids=None if prefixes is None else prefixes.select(sel), **generate_kw)
             rows = (sel.view(-1, 1) * n + hyp.view(1, n)).reshape(-1).to(dev)
             g = got[0]
             block = torch.full((rows.numel(), Lh), c.pad_id, dtype=torch.int64, device=dev)

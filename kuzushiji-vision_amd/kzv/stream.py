@@ -65,7 +65,13 @@ def new_state(n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int,
     return st
 
 
-def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, limit=None, process=None):
+def _slot_prefix(prefix, i64, device):
+    """``prefix`` = (ids [N, P], lengths [N]) per image -> the tables of the images the slots hold: (ids [S, P], lengths int64 [S])."""
+    pfx, plen = prefix
+    return pfx.to(device).long()[i64], plen.to(device).long().reshape(-1)[i64]
+
+
+def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, limit=None, process=None, prefix=None):
     """One step's selection and seating.  ``logits`` [slots, V] are the next-token logits of every slot (rows of idle slots are
     ignored).  Per live slot holding image i at step t: token = the FIRST arg-max column; out_ids[i][t + 1] = token;
     out_logprob[i][t + 1] = max - logsumexp; the line has ended when token == eos_id, t + 2 >= limit[i] or t + 2 >= max_len.
@@ -75,7 +81,10 @@ def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id:
     alt_ids / alt_logprob[i][t + 1] = topk_rows of the slot's row.
     ``process(logits, hist [slots, L], lens [slots], live [slots]) -> logits`` (optional; kzv/controls.py: GenerationControls.rows_hook):
     generation controls on the raw logits, slot s with the history out_ids[slot_image[s]][:slot_t[s] + 1]; token, log-probability and
-    alternatives are then those of the processed row.  None: what this computed before.  Returns ``st``."""
+    alternatives are then those of the processed row.  None: what this computed before.
+    ``prefix`` = (ids [n_images, P], lengths [n_images]) (optional; kzv/prefix.py): forced prefixes per IMAGE.  A live slot whose chosen
+    index slot_t + 1 lies inside its image's prefix gets force_reference's row after ``process``; a reseated slot reads its new image's
+    prefix from step 0.  Returns ``st``."""
     import torch
     dev = logits.device
     img, t = st["slot_image"], st["slot_t"]
@@ -83,6 +92,10 @@ def select_seat(logits, st, *, n_images: int, max_len: int, pad_id: int, bos_id:
     x = logits.float()
     if process is not None:
         x = process(x, st["out_ids"][img.clamp(min=0).long()], t.long() + 1, live)
+    if prefix is not None:
+        from . import prefix as PF
+        pfx_s, plen_s = _slot_prefix(prefix, img.clamp(min=0).long(), dev)
+        x = PF.force_reference(x, t.long() + 1, pfx_s, torch.where(live, plen_s, torch.zeros_like(plen_s)))
     mx = x.max(dim=-1, keepdim=True)[0]
     V = x.shape[-1]
     cols = torch.arange(V, device=dev).expand_as(x)
@@ -122,12 +135,12 @@ def step_bound(n_images: int, slots: int, max_len: int) -> int:
 
 
 def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int, bos_id: int, eos_id: int, device, limits=None,
-                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False, top_k: int = 0, process=None):
+                  return_logprobs: bool = False, poll: int = 8, return_state: bool = False, top_k: int = 0, process=None, prefix=None):
     """Greedy decoding of ``n_images`` images over ``slots`` decoder slots.  ``step_fn(state) -> logits [slots, V]`` runs one decoder
     step for every slot: slot b feeds state["tokens"][b] at step state["slot_t"][b] for image state["slot_image"][b] (idle slots may
     return anything).  The counters are looked at every ``poll``-th step; RuntimeError once the steps exceed ``step_bound``.
     Returns out_ids [N, max_len] (and out_logprob with ``return_logprobs``; and the final state with ``return_state``, which holds
-    the alternatives asked for with ``top_k``).  ``process``: select_seat's optional hook."""
+    the alternatives asked for with ``top_k``).  ``process`` / ``prefix``: select_seat's optional hook and forced prefixes."""
     import torch
     st = new_state(n_images, slots, max_len, pad_id, bos_id, device, return_logprobs, top_k)
     lim = None if limits is None else torch.as_tensor(limits, dtype=torch.int32, device=device)
@@ -135,7 +148,7 @@ def greedy_stream(step_fn, n_images: int, slots: int, max_len: int, pad_id: int,
     steps = 0
     while True:
         st = select_seat(step_fn(st), st, n_images=n_images, max_len=max_len, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, limit=lim,
-                         process=process)
+                         process=process, prefix=prefix)
         steps += 1
         if steps % poll == 0 or steps >= bound:
             if int(st["counters"][1]) >= n_images:
@@ -225,13 +238,16 @@ def new_beam_state(n_images: int, slots: int, num_beams: int, max_len: int, pad_
 
 
 def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int,
-                     early_stopping=True, length_penalty: float = 1.0, limit=None, divisors=None):
+                     early_stopping=True, length_penalty: float = 1.0, limit=None, divisors=None, prefix_len=None):
     """One step's beam bookkeeping and seating.  ``top_lp`` / ``top_ix`` [slots, 2 nb]: the ranked continuations of every slot (flat
     index beam * vocab + token; rows of idle slots are ignored).  A live slot holding image i at cur = slot_t + 1 does the body of
     beam.beam_search's loop for B = 1 with max_len = min(limit[i], max_len); equal scores rank by the smaller index (a stable sort:
     what the kernel's scalar ranking does).  The search has ended when beam_search's ``go_on`` is false for that image: then
     out_ids[i] = fin_seq[0][:fin_len[0]] and out_score[i] = fin_sc[0], and the slot is seated as in select_seat, its beam state back
-    at the start.  Returns ``st``."""
+    at the start.
+    ``prefix_len`` [n_images] (optional): the images carry forced prefixes (the ranking was taken on forced rows), so the divisor of a
+    slot holding image i is that of its own generated length max(cur - prefix_len[i], 1) -- beam.beam_search's rule, clamp included.
+    Returns ``st``."""
     import torch
     dev = top_lp.device
     nb, K, L, V = num_beams, 2 * num_beams, max_len, vocab
@@ -242,7 +258,8 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
     cur = (t.long() + 1).clamp(max=L - 1)                                                  # [S]
     lim = torch.full_like(t, L) if limit is None else limit.to(dev, dtype=torch.int32)[i64].clamp(max=L)
     div = divisor_table(L, length_penalty, dev) if divisors is None else divisors
-    d = div[cur].view(S, 1)                                                                # (cur + 1 - prompt) ** length_penalty, as fp32
+    gen = cur if prefix_len is None else (cur - prefix_len.to(dev).long().reshape(-1)[i64]).clamp(min=1)
+    d = div[gen].view(S, 1)                                                                # (cur + 1 - prompt) ** length_penalty, as fp32
     run_seq, fin_seq, run_sc, fin_sc = st["run_seq"], st["fin_seq"], st["run_sc"], st["fin_sc"]
     fin_done, fin_len, unsat = st["fin_done"].bool(), st["fin_len"], st["unsat"].bool().view(S, 1)
     top_lp = top_lp.float()
@@ -339,7 +356,7 @@ def beam_select_seat(top_lp, top_ix, st, *, n_images: int, num_beams: int, max_l
 
 def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int, vocab: int, pad_id: int, bos_id: int, eos_id: int, device,
                 early_stopping=True, length_penalty: float = 1.0, limits=None, topk=None, poll: int = 8, return_state: bool = False,
-                process=None, num_return_sequences: int = 1, return_logprobs: bool = False):
+                process=None, num_return_sequences: int = 1, return_logprobs: bool = False, prefix=None):
     """Beam search of ``n_images`` images over ``slots`` slots of ``num_beams`` decoder rows.  ``step_fn(state) -> logits [slots * nb, V]``
     runs one decoder step for every row: row slot * nb + i feeds state["tokens"][row] at step state["slot_t"][slot] for image
     state["slot_image"][slot], its prefix state["run_seq"][slot][i][:slot_t + 1] (idle slots may return anything finite).
@@ -351,7 +368,10 @@ def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int
     this computed before.
     ``num_return_sequences`` n in 1..num_beams / ``return_logprobs``: with n > 1 or log-probabilities asked for, the result is
     beam.nbest_result's dict instead (ids [N * n, width], scores, lengths, logprobs: image-major, best first), read off the n-best
-    outputs that every ended search wrote; per image it equals beam.beam_search's with the same two keywords."""
+    outputs that every ended search wrote; per image it equals beam.beam_search's with the same two keywords.
+    ``prefix`` = (ids [n_images, P], lengths [n_images]) (optional): forced prefixes per image, beam.beam_search's keyword; the torch
+    ranking forces the rows after ``process`` (with ``topk`` the caller forces inside ``step_fn``), and the lengths go to
+    beam_select_seat."""
     import torch
     if process is not None and topk is not None:
         raise ValueError("beam_stream: `process` belongs to the torch ranking")
@@ -374,10 +394,17 @@ def beam_stream(step_fn, n_images: int, slots: int, num_beams: int, max_len: int
             if process is not None:
                 logp = process(logp, st["run_seq"].view(slots * nb, max_len), (st["slot_t"].long() + 1).repeat_interleave(nb),
                                (st["slot_image"] >= 0).repeat_interleave(nb))
+            if prefix is not None:
+                from . import prefix as PF
+                live = st["slot_image"] >= 0
+                pfx_s, plen_s = _slot_prefix(prefix, st["slot_image"].clamp(min=0).long(), logp.device)
+                logp = PF.force_reference(logp, (st["slot_t"].long() + 1).repeat_interleave(nb), pfx_s.repeat_interleave(nb, dim=0),
+                                          torch.where(live, plen_s, torch.zeros_like(plen_s)).repeat_interleave(nb))
             acc = logp.view(slots, nb, vocab) + st["run_sc"].unsqueeze(-1)
             top_lp, top_ix = acc.view(slots, nb * vocab).topk(K, dim=1)
         st = beam_select_seat(top_lp, top_ix, st, n_images=n_images, num_beams=nb, max_len=max_len, vocab=vocab, pad_id=pad_id, bos_id=bos_id,
-                              eos_id=eos_id, early_stopping=early_stopping, length_penalty=length_penalty, limit=lim, divisors=div)
+                              eos_id=eos_id, early_stopping=early_stopping, length_penalty=length_penalty, limit=lim, divisors=div,
+                              prefix_len=None if prefix is None else prefix[1])
         steps += 1
         if steps % poll == 0 or steps >= bound:
             if int(st["counters"][1]) >= n_images:
