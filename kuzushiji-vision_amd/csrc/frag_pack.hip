@@ -1,5 +1,5 @@
 // The decoder's weights -> MFMA fragment order (frag_stream.h has the layout): the B operands of the training chains (decoder_chain.hip,
-// decoder_chain_bwd.hip, cross_entropy.hip's head) AND of the generation step (decode_fused.hip), refreshed by model_decode.cpp.
+// decoder_chain_bwd.hip, cross_entropy.hip's head) AND of the generation step (decode_fused.hip), refreshed by model_decode.cpp (for model_stream.cpp as well).
 #include "kzv_common.h"
 #include "../../include/kzv.h"
 #include "kzv_host.h"

@@ -1,4 +1,4 @@
-// Internal launcher API (C++ linkage) used by the model handle's units (model.cpp, model_train.cpp, model_decode.cpp); the per-op C ABI in include/kzv.h wraps a subset.
+// Internal launcher API (C++ linkage) used by the model handle's units (model.cpp, model_train.cpp, model_decode.cpp, model_stream.cpp); the per-op C ABI in include/kzv.h wraps a subset.
 // Where a wrapper carries its launcher's name (kzv_ln_*_ex, the elementwise.hip and cross_entropy.hip entries) the two are overloads: the launcher takes a hipStream_t,
 // the extern "C" wrapper a void* stream (and an args struct or void* buffers), and is defined next to it.  Where the two differ in the stream's
 // type alone (kzv_copy_logits, kzv_dec_prepare, kzv_embed_gather, kzv_embed_scatter_bwd) the wrapper's (hipStream_t) cast is what selects the launcher:

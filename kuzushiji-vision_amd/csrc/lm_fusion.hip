@@ -2,12 +2,8 @@
 // (kzv/lm.py: NGramLM.row states lm[], fuse_reference the fusion; this is pinned against them bit for bit; include/kzv.h: kzv_ngram_lm
 // documents the tables).
 //
-// One workgroup of 256 threads per row, logits_process_kernel's shape and its three ways of finding the row's history h[0 .. n):
-//   lockstep      row r: ids[r][0 .. t + 1), t a host scalar
-//   greedy slots  slot s = r: ids[slot_image[s]][0 .. slot_t[s] + 1)
-//   beam slots    row r of slot s = r / group: ids[r][0 .. slot_t[s] + 1)
-// with the step index of the slot cases read from device memory (one captured graph serves every step); the rows of an idle slot return
-// before any barrier and stay as they are.
+// One workgroup of 256 threads per row, logits_process_kernel's shape, on the same histories h[0 .. n): score_rows.h has the three ways
+// of finding one (lockstep, greedy slots, beam slots); the rows of an idle slot return before any barrier and stay as they are.
 // Look-ups: wave k - 1 searches the sorted keys of length k for h[n - k .. n), k = 1 .. min(order - 1, n), 64 probes per round (a 65-ary
 // search: the three look-ups run side by side, each in 3 - 4 dependent loads); the results (successor range, back-off; a negative range
 // where nothing was found) reach the workgroup through LDS.
@@ -16,17 +12,14 @@
 // only writer of that element; a barrier between lengths makes the longest context win.  acc collects the back-offs in that order.
 // Dense pass, batches of independent loads: every unclaimed v gets row[v] + weight * (acc + uni[v]).  Every element is edited once.
 // The adds and the multiply are __fadd_rn / __fmul_rn and this unit is built with -ffp-contract=off, or no torch.equal could hold.
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+#include "score_rows.h"
 
 #include <atomic>
 #include <cmath>
 
 namespace {
 
-constexpr int LF_MAX_VOCAB = 64 * 256;           // kzv_logits_process's bound, for the same reason: the claim mask is 2 KiB of LDS
-constexpr int LF_WORDS = LF_MAX_VOCAB / 32;
+constexpr int LF_WORDS = SCORE_MAX_VOCAB / 32;   // the claim mask is 2 KiB of LDS
 constexpr int LF_MAX_ORDER = 4;
 
 std::atomic<long long> g_launches{0};
@@ -44,18 +37,11 @@ __global__ __launch_bounds__(256) void lm_fuse_kernel(const kzv_lm_fuse_args p, 
     __shared__ int s_beg[LF_MAX_ORDER - 1], s_end[LF_MAX_ORDER - 1];
     __shared__ float s_bo[LF_MAX_ORDER - 1];
     const int r = blockIdx.x, tid = threadIdx.x;
-    int t = p.t;
-    int64_t hrow = r;
-    if (p.slot_image) {                          // workgroup-uniform, before any barrier
-        const int slot = r / p.group;
-        const int img = p.slot_image[slot];
-        if (img < 0 || img >= p.n_images) return;
-        t = p.slot_t[slot];
-        if (p.by_image) hrow = img;
-    }
+    ScoreRow at;
+    if (!score_row<false>(p, r, at)) return;     // workgroup-uniform, before any barrier
     const int V = p.vocab, words = (V + 31) >> 5;
-    const int n = (int)min((int64_t)max(t + 1, 0), p.ld_ids);       // the history never leaves its row
-    const int64_t* __restrict__ h = p.ids + hrow * p.ld_ids;
+    int n;
+    const int64_t* __restrict__ h = score_history(p, at, n);
     const int K = min(lm.order - 1, n);
     for (int i = tid; i < words; i += 256) s_claim[i] = 0u;
     const int w = tid >> 6, lane = tid & 63;
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(256) void lm_fuse_kernel(const kzv_lm_fuse_args p, 
         for (int j = 0; j < k; ++j) {            // oldest token most significant
             const int64_t v = h[n - k + j];
             ok = ok && v >= 0 && v < V;
-            key = key * LF_MAX_VOCAB + v;
+            key = key * SCORE_MAX_VOCAB + v;
         }
         int beg = -1, end = -1;
         float bo = 0.f;
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(256) void lm_fuse_kernel(const kzv_lm_fuse_args p, 
 const char* kzv_ngram_lm_problem(const kzv_ngram_lm* lm, int vocab) {
     if (!lm) return "null language model";
     if (lm->order < 1 || lm->order > LF_MAX_ORDER) return "order outside 1..4";
-    if (lm->vocab < 1 || lm->vocab > LF_MAX_VOCAB) return "the language model's vocabulary lies outside 1..16384";
+    if (lm->vocab < 1 || lm->vocab > SCORE_MAX_VOCAB) return "the language model's vocabulary lies outside 1..16384";
     if (lm->vocab != vocab) return "the language model's vocabulary differs from the scores'";
     if (!lm->uni) return "null unigram table";
     for (int k = 0; k < lm->order - 1; ++k) {
@@ -139,20 +125,9 @@ const char* kzv_ngram_lm_problem(const kzv_ngram_lm* lm, int vocab) {
 
 extern "C" int kzv_lm_fuse(const kzv_lm_fuse_args* a, void* stream) {
     if (!a) return kzv_fail(KZV_E_ARG, "lm_fuse: null arguments");
-    if (!a->logits || !a->ids) return kzv_fail(KZV_E_ARG, "lm_fuse: null logits / ids");
-    if (a->rows < 1) return kzv_fail(KZV_E_ARG, "lm_fuse: rows must be positive (got %d)", a->rows);
-    if (a->vocab < 1 || a->vocab > LF_MAX_VOCAB) return kzv_fail(KZV_E_ARG, "lm_fuse: vocab %d outside 1..%d", a->vocab, LF_MAX_VOCAB);
-    if (a->ld < a->vocab) return kzv_fail(KZV_E_ARG, "lm_fuse: ld %lld < vocab %d", (long long)a->ld, a->vocab);
-    if (a->ld_ids < 1) return kzv_fail(KZV_E_ARG, "lm_fuse: ld_ids must be positive");
+    KZV_TRY_RC(score_rows_check<true>(a, "lm_fuse"));
     if (const char* why = kzv_ngram_lm_problem(a->lm, a->vocab)) return kzv_fail(KZV_E_ARG, "lm_fuse: %s", why);
     if (!std::isfinite(a->weight)) return kzv_fail(KZV_E_ARG, "lm_fuse: the weight must be finite (got %g)", (double)a->weight);
-    if ((a->slot_image == nullptr) != (a->slot_t == nullptr)) return kzv_fail(KZV_E_ARG, "lm_fuse: slot_image and slot_t go together");
-    if (a->slot_image) {
-        if (a->group < 1 || a->rows % a->group) return kzv_fail(KZV_E_ARG, "lm_fuse: %d rows are no multiple of %d rows per slot", a->rows, a->group);
-        if (a->n_images < 1) return kzv_fail(KZV_E_ARG, "lm_fuse: n_images must be positive");
-    } else if (a->t < 0) {
-        return kzv_fail(KZV_E_ARG, "lm_fuse: step %d is negative", a->t);
-    }
     hipLaunchKernelGGL(lm_fuse_kernel, dim3((unsigned)a->rows), dim3(256), 0, (hipStream_t)stream, *a, *a->lm);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     return kzv_check_launch("lm_fuse");

@@ -4,7 +4,8 @@
 // penalty maps -inf to -inf, so the order is immaterial for the result: the kernel collects two vocabulary bitmasks first and edits every
 // element once.
 //
-// One workgroup of 256 threads per row (stream_select_kernel's shape).  The row's token history h[0 .. n) is read where it lies:
+// One workgroup of 256 threads per row (stream_select_kernel's shape).  The row's token history h[0 .. n) is read where it lies
+// (score_rows.h: score_row / score_history, shared with the chain's other two nodes):
 //   lockstep      row r: ids[r][0 .. t + 1), t a host scalar
 //   greedy slots  slot s = r: ids[slot_image[s]][0 .. slot_t[s] + 1) (out_ids of the wave)
 //   beam slots    row r of slot s = r / group: ids[r][0 .. slot_t[s] + 1) (run_seq of the wave)
@@ -17,16 +18,13 @@
 // and sum of exponentials in the order of beam_topk_kernel's first phase (token_search.hip): thread tid owns tokens tid + 256 e; the WAVE's
 // maximum first (wave_max of the threads' maxima), each thread's exponentials summed against it in ascending e, wave_sum, then the four
 // waves' (max, sum) merged under the row maximum.  The dense pass writes (x - max) - log(sum), that kernel's own expression.
-#include "kzv_common.h"
-#include "../../include/kzv.h"
-#include "kzv_host.h"
+#include "score_rows.h"
 
 #include <atomic>
 
 namespace {
 
-constexpr int LP_MAX_VOCAB = 64 * 256;           // kzv_beam_topk's bound: the two masks are 2 * 2 KiB of LDS
-constexpr int LP_WORDS = LP_MAX_VOCAB / 32;
+constexpr int LP_WORDS = SCORE_MAX_VOCAB / 32;   // the two masks are 2 * 2 KiB of LDS
 constexpr int LP_MAX_NGRAM = 8;
 
 std::atomic<long long> g_launches{0};
@@ -35,19 +33,12 @@ template <bool NORM>
 __global__ __launch_bounds__(256) void logits_process_kernel(const kzv_logits_process_args p) {
     __shared__ unsigned s_seen[LP_WORDS], s_ban[LP_WORDS];
     __shared__ float s_m[4], s_s[4];
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int t = p.t;
-    int64_t hrow = r;
-    if (p.slot_image) {                          // workgroup-uniform, before any barrier
-        const int slot = r / p.group;
-        const int img = p.slot_image[slot];
-        if (img < 0 || img >= p.n_images) return;
-        t = p.slot_t[slot];
-        if (p.by_image) hrow = img;
-    }
+    const int r = blockIdx.x, tid = threadIdx.x;
+    ScoreRow at;
+    if (!score_row<false>(p, r, at)) return;     // workgroup-uniform, before any barrier
     const int V = p.vocab, words = (V + 31) >> 5;
-    const int n = (int)min((int64_t)max(t + 1, 0), p.ld_ids);       // the history never leaves its row
-    const int64_t* __restrict__ h = p.ids + hrow * p.ld_ids;
+    int n;
+    const int64_t* __restrict__ h = score_history(p, at, n);
     const int g = p.no_repeat_ngram_size;
     const float pen = p.repetition_penalty;
     const bool penalise = pen != 1.f;
@@ -75,33 +66,7 @@ __global__ __launch_bounds__(256) void logits_process_kernel(const kzv_logits_pr
     float* __restrict__ row = p.logits + (int64_t)r * p.ld;
     constexpr int E = 8;
     float M = 0.f, lse = 0.f;
-    if (NORM) {
-        float lm = -INFINITY;
-        for (int v0 = tid; v0 < V; v0 += 256 * E) {
-            float x[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
-#pragma unroll
-            for (int e = 0; e < E; ++e) if (v0 + e * 256 < V) lm = fmaxf(lm, x[e]);
-        }
-        const float wm = wave_max(lm);
-        float ls = 0.f;
-        for (int v0 = tid; v0 < V; v0 += 256 * E) {
-            float x[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) x[e] = row[min(v0 + e * 256, V - 1)];
-#pragma unroll
-            for (int e = 0; e < E; ++e) ls += (v0 + e * 256 < V && x[e] != -INFINITY) ? expf(x[e] - wm) : 0.f;
-        }
-        ls = wave_sum(ls);
-        if (lane == 0) { s_m[w] = wm; s_s[w] = ls; }
-        __syncthreads();                         // every read of the first phase is done before the first store below
-        M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float S = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) S += (s_m[q] == -INFINITY) ? 0.f : s_s[q] * expf(s_m[q] - M);
-        lse = logf(S);
-    }
+    if (NORM) KZV_ROW_MAX_LSE(E, row, V, tid, s_m, s_s, M, lse);      // its barrier: every read of the first phase is done before the first store below
     for (int v0 = tid; v0 < V; v0 += 256 * E) {
         float x[E];
 #pragma unroll
@@ -124,23 +89,12 @@ __global__ __launch_bounds__(256) void logits_process_kernel(const kzv_logits_pr
 
 extern "C" int kzv_logits_process(const kzv_logits_process_args* a, void* stream) {
     if (!a) return kzv_fail(KZV_E_ARG, "logits_process: null arguments");
-    if (!a->logits || !a->ids) return kzv_fail(KZV_E_ARG, "logits_process: null logits / ids");
-    if (a->rows < 1) return kzv_fail(KZV_E_ARG, "logits_process: rows must be positive (got %d)", a->rows);
-    if (a->vocab < 1 || a->vocab > LP_MAX_VOCAB) return kzv_fail(KZV_E_ARG, "logits_process: vocab %d outside 1..%d", a->vocab, LP_MAX_VOCAB);
-    if (a->ld < a->vocab) return kzv_fail(KZV_E_ARG, "logits_process: ld %lld < vocab %d", (long long)a->ld, a->vocab);
-    if (a->ld_ids < 1) return kzv_fail(KZV_E_ARG, "logits_process: ld_ids must be positive");
+    KZV_TRY_RC(score_rows_check<true>(a, "logits_process"));
     if (a->no_repeat_ngram_size < 0 || a->no_repeat_ngram_size > LP_MAX_NGRAM)
         return kzv_fail(KZV_E_ARG, "logits_process: no_repeat_ngram_size %d outside 0..%d", a->no_repeat_ngram_size, LP_MAX_NGRAM);
     if (!(a->repetition_penalty > 0.f)) return kzv_fail(KZV_E_ARG, "logits_process: repetition_penalty must be positive (got %g)", (double)a->repetition_penalty);
     if (a->min_length < 0) return kzv_fail(KZV_E_ARG, "logits_process: min_length must not be negative");
     if (a->min_length > 0 && (a->eos_id < 0 || a->eos_id >= a->vocab)) return kzv_fail(KZV_E_ARG, "logits_process: EOS %d outside the vocabulary", a->eos_id);
-    if ((a->slot_image == nullptr) != (a->slot_t == nullptr)) return kzv_fail(KZV_E_ARG, "logits_process: slot_image and slot_t go together");
-    if (a->slot_image) {
-        if (a->group < 1 || a->rows % a->group) return kzv_fail(KZV_E_ARG, "logits_process: %d rows are no multiple of %d rows per slot", a->rows, a->group);
-        if (a->n_images < 1) return kzv_fail(KZV_E_ARG, "logits_process: n_images must be positive");
-    } else if (a->t < 0) {
-        return kzv_fail(KZV_E_ARG, "logits_process: step %d is negative", a->t);
-    }
     if (a->normalise) hipLaunchKernelGGL(logits_process_kernel<true>, dim3((unsigned)a->rows), dim3(256), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(logits_process_kernel<false>, dim3((unsigned)a->rows), dim3(256), 0, (hipStream_t)stream, *a);
     g_launches.fetch_add(1, std::memory_order_relaxed);

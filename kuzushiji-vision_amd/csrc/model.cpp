@@ -1,5 +1,6 @@
 // Model handle: create / destroy, parameter table, workspace plan, bind and the weight copies' refresh.  The training schedules are in
-// model_train.cpp, the generation steps in model_decode.cpp; model_internal.h holds what the three share.
+// model_train.cpp, the lockstep generation steps in model_decode.cpp, slot-refill decoding in model_stream.cpp; model_internal.h holds what
+// the four share.
 //
 // Numeric policy (scripts/train_trocr.py:165-176 "bf16-mixed"): fp32 master weights and gradients, fp32
 // residual stream / LayerNorm / softmax / loss, bf16 GEMM operands with fp32 accumulation.

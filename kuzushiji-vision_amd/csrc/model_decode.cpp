@@ -1,5 +1,6 @@
 // KV-cached generation on the model handle (N1): the cache, the cross-attention K/V layout and the fragment-ordered weight pack, the
-// three bodies of one decoder step (one launch; LayerNorm folded into the GEMMs; a launch per operation) and the graph replay.
+// three bodies of one decoder step (one launch; LayerNorm folded into the GEMMs; a launch per operation) and the graph replay of the
+// lockstep step (kzv_decode_*).  Slot-refill decoding (kzv_stream_*) is model_stream.cpp, on the helpers model_internal.h declares.
 #include "model_internal.h"
 
 static int g_decode_one_launch = -1;           // -1: KZV_DECODE_ONE_LAUNCH (default 1)
@@ -38,13 +39,13 @@ extern "C" int kzv_decode_weights_impl(const kzv_model* m) {
 }
 
 // `bytes` in one of the handle's buffers (false: the allocation failed); a buffer that moved drops the graphs that hold its old pointer
-static bool reserve(kzv_model* m, KzvDevBuf& buf, size_t bytes) {
+bool reserve(kzv_model* m, KzvDevBuf& buf, size_t bytes) {
     const KzvDevBuf::Result r = buf.reserve(bytes);
     if (r == KzvDevBuf::MOVED) drop_decode_graphs(m);
     return r != KzvDevBuf::FAILED;
 }
 
-static int ensure_kv_cache(kzv_model* m) {
+int ensure_kv_cache(kzv_model* m) {
     if (m->kvc && m->kvB == m->B && m->kvT == m->T) return KZV_OK;
     // ONE cache [2*Ld][B][T][Hd]: beam steps re-parent rows through the row tables instead of copying into a second cache
     const size_t bytes = (size_t)2 * m->Ld * m->B * m->T * m->Hd * sizeof(bf16_t);
@@ -102,7 +103,7 @@ int ensure_dec_pack(kzv_model* m, hipStream_t s) {
 }
 
 // the e4m3 stream and row scales of the same linears (4.7 MB), quantised from their bf16 copies in ONE launch (outside any capture)
-static int build_dec_pack8(kzv_model* m, hipStream_t s) {
+int build_dec_pack8(kzv_model* m, hipStream_t s) {
     if (m->dec_pack8_ok) return KZV_OK;
     if (!reserve(m, m->dec_pack8, (size_t)kzv_decode_fused_pack8_bytes(m->Ld))) return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
     if (!reserve(m, m->dec_scale8, sizeof(float) * (size_t)kzv_decode_fused_scales8(m->Ld))) return kzv_fail(KZV_E_HIP, "decode: e4m3 weight stream allocation");
@@ -140,7 +141,7 @@ static int lin_fwd_ln(const kzv_model* m, const Lin& l, const bf16_t* A, int64_t
 
 // The vocabulary GEMM of a step: straight into the caller's [B, V] buffer where V % 4 == 0 (the padded scratch + copy costs a launch per
 // token), else padded into m->logits and copied.  fold_ln: A = LN(hd_gelu) normalised inside the GEMM, else the stored m->hd_ln.
-static int vocab_logits(kzv_model* m, bool fold_ln, float* d_logits, hipStream_t s) {
+int vocab_logits(kzv_model* m, bool fold_ln, float* d_logits, hipStream_t s) {
     const bool direct = m->V % 4 == 0;
     float* C = direct ? d_logits : m->logits;
     const int n = direct ? m->V : m->Vp;
@@ -195,7 +196,7 @@ static int decode_step_body_fused(kzv_model* m, const StepArgs& st, hipStream_t 
 // The whole step up to the LM head's dense layer in ONE launch (decode_fused.hip: a workgroup per image owns its beams through all
 // layers), then the vocabulary GEMM with the head's LayerNorm folded into its A operand as before.
 // what every one-launch step reads whatever it serves: the weights in fragment order (or the e4m3 stream), embeddings, head, cache
-static int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* who) {
+int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* who) {
     const int B = m->B, Hd = m->Hd, T = m->T;
     float* P = m->P;
     memset(&a, 0, sizeof(a));
@@ -279,22 +280,6 @@ static int decode_step_check(kzv_model* m, const void* a, const void* b, const v
     return KZV_OK;
 }
 
-// Captures what `body` launches on `s` into an instantiated graph: the capture is ended and the graph destroyed on every path; the
-// body's error comes back as it is, a failure of the capture itself as KZV_E_HIP
-template <typename Body>
-static int capture_into(hipGraphExec_t* out, hipStream_t s, const char* what, Body&& body) {
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: begin capture", what);
-    const int rc = body();
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc != KZV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess || !graph) return kzv_fail(KZV_E_HIP, "%s: end capture (%s)", what, hipGetErrorString(e));
-    const hipError_t ei = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) { *out = nullptr; return kzv_fail(KZV_E_HIP, "%s: instantiate (%s)", what, hipGetErrorString(ei)); }
-    return KZV_OK;
-}
-
 extern "C" int kzv_decode_step(kzv_model* m, const int64_t* d_tokens, const int* d_posids, int t, const unsigned char* d_valid,
                                int64_t ld_valid, float* d_logits, void* stream) {
     KZV_TRY(decode_step_check(m, d_tokens, d_posids, d_valid, d_logits, "decode_step"));
@@ -354,345 +339,4 @@ extern "C" int kzv_decode_reorder(kzv_model* m, const int64_t* d_rows, int len, 
     KZV_TRY(kzv_kv_rows(m->rt_cur < 0 ? nullptr : m->rowtab[m->rt_cur].as<int>(), m->rowtab[nxt].as<int>(), d_rows, m->B, m->T, len, (hipStream_t)stream));
     m->rt_cur = nxt;
     return KZV_OK;
-}
-
-// ---- slot-refill decoding (include/kzv.h: kzv_stream_*): greedy, one row per slot; or beam search, a slot holding an image's beam group ----
-static bool stream_supported(const kzv_model* m, int nb = 1) {
-    return decode_one_launch_mode() && kzv_decode_fused_supported(m->Hd, m->c.dec_heads, m->Fd, m->Ld, nb, m->T, m->npa) &&
-           (nb == 1 || ((nb == 2 || nb == 4) && m->B % nb == 0 && m->V <= 64 * 256));       // kzv_beam_topk ranks up to 16,384 columns
-}
-extern "C" int kzv_stream_decode_impl(const kzv_model* m) {
-    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_decode_impl: model not bound");
-    return stream_supported(m) ? 1 : 0;
-}
-extern "C" int kzv_stream_beam_impl(const kzv_model* m, int num_beams) {
-    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_beam_impl: model not bound");
-    return (num_beams == 2 || num_beams == 4) && stream_supported(m, num_beams) ? 1 : 0;
-}
-static bool stream_e4m3(const kzv_model* m) { return m->dec_weights == KZV_DECODE_WEIGHTS_E4M3; }
-
-// nb = 1: kzv_stream_begin; nb = 2 / 4: kzv_stream_begin_beams (slots = bound batch / nb)
-static int stream_begin(kzv_model* m, const char* who, int nb, int early, float length_penalty, float* d_out_scores, int pool_images, int n_images, int max_len,
-                        int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit,
-                        void* stream) {
-    // what needs no bound state first: these are argument errors on any handle
-    if (!m) return kzv_fail(KZV_E_ARG, "%s: null model", who);
-    if (nb != 1 && nb != 2 && nb != 4) return kzv_fail(KZV_E_ARG, "%s: num_beams %d: a slot holds 2 or 4 beams", who, nb);
-    if (!d_out_ids) return kzv_fail(KZV_E_ARG, "%s: null out_ids", who);
-    if (max_len < 2) return kzv_fail(KZV_E_ARG, "%s: max_len %d: a line is BOS and at least one token", who, max_len);
-    if (n_images < 1 || n_images > pool_images) return kzv_fail(KZV_E_ARG, "%s: a wave of %d images for a pool of %d", who, n_images, pool_images);
-    if (ld_ids < max_len || (d_out_logprob && ld_logprob < max_len)) return kzv_fail(KZV_E_ARG, "%s: output rows shorter than max_len", who);
-    if (nb > 1 && d_out_logprob) return kzv_fail(KZV_E_ARG, "%s: a beam search returns no per-token log-probabilities (d_out_logprob must be null)", who);
-    if (!m->bound) return kzv_fail(KZV_E_STATE, "%s: model not bound", who);
-    m->swave = false;
-    if (m->B % nb) return kzv_fail(KZV_E_ARG, "%s: the %d bound rows are no multiple of %d beams", who, m->B, nb);
-    const int B = m->B, V = m->V, slots = B / nb;
-    if (pool_images < slots) return kzv_fail(KZV_E_ARG, "%s: a pool of %d images is smaller than the %d slots", who, pool_images, slots);
-    if (bos_id < 0 || bos_id >= m->V || eos_id < 0 || eos_id >= m->V) return kzv_fail(KZV_E_ARG, "%s: BOS / EOS outside the vocabulary", who);
-    if (max_len > m->L) return kzv_fail(KZV_E_ARG, "%s: max_len %d outside 2..%d (the bound length)", who, max_len, m->L);
-    if (max_len - 1 + m->c.pad_id >= m->c.max_pos) return kzv_fail(KZV_E_ARG, "%s: max_len %d needs position id %d, the table has %d rows", who, max_len, max_len - 1 + m->c.pad_id, m->c.max_pos);
-    if (!stream_supported(m, nb)) return kzv_fail(KZV_E_STATE, "%s: this geometry has no slot-refill decoding (kzv_stream_decode_impl / kzv_stream_beam_impl)", who);
-    hipStream_t s = (hipStream_t)stream;
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // it holds the last wave's outputs and counts
-    const size_t bytes = (size_t)m->Ld * 2 * pool_images * m->npa * m->Hd * sizeof(bf16_t);
-    if (!reserve(m, m->spool, bytes)) return kzv_fail(KZV_E_HIP, "%s: pool allocation (%zu bytes)", who, bytes);
-    m->spool_images = pool_images;
-    // logits [B, V] | tokens [B] int64 | slot_image, slot_t, posids [B] | scratch [2 B] | counters [4]; a beam wave adds
-    // run_seq, fin_seq [B, L] and fin_len [B] int64 | top_ix [2 B] int64 | run / fin scores [B], top_lp [2 B] | divisors [L + 1] | fin_done [B], unsat [B]
-    const int L = m->L;
-    const size_t sb = align_up((size_t)B * V * sizeof(float), 256) + (size_t)B * 8 + (size_t)B * 5 * 4 + 16 +
-                      (nb > 1 ? (size_t)B * (2 * L + 1 + 2) * 8 + (size_t)B * 4 * 4 + align_up((size_t)(L + 1) * 4, 8) + (size_t)B * 2 : 0);
-    if (!m->sstate || m->sstate_slots < B || m->sstate_V < V || m->sstate.capacity() < sb) {
-        if (!reserve(m, m->sstate, sb)) return kzv_fail(KZV_E_HIP, "%s: slot state allocation (%zu bytes)", who, sb);
-        m->sstate_slots = B; m->sstate_V = V;
-    }
-    char* q = m->sstate.as<char>();
-    m->slogits = (float*)q; q += align_up((size_t)B * V * sizeof(float), 256);
-    m->sbeams = nb > 1 ? nb : 0;
-    m->stopk = 0;                                // kzv_stream_set_topk belongs to one wave
-    m->sctl_on = false; m->smask_on = false;     // and so does kzv_stream_set_controls (neutral until it is called)
-    m->sctl = kzv_logits_controls{}; m->sctl.repetition_penalty = 1.f;
-    m->slm_on = false;                           // and kzv_stream_set_lm
-    m->spfx_on = false; m->spfx = nullptr; m->spfx_len = nullptr; m->spfx_lp = nullptr; m->spfx_ld = m->spfx_lp_ld = 0;      // and kzv_stream_set_prefix
-    if (nb == 1) {
-        kzv_stream_state& st = m->sst;
-        st.slots = B; st.n_images = n_images; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id; st.eos_id = eos_id; st.reserved = 0;
-        st.tokens = (int64_t*)q; q += (size_t)B * 8;
-        st.slot_image = (int32_t*)q; q += (size_t)B * 4;
-        st.slot_t = (int32_t*)q; q += (size_t)B * 4;
-        st.posids = (int32_t*)q; q += (size_t)B * 4;
-        st.scratch = (int32_t*)q; q += (size_t)B * 8;
-        st.counters = (int32_t*)q;
-        st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_logprob = d_out_logprob; st.ld_logprob = ld_logprob; st.limit = d_limit;
-    } else {
-        kzv_stream_beam_state& st = m->sbst;
-        st.slots = slots; st.n_images = n_images; st.num_beams = nb; st.max_len = max_len; st.vocab = V; st.pad_id = m->c.pad_id; st.bos_id = bos_id;
-        st.eos_id = eos_id; st.early_stopping = early ? 1 : 0;
-        st.n_best = 0; st.run_lp = st.fin_lp = nullptr;      // kzv_stream_set_nbest belongs to one wave
-        st.nbest_ids = nullptr; st.ld_nbest = 0; st.nbest_scores = nullptr; st.nbest_len = nullptr; st.nbest_logprob = nullptr; st.ld_nbest_logprob = 0;
-        st.tokens = (int64_t*)q; q += (size_t)B * 8;                       // 8-byte words first
-        st.run_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
-        st.fin_seq = (int64_t*)q; q += (size_t)B * max_len * 8;
-        st.fin_len = (int64_t*)q; q += (size_t)B * 8;
-        m->stop_ix = (int64_t*)q; q += (size_t)B * 2 * 8;
-        st.run_scores = (float*)q; q += (size_t)B * 4;
-        st.fin_scores = (float*)q; q += (size_t)B * 4;
-        m->stop_lp = (float*)q; q += (size_t)B * 2 * 4;
-        st.posids = (int32_t*)q; q += (size_t)B * 4;
-        st.slot_image = (int32_t*)q; q += (size_t)slots * 4;
-        st.slot_t = (int32_t*)q; q += (size_t)slots * 4;
-        st.scratch = (int32_t*)q; q += (size_t)slots * 8;
-        st.counters = (int32_t*)q; q += 16;
-        float* div = (float*)q; q += align_up((size_t)(max_len + 1) * 4, 8);
-        st.fin_done = (uint8_t*)q; q += (size_t)B;
-        st.unsatisfied = (uint8_t*)q;
-        st.out_ids = d_out_ids; st.ld_ids = ld_ids; st.out_score = d_out_scores; st.limit = d_limit; st.divisors = div;
-        // the divisors kzv_beam_update takes per call: (float)pow((double)n, (double)length_penalty), as a table since every slot has its own n
-        m->sdiv.assign((size_t)max_len + 1, 1.f);
-        for (int n = 1; n <= max_len; ++n) m->sdiv[n] = (float)pow((double)n, (double)length_penalty);
-        if (hipMemcpyAsync(div, m->sdiv.data(), sizeof(float) * m->sdiv.size(), hipMemcpyHostToDevice, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: divisor table copy", who);
-    }
-    KZV_TRY(ensure_kv_cache(m));
-    if (nb > 1) { m->sbst.rows = m->rowtab[0].as<int>(); m->sbst.ld_rows = m->T; }       // ensure_kv_cache may have moved it
-    KZV_TRY(ensure_dec_pack(m, s));
-    if (stream_e4m3(m)) KZV_TRY(build_dec_pack8(m, s));
-    m->rt_cur = -1;
-    if (hipMemsetAsync(m->hd_gelu, 0, sizeof(float) * (size_t)B * m->Hd, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: memset", who);
-    m->train = false; m->have_fwd = false; m->have_dec = false;
-    m->swave = true;
-    return KZV_OK;
-}
-
-extern "C" int kzv_stream_begin(kzv_model* m, int pool_images, int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids,
-                                float* d_out_logprob, int64_t ld_logprob, const int32_t* d_limit, void* stream) {
-    return stream_begin(m, "stream_begin", 1, 0, 1.f, nullptr, pool_images, n_images, max_len, bos_id, eos_id, d_out_ids, ld_ids, d_out_logprob, ld_logprob,
-                        d_limit, stream);
-}
-
-extern "C" int kzv_stream_begin_beams(kzv_model* m, int num_beams, int early_stopping, float length_penalty, float* d_out_scores, int pool_images,
-                                      int n_images, int max_len, int bos_id, int eos_id, int64_t* d_out_ids, int64_t ld_ids, float* d_out_logprob,
-                                      int64_t ld_logprob, const int32_t* d_limit, void* stream) {
-    if (num_beams != 2 && num_beams != 4) return kzv_fail(KZV_E_ARG, "stream_begin_beams: num_beams %d: a slot holds 2 or 4 beams", num_beams);
-    return stream_begin(m, "stream_begin_beams", num_beams, early_stopping, length_penalty, d_out_scores, pool_images, n_images, max_len, bos_id, eos_id,
-                        d_out_ids, ld_ids, d_out_logprob, ld_logprob, d_limit, stream);
-}
-
-extern "C" int kzv_stream_set_topk(kzv_model* m, int k, int32_t* d_alt_ids, float* d_alt_logprob, int64_t ld_alt, void* stream) {
-    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_topk: call kzv_stream_begin first");
-    if (m->sbeams) return kzv_fail(KZV_E_STATE, "stream_set_topk: the wave is a beam search (alternatives are greedy only)");
-    if (k < 0 || k > 8) return kzv_fail(KZV_E_ARG, "stream_set_topk: k must be in 0..8 (got %d; 0 switches the alternatives off)", k);
-    if (k && (!d_alt_ids || !d_alt_logprob)) return kzv_fail(KZV_E_ARG, "stream_set_topk: null result array");
-    if (k && ld_alt < (int64_t)m->sst.max_len * k) return kzv_fail(KZV_E_ARG, "stream_set_topk: ld_alt %lld < max_len * k = %lld", (long long)ld_alt, (long long)m->sst.max_len * k);
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
-    m->stopk = k; m->salt_ids = k ? d_alt_ids : nullptr; m->salt_lp = k ? d_alt_logprob : nullptr; m->sld_alt = k ? ld_alt : 0;
-    return KZV_OK;
-}
-
-extern "C" int kzv_stream_set_nbest(kzv_model* m, int n_best, int64_t* d_ids, int64_t ld_ids, float* d_scores, int32_t* d_lengths, float* d_logprob,
-                                    int64_t ld_logprob, void* stream) {
-    (void)stream;                                // nothing is launched: kzv_stream_start zeroes the log-probability rows with the token rows
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_nbest: call kzv_stream_begin_beams first");
-    if (!m->sbeams) return kzv_fail(KZV_E_ARG, "stream_set_nbest: the wave is greedy (an n-best list needs a beam search: kzv_stream_begin_beams)");
-    kzv_stream_beam_state& st = m->sbst;
-    if (n_best < 1 || n_best > st.num_beams) return kzv_fail(KZV_E_ARG, "stream_set_nbest: n_best %d outside 1..num_beams = %d", n_best, st.num_beams);
-    if (!d_ids || !d_scores || !d_lengths) return kzv_fail(KZV_E_ARG, "stream_set_nbest: null ids / scores / lengths");
-    if (ld_ids < st.max_len || (d_logprob && ld_logprob < st.max_len)) return kzv_fail(KZV_E_ARG, "stream_set_nbest: output rows shorter than max_len = %d", st.max_len);
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
-    st.run_lp = st.fin_lp = nullptr;
-    if (d_logprob) {                             // the log-probability rows, laid out as the token rows are: [slots, num_beams, max_len]
-        const size_t rows = (size_t)m->B * st.max_len;
-        if (!reserve(m, m->snbest, 2 * rows * sizeof(float))) return kzv_fail(KZV_E_HIP, "stream_set_nbest: log-probability rows allocation");
-        st.run_lp = m->snbest.as<float>(); st.fin_lp = st.run_lp + rows;
-    }
-    st.n_best = n_best; st.nbest_ids = d_ids; st.ld_nbest = ld_ids; st.nbest_scores = d_scores; st.nbest_len = d_lengths;
-    st.nbest_logprob = d_logprob; st.ld_nbest_logprob = d_logprob ? ld_logprob : 0;
-    return KZV_OK;
-}
-
-extern "C" int kzv_stream_set_controls(kzv_model* m, const kzv_logits_controls* c, void* stream) {
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_controls: call kzv_stream_begin / kzv_stream_begin_beams first");
-    if (!c) return kzv_fail(KZV_E_ARG, "stream_set_controls: null controls");
-    if (c->no_repeat_ngram_size < 0 || c->no_repeat_ngram_size > 8) return kzv_fail(KZV_E_ARG, "stream_set_controls: no_repeat_ngram_size %d outside 0..8", c->no_repeat_ngram_size);
-    if (!(c->repetition_penalty > 0.f)) return kzv_fail(KZV_E_ARG, "stream_set_controls: repetition_penalty must be positive (got %g)", (double)c->repetition_penalty);
-    if (c->min_length < 0) return kzv_fail(KZV_E_ARG, "stream_set_controls: min_length must not be negative");
-    if (m->V > 64 * 256) return kzv_fail(KZV_E_ARG, "stream_set_controls: vocabulary %d beyond 16,384", m->V);
-    const int words = (m->V + 31) / 32, eos = m->sbeams ? m->sbst.eos_id : m->sst.eos_id;
-    bool any = false;
-    if (c->suppress_mask) {
-        if ((c->suppress_mask[eos >> 5] >> (eos & 31)) & 1u) return kzv_fail(KZV_E_ARG, "stream_set_controls: the mask suppresses EOS (%d): no line could end", eos);
-        int left = m->V;                         // tokens the mask leaves (bits past the vocabulary do not count)
-        for (int i = 0; i < words; ++i) left -= __builtin_popcount(c->suppress_mask[i] & (i == words - 1 && (m->V & 31) ? (1u << (m->V & 31)) - 1u : ~0u));
-        any = left < m->V;
-        // a beam step ranks 2 * num_beams continuations of num_beams rows: with one token left they do not exist
-        if (m->sbeams && left < 2) return kzv_fail(KZV_E_ARG, "stream_set_controls: the mask leaves %d token(s), a beam wave needs at least 2", left);
-    }
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
-    m->sctl = *c; m->sctl.suppress_mask = nullptr; m->smask_on = false;
-    if (any) {                                   // a copy on the stream, no kernel: the steps that follow read it
-        m->smask_h.assign(c->suppress_mask, c->suppress_mask + words);
-        if (!reserve(m, m->smask, sizeof(uint32_t) * (size_t)words)) return kzv_fail(KZV_E_HIP, "stream_set_controls: mask allocation");
-        if (hipMemcpyAsync(m->smask.as<uint32_t>(), m->smask_h.data(), sizeof(uint32_t) * (size_t)words, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-            return kzv_fail(KZV_E_HIP, "stream_set_controls: mask copy");
-        m->smask_on = true;
-    }
-    m->sctl_on = any || c->no_repeat_ngram_size != 0 || c->repetition_penalty != 1.f || c->min_length != 0;
-    return KZV_OK;
-}
-
-const char* kzv_ngram_lm_problem(const kzv_ngram_lm* lm, int vocab);      // lm_fusion.hip
-
-extern "C" int kzv_stream_set_lm(kzv_model* m, const kzv_ngram_lm* lm, float weight, void* stream) {
-    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_lm: call kzv_stream_begin / kzv_stream_begin_beams first");
-    if (const char* why = kzv_ngram_lm_problem(lm, m->V)) return kzv_fail(KZV_E_ARG, "stream_set_lm: %s", why);
-    if (!std::isfinite(weight)) return kzv_fail(KZV_E_ARG, "stream_set_lm: the weight must be finite (got %g)", (double)weight);
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
-    m->slm = *lm; m->slm_weight = weight;
-    m->slm_on = weight != 0.f;
-    return KZV_OK;
-}
-
-extern "C" int kzv_stream_set_prefix(kzv_model* m, const int64_t* d_prefix, int64_t ld_prefix, const int32_t* d_prefix_len, float* d_forced_logprob,
-                                     int64_t ld_forced_logprob, void* stream) {
-    (void)stream;                                // nothing is launched: the steps that follow carry one more kernel
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_set_prefix: call kzv_stream_begin / kzv_stream_begin_beams first");
-    const int max_len = m->sbeams ? m->sbst.max_len : m->sst.max_len;
-    if (ld_prefix < 0) return kzv_fail(KZV_E_ARG, "stream_set_prefix: ld_prefix must not be negative");
-    if (ld_prefix > 0 && (!d_prefix || !d_prefix_len)) return kzv_fail(KZV_E_ARG, "stream_set_prefix: null prefix / prefix_len table");
-    if (1 + ld_prefix > (int64_t)max_len - 1)
-        return kzv_fail(KZV_E_ARG, "stream_set_prefix: BOS + %lld forced tokens reach max_len - 1 = %d: no token would be generated", (long long)ld_prefix, max_len - 1);
-    if (m->V > 64 * 256) return kzv_fail(KZV_E_ARG, "stream_set_prefix: vocabulary %d beyond 16,384", m->V);
-    if (ld_prefix > 0 && d_forced_logprob && ld_forced_logprob < ld_prefix + 1)
-        return kzv_fail(KZV_E_ARG, "stream_set_prefix: forced_logprob rows of %lld columns are shorter than BOS + the %lld prefix columns", (long long)ld_forced_logprob, (long long)ld_prefix);
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }      // a captured step holds the former setting
-    m->spfx_on = ld_prefix > 0;
-    m->spfx = m->spfx_on ? d_prefix : nullptr; m->spfx_ld = ld_prefix; m->spfx_len = m->spfx_on ? d_prefix_len : nullptr;
-    m->spfx_lp = m->spfx_on ? d_forced_logprob : nullptr; m->spfx_lp_ld = m->spfx_lp ? ld_forced_logprob : 0;
-    return KZV_OK;
-}
-
-// the wave's controls on the step's logits: one more node between the vocabulary GEMM and what reads the rows (order: repetition penalty,
-// n-gram ban, minimum length, suppression -- immaterial, see logits_process.hip)
-static int stream_process(kzv_model* m, hipStream_t s) {
-    const int nb = m->sbeams;
-    kzv_logits_process_args a;
-    memset(&a, 0, sizeof(a));
-    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
-    if (!nb) { a.ids = m->sst.out_ids; a.ld_ids = m->sst.ld_ids; a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; a.eos_id = m->sst.eos_id; }
-    else { a.ids = m->sbst.run_seq; a.ld_ids = m->sbst.max_len; a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; a.eos_id = m->sbst.eos_id; }
-    a.no_repeat_ngram_size = m->sctl.no_repeat_ngram_size; a.repetition_penalty = m->sctl.repetition_penalty; a.min_length = m->sctl.min_length;
-    a.suppress_mask = m->smask_on ? m->smask.as<uint32_t>() : nullptr;
-    a.normalise = nb ? 1 : 0;
-    return kzv_logits_process(&a, s);
-}
-
-// the wave's language model on the step's (processed) scores: the next node, on the same histories
-static int stream_lm_fuse(kzv_model* m, hipStream_t s) {
-    const int nb = m->sbeams;
-    kzv_lm_fuse_args a;
-    memset(&a, 0, sizeof(a));
-    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
-    if (!nb) { a.ids = m->sst.out_ids; a.ld_ids = m->sst.ld_ids; a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; }
-    else { a.ids = m->sbst.run_seq; a.ld_ids = m->sbst.max_len; a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; }
-    a.weight = m->slm_weight; a.lm = &m->slm;
-    return kzv_lm_fuse(&a, s);
-}
-
-// the wave's forced prefixes on the step's scores: the chain's last node before selection, on every slot's own image and step
-static int stream_force_prefix(kzv_model* m, hipStream_t s, bool normalised) {
-    const int nb = m->sbeams;
-    kzv_force_prefix_args a;
-    memset(&a, 0, sizeof(a));
-    a.logits = m->slogits; a.ld = m->V; a.rows = m->B; a.vocab = m->V;
-    if (!nb) { a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t; a.by_image = 1; a.n_images = m->sst.n_images; }
-    else { a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.by_image = 0; a.n_images = m->sbst.n_images; }
-    a.prefix = m->spfx; a.ld_prefix = m->spfx_ld; a.prefix_len = m->spfx_len;
-    a.normalised = normalised ? 1 : 0;
-    a.forced_logprob = m->spfx_lp; a.ld_forced_logprob = m->spfx_lp_ld;
-    return kzv_force_prefix(&a, s);
-}
-
-extern "C" int kzv_stream_encode(kzv_model* m, const float* d_pixel_values, int n, int first, void* stream) {
-    if (!m || !m->bound) return kzv_fail(KZV_E_STATE, "stream_encode: model not bound");
-    if (!m->swave) return kzv_fail(KZV_E_STATE, "stream_encode: call kzv_stream_begin first");
-    if (first < 0 || n < 1 || first + n > m->spool_images) return kzv_fail(KZV_E_ARG, "stream_encode: entries %d .. %d outside the pool of %d images", first, first + n - 1, m->spool_images);
-    if ((size_t)m->Ld * 2 * m->spool_images * m->npa * m->Hd * sizeof(bf16_t) > m->spool.capacity()) return kzv_fail(KZV_E_STATE, "stream_encode: the image width changed since kzv_stream_begin");
-    KZV_TRY(kzv_encode_images(m, d_pixel_values, n, stream));
-    return kzv_cross_relayout_pool(m->crosskv, m->spool.as<bf16_t>(), n, m->npa, m->c.dec_heads, 2 * m->Ld, m->spool_images, first, (hipStream_t)stream);
-}
-
-extern "C" int kzv_stream_start(kzv_model* m, void* stream) {
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_start: call kzv_stream_begin first");
-    return m->sbeams ? kzv_stream_beam_seat_first(&m->sbst, stream) : kzv_stream_seat_first(&m->sst, stream);
-}
-
-static int stream_step_body(kzv_model* m, hipStream_t s) {
-    KzvDecodeFused a;
-    const int nb = m->sbeams;
-    KZV_TRY(fused_common(m, a, stream_e4m3(m), "stream_step"));
-    a.ckv = m->spool.as<bf16_t>(); a.plane2 = (int64_t)m->spool_images * m->npa * m->Hd;
-    if (!nb) {
-        a.tokens = m->sst.tokens; a.posids = m->sst.posids;
-        a.group = 1; a.slot_image = m->sst.slot_image; a.slot_t = m->sst.slot_t;
-    } else {                                     // a slot's workgroup serves its nb rows through the handle's first row table
-        a.tokens = m->sbst.tokens; a.posids = m->sbst.posids;
-        a.group = nb; a.slot_image = m->sbst.slot_image; a.slot_t = m->sbst.slot_t; a.rows = m->sbst.rows;
-    }
-    KZV_TRY(kzv_decode_fused_launch(a, s));
-    KZV_TRY(vocab_logits(m, true, m->slogits, s));
-    // neutral controls and no language model: nothing is added to the chain.  A beam wave with the language model on normalises through
-    // the controls' node even when the controls are neutral: the fusion acts on log-probabilities
-    // Forced prefixes come last (the prompt is subject to neither) and take the same route in a beam wave: a forced row is no logits row.
-    const bool lm = m->slm_on, pfx = m->spfx_on;
-    if (m->sctl_on || ((lm || pfx) && nb)) KZV_TRY(stream_process(m, s));
-    if (lm) KZV_TRY(stream_lm_fuse(m, s));
-    if (pfx) KZV_TRY(stream_force_prefix(m, s, nb != 0));
-    if (m->sctl_on || lm || pfx) {
-        if (nb) {                                // the rows are processed log-probabilities now: ranked without a second normalisation
-            KZV_TRY(kzv_beam_rank_logprobs(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
-            return kzv_stream_beam_update_prefix(&m->sbst, m->stop_lp, m->stop_ix, pfx ? m->spfx_len : nullptr, s);
-        }
-    }
-    if (!nb) {                                   // the alternatives read slot_image / slot_t before seating replaces them
-        if (m->stopk) KZV_TRY(kzv_stream_topk(&m->sst, m->slogits, m->V, m->stopk, m->salt_ids, m->salt_lp, m->sld_alt, s));
-        return kzv_stream_update(&m->sst, m->slogits, m->V, s);
-    }
-    KZV_TRY(kzv_beam_topk(m->slogits, m->V, m->sbst.run_scores, m->sbst.slots, nb, m->V, 2 * nb, m->stop_lp, m->stop_ix, s));
-    return kzv_stream_beam_update(&m->sbst, m->stop_lp, m->stop_ix, s);
-}
-
-extern "C" int kzv_stream_step(kzv_model* m, int graph, void* stream) {
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "stream_step: call kzv_stream_begin first");
-    if (!stream_supported(m, m->sbeams ? m->sbeams : 1)) return kzv_fail(KZV_E_STATE, "stream_step: the geometry or the step mode changed since kzv_stream_begin");
-    hipStream_t s = (hipStream_t)stream;
-    if (!graph) return stream_step_body(m, s);
-    if (!stream) return kzv_fail(KZV_E_ARG, "stream_step: graph replay needs a non-default stream (stream capture)");
-    if (!m->sgraph) {                            // kzv_stream_begin dropped the last wave's: captured at the wave's first step
-        KZV_TRY(capture_into(&m->sgraph, s, "stream_step", [&] { return stream_step_body(m, s); }));
-    }
-    if (hipGraphLaunch(m->sgraph, s) != hipSuccess) return kzv_fail(KZV_E_HIP, "stream_step: launch");
-    return KZV_OK;
-}
-
-static int stream_poll(kzv_model* m, const char* who, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream) {
-    if (!m || !m->bound || !m->swave) return kzv_fail(KZV_E_STATE, "%s: call kzv_stream_begin first", who);
-    if (!finished || !steps) return kzv_fail(KZV_E_ARG, "%s: null result", who);
-    int32_t c[4] = {0, 0, 0, 0};
-    const int n = m->sbeams ? 4 : 3;
-    if (hipMemcpyAsync(c, m->sbeams ? m->sbst.counters : m->sst.counters, sizeof(int32_t) * n, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-        return kzv_fail(KZV_E_HIP, "%s: copy", who);
-    *finished = c[1]; *steps = c[2];
-    if (pad_tokens) *pad_tokens = c[3];
-    return KZV_OK;
-}
-
-extern "C" int kzv_stream_poll(kzv_model* m, int32_t* finished, int32_t* steps, void* stream) {
-    return stream_poll(m, "stream_poll", finished, steps, nullptr, stream);
-}
-
-extern "C" int kzv_stream_poll_beams(kzv_model* m, int32_t* finished, int32_t* steps, int32_t* pad_tokens, void* stream) {
-    if (m && m->bound && m->swave && !pad_tokens) return kzv_fail(KZV_E_ARG, "stream_poll_beams: null result");
-    return stream_poll(m, "stream_poll_beams", finished, steps, pad_tokens, stream);
 }

@@ -1,5 +1,5 @@
-// The model handle and what its three units share (model.cpp: table, plan, bind; model_train.cpp: forward / backward schedules;
-// model_decode.cpp: generation steps): the handle itself, one descriptor per Linear (Lin), the fragment-pack layout (DecPack),
+// The model handle and what its four units share (model.cpp: table, plan, bind; model_train.cpp: forward / backward schedules;
+// model_decode.cpp: lockstep generation steps; model_stream.cpp: slot-refill decoding): the handle itself, one descriptor per Linear (Lin), the fragment-pack layout (DecPack),
 // and the call helpers that take their shapes, weight copies and gradient destinations from a Lin instead of positional arguments.
 // Nothing declared here is part of the library's dynamic symbol table.
 #pragma once
@@ -61,6 +61,25 @@ struct DecPack {
     int64_t head_dense_t() const { return half + head_dense(); }
     int64_t head_t() const { return half + head(); }
     int64_t total() const { return 2 * half; }
+};
+
+// What the kzv_stream_set_* calls hand a wave of slot-refill decoding.  The initialisers are the neutral values and kzv_stream_begin
+// resets the whole by one assignment, so that no option leaks from one wave into the next.  (The n-best arrays live in the public
+// kzv_stream_beam_state and are reset beside that assignment; the host copy of the suppress mask lives beside sdiv, for its lifetime.)
+struct StreamWaveOpts {
+    // alternatives of a greedy wave (kzv_stream_set_topk): candidates per position (0: off) and the caller's arrays [n_images, ld_alt]
+    int topk = 0; int32_t* alt_ids = nullptr; float* alt_lp = nullptr; int64_t ld_alt = 0;
+    // generation controls (kzv_stream_set_controls): on only while a control is not neutral; whether kzv_model::smask holds a mask
+    bool ctl_on = false, mask_on = false;
+    kzv_logits_controls ctl = {0, /* repetition_penalty */ 1.f, 0, 0, nullptr};
+    // language-model fusion (kzv_stream_set_lm): on only while the weight is not zero; the struct is a copy, its tables are the
+    // caller's device memory
+    bool lm_on = false; float lm_weight = 0.f;
+    kzv_ngram_lm lm = {};
+    // forced prefixes (kzv_stream_set_prefix): on only while ld_prefix > 0; the tables are the caller's device memory
+    bool pfx_on = false;
+    const int64_t* pfx = nullptr; int64_t pfx_ld = 0; const int32_t* pfx_len = nullptr;
+    float* pfx_lp = nullptr; int64_t pfx_lp_ld = 0;
 };
 
 #pragma GCC visibility pop       // the handle's type is the C ABI's (include/kzv.h): default visibility, as ever
@@ -126,26 +145,14 @@ struct kzv_model_plain {
     // state and logits inside it, the wave in progress
     int spool_images = 0, sstate_slots = 0, sstate_V = 0;
     kzv_stream_state sst = {}; float* slogits = nullptr; bool swave = false;
-    // alternatives of a greedy wave (kzv_stream_set_topk): candidates per position (0: off) and the caller's arrays [n_images, sld_alt]
-    int stopk = 0; int32_t* salt_ids = nullptr; float* salt_lp = nullptr; int64_t sld_alt = 0;
-    // beam search on the slots (kzv_stream_begin_beams): beams per slot (0: the wave is greedy), the beam state, the ranking buffers, and
-    // the host copy of the divisor table, kept for as long as the asynchronous copy to the device may still read it (until the next begin)
+    // beam search on the slots (kzv_stream_begin_beams): beams per slot (0: the wave is greedy), the beam state, the ranking buffers
     int sbeams = 0;
     kzv_stream_beam_state sbst = {}; float* stop_lp = nullptr; int64_t* stop_ix = nullptr;
+    StreamWaveOpts sopt;         // what the kzv_stream_set_* calls gave the wave in progress
+    // the host copies of the divisor table and of the suppress mask, each kept for as long as the asynchronous copy to the device may
+    // still read it (until the next kzv_stream_begin_beams / kzv_stream_set_controls writes it again)
     std::vector<float> sdiv;
-    // generation controls of the wave (kzv_stream_set_controls): on only while a control is not neutral; the host copy of the suppress mask,
-    // kept like sdiv, and whether kzv_model::smask holds it
-    bool sctl_on = false, smask_on = false;
-    kzv_logits_controls sctl = {};
     std::vector<uint32_t> smask_h;
-    // language-model fusion of the wave (kzv_stream_set_lm): on only while the weight is not zero; the struct is a copy, its tables
-    // are the caller's device memory
-    bool slm_on = false; float slm_weight = 0.f;
-    kzv_ngram_lm slm = {};
-    // forced prefixes of the wave (kzv_stream_set_prefix): on only while ld_prefix > 0; the tables are the caller's device memory
-    bool spfx_on = false;
-    const int64_t* spfx = nullptr; int64_t spfx_ld = 0; const int32_t* spfx_len = nullptr;
-    float* spfx_lp = nullptr; int64_t spfx_lp_ld = 0;
     // fp8 weight path (kzv_set_fp8; BASELINE configs[4]): the encoder's QKV, fc1 and fc2 FORWARD GEMMs read e4m3 operands.
     // Weights: one e4m3 copy per matrix (Lin::q), quantised per output row from the fp32 master at kzv_model_sync_weights.  Activations:
     // LayerNorm writes an e4m3 copy of its output beside the bf16 one, quantised per token row (x8, x8_scale); the fc1 GELU
@@ -210,11 +217,36 @@ KZV_LOCAL bool dec_pack_wanted(const kzv_model* m);
 KZV_LOCAL int ensure_dec_pack(kzv_model* m, hipStream_t s);
 KZV_LOCAL int ensure_dec_pack8(kzv_model* m, hipStream_t s);      // the e4m3 stream, where the next cached step would read it
 KZV_LOCAL int decode_one_launch_mode(); // KZV_DECODE_ONE_LAUNCH / kzv_set_decode_one_launch (default on)
+KZV_LOCAL bool reserve(kzv_model* m, KzvDevBuf& buf, size_t bytes);      // false: the allocation failed; a buffer that moved drops the graphs
+KZV_LOCAL int ensure_kv_cache(kzv_model* m);
+KZV_LOCAL int build_dec_pack8(kzv_model* m, hipStream_t s);
+KZV_LOCAL int fused_common(kzv_model* m, KzvDecodeFused& a, bool e4m3, const char* who);
+KZV_LOCAL int vocab_logits(kzv_model* m, bool fold_ln, float* d_logits, hipStream_t s);
 
+// the captured step of a slot-refill wave holds the wave's outputs, counts and options: dropped when one of them changes
+static inline void drop_stream_graph(kzv_model* m) {
+    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }
+}
 // a captured decode step holds pointers into the workspace, the caches and the pack: dropped whenever one of them moves
 static inline void drop_decode_graphs(kzv_model* m) {
     for (int i = 0; i < 3; ++i) if (m->dgraph[i]) { (void)hipGraphExecDestroy(m->dgraph[i]); m->dgraph[i] = nullptr; }
-    if (m->sgraph) { (void)hipGraphExecDestroy(m->sgraph); m->sgraph = nullptr; }
+    drop_stream_graph(m);
+}
+
+// Captures what `body` launches on `s` into an instantiated graph: the capture is ended and the graph destroyed on every path; the
+// body's error comes back as it is, a failure of the capture itself as KZV_E_HIP
+template <typename Body>
+static int capture_into(hipGraphExec_t* out, hipStream_t s, const char* what, Body&& body) {
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kzv_fail(KZV_E_HIP, "%s: begin capture", what);
+    const int rc = body();
+    hipGraph_t graph = nullptr;
+    const hipError_t e = hipStreamEndCapture(s, &graph);
+    if (rc != KZV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess || !graph) return kzv_fail(KZV_E_HIP, "%s: end capture (%s)", what, hipGetErrorString(e));
+    const hipError_t ei = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ei != hipSuccess) { *out = nullptr; return kzv_fail(KZV_E_HIP, "%s: instantiate (%s)", what, hipGetErrorString(ei)); }
+    return KZV_OK;
 }
 
 // dropout site ids (distinct hash keys per call site and layer)

@@ -12,7 +12,9 @@ instances of the one-launch step; csrc/token_search.hip: selection and seating):
   4. more slots than compute units and idle slots: 300 slots for 310 images, 1 image on 6 slots, as many images as slots;
   5. several waves in one call equal one wave;
   6. the fallback: a 64-wide decoder, or the one-launch mode off, runs generate() and says so;
-  7. recognize_many on the fitted fixture against recognize(num_beams=1).
+  7. recognize_many on the fitted fixture against recognize(num_beams=1);
+  8. a wave given every option at once (controls + mask, language model, prefixes, alternatives / n-best) is followed on the same handle
+     by a wave given none, which equals a fresh handle's and launches no score node; the lockstep score nodes with group = 0.
 The decoder is the one-launch tests' (hidden 256, 4 heads, FFN 768, 3 layers) on the tiny encoder: Lh = 38.
 Observed on MI355X: kernel log-probabilities within 7.2e-7 of torch.log_softmax (1.4e-6 at 4,300 columns); with the EOS bias + 0.5 the engine's static decodes
 stop by EOS at columns 11 / 14 / 24 / 32 (8 keys, bf16; fewer distinct stops with e4m3 or 164 keys), 27 of 40 lines ending by EOS before
@@ -288,3 +290,68 @@ def test_recognize_many_on_the_fitted_fixture(tmp_path):
         worst = max(worst, abs(a["confidence"] - b["confidence"]))
     print(f"recognize_many against recognize(num_beams=1): largest confidence difference {worst:.3e}")
     assert worst <= LP_TOL
+
+
+# ---- 8. a wave's options end with the wave; the lockstep score nodes never read `group` ------------------------------------------------------
+def test_a_wave_with_every_option_leaves_nothing_to_the_next(decoder_dir):
+    """Wave 1 sets everything a wave can be given at once -- controls with a suppress mask, a 2-gram language model, 2-token prefixes,
+    and the top-2 alternatives (greedy) or the 2-best list (2 beams); wave 2 on the SAME handle sets nothing and must be the plain wave of
+    a fresh handle, ids and log-probabilities / scores ``torch.equal``, with none of the three score nodes launched.  6 images on 4 slots,
+    max_length 8: slots are reseated inside wave 1.  Then the lockstep kzv_logits_process / kzv_lm_fuse with group = 0 (never validated,
+    never divided by in that case) against group = 1."""
+    from kzv.lm import NGramLM
+    lib = L.load()
+    cfg = _cfg(8)
+
+    dec = build_decoder_dir(decoder_dir + "/opts", cfg)
+
+    def fresh():
+        m = TrOCRModel(cfg.encoder_config_dict(), dec, init_seed=7, load_tokenizer=False)
+        bias = m.state_dict_views()["decoder.lm_head.bias"]
+        bias[cfg.eos_id] += EOS_BIAS
+        bias[cfg.pad_id] -= 8.0                             # no running beam takes padding: the slots decode every beam wave themselves
+        m.eval()
+        return m
+    used, plain = fresh(), fresh()
+    px = torch.from_numpy(synthetic_batch(cfg, 6, LH, seed=3)[0]).cuda()
+    lm = NGramLM.fit([[cfg.bos_id, 5, 6, 7, 5, 6, cfg.eos_id], [cfg.bos_id, 6, 5, 9, cfg.eos_id]], 2, cfg.vocab)
+    everything = dict(no_repeat_ngram_size=2, repetition_penalty=1.2, suppress_tokens=[cfg.pad_id, 20, 40], lm=lm, lm_weight=1.5,
+                      prefix_ids=[[5 + i, 6 + i] for i in range(6)])
+    counters = (lib.kzv_test_logits_process_calls, lib.kzv_test_lm_fuse_calls, lib.kzv_test_force_prefix_calls)
+    for kw1, kw2 in ((dict(top_k=2), dict(return_logprobs=True)),
+                     (dict(num_beams=2, num_return_sequences=2, return_scores=True), dict(num_beams=2, return_scores=True))):
+        before = [c() for c in counters]
+        first = used.generate_stream(px, max_length=8, slots=4, **everything, **kw1)
+        assert all(c() > b for c, b in zip(counters, before)), "wave 1 did not run the three score nodes"
+        rows = first[0][0::2] if "num_beams" in kw1 else first[0]
+        assert all(rows[i, 1:3].tolist() == [5 + i, 6 + i] for i in range(6))      # the options were on: every line starts with its prefix
+        before = [c() for c in counters]
+        ids, sc = used.generate_stream(px, max_length=8, slots=4, **kw2)
+        assert [c() for c in counters] == before, "an option of wave 1 reached wave 2"
+        want_ids, want_sc = plain.generate_stream(px, max_length=8, slots=4, **kw2)
+        if "num_beams" in kw2:
+            assert used.stream_beam_impl == "slot-refill" and used.last_stream_pad_fallbacks == 0 and plain.last_stream_pad_fallbacks == 0
+        else:
+            assert used.stream_decode_impl == "slot-refill"
+        assert torch.equal(ids, want_ids) and torch.equal(sc, want_sc)
+    # lockstep: rows of scores with their own histories, group = 0 against group = 1
+    g = torch.Generator().manual_seed(5)
+    V, ld, R, T = cfg.vocab, cfg.vocab + 3, 5, 6
+    x = torch.randn(R, ld, generator=g).cuda()
+    hist = torch.randint(4, 12, (R, T), generator=g).cuda()
+    dlm = lm.to_device("cuda")
+    st = L.stream_handle()
+    out = {}
+    for group in (1, 0):
+        a, b = x.clone(), x.clone()
+        pa = L.kzv_logits_process_args(logits=a.data_ptr(), ld=ld, rows=R, vocab=V, ids=hist.data_ptr(), ld_ids=T, t=T - 2, group=group, slot_image=None,
+                                       slot_t=None, by_image=0, n_images=0, no_repeat_ngram_size=2, min_length=0, eos_id=cfg.eos_id, normalise=1,
+                                       repetition_penalty=1.3, reserved=0, suppress_mask=None)
+        fa = L.kzv_lm_fuse_args(logits=b.data_ptr(), ld=ld, rows=R, vocab=V, ids=hist.data_ptr(), ld_ids=T, t=T - 2, group=group, slot_image=None,
+                                slot_t=None, by_image=0, n_images=0, weight=0.7, reserved=0, lm=C.pointer(dlm.struct))
+        assert lib.kzv_logits_process(C.byref(pa), st) == 0, lib.kzv_last_error()
+        assert lib.kzv_lm_fuse(C.byref(fa), st) == 0, lib.kzv_last_error()
+        torch.cuda.synchronize()
+        out[group] = (a, b)
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+    assert not torch.equal(out[1][0], x) and not torch.equal(out[1][1], x)          # both nodes did edit the rows

@@ -1,4 +1,4 @@
-"""Proof that a source change left kernels alone: compiles the same .hip units of two trees with the Makefile's flags and compares
+"""Proof that a source change left kernels alone: compiles the same .hip units of two trees with the Makefile's flags (its per-unit overrides included: UNIT_FLAGS) and compares
 the gfx950 assembly kernel by kernel.
    python tools/isa_diff.py PARENT_CSRC [--new CSRC] [--units attention.hip gemm_nt256p.hip ...] [--cache DIR] [--show] [--strict]
                             [--rename REGEX REPLACEMENT] [--parent-units decode.hip ...]
@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kuzushiji-vision_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-ffp-contract=fast"]   # csrc/Makefile
+UNIT_FLAGS = {"lm_fusion.hip": ["-ffp-contract=off"]}      # csrc/Makefile's per-unit rules (build/lm_fusion.o: FLAGS += ...): appended, the last one wins
 META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count"]
 
 
@@ -26,7 +27,7 @@ def asm_of(unit, out):      # "<stem>-hip-amdgcn-amd-amdhsa-gfx950.s": the whole
 
 def compile_unit(csrc, unit, out):
     os.makedirs(out, exist_ok=True)
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "--save-temps=obj", "-c", unit, "-o", os.path.join(out, unit + ".o")], check=True, cwd=csrc)
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *UNIT_FLAGS.get(unit, []), "--save-temps=obj", "-c", unit, "-o", os.path.join(out, unit + ".o")], check=True, cwd=csrc)
     return asm_of(unit, out)[0]
 
 
