@@ -531,7 +531,8 @@ extern "C" int kzv_gemm_nt_fp8(const kzv_gemm_nt_fp8_args* a, int epilogue, void
     return kzv_check_launch("gemm_nt_fp8");
 }
 
-static int tn_fill(const kzv_gemm_tn_args* a, TnParams& p) {
+// validation of a kzv_gemm_tn call and its kernel parameter block (shared with the dgrad + wgrad pair launch of gemm_tn256.hip)
+int kzv_tn_params(const kzv_gemm_tn_args* a, TnParams& p) {
     if (!a || !a->P || !a->Q || !a->OUT) return kzv_fail(KZV_E_ARG, "gemm_tn: null operand");
     if (a->Mtok <= 0 || a->N <= 0 || a->K <= 0) return kzv_fail(KZV_E_ARG, "gemm_tn: empty shape");
     if (a->N % 8 || a->K % 8 || a->ldp % 8 || a->ldq % 8 || a->ldo % 4) return kzv_fail(KZV_E_ARG, "gemm_tn: N,K,ldp,ldq %8, ldo %4");
@@ -568,10 +569,12 @@ static int tn_target() {
 
 extern "C" int kzv_gemm_tn(const kzv_gemm_tn_args* a, void* stream) {
     TnParams p;
-    const int rc = tn_fill(a, p);
+    const int rc = kzv_tn_params(a, p);
     if (rc != KZV_OK) return rc;
     KzvProfScope prof(1, 2.0 * a->Mtok * p.n_store * a->K, (hipStream_t)stream);
-    if (kzv_tn256_launch(p, (hipStream_t)stream)) return kzv_check_launch("gemm_tn");     // >= 9 tiles of 256x256: eight-phase kernel
+    const int took = kzv_tn256_launch(p, (hipStream_t)stream);                            // >= 9 tiles of 256x256: eight-phase kernel
+    if (took < 0) return took;                                                            // a pending fold failed: its code and message
+    if (took) return kzv_check_launch("gemm_tn");
     const int blocks = tn_plan(p, tn_target());
     kzv_launch_lds<gemm_tn_kernel>(dim3(blocks), dim3(256), NT_LDS, (hipStream_t)stream, p);
     return kzv_check_launch("gemm_tn");
@@ -592,7 +595,7 @@ int kzv_gemm_tn_group(const kzv_gemm_tn_args* a, int n, hipStream_t s) {
     double work = 0;
     for (int i = 0; i < n; ++i) {
         TnParams p;
-        const int rc = tn_fill(a + i, p);
+        const int rc = kzv_tn_params(a + i, p);
         if (rc != KZV_OK) return rc;
         const int t256 = ((p.n_store + 255) / 256) * ((p.K + 255) / 256);
         if (t256 >= 24) { const int r2 = kzv_gemm_tn(a + i, s); if (r2 != KZV_OK) return r2; continue; }   // the eight-phase kernel's shapes

@@ -16,12 +16,23 @@ inline bool tn_dma_offsets_fit(const TnParams& p) {
 }
 
 // gemm_tn256.hip: returns 1 when it took the launch (p.splits / p.chunk are chosen inside), 0 when the shape is left
-// to the 128x128 kernel.
+// to the 128x128 kernel, < 0 = error (the fold of pending partial tiles it had to launch first failed: kzv_last_error has it).
 int kzv_tn256_launch(const TnParams& p, hipStream_t s);
+// gemm.hip: validation of a kzv_gemm_tn call and its kernel parameter block (splits / chunk are the launcher's)
+struct kzv_gemm_tn_args;
+int kzv_tn_params(const kzv_gemm_tn_args* a, TnParams& p);
 
 // While one of these is alive, kzv_tn256_launch leaves the fold of its partial tiles pending (each launch gets a workspace region of
-// its own, up to 5); the outermost scope's destructor folds all of them in ONE launch on `stream` (the launches must be on it too).
-struct KzvTnFoldScope { explicit KzvTnFoldScope(hipStream_t stream); ~KzvTnFoldScope(); hipStream_t s; };
+// its own, up to 5); closing the outermost scope folds all of them in ONE launch on `stream` (the launches must be on it too;
+// fold_queue.h).  close() returns that fold's code (KZV_OK for an inner scope); the destructor closes a scope nobody closed and drops
+// the code, which is for paths that already return an error.
+struct KzvTnFoldScope {
+    explicit KzvTnFoldScope(hipStream_t stream);
+    KzvTnFoldScope(const KzvTnFoldScope&) = delete;
+    ~KzvTnFoldScope() { (void)close(); }
+    int close();
+    hipStream_t s; bool closed = false;
+};
 
 // gemm_tn256.hip: a layer's input-gradient GEMM (kzv_gemm_nt arguments, one-store epilogue) and its weight-gradient GEMM (kzv_gemm_tn
 // arguments) as ONE launch when both take the 256x256 kernels: every workgroup runs its gemm_nt tiles and then a token range of one

@@ -30,6 +30,7 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "gemm_tn.h"
+#include "fold_queue.h"
 #include "gemm_nt.h"
 #include "gemm256_common.h"
 #include "gemm_nt256p_body.h"      // the persistent gemm_nt kernel's body: first phase of the dgrad + wgrad pair kernel below
@@ -504,37 +505,45 @@ __global__ __launch_bounds__(512) void gemm_pair_kernel(const NtParams pn, const
     tn256f_body(pt, part_ws + ((size_t)split * per + tile) * PART_FLOATS, tile / tilesK, tile % tilesK, (int)plan.t0[blockIdx.x] * 64, cnt, smem);
 }
 
-// OUT[n][k] += sum over splits of the partial tiles (4 columns per thread, one 1-KiB row segment per wave-instruction)
-__global__ __launch_bounds__(256) void gemm_tn256_fold_kernel(const float* part_ws, float* OUT, int64_t ldo, int n_store, int K,
-                                                             int tilesK, int per, int splits) {
-    const int tile = blockIdx.x >> 6;                                 // 64 workgroups per tile: 4 rows each
-    const int row = (blockIdx.x & 63) * 4 + (threadIdx.x >> 6), k4 = (threadIdx.x & 63) * 4;
-    const int tnb = tile / tilesK, tkb = tile - tnb * tilesK;
+// OUT[n][k] += sum over splits of the partial tiles (4 columns per thread, one 1-KiB row segment per wave-instruction); bid = the
+// workgroup's index among the 64 per tile of this output (block0 is the table-driven kernel's).  The entry comes by POINTER and the
+// index in the caller's type, for the two kernels' code objects: through a reference hipcc may load every field ahead of the bounds
+// check (the table-driven kernel then reads n_store / K / tilesK in one s_load_dwordx4 where it had three loads and an early exit),
+// and blockIdx.x >> 6 is a logical shift, (int) >> 6 an arithmetic one.
+struct TnFold { const float* ws; float* OUT; int64_t ldo; int n_store, K, tilesK, per, splits, block0; };
+template <class Bid>                     // unsigned (blockIdx.x itself) or int
+__device__ __forceinline__ void tn_fold_body(const TnFold* e, const Bid bid) {
+    const int tile = bid >> 6;                                        // 64 workgroups per tile: 4 rows each
+    const int row = (bid & 63) * 4 + (threadIdx.x >> 6), k4 = (threadIdx.x & 63) * 4;
+    const int tnb = tile / e->tilesK, tkb = tile - tnb * e->tilesK;
     const int gn = tnb * 256 + row, gk = tkb * 256 + k4;
-    if (gn >= n_store || gk >= K) return;                             // K % 4 == 0 (launcher): a 4-column group is all in or all out
+    if (gn >= e->n_store || gk >= e->K) return;                       // K % 4 == 0 (launcher): a 4-column group is all in or all out
     f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
 #ifndef KZV_TN_F32_PARTIALS
     typedef __attribute__((ext_vector_type(2))) unsigned u32x2p;
 #pragma unroll 4
-    for (int sp = 0; sp < splits; ++sp) {
-        const u32x2p u = __builtin_nontemporal_load((const u32x2p*)((const bf16_t*)(part_ws + ((size_t)sp * per + tile) * PART_FLOATS) + row * 256 + k4));
+    for (int sp = 0; sp < e->splits; ++sp) {
+        const u32x2p u = __builtin_nontemporal_load((const u32x2p*)((const bf16_t*)(e->ws + ((size_t)sp * e->per + tile) * PART_FLOATS) + row * 256 + k4));
         s[0] += bf2f((bf16_t)(u[0] & 0xffffu)); s[1] += bf2f((bf16_t)(u[0] >> 16)); s[2] += bf2f((bf16_t)(u[1] & 0xffffu)); s[3] += bf2f((bf16_t)(u[1] >> 16));
     }
 #else
-    const float* src = part_ws + ((size_t)tile * 256 + row) * 256 + k4;
+    const float* src = e->ws + ((size_t)tile * 256 + row) * 256 + k4;
 #pragma unroll 4
-    for (int sp = 0; sp < splits; ++sp) s += __builtin_nontemporal_load((const f32x4*)(src + (size_t)sp * per * PART_FLOATS));
+    for (int sp = 0; sp < e->splits; ++sp) s += __builtin_nontemporal_load((const f32x4*)(src + (size_t)sp * e->per * PART_FLOATS));
 #endif
-    f32x4* o = (f32x4*)(OUT + (int64_t)gn * ldo + gk);
+    f32x4* o = (f32x4*)(e->OUT + (int64_t)gn * e->ldo + gk);
     *o += s;
 }
+__global__ __launch_bounds__(256) void gemm_tn256_fold_kernel(const float* part_ws, float* OUT, int64_t ldo, int n_store, int K,
+                                                             int tilesK, int per, int splits) {
+    const TnFold e{part_ws, OUT, ldo, n_store, K, tilesK, per, splits, 0};
+    tn_fold_body(&e, blockIdx.x);
+}
 
-// Invariant of the deferred folds (KzvTnFoldScope, and KzvLnDeferScope in layernorm.hip): the pending lists are process-global and
-// unsynchronised -- ONE host thread issues the launches of a scope, on ONE stream (model.cpp's backward); a scope held open defers
-// every kzv_gemm_tn of the process.  Outputs inside a scope must be distinct (a repeated one is folded first, below).
 // Partial-tile workspace: TN_REGIONS regions of the largest size asked for so far (calls are stream-ordered; dev_buf.h).  Region 0
 // serves a launch whose fold follows at once; regions 1.. the launches of a KzvTnFoldScope (the four weight gradients of an encoder
-// layer), whose folds are ONE launch when the scope closes: a fold is ~5 us of launch latency + ~5 us of data, 49 times per step.
+// layer), whose folds are ONE launch when the scope closes (fold_queue.h): a fold is ~5 us of launch latency + ~5 us of data, 49
+// times per step.
 constexpr int TN_REGIONS = 6;
 KzvScratch g_tn_buf;
 size_t g_tn_region = 0;                  // floats per region
@@ -546,46 +555,32 @@ float* tn_partials(size_t floats, int region) {
     return base + (size_t)region * stride;
 }
 
-struct TnFold { const float* ws; float* OUT; int64_t ldo; int n_store, K, tilesK, per, splits, block0; };
 struct TnFoldTable { TnFold e[TN_REGIONS - 1]; int n; };
 // the folds of a scope in one launch: a block finds its entry by its index (entries hold 64 blocks per output tile)
 __global__ __launch_bounds__(256) void gemm_tn256_fold_multi_kernel(const TnFoldTable t) {
     int k = 0;
     while (k + 1 < t.n && (int)blockIdx.x >= t.e[k + 1].block0) ++k;
     const TnFold& e = t.e[k];
-    const int bid = blockIdx.x - e.block0;
-    const int tile = bid >> 6;
-    const int row = (bid & 63) * 4 + (threadIdx.x >> 6), k4 = (threadIdx.x & 63) * 4;
-    const int tnb = tile / e.tilesK, tkb = tile - tnb * e.tilesK;
-    const int gn = tnb * 256 + row, gk = tkb * 256 + k4;
-    if (gn >= e.n_store || gk >= e.K) return;
-    f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifndef KZV_TN_F32_PARTIALS
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2p;
-#pragma unroll 4
-    for (int sp = 0; sp < e.splits; ++sp) {
-        const u32x2p u = __builtin_nontemporal_load((const u32x2p*)((const bf16_t*)(e.ws + ((size_t)sp * e.per + tile) * PART_FLOATS) + row * 256 + k4));
-        s[0] += bf2f((bf16_t)(u[0] & 0xffffu)); s[1] += bf2f((bf16_t)(u[0] >> 16)); s[2] += bf2f((bf16_t)(u[1] & 0xffffu)); s[3] += bf2f((bf16_t)(u[1] >> 16));
-    }
-#else
-    const float* src = e.ws + ((size_t)tile * 256 + row) * 256 + k4;
-#pragma unroll 4
-    for (int sp = 0; sp < e.splits; ++sp) s += __builtin_nontemporal_load((const f32x4*)(src + (size_t)sp * e.per * PART_FLOATS));
-#endif
-    f32x4* o = (f32x4*)(e.OUT + (int64_t)gn * e.ldo + gk);
-    *o += s;
+    tn_fold_body(&e, (int)(blockIdx.x - e.block0));
 }
-int g_tn_defer = 0;
-std::vector<TnFold> g_tn_pending;
-int tn_flush(hipStream_t s) {
-    if (g_tn_pending.empty()) return KZV_OK;
+int tn_fold_pending(const TnFold* e, int n, void* stream) {
     TnFoldTable t;
     int blocks = 0;
-    for (size_t i = 0; i < g_tn_pending.size(); ++i) { t.e[i] = g_tn_pending[i]; t.e[i].block0 = blocks; blocks += g_tn_pending[i].per * 64; }
-    t.n = (int)g_tn_pending.size();
-    hipLaunchKernelGGL(gemm_tn256_fold_multi_kernel, dim3(blocks), dim3(256), 0, s, t);
-    g_tn_pending.clear();
+    for (int i = 0; i < n; ++i) { t.e[i] = e[i]; t.e[i].block0 = blocks; blocks += e[i].per * 64; }
+    t.n = n;
+    hipLaunchKernelGGL(gemm_tn256_fold_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t);
     return kzv_check_launch("gemm_tn256_fold");
+}
+KzvFoldQueue<TnFold, TN_REGIONS> g_tn_folds(tn_fold_pending);
+static_assert(sizeof(TnFoldTable::e) / sizeof(TnFold) == decltype(g_tn_folds)::CAPACITY, "the fold table holds what the queue can hold");
+// The workspace of a launch that needs `need` floats into OUT: region 0 when its fold follows at once, else (*deferred) a region of its
+// own.  What is pending is folded first when the queue says so or the workspace is about to be re-allocated; *rc is that fold's code.
+// nullptr: the fold or the allocation failed.
+float* tn_claim(size_t need, const float* OUT, hipStream_t s, bool* deferred, int* rc) {
+    int region;
+    *rc = g_tn_folds.claim([=](const TnFold& e) { return e.OUT == OUT; }, need > g_tn_region, s, &region);
+    *deferred = region > 0;
+    return *rc == KZV_OK ? tn_partials(need, region) : nullptr;
 }
 
 // stage schedule: 0 = eight-phase ping-pong (gemm_tn256_kernel), 1 = free-running (gemm_tn256f_kernel); kzv_set_tn_schedule / KZV_TN_FREE
@@ -623,18 +618,13 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     p.splits = splits; p.chunk = chunk_tiles * 64;
     if (p.K % 4 || p.ldo % 4 || ((uintptr_t)p.OUT & 15)) return 0;
     const size_t need = (size_t)tiles * splits * PART_FLOATS;
-    const bool deferred = g_tn_defer > 0;
-    bool same_out = false;                       // a second gradient into the SAME output inside one scope: the single fold launch adds every
-    for (const TnFold& e : g_tn_pending) same_out |= e.OUT == p.OUT;      // entry with a plain read-modify-write, so the two would race
-    if (deferred && ((int)g_tn_pending.size() == TN_REGIONS - 1 || need > g_tn_region || same_out)) {
-        if (tn_flush(s) != KZV_OK) return 0;     // no free region, the workspace is about to be re-allocated, or a repeated output: fold what is pending first
-    }
-    float* ws = tn_partials(need, deferred ? 1 + (int)g_tn_pending.size() : 0);
-    if (!ws) return 0;
+    bool deferred; int rc;
+    float* ws = tn_claim(need, p.OUT, s, &deferred, &rc);
+    if (!ws) return rc;                          // the pending folds' error, or 0: no workspace, not taken
     if (tn_schedule()) kzv_launch_lds<gemm_tn256f_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
     else kzv_launch_lds<gemm_tn256_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
     if (deferred) {
-        g_tn_pending.push_back(TnFold{ws, p.OUT, p.ldo, p.n_store, p.K, (p.K + 255) / 256, tiles, splits, 0});
+        g_tn_folds.push(TnFold{ws, p.OUT, p.ldo, p.n_store, p.K, (p.K + 255) / 256, tiles, splits, 0});
         return 1;
     }
     hipLaunchKernelGGL(gemm_tn256_fold_kernel, dim3(tiles * 64), dim3(256), 0, s, ws, p.OUT, p.ldo, p.n_store, p.K,
@@ -642,7 +632,7 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     return 1;
 }
 
-// gemm.hip: the parameter block of a kzv_gemm_nt call (validated there)
+// gemm.hip: the parameter block of a kzv_gemm_nt call (validated there; kzv_tn_params, its kzv_gemm_tn twin: gemm_tn.h)
 int kzv_nt_params(const kzv_gemm_nt_args* a, int epilogue, NtParams* out);
 
 namespace {
@@ -677,15 +667,11 @@ int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gem
     if (!nt_dma_offsets_fit(pn, 2)) return 0;
     // ... and of kzv_tn256_launch
     TnParams pt{};
-    pt.P = (const bf16_t*)ta->P; pt.Q = (const bf16_t*)ta->Q; pt.OUT = ta->OUT; pt.zero16 = kzv_zero_page();
-    pt.ldp = ta->ldp; pt.ldq = ta->ldq; pt.ldo = ta->ldo; pt.Mtok = ta->Mtok; pt.N = ta->N; pt.K = ta->K;
-    pt.n_store = ta->n_store > 0 ? ta->n_store : ta->N; pt.dbias = ta->dbias;
-    if (!pt.P || !pt.Q || !pt.OUT || !pt.zero16) return 0;
+    if (kzv_tn_params(ta, pt) != KZV_OK) return 0;
     const int tilesKw = (pt.K + 255) / 256, tilesNw = (pt.N + 255) / 256, per = tilesNw * tilesKw;
     const int stages = pt.Mtok / 64;
-    if (per < tn256_min_tiles() || per > 128 || pt.Mtok % 64 || pt.N < 8 || pt.K < 8 || pt.N % 8 || pt.K % 8) return 0;
+    if (per < tn256_min_tiles() || per > 128 || pt.Mtok % 64) return 0;      // (sizes, strides and alignment: kzv_tn_params)
     if (!tn_dma_offsets_fit(pt)) return 0;
-    if (pt.K % 4 || pt.ldo % 4 || ((uintptr_t)pt.OUT & 15) || ((uintptr_t)pt.P & 15) || ((uintptr_t)pt.Q & 15) || pt.ldp % 8 || pt.ldq % 8) return 0;
     const int G = 256, S = G / per;
     if (S < 1 || stages < 8 * S || stages > 65000) return 0;
     // ---- the plan ----
@@ -728,16 +714,9 @@ int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gem
         plan.tile[b] = (unsigned short)tl; plan.split[b] = (unsigned short)sp; plan.t0[b] = (unsigned short)t0[gi]; plan.cnt[b] = (unsigned short)cnt[gi];
     }
     pt.splits = S; pt.chunk = 0;
-    // ---- workspace / fold bookkeeping of kzv_tn256_launch ----
-    const size_t need = (size_t)per * S * PART_FLOATS;
-    const bool deferred = g_tn_defer > 0;
-    bool same_out = false;
-    for (const TnFold& e : g_tn_pending) same_out |= e.OUT == pt.OUT;
-    if (deferred && ((int)g_tn_pending.size() == TN_REGIONS - 1 || need > g_tn_region || same_out)) {
-        if (tn_flush(s) != KZV_OK) return 0;
-    }
-    float* ws = tn_partials(need, deferred ? 1 + (int)g_tn_pending.size() : 0);
-    if (!ws) return 0;
+    bool deferred; int rc;
+    float* ws = tn_claim((size_t)per * S * PART_FLOATS, pt.OUT, s, &deferred, &rc);
+    if (!ws) return rc;                          // the pending folds' error, or 0: no workspace, not taken
     KzvProfScope prof(5, 2.0 * pn.M * pn.n_valid * pn.K + 2.0 * pt.Mtok * pt.N * pt.K, s);
 #define KZV_PAIR_CASE(E) case E: kzv_launch_lds<gemm_pair_kernel<E>>(dim3(G), dim3(512), NT256P_LDS_BYTES, s, pn, tiles, tilesN, kzv_nt_strip(), pt, ws, per, plan); break;
     switch (epilogue) {
@@ -745,7 +724,7 @@ int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gem
         default: return 0;
     }
 #undef KZV_PAIR_CASE
-    if (deferred) g_tn_pending.push_back(TnFold{ws, pt.OUT, pt.ldo, pt.n_store, pt.K, tilesKw, per, S, 0});
+    if (deferred) g_tn_folds.push(TnFold{ws, pt.OUT, pt.ldo, pt.n_store, pt.K, tilesKw, per, S, 0});
     else hipLaunchKernelGGL(gemm_tn256_fold_kernel, dim3(per * 64), dim3(256), 0, s, ws, pt.OUT, pt.ldo, pt.n_store, pt.K, tilesKw, per, S);
     return kzv_check_launch("gemm_pair") == KZV_OK ? 1 : -1;
 }
@@ -761,5 +740,5 @@ extern "C" int kzv_gemm_dgrad_wgrad(const kzv_gemm_nt_args* na, int epilogue, co
 }
 extern "C" int kzv_set_tn_schedule(int n) { g_tn_schedule = n < 0 ? -1 : (n != 0); return KZV_OK; }
 
-KzvTnFoldScope::KzvTnFoldScope(hipStream_t stream) : s(stream) { ++g_tn_defer; }
-KzvTnFoldScope::~KzvTnFoldScope() { if (--g_tn_defer == 0) (void)tn_flush(s); }
+KzvTnFoldScope::KzvTnFoldScope(hipStream_t stream) : s(stream) { g_tn_folds.open(); }
+int KzvTnFoldScope::close() { if (closed) return KZV_OK; closed = true; return g_tn_folds.close(s); }

@@ -21,9 +21,16 @@ int kzv_ln_bwd_ex(const void* dy, int dy_is_f32, const float* x, const float* st
                   uint32_t out_drop_key = 0, const KzvLnBwdF8* f8 = nullptr);
 
 // While one of these is alive, kzv_ln_bwd_ex leaves the fold of its gamma / beta partial sums pending (each call gets a partial
-// region of its own); the outermost scope's destructor folds all of them in ONE launch on `stream`.  Without a scope every call
-// folds at once (the per-op C ABI).
-struct KzvLnDeferScope { explicit KzvLnDeferScope(hipStream_t stream); ~KzvLnDeferScope(); hipStream_t s; };
+// region of its own); closing the outermost scope folds all of them in ONE launch on `stream` (fold_queue.h).  Without a scope every
+// call folds at once (the per-op C ABI).  close() returns that fold's code (KZV_OK for an inner scope); the destructor closes a scope
+// nobody closed and drops the code, which is for paths that already return an error.
+struct KzvLnDeferScope {
+    explicit KzvLnDeferScope(hipStream_t stream);
+    KzvLnDeferScope(const KzvLnDeferScope&) = delete;
+    ~KzvLnDeferScope() { (void)close(); }
+    int close();
+    hipStream_t s; bool closed = false;
+};
 
 // for kernels that fuse a LayerNorm backward (decoder_chain_bwd.hip): see layernorm.hip
 constexpr int KZV_LN_SLOTS = 32;

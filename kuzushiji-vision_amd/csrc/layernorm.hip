@@ -15,8 +15,8 @@
 #include "../../include/kzv.h"
 #include "kzv_host.h"
 #include "kzv_kernels.h"
+#include "fold_queue.h"
 #include <mutex>
-#include <vector>
 #include <algorithm>
 
 #define KZV_LN_TRY(expr) do { int rc__ = (expr); if (rc__ != KZV_OK) return rc__; } while (0)
@@ -314,37 +314,8 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const LnBwd p) {
 }
 
 // dgamma / dbeta += sum over the LN_SLOTS partial rows; the partials are left zeroed for the next call.
-__global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(float* partial, float* dgamma, float* dbeta, int H) {
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    if (col >= 2 * H) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < LN_SLOTS; ++k) { s += partial[(size_t)k * 2 * H + col]; partial[(size_t)k * 2 * H + col] = 0.f; }
-    float* out = col < H ? dgamma + col : dbeta + (col - H);
-    *out += s;
-}
-
-// LN_REGIONS zeroed [LN_SLOTS][2][2048] partial-sum regions per process (calls are stream-ordered).  Region 0 serves a call whose
-// fold follows at once; regions 1.. serve the calls of a KzvLnDeferScope (a whole backward pass), whose folds are ONE launch at the
-// end of the scope: a fold is 4.9 us of launch latency for 6 KB of work, 45 times per training step.
-constexpr int LN_REGIONS = 64;
-constexpr size_t LN_REGION_FLOATS = (size_t)LN_SLOTS * 2 * MAXC * 256;
-float* ln_partials() {
-    static float* buf = nullptr;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        void* q = nullptr;
-        const size_t bytes = LN_REGIONS * LN_REGION_FLOATS * sizeof(float);
-        if (hipMalloc(&q, bytes) == hipSuccess && hipMemset(q, 0, bytes) == hipSuccess) buf = (float*)q;
-    });
-    return buf;
-}
-
 struct LnFold { float* partial; float* dgamma; float* dbeta; int H; };
-struct LnFoldTable { LnFold e[LN_REGIONS - 1]; };
-// the folds of a scope in one launch: blockIdx.y = entry
-__global__ __launch_bounds__(256) void ln_bwd_reduce_multi_kernel(const LnFoldTable t) {
-    const LnFold& e = t.e[blockIdx.y];
+__device__ __forceinline__ void ln_fold_body(const LnFold& e) {
     const int col = blockIdx.x * 256 + threadIdx.x;
     if (col >= 2 * e.H) return;
     float s = 0.f;
@@ -353,16 +324,43 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_multi_kernel(const LnFoldTa
     float* out = col < e.H ? e.dgamma + col : e.dbeta + (col - e.H);
     *out += s;
 }
-int g_ln_defer = 0;
-std::vector<LnFold> g_ln_pending;
-int ln_flush(hipStream_t s) {
-    if (g_ln_pending.empty()) return KZV_OK;
+__global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(float* partial, float* dgamma, float* dbeta, int H) {
+    ln_fold_body(LnFold{partial, dgamma, dbeta, H});
+}
+
+// LN_REGIONS zeroed [LN_SLOTS][2][2048] partial-sum regions per process (calls are stream-ordered).  Region 0 serves a call whose
+// fold follows at once; regions 1.. serve the calls of a KzvLnDeferScope (a whole backward pass), whose folds are ONE launch at the
+// end of the scope (fold_queue.h): a fold is 4.9 us of launch latency for 6 KB of work, 45 times per training step.
+constexpr int LN_REGIONS = 64;
+constexpr size_t LN_REGION_FLOATS = (size_t)LN_SLOTS * 2 * MAXC * 256;
+float* ln_partials() {
+    static float* buf = nullptr;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        void* q = nullptr;
+        const size_t bytes = LN_REGIONS * LN_REGION_FLOATS * sizeof(float);
+        if (kzv_dev_alloc(&q, bytes) == 0 && hipMemset(q, 0, bytes) == hipSuccess) buf = (float*)q;
+    });
+    return buf;
+}
+
+struct LnFoldTable { LnFold e[LN_REGIONS - 1]; };
+// the folds of a scope in one launch: blockIdx.y = entry
+__global__ __launch_bounds__(256) void ln_bwd_reduce_multi_kernel(const LnFoldTable t) {
+    ln_fold_body(t.e[blockIdx.y]);
+}
+int ln_fold_pending(const LnFold* e, int n, void* stream) {
     LnFoldTable t;
     int hmax = 0;
-    for (size_t i = 0; i < g_ln_pending.size(); ++i) { t.e[i] = g_ln_pending[i]; hmax = std::max(hmax, g_ln_pending[i].H); }
-    hipLaunchKernelGGL(ln_bwd_reduce_multi_kernel, dim3((2 * hmax + 255) / 256, (unsigned)g_ln_pending.size()), dim3(256), 0, s, t);
-    g_ln_pending.clear();
+    for (int i = 0; i < n; ++i) { t.e[i] = e[i]; hmax = std::max(hmax, e[i].H); }
+    hipLaunchKernelGGL(ln_bwd_reduce_multi_kernel, dim3((2 * hmax + 255) / 256, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t);
     return kzv_check_launch("layernorm_bwd_fold");
+}
+KzvFoldQueue<LnFold, LN_REGIONS> g_ln_folds(ln_fold_pending);
+static_assert(sizeof(LnFoldTable::e) / sizeof(LnFold) == decltype(g_ln_folds)::CAPACITY, "the fold table holds what the queue can hold");
+// claims the partial region of a backward into dgamma / dbeta: *region >= 1 when its fold is left to the open scope
+int ln_claim(float* dgamma, float* dbeta, hipStream_t s, int* region) {
+    return g_ln_folds.claim([=](const LnFold& e) { return e.dgamma == dgamma || e.dbeta == dbeta; }, false, s, region);
 }
 
 }  // namespace
@@ -408,13 +406,10 @@ int kzv_ln_bwd_ex(const void* dy, int dy_is_f32, const float* x, const float* st
     const size_t lds = 8 * H * sizeof(float);
     p.partial = ln_partials();
     if (!p.partial) return kzv_fail(KZV_E_HIP, "layernorm_bwd: partial-sum buffer unavailable");
-    const bool deferred = g_ln_defer > 0;
-    if (deferred) {                                  // a region of its own until the scope's fold
-        bool same_out = false;                       // the single fold launch adds every entry with a plain `*out += s`: a LayerNorm that
-        for (const LnFold& e : g_ln_pending) same_out |= e.dgamma == dgamma || e.dbeta == dbeta;      // appears twice in a scope is folded first
-        if ((int)g_ln_pending.size() == LN_REGIONS - 1 || same_out) KZV_LN_TRY(ln_flush(s));
-        p.partial += (1 + g_ln_pending.size()) * LN_REGION_FLOATS;
-    }
+    int region;                                      // inside a scope: a region of its own until the scope's fold
+    KZV_LN_TRY(ln_claim(dgamma, dbeta, s, &region));
+    const bool deferred = region > 0;
+    p.partial += region * LN_REGION_FLOATS;
     const bool fast = H == ncl * 256 && ncl <= 4;
 #define KZV_LN_FAST2(NC, A, B)                                                                                 \
     do { if (f8) hipLaunchKernelGGL((ln_bwd_fast_kernel<NC, A, B, true>), grid, dim3(256), lds, s, p);          \
@@ -435,7 +430,7 @@ int kzv_ln_bwd_ex(const void* dy, int dy_is_f32, const float* x, const float* st
     else hipLaunchKernelGGL(ln_bwd_kernel<8>, grid, dim3(256), lds, s, p);
 #undef KZV_LN_FAST
 #undef KZV_LN_FAST2
-    if (deferred) { g_ln_pending.push_back(LnFold{p.partial, dgamma, dbeta, H}); return kzv_check_launch("layernorm_bwd"); }
+    if (deferred) { g_ln_folds.push(LnFold{p.partial, dgamma, dbeta, H}); return kzv_check_launch("layernorm_bwd"); }
     hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * H + 255) / 256), dim3(256), 0, s, p.partial, dgamma, dbeta, H);
     return kzv_check_launch("layernorm_bwd");
 }
@@ -448,14 +443,11 @@ static_assert(LN_SLOTS == KZV_LN_SLOTS, "kzv_kernels.h: KZV_LN_SLOTS");
 float* kzv_ln_partial_region(float* dgamma, float* dbeta, int H, hipStream_t s, bool* fold_now) {
     float* partial = ln_partials();
     if (!partial || !dgamma || !dbeta || H % 4 || H > MAXC * 256) { (void)kzv_fail(KZV_E_ARG, "layernorm partial region: bad argument or no buffer"); return nullptr; }
-    *fold_now = g_ln_defer <= 0;
-    if (g_ln_defer > 0) {
-        bool same_out = false;
-        for (const LnFold& e : g_ln_pending) same_out |= e.dgamma == dgamma || e.dbeta == dbeta;
-        if (((int)g_ln_pending.size() == LN_REGIONS - 1 || same_out) && ln_flush(s) != KZV_OK) return nullptr;
-        partial += (1 + g_ln_pending.size()) * LN_REGION_FLOATS;
-        g_ln_pending.push_back(LnFold{partial, dgamma, dbeta, H});
-    }
+    int region;
+    if (ln_claim(dgamma, dbeta, s, &region) != KZV_OK) return nullptr;
+    partial += region * LN_REGION_FLOATS;
+    *fold_now = region == 0;
+    if (region > 0) g_ln_folds.push(LnFold{partial, dgamma, dbeta, H});
     return partial;
 }
 int kzv_ln_partial_fold(float* partial, float* dgamma, float* dbeta, int H, hipStream_t s) {
@@ -463,8 +455,8 @@ int kzv_ln_partial_fold(float* partial, float* dgamma, float* dbeta, int H, hipS
     return kzv_check_launch("layernorm_bwd_fold");
 }
 
-KzvLnDeferScope::KzvLnDeferScope(hipStream_t stream) : s(stream) { ++g_ln_defer; }
-KzvLnDeferScope::~KzvLnDeferScope() { if (--g_ln_defer == 0) (void)ln_flush(s); }
+KzvLnDeferScope::KzvLnDeferScope(hipStream_t stream) : s(stream) { g_ln_folds.open(); }
+int KzvLnDeferScope::close() { if (closed) return KZV_OK; closed = true; return g_ln_folds.close(s); }
 
 extern "C" int kzv_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y_bf16, float* y_f32,
                                  float* stats, int rows, int H, float eps, void* stream) {

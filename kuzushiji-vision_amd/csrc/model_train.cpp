@@ -8,6 +8,7 @@
 #include "model_internal.h"
 #include <algorithm>
 #include <cmath>
+#include <optional>
 
 // decoder_chain.hip: the linear chains of a decoder layer as two launches (KZV_DEC_CHAIN, kzv_set_dec_chain): 0 = off, 1 = the forward
 // chains (+ the 256 x 256 input gradients on the row-panel kernel), 2 (default) = also the backward's row-local segments, one launch each
@@ -503,7 +504,8 @@ int backward_enc_layer(kzv_model* m, int i, hipStream_t s) {
     // the layer below (LN1; layer 0 hands fp32 dx_e to the embedding backward)
     const uint32_t key_o = key(m, SITE_ENC_L + 4 * i + 1), key_fc2_below = key(m, SITE_ENC_L + 4 * (i - 1) + 2);
     // the layer's four weight-gradient GEMMs fold their partial tiles in one launch at the end of the layer (one stream only)
-    struct TnFolds { KzvTnFoldScope* sc; ~TnFolds() { delete sc; } } tn_folds{m->use_side ? nullptr : new KzvTnFoldScope(s)};
+    std::optional<KzvTnFoldScope> tn_folds;
+    if (!m->use_side) tn_folds.emplace(s);
     if (m->side_mode == 2) {
         // Overlap mode 2: the four weight-gradient GEMMs (MFMA-bound, 710 us per layer) run on the side stream ONLY while
         // the caller's stream runs an HBM- or issue-bound kernel (LayerNorm backward x2, attention backward: 344 us per
@@ -526,7 +528,7 @@ int backward_enc_layer(kzv_model* m, int i, hipStream_t s) {
         KZV_TRY(lin_wgrad(m, e.qkv, CLS_DQKV, s, m->dqkv_e, 3 * He, a.ln1, He, Me));
         KZV_TRY(ln_bwd(m, m->dh_e, 0, a.x_in, a.st1, e.ln1w, e.ln1b, m->dx_e, 1, Me, He, s,
                        {.out16 = i > 0 ? m->dy_e : nullptr, .out_drop_p = hp, .out_drop_key = key_fc2_below}));
-        return KZV_OK;
+        return tn_folds ? tn_folds->close() : KZV_OK;
     }
     // x_out = x_mid + drop(fc2(gelu(fc1(LN2(x_mid)))))
     // on entry dy_e = dropout-masked bf16 copy of dx_e for this layer's fc2 site (written by the LN backward above it)
@@ -556,7 +558,7 @@ int backward_enc_layer(kzv_model* m, int i, hipStream_t s) {
     const KzvLnBwdF8 f8n{m->dy8, m->dy8_scale, m->dy8_rq, m->dy8_rqinv, (m->f8_wnorm && i > 0) ? m->f8_wnorm + (i - 1) : nullptr};
     KZV_TRY(ln_bwd(m, m->dh_e, 0, a.x_in, a.st1, e.ln1w, e.ln1b, m->dx_e, 1, Me, He, s,
                    {.out16 = i > 0 ? m->dy_e : nullptr, .out_drop_p = hp, .out_drop_key = key_fc2_below, .f8 = (f8g && i > 0) ? &f8n : nullptr}));
-    return KZV_OK;
+    return tn_folds ? tn_folds->close() : KZV_OK;
 }
 
 int backward_embed(kzv_model* m, hipStream_t s) {
@@ -670,6 +672,8 @@ extern "C" int kzv_backward_segment(kzv_model* m, int seg, void* stream) {
         if (seg == 0) rc = backward_decoder(m, s);              // kzv_backward: when ITS scope closes, once per backward pass)
         else if (seg <= m->Le) rc = backward_enc_layer(m, m->Le - seg, s);
         else rc = backward_embed(m, s);
+        const int folds = ln_folds.close();
+        if (rc == KZV_OK) rc = folds;
     }
     if (rc != KZV_OK) return rc;
     // contract: in `stream` order, this segment's gradient range is final -> the side stream must be joined
@@ -686,6 +690,8 @@ extern "C" int kzv_backward(kzv_model* m, void* stream) {
     {
         KzvLnDeferScope ln_folds((hipStream_t)stream);
         for (int sgm = 0; sgm < n && rc == KZV_OK; ++sgm) rc = kzv_backward_segment(m, sgm, stream);
+        const int folds = ln_folds.close();
+        if (rc == KZV_OK) rc = folds;
     }
     m->join_each_segment = true;
     if (rc != KZV_OK) (void)join_side(m, (hipStream_t)stream);
