@@ -781,6 +781,33 @@ int kzv_gemm_tn(const kzv_gemm_tn_args* a, void* stream);
 int kzv_gemm_dgrad_wgrad(const kzv_gemm_nt_args* nt, int epilogue, const kzv_gemm_tn_args* tn, void* stream);
 int kzv_set_pair(int on);
 
+/* What would run a kzv_gemm_nt / kzv_gemm_tn call, without running it (in the spirit of kzv_attn_impl_ex): the kernel and its launch
+ * geometry under the switches in force (the kzv_set_* above, the KZV_* environment, kzv_set_cu_reserve).  The same host function
+ * decides for the launching entries (csrc/gemm_plan.h).  The arguments are validated exactly as kzv_gemm_nt / kzv_gemm_tn validate
+ * them (same codes, same kzv_last_error text); no memory is read and no device is touched when cus > 0.
+ * in_rows_scope: answer for a call from inside the generation step (few-rows kernel up to M = 4096).  cus: compute units to plan
+ * for; <= 0 = the current device's.  A KZV_GEMM_TN256* plan still needs a workspace at launch: without one the call runs TN128. */
+enum { KZV_GEMM_ROWS = 0,        /* gemm_rows.hip: one wave per 16x64 tile (grid x grid_y) */
+       KZV_GEMM_NT256H = 1,      /* gemm_nt256h.hip: four waves, 256x128 tiles, persistent */
+       KZV_GEMM_NT256F = 2,      /* gemm_nt256f.hip: 256x256 tiles, persistent, free-running K loop */
+       KZV_GEMM_NT256P = 3,      /* gemm_nt256p.hip: 256x256 tiles, persistent, eight-phase K loop */
+       KZV_GEMM_NT256 = 4,       /* gemm_nt256.hip: one 256x256 tile per workgroup */
+       KZV_GEMM_NT128 = 5,       /* gemm.hip: one 128x128 tile per workgroup */
+       KZV_GEMM_NT256P_F8 = 6,   /* gemm_nt256p.hip on e4m3 operands (kzv_gemm_nt_fp8; never a kzv_gemm_nt_plan answer) */
+       KZV_GEMM_TN256F = 7,      /* gemm_tn256.hip: 256x256 tiles x token splits, free-running stages */
+       KZV_GEMM_TN256 = 8,       /* gemm_tn256.hip: the same on the eight-phase schedule */
+       KZV_GEMM_TN128 = 9        /* gemm.hip: 128x128 tiles x token splits, atomics epilogue */ };
+typedef struct kzv_gemm_plan_info {
+    int32_t kernel;               /* KZV_GEMM_* */
+    int32_t grid, grid_y, block;  /* workgroups (x, y) and threads per workgroup */
+    int32_t tiles;                /* output tiles of the kernel's tile shape */
+    int32_t splits, chunk;        /* gemm_tn: token splits and tokens per split; gemm_nt: 0 */
+    int32_t pair;                 /* 1: as one half of a kzv_gemm_dgrad_wgrad call this call meets its half of the one-launch form's
+                                   * conditions (kzv_set_pair, shapes); when both halves say 1 the two run as ONE launch instead */
+} kzv_gemm_plan_info;
+int kzv_gemm_nt_plan(const kzv_gemm_nt_args* a, int epilogue, int in_rows_scope, int cus, kzv_gemm_plan_info* out);
+int kzv_gemm_tn_plan(const kzv_gemm_tn_args* a, int cus, kzv_gemm_plan_info* out);
+
 /* The same two products on fp32 OPERANDS (A, B, P, Q are float; leading dimensions in elements, multiples of 4; K % 32 == 0 for
  * the NT form), on the f32-input matrix instruction: exact fp32 products, fp32 accumulation (csrc/gemm_f32.hip).  For the model of
  * ocr_lightning/model.py, which the reference trains in fp32 (ocr_lightning/train.py:132-140; its own test wants singles ==

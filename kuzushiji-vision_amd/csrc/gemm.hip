@@ -3,9 +3,9 @@
 //  gemm_nt : C[M,N]  = A[M,K] . B[N,K]^T  (+ fused epilogue)   -- every nn.Linear forward and dgrad
 //  gemm_tn : O[N,K] += P[Mt,N]^T . Q[Mt,K]                      -- every weight gradient
 //
-// kzv_gemm_nt / kzv_gemm_tn first offer the shape to the 256x256 eight-phase kernels (gemm_nt256p.hip, gemm_nt256.hip,
-// gemm_tn256.hip: every large GEMM of a ViT layer); what they decline -- the decoder's small GEMMs, K < 128, odd shapes --
-// runs on the kernels in this file: 128x128 output tile per 256-thread workgroup (4 waves, 2x2, 64x64 per wave = 4x4
+// kzv_gemm_nt / kzv_gemm_tn validate, ask gemm_plan.h which kernel runs the shape on what grid, and launch that plan.  Every large
+// GEMM of a ViT layer goes to the 256x256 eight-phase kernels (gemm_nt256p.hip, gemm_nt256.hip, gemm_tn256.hip); the rest -- the
+// decoder's small GEMMs, K < 128, odd shapes -- runs on the kernels in this file: 128x128 output tile per 256-thread workgroup (4 waves, 2x2, 64x64 per wave = 4x4
 // MFMA 16x16x32 tiles), reduction step 64, operands streamed global->LDS with 16-byte LDS-DMA (global_load_lds_dwordx4)
 // into a 2-stage ring, XOR-swizzled on the SOURCE address so the LDS image stays lane-linear while fragment reads are
 // bank-conflict free; two workgroups per CU.
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) { gem
 
 // Grouped launch: several independent weight gradients (e.g. the six of one decoder layer, 4..12 tiles of 128x128 each)
 // share ONE grid, so the 256 CUs x 2 resident workgroups are filled in a single round instead of six part-filled ones.
-constexpr int TN_GROUP_MAX = 40;     // 88-byte descriptors in the kernel arguments (4 KiB): the 36 weight gradients of a six-layer decoder in one grid
+constexpr int TN_GROUP_MAX = KZV_TN_GROUP_MAX;
 struct TnGroup { TnParams p[TN_GROUP_MAX]; int start[TN_GROUP_MAX + 1]; int n; };
 __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(const TnGroup g) {
     int i = 0;
@@ -400,84 +400,51 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(const TnGroup g) 
 
 }  // namespace
 
-// K-loop schedule of the persistent 256x256 kernel: 0 eight-phase ping-pong (gemm_nt256p.hip), 1 free-running (gemm_nt256f.hip);
-// bit 1 (2, 3): the epilogues of g_nt_half_mask go to the four-wave 256x128 kernel, two workgroups per CU (gemm_nt256h.hip)
-static int g_nt_schedule = -1;
-static int g_nt_half_mask = -1;
-static int nt_schedule() {
-    if (g_nt_schedule < 0) {
-        g_nt_schedule = kzv_env_int("KZV_NT_FREE", 0) != 0;
-        if (kzv_env_int("KZV_NT_HALF", 0)) g_nt_schedule |= 2;
-    }
-    return g_nt_schedule;
-}
-static int nt_half_mask() {
-    if (g_nt_half_mask < 0) g_nt_half_mask = kzv_env_int("KZV_NT_HALF_EPIS", 0x3f);
-    return g_nt_half_mask;
-}
-extern "C" int kzv_set_nt_schedule(int n) { g_nt_schedule = n < 0 ? -1 : (n & 3); return KZV_OK; }
-extern "C" int kzv_set_nt_half_epilogues(int mask) { g_nt_half_mask = mask; return KZV_OK; }
-
-// validation of a kzv_gemm_nt call and its kernel parameter block (shared with the dgrad + wgrad pair launch of gemm_tn256.hip)
-int kzv_nt_params(const kzv_gemm_nt_args* a, int epilogue, NtParams* out) {
-    if (!a || !a->A || !a->B || !a->C) return kzv_fail(KZV_E_ARG, "gemm_nt: null operand");
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return kzv_fail(KZV_E_ARG, "gemm_nt: empty shape");
-    if (a->K % 64) return kzv_fail(KZV_E_ARG, "gemm_nt: K must be a multiple of 64");
-    if (a->N % 4 || a->ldc % 4) return kzv_fail(KZV_E_ARG, "gemm_nt: N and ldc must be multiples of 4");
-    if (a->lda % 8 || a->ldb % 8) return kzv_fail(KZV_E_ARG, "gemm_nt: lda/ldb must be multiples of 8 (16-byte rows)");
-    if (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C) & 15) return kzv_fail(KZV_E_ARG, "gemm_nt: operands must be 16-byte aligned");
-    if (epilogue == KZV_EPI_RESID && (!a->resid || a->ldr % 4)) return kzv_fail(KZV_E_ARG, "gemm_nt: RESID needs resid, ldr%4==0");
-    if ((epilogue == KZV_EPI_GELU || epilogue == KZV_EPI_DGELU || epilogue == KZV_EPI_GELU_F32) && (!a->aux || a->ldaux % 4)) return kzv_fail(KZV_E_ARG, "gemm_nt: GELU/DGELU need aux");
+// the kernel parameter block of a kzv_gemm_nt call that kzv_nt_validate has passed (shared with the dgrad + wgrad pair launch of gemm_tn256.hip)
+int kzv_nt_params(const kzv_gemm_nt_args* a, const KzvNtShape& sh, NtParams* out) {
     NtParams p{};
     p.A = (const bf16_t*)a->A; p.B = (const bf16_t*)a->B; p.C = a->C; p.bias = a->bias; p.resid = a->resid;
     p.aux = (bf16_t*)a->aux; p.zero16 = kzv_zero_page();
     if (!p.zero16) return kzv_fail(KZV_E_HIP, "gemm_nt: zero page unavailable");
     p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldaux = a->ldaux;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.n_valid = a->n_valid > 0 ? a->n_valid : a->N;
+    p.M = a->M; p.N = a->N; p.K = a->K; p.n_valid = sh.n_valid;
     kzv_drop_params(a->drop_p, &p.drop_thr16, &p.drop_inv_keep);
     p.drop_key = a->drop_key;
-    p.strip = kzv_nt_strip() & 0xff;
+    p.strip = kzv_gemm_switches().nt_strip & 0xff;
     *out = p;
     return KZV_OK;
 }
 
+// validate, plan (gemm_plan.h: the whole choice of kernel and grid), launch
 extern "C" int kzv_gemm_nt(const kzv_gemm_nt_args* a, int epilogue, void* stream) {
+    KzvNtShape sh;
     NtParams p;
-    { const int rc = kzv_nt_params(a, epilogue, &p); if (rc != KZV_OK) return rc; }
+    KZV_TRY_RC(kzv_nt_validate(a, epilogue, &sh));
+    KZV_TRY_RC(kzv_nt_params(a, sh, &p));
     hipStream_t s = (hipStream_t)stream;
     KzvProfScope prof(0, 2.0 * a->M * p.n_valid * a->K, s);
-    // large shapes: 256x256 eight-phase kernels.  The persistent one wins wherever its per-wave drain is light (one
-    // store per element: -2..-10 % vs the one-tile-per-workgroup kernel); the two-store GELU epilogues are faster through
-    // the workgroup-wide LDS epilogue of gemm_nt256.hip (512-B / 1-KiB row segments).
-    static int use_p = -1;
-    if (use_p < 0) use_p = kzv_env_int("KZV_NT256P", 1);
-    if (kzv_rows_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");      // M <= 1024: the generation step's GEMMs
-    static int p_gelu = -1;      // dev knob: the two-store GELU epilogues on the persistent kernel too (A/B; default off)
-    if (p_gelu < 0) p_gelu = kzv_env_int("KZV_NT256P_GELU", 0);
-    const bool two_store = !p_gelu && (epilogue == KZV_EPI_GELU || epilogue == KZV_EPI_GELU_F32);
-    static int half_maxk = -1;   // the four-wave kernel's K loop is latency-bound (three-group ring): it pays only where the drain is a large part of a tile
-    if (half_maxk < 0) half_maxk = kzv_env_int("KZV_NTH_MAX_K", 1 << 30);
-    if ((nt_schedule() & 2) && ((nt_half_mask() >> epilogue) & 1) && p.K <= half_maxk && kzv_cu_reserve() == 0 && kzv_nt256h_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
-    if ((nt_schedule() & 1) && use_p && !two_store && kzv_cu_reserve() == 0 && kzv_nt256f_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
-    if (use_p && !two_store && kzv_cu_reserve() == 0 && kzv_nt256p_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
-    if (kzv_nt256_launch(p, epilogue, s)) return kzv_check_launch("gemm_nt");
+    const KzvNtPlan pl = kzv_nt_plan(sh, kzv_gemm_switches_nt(), kzv_gemm_env());
+    if (pl.rc != KZV_OK) return kzv_fail(pl.rc, "%s", pl.err);
 #define KZV_NT_CASE(E, WM, WN, NS, KB, AD)                                                                \
     case E: {                                                                                             \
         constexpr int lds = NS * (WM + WN) * 64 * KB * 2;                                                 \
-        const int grid = ((a->M + WM * 64 - 1) / (WM * 64)) * ((a->N + WN * 64 - 1) / (WN * 64));         \
-        kzv_launch_lds<gemm_nt_kernel<E, WM, WN, NS, KB, AD>>(dim3(grid), dim3(WM * WN * 64), lds, s, p); \
+        kzv_launch_lds<gemm_nt_kernel<E, WM, WN, NS, KB, AD>>(dim3(pl.grid), dim3(WM * WN * 64), lds, s, p); \
     } break;
 #define KZV_NT_VARIANT(WM, WN, NS, KB, AD)                                                                \
     switch (epilogue) {                                                                                   \
         KZV_NT_CASE(KZV_EPI_BF16, WM, WN, NS, KB, AD) KZV_NT_CASE(KZV_EPI_F32, WM, WN, NS, KB, AD)        \
         KZV_NT_CASE(KZV_EPI_GELU, WM, WN, NS, KB, AD) KZV_NT_CASE(KZV_EPI_RESID, WM, WN, NS, KB, AD)      \
         KZV_NT_CASE(KZV_EPI_DGELU, WM, WN, NS, KB, AD) KZV_NT_CASE(KZV_EPI_GELU_F32, WM, WN, NS, KB, AD)  \
-        default: return kzv_fail(KZV_E_ARG, "gemm_nt: unknown epilogue");                                 \
     }
-    // Measured on MI355X (tools/dev/gemm_bench.py, round 1): 128x128x64 / 2-stage ring / 2 workgroups per CU is the
-    // fastest of the variants this template expresses (KB = 32 with 2-4 stages: -5..-15 %; 256x128 tiles at one
-    // workgroup per CU: -3 %; a 3-stage ring at one workgroup per CU: -30 %), so only it is instantiated.
-    KZV_NT_VARIANT(2, 2, 2, 64, false)
+    switch (pl.kernel) {
+        case KZV_GEMM_ROWS: kzv_rows_launch(p, pl, s); break;        // M <= 1024: the generation step's GEMMs
+        case KZV_GEMM_NT256H: kzv_nt256h_launch(p, pl, s); break;
+        case KZV_GEMM_NT256F: kzv_nt256f_launch(p, pl, s); break;
+        case KZV_GEMM_NT256P: kzv_nt256p_launch(p, pl, s); break;
+        case KZV_GEMM_NT256: kzv_nt256_launch(p, pl, s); break;
+        // 128x128x64 / 2-stage ring / 2 workgroups per CU, the only variant of the template that is instantiated (gemm_plan.h)
+        default: KZV_NT_VARIANT(2, 2, 2, 64, false)
+    }
 #undef KZV_NT_VARIANT
 #undef KZV_NT_CASE
     return kzv_check_launch("gemm_nt");
@@ -521,68 +488,49 @@ extern "C" int kzv_gemm_nt_fp8(const kzv_gemm_nt_fp8_args* a, int epilogue, void
     p.M = a->M; p.N = a->N; p.K = a->K; p.n_valid = a->n_valid > 0 ? a->n_valid : a->N;
     kzv_drop_params(a->drop_p, &p.drop_thr16, &p.drop_inv_keep);
     p.drop_key = a->drop_key;
-    p.strip = kzv_nt_strip() & 0xff;
+    p.strip = kzv_gemm_switches().nt_strip & 0xff;
     p.a_scale = a->a_scale; p.b_scale = a->b_scale;
     p.c8 = (unsigned char*)a->c8; p.ldc8 = a->ldc8; p.c8_qscale = a->c8_qscale; p.c8_amax = a->c8_amax; p.c8_rowq = a->c8_rowq;
     hipStream_t s = (hipStream_t)stream;
     KzvProfScope prof(4, 2.0 * a->M * p.n_valid * a->K, s);
-    const int rc = kzv_nt256p_fp8_launch(p, epilogue, s);
-    if (rc != KZV_OK) return rc;
+    const KzvNtPlan pl = kzv_nt_plan(KzvNtShape{p.M, p.N, p.K, p.n_valid, p.lda, p.ldb, epilogue, 1}, kzv_gemm_switches(), kzv_gemm_env());
+    if (pl.rc != KZV_OK) return kzv_fail(pl.rc, "%s", pl.err);
+    kzv_nt256p_fp8_launch(p, pl, s);
     return kzv_check_launch("gemm_nt_fp8");
 }
 
-// validation of a kzv_gemm_tn call and its kernel parameter block (shared with the dgrad + wgrad pair launch of gemm_tn256.hip)
-int kzv_tn_params(const kzv_gemm_tn_args* a, TnParams& p) {
-    if (!a || !a->P || !a->Q || !a->OUT) return kzv_fail(KZV_E_ARG, "gemm_tn: null operand");
-    if (a->Mtok <= 0 || a->N <= 0 || a->K <= 0) return kzv_fail(KZV_E_ARG, "gemm_tn: empty shape");
-    if (a->N % 8 || a->K % 8 || a->ldp % 8 || a->ldq % 8 || a->ldo % 4) return kzv_fail(KZV_E_ARG, "gemm_tn: N,K,ldp,ldq %8, ldo %4");
-    if (((uintptr_t)a->P | (uintptr_t)a->Q | (uintptr_t)a->OUT) & 15) return kzv_fail(KZV_E_ARG, "gemm_tn: operands must be 16-byte aligned");
+// the kernel parameter block of a kzv_gemm_tn call that kzv_tn_validate has passed (shared with the dgrad + wgrad pair launch of
+// gemm_tn256.hip); splits / chunk come from the plan
+int kzv_tn_params(const kzv_gemm_tn_args* a, const KzvTnShape& sh, TnParams& p) {
     p.P = (const bf16_t*)a->P; p.Q = (const bf16_t*)a->Q; p.OUT = a->OUT; p.zero16 = kzv_zero_page();
     if (!p.zero16) return kzv_fail(KZV_E_HIP, "gemm_tn: zero page unavailable");
     p.ldp = a->ldp; p.ldq = a->ldq; p.ldo = a->ldo;
-    p.Mtok = a->Mtok; p.N = a->N; p.K = a->K; p.n_store = a->n_store > 0 ? a->n_store : a->N;
+    p.Mtok = a->Mtok; p.N = a->N; p.K = a->K; p.n_store = sh.n_store;
     p.dbias = a->dbias;
     return KZV_OK;
 }
-// Token splits of one problem given the workgroup budget `target` it may fill: ONE resident round without overshooting
-// it, and >= min_steps reduction steps per workgroup so the 64 float atomics per lane of the epilogue (issue-bound, and
-// contended when many splits hit one small output) stay a small share.  Returns the workgroup count.
-static int tn_plan(TnParams& p, int target) {
-    static int min_steps = -1;
-    if (min_steps < 0) min_steps = kzv_env_int("KZV_TN_MINSTEPS", 16);
-    const int tiles = ((p.N + 127) / 128) * ((p.K + 127) / 128);
-    const int tok_tiles = (p.Mtok + 63) / 64;
-    int splits = target / tiles;
-    if (splits > tok_tiles / min_steps) splits = tok_tiles / min_steps;
-    if (splits > tok_tiles) splits = tok_tiles;
-    if (splits < 1) splits = 1;
-    const int chunk_tiles = (tok_tiles + splits - 1) / splits;
-    splits = (tok_tiles + chunk_tiles - 1) / chunk_tiles;
-    p.splits = splits; p.chunk = chunk_tiles * 64;
-    return tiles * splits;
-}
-static int tn_target() {
-    static int target = -1;
-    if (target < 0) target = kzv_env_int("KZV_TN_BLOCKS", 512);
-    return target;
-}
 
 extern "C" int kzv_gemm_tn(const kzv_gemm_tn_args* a, void* stream) {
+    KzvTnShape sh;
     TnParams p;
-    const int rc = kzv_tn_params(a, p);
-    if (rc != KZV_OK) return rc;
+    KZV_TRY_RC(kzv_tn_validate(a, &sh));
+    KZV_TRY_RC(kzv_tn_params(a, sh, p));
     KzvProfScope prof(1, 2.0 * a->Mtok * p.n_store * a->K, (hipStream_t)stream);
-    const int took = kzv_tn256_launch(p, (hipStream_t)stream);                            // >= 9 tiles of 256x256: eight-phase kernel
-    if (took < 0) return took;                                                            // a pending fold failed: its code and message
-    if (took) return kzv_check_launch("gemm_tn");
-    const int blocks = tn_plan(p, tn_target());
-    kzv_launch_lds<gemm_tn_kernel>(dim3(blocks), dim3(256), NT_LDS, (hipStream_t)stream, p);
+    const KzvGemmSwitches& sw = kzv_gemm_switches_tn();
+    KzvTnPlan pl = kzv_tn_plan(sh, sw, kzv_gemm_env());
+    if (pl.kernel != KZV_GEMM_TN128) {                                                    // >= 9 tiles of 256x256: eight-phase kernel
+        const int took = kzv_tn256_launch(p, pl, (hipStream_t)stream);
+        if (took < 0) return took;                                                        // a pending fold failed: its code and message
+        if (took) return kzv_check_launch("gemm_tn");
+        pl = kzv_tn128_plan(sh, sw.tn_blocks, sw);                                        // no workspace: the one choice a plan cannot make ahead
+    }
+    p.splits = pl.splits; p.chunk = pl.chunk;
+    kzv_launch_lds<gemm_tn_kernel>(dim3(pl.grid), dim3(256), NT_LDS, (hipStream_t)stream, p);
     return kzv_check_launch("gemm_tn");
 }
 
 // n independent weight gradients in one grid (model.cpp: the six of a decoder layer; head; cross-K/V + projection).
-// Problems the 256x256 kernel would take are launched on their own.  The workgroup budget (one resident round) is shared
-// in proportion to the tile counts.
+// Problems of kzv_tn_group_own_launch are launched on their own; the rest share one grid as kzv_tn_group_plan says.
 int kzv_gemm_tn_group(const kzv_gemm_tn_args* a, int n, hipStream_t s) {
     if (n <= 0) return KZV_OK;
     if (n == 1 || n > TN_GROUP_MAX) {
@@ -590,34 +538,21 @@ int kzv_gemm_tn_group(const kzv_gemm_tn_args* a, int n, hipStream_t s) {
         return KZV_OK;
     }
     TnGroup g;
+    KzvTnShape sh[TN_GROUP_MAX];
     g.n = 0;
-    int tiles_total = 0;
     double work = 0;
     for (int i = 0; i < n; ++i) {
-        TnParams p;
-        const int rc = kzv_tn_params(a + i, p);
-        if (rc != KZV_OK) return rc;
-        const int t256 = ((p.n_store + 255) / 256) * ((p.K + 255) / 256);
-        if (t256 >= 24) { const int r2 = kzv_gemm_tn(a + i, s); if (r2 != KZV_OK) return r2; continue; }   // the eight-phase kernel's shapes
-        g.p[g.n++] = p;
-        tiles_total += ((p.N + 127) / 128) * ((p.K + 127) / 128);
-        work += 2.0 * p.Mtok * p.n_store * p.K;
+        KZV_TRY_RC(kzv_tn_validate(a + i, &sh[g.n]));
+        KZV_TRY_RC(kzv_tn_params(a + i, sh[g.n], g.p[g.n]));
+        if (kzv_tn_group_own_launch(sh[g.n])) { KZV_TRY_RC(kzv_gemm_tn(a + i, s)); continue; }
+        work += 2.0 * sh[g.n].Mtok * sh[g.n].n_store * sh[g.n].K;
+        ++g.n;
     }
     if (g.n == 0) return KZV_OK;
     KzvProfScope prof(1, work, s);
-    int blocks = 0;
-    for (int i = 0; i < g.n; ++i) {
-        const int tiles = ((g.p[i].N + 127) / 128) * ((g.p[i].K + 127) / 128);
-        // one resident round (512 workgroups) for the small groups; a group with more tiles than that round's half (the 36 weight
-        // gradients of the decoder's layers: 288 tiles) takes two: 3 token splits of 80 stages, 261 us against 335 with one split per
-        // tile and 348 for six launches of ten splits (tools/dev/r5_tnblocks.sh)
-        const int target = tiles_total >= 256 ? 2 * tn_target() : tn_target();
-        int share = (int)((int64_t)target * tiles / tiles_total);
-        if (share < tiles) share = tiles;
-        g.start[i] = blocks;
-        blocks += tn_plan(g.p[i], share);
-    }
-    g.start[g.n] = blocks;
-    kzv_launch_lds<gemm_tn_group_kernel>(dim3(blocks), dim3(256), NT_LDS, s, g);
+    const KzvTnGroupPlan pl = kzv_tn_group_plan(sh, g.n, kzv_gemm_switches());
+    for (int i = 0; i < g.n; ++i) { g.p[i].splits = pl.splits[i]; g.p[i].chunk = pl.chunk[i]; g.start[i] = pl.start[i]; }
+    g.start[g.n] = pl.grid;
+    kzv_launch_lds<gemm_tn_group_kernel>(dim3(pl.grid), dim3(256), NT_LDS, s, g);
     return kzv_check_launch("gemm_tn_group");
 }

@@ -4,6 +4,8 @@
 #pragma once
 #include "kzv_common.h"
 #include "../../include/kzv.h"
+#include "kzv_host.h"
+#include "gemm_plan.h"
 
 struct NtParams {
     const bf16_t* A; const bf16_t* B; void* C; const float* bias; const float* resid; bf16_t* aux;
@@ -86,30 +88,28 @@ __device__ __forceinline__ void nt_tile_coords(int id, int tilesM, int tilesN, i
     tm = rem / w;
     tn = st * strip + (rem - tm * w);
 }
-int kzv_nt_strip();      // KZV_NT_STRIP (default 3)
 
-// The 256x256 kernels address their operands as a wave-uniform 64-bit base + a 32-bit per-lane byte offset (LDS-DMA): the A row panel of a
-// tile and all valid rows of B must lie within 4 GiB of their bases.  `es` = bytes per operand element (2: bf16, 1: e4m3).
-inline bool nt_dma_offsets_fit(const NtParams& p, int es) {
-    return (uint64_t)256 * (uint64_t)p.lda * es <= 0xffffffffull && (uint64_t)p.n_valid * (uint64_t)p.ldb * es <= 0xffffffffull;
-}
+// ---- dispatch (gemm_plan.h) ----
+// gemm_plan.cpp: the process's switches, resolved (_nt: KZV_NT_GRID read again, as at every launch), and what else a plan needs to know
+KZV_LOCAL const KzvGemmSwitches& kzv_gemm_switches();
+KZV_LOCAL const KzvGemmSwitches& kzv_gemm_switches_nt();
+KZV_LOCAL KzvGemmEnv kzv_gemm_env();
+// gemm_plan.cpp: the argument validation of a kzv_gemm_nt call (code and kzv_last_error text), no device needed; *out = the planner's view
+struct kzv_gemm_nt_args;
+KZV_LOCAL int kzv_nt_validate(const kzv_gemm_nt_args* a, int epilogue, KzvNtShape* out);
+// gemm.hip: the kernel parameter block of a validated call; needs the device (the zero page)
+KZV_LOCAL int kzv_nt_params(const kzv_gemm_nt_args* a, const KzvNtShape& sh, NtParams* out);
 
-// gemm_nt256.hip: returns 1 when it took the launch, 0 when the shape is left to the 128x128 kernel.
-int kzv_nt256_launch(const NtParams& p, int epilogue, hipStream_t s);
-// gemm_nt256p.hip (persistent variant of the same schedule): same contract.
-int kzv_nt256p_launch(const NtParams& p, int epilogue, hipStream_t s);
-// gemm_nt256f.hip (free-running schedule: two barriers per K-tile, loads hidden under each wave's own MFMAs): same contract.
-int kzv_nt256f_launch(const NtParams& p, int epilogue, hipStream_t s);
-// gemm_nt256h.hip (four waves, 256x128 tile, two workgroups per CU out of phase, free-running K loop; K % 384 == 0): same contract.
-int kzv_nt256h_launch(const NtParams& p, int epilogue, hipStream_t s);
-// fp8 (e4m3) operands on the block-scaled MFMA, same persistent schedule (gemm_nt256p.hip); epilogues BF16, GELU, RESID, DGELU.
-// Returns KZV_OK or an error: there is no other fp8 kernel to fall back to.
-int kzv_nt256p_fp8_launch(const NtParams& p, int epilogue, hipStream_t s);
-// gemm_rows.hip (few rows: one wave per 16x64 tile, operands straight from L2): same contract.  Taken inside a KzvRowsScope
-// (the generation step, model.cpp) for M <= 4096, elsewhere only below kzv_set_rows_max_m (default 0: never), so that the
-// training step and its parity tests keep running the tiled kernels at every size.
-int kzv_rows_launch(const NtParams& p, int epilogue, hipStream_t s);
-struct KzvRowsScope { KzvRowsScope(); ~KzvRowsScope(); };
+// The launchers launch the plan they are given (pl.kernel is theirs: kzv_gemm_nt's switch); the only choice left to them is the
+// kernel instantiation per epilogue.
+KZV_LOCAL void kzv_nt256_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);       // gemm_nt256.hip: one 256x256 tile per workgroup
+KZV_LOCAL void kzv_nt256p_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);      // gemm_nt256p.hip: persistent variant of the same schedule
+KZV_LOCAL void kzv_nt256f_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);      // gemm_nt256f.hip: free-running schedule (two barriers per K-tile, loads hidden under each wave's own MFMAs)
+KZV_LOCAL void kzv_nt256h_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);      // gemm_nt256h.hip: four waves, 256x128 tile, two workgroups per CU out of phase, free-running K loop
+// fp8 (e4m3) operands on the block-scaled MFMA, same persistent schedule (gemm_nt256p.hip); epilogues BF16, GELU, RESID, DGELU
+KZV_LOCAL void kzv_nt256p_fp8_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);
+KZV_LOCAL void kzv_rows_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s);        // gemm_rows.hip: few rows, one wave per 16x64 tile, operands straight from L2
+struct KzvRowsScope { KzvRowsScope(); ~KzvRowsScope(); };      // while one is open (the generation step, model_decode.cpp) plans take the few-rows kernel up to M = 4096
 // the few-rows kernel with the decoder's LayerNorm folded into its A operand and / or its residual (gemm_rows.hip)
 int kzv_rows_ln_launch(const NtParams& p, int epilogue, const float* ln_a, const float* ga, const float* ba, const float* ln_r, const float* gr,
                        const float* br, float eps, hipStream_t s);

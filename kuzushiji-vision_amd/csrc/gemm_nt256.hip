@@ -222,25 +222,13 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const NtParams p) {
     }
 }
 
-int nt256_min_tiles() {
-    static int v = -1;
-    if (v < 0) v = kzv_env_int("KZV_NT256_MIN_TILES", 384);
-    return v;
-}
-
 }  // namespace
 
-int kzv_nt256_launch(const NtParams& p, int epilogue, hipStream_t s) {
-    const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    // below ~1.5 rounds of the 256 CUs the 128x128 kernel (4x the tiles, 2 workgroups per CU) fills the chip better
-    if (p.K < 128 || tiles < nt256_min_tiles()) return 0;
-    if (!nt_dma_offsets_fit(p, 2)) return 0;
-#define KZV_NT256_CASE(E) case E: kzv_launch_lds<gemm_nt256_kernel<E>>(dim3(tiles), dim3(512), NT256_RING_BYTES, s, p); break;
-    switch (epilogue) {
+void kzv_nt256_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s) {
+#define KZV_NT256_CASE(E) case E: kzv_launch_lds<gemm_nt256_kernel<E>>(dim3(pl.grid), dim3(512), NT256_RING_BYTES, s, p); break;
+    switch (pl.epilogue) {
         KZV_NT256_CASE(KZV_EPI_BF16) KZV_NT256_CASE(KZV_EPI_F32) KZV_NT256_CASE(KZV_EPI_GELU)
         KZV_NT256_CASE(KZV_EPI_RESID) KZV_NT256_CASE(KZV_EPI_DGELU) KZV_NT256_CASE(KZV_EPI_GELU_F32)
-        default: return 0;
     }
 #undef KZV_NT256_CASE
-    return 1;
 }

@@ -413,27 +413,13 @@ __global__ __launch_bounds__(512) void gemm_nt256f_kernel(const NtParams p, cons
     vmcnt<0>();                                     // the refills issued past the end of the stream (into dead slots) land before the LDS is released
 }
 
-int nt256f_min_tiles() {
-    static int v = -1;
-    if (v < 0) v = kzv_env_int("KZV_NT256P_MIN_TILES", 384);
-    return v;
-}
-
 }  // namespace
 
-int kzv_nt256f_launch(const NtParams& p, int epilogue, hipStream_t s) {
-    const int tilesN = (p.N + 255) / 256;
-    const int tiles = ((p.M + 255) / 256) * tilesN;
-    if (p.K < 128 || p.K % 128 || tiles < nt256f_min_tiles()) return 0;   // even number of K-tiles (odd: gemm_nt256.hip)
-    if (!nt_dma_offsets_fit(p, 2)) return 0;
-    if (p.n_valid <= (tilesN - 1) * 256 || p.lda * 2 < 128 || p.ldb * 2 < 128) return 0;          // every tile starts on a valid column (the DMA clamp needs one)
-    const int grid = tiles < kzv_device_cus() ? tiles : kzv_device_cus();
-#define KZV_NT256F_CASE(E) case E: kzv_launch_lds<gemm_nt256f_kernel<E>>(dim3(grid), dim3(512), NT256P_LDS_BYTES, s, p, tiles, tilesN, kzv_nt_strip()); break;
-    switch (epilogue) {
+void kzv_nt256f_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s) {
+#define KZV_NT256F_CASE(E) case E: kzv_launch_lds<gemm_nt256f_kernel<E>>(dim3(pl.grid), dim3(512), NT256P_LDS_BYTES, s, p, pl.tiles, pl.tilesN, pl.strip); break;
+    switch (pl.epilogue) {
         KZV_NT256F_CASE(KZV_EPI_BF16) KZV_NT256F_CASE(KZV_EPI_F32) KZV_NT256F_CASE(KZV_EPI_GELU)
         KZV_NT256F_CASE(KZV_EPI_RESID) KZV_NT256F_CASE(KZV_EPI_DGELU) KZV_NT256F_CASE(KZV_EPI_GELU_F32)
-        default: return 0;
     }
 #undef KZV_NT256F_CASE
-    return 1;
 }

@@ -320,32 +320,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt256h_kernel(const NtParams p, c
     vmcnt<0>();                                     // the refills issued past the end of the stream (into dead slots) land before the LDS is released
 }
 
-int nt256h_min_tiles() {
-    static int v = -1;
-    if (v < 0) v = kzv_env_int("KZV_NT256H_MIN_TILES", 768);
-    return v;
-}
-int g_stagger = -1;
-
 }  // namespace
 
-extern "C" int kzv_set_nt_half_stagger(int us) { g_stagger = us; return KZV_OK; }
-
-int kzv_nt256h_launch(const NtParams& p, int epilogue, hipStream_t s) {
-    const int tilesN = (p.N + 127) / 128;
-    const int tiles = ((p.M + 255) / 256) * tilesN;
-    if (p.K < 384 || p.K % 384 || tiles < nt256h_min_tiles()) return 0;   // six K-tile bodies per round of the slot / fragment-set pattern
-    if (!nt_dma_offsets_fit(p, 2)) return 0;
-    if (p.n_valid <= (tilesN - 1) * 128 || p.lda * 2 < 128 || p.ldb * 2 < 128) return 0;          // every tile starts on a valid column (the DMA clamp needs one)
-    if (g_stagger < 0) g_stagger = kzv_env_int("KZV_NTH_STAGGER", 8);
-    const int grid = tiles < 2 * kzv_device_cus() ? tiles : 2 * kzv_device_cus();
-    const int strip = (kzv_nt_strip() & 0xff) * 2;
-#define KZV_NT256H_CASE(E) case E: kzv_launch_lds<gemm_nt256h_kernel<E>>(dim3(grid), dim3(256), LDS_BYTES, s, p, tiles, tilesN, strip, g_stagger); break;
-    switch (epilogue) {
+void kzv_nt256h_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s) {
+#define KZV_NT256H_CASE(E) case E: kzv_launch_lds<gemm_nt256h_kernel<E>>(dim3(pl.grid), dim3(256), LDS_BYTES, s, p, pl.tiles, pl.tilesN, pl.strip, pl.stagger); break;
+    switch (pl.epilogue) {
         KZV_NT256H_CASE(KZV_EPI_BF16) KZV_NT256H_CASE(KZV_EPI_F32) KZV_NT256H_CASE(KZV_EPI_GELU)
         KZV_NT256H_CASE(KZV_EPI_RESID) KZV_NT256H_CASE(KZV_EPI_DGELU) KZV_NT256H_CASE(KZV_EPI_GELU_F32)
-        default: return 0;
     }
 #undef KZV_NT256H_CASE
-    return 1;
 }

@@ -211,9 +211,6 @@ __global__ __launch_bounds__(256) void gemm_rows_ln_kernel(const NtParams p, con
     nt_emit<EPI>(p, em, en, v, r4, u2);
 }
 
-int g_rows_max_m = -1;
-int g_rows_scope = 0;
-
 }  // namespace
 
 // Few-rows GEMM whose A operand and / or residual is the LayerNorm of an fp32 [M, 256] tensor (see gemm_rows_ln_kernel).
@@ -243,32 +240,16 @@ int kzv_rows_ln_launch(const NtParams& p, int epilogue, const float* ln_a, const
     return kzv_check_launch("gemm_rows_ln");
 }
 
-KzvRowsScope::KzvRowsScope() { ++g_rows_scope; }
-KzvRowsScope::~KzvRowsScope() { --g_rows_scope; }
-
-extern "C" int kzv_set_rows_max_m(int n) {
-    if (n < 0) return kzv_fail(KZV_E_ARG, "set_rows_max_m: >= 0");
-    g_rows_max_m = n;
-    return KZV_OK;
-}
-
-// returns 1 when it took the launch
-int kzv_rows_launch(const NtParams& p, int epilogue, hipStream_t s) {
-    if (g_rows_max_m < 0) g_rows_max_m = kzv_env_int("KZV_ROWS_MAX_M", 0);
-    if (p.M > (g_rows_scope > 0 ? 4096 : g_rows_max_m)) return 0;      // the generation step (KzvRowsScope) or an explicit threshold
-    if (p.K > 4096) return 0;
-    const dim3 grid((p.N + 63) / 64, (p.M + 15) / 16);
-    const int per = (p.K / 32 + 3) / 4;                              // 32-deep steps per wave
+void kzv_rows_launch(const NtParams& p, const KzvNtPlan& pl, hipStream_t s) {
+    const dim3 grid(pl.grid, pl.grid_y);
 #define KZV_ROWS_CASE(E) case E:                                                                                  \
-        if (per <= 2) hipLaunchKernelGGL((gemm_rows_kernel<E, 2>), grid, dim3(256), 0, s, p);                      \
-        else if (per <= 8) hipLaunchKernelGGL((gemm_rows_kernel<E, 8>), grid, dim3(256), 0, s, p);                 \
+        if (pl.steps == 2) hipLaunchKernelGGL((gemm_rows_kernel<E, 2>), grid, dim3(256), 0, s, p);                 \
+        else if (pl.steps == 8) hipLaunchKernelGGL((gemm_rows_kernel<E, 8>), grid, dim3(256), 0, s, p);            \
         else hipLaunchKernelGGL((gemm_rows_kernel<E, 32>), grid, dim3(256), 0, s, p);                              \
         break;
-    switch (epilogue) {
+    switch (pl.epilogue) {
         KZV_ROWS_CASE(KZV_EPI_BF16) KZV_ROWS_CASE(KZV_EPI_F32) KZV_ROWS_CASE(KZV_EPI_GELU) KZV_ROWS_CASE(KZV_EPI_RESID)
         KZV_ROWS_CASE(KZV_EPI_DGELU) KZV_ROWS_CASE(KZV_EPI_GELU_F32)
-        default: return 0;
     }
 #undef KZV_ROWS_CASE
-    return 1;
 }

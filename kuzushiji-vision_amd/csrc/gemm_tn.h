@@ -2,6 +2,8 @@
 // eight-phase, free-running, and the dgrad + wgrad pair kernel): launch parameters and the launchers' contracts.
 #pragma once
 #include "kzv_common.h"
+#include "kzv_host.h"
+#include "gemm_plan.h"
 
 struct TnParams {
     const bf16_t* P; const bf16_t* Q; float* OUT; const void* zero16;
@@ -10,17 +12,17 @@ struct TnParams {
     float* dbias;                              // optional: dbias[n] += sum_t P[t][n]  (the nn.Linear bias gradient)
 };
 
-// gemm_tn256.hip's twin of nt_dma_offsets_fit (gemm_nt.h): a 64-token stage of P and of Q within the 32-bit per-lane LDS-DMA offsets
-inline bool tn_dma_offsets_fit(const TnParams& p) {
-    return (uint64_t)64 * (uint64_t)p.ldp * 2 + (uint64_t)p.N * 2 <= 0xffffffffull && (uint64_t)64 * (uint64_t)p.ldq * 2 + (uint64_t)p.K * 2 <= 0xffffffffull;
-}
-
-// gemm_tn256.hip: returns 1 when it took the launch (p.splits / p.chunk are chosen inside), 0 when the shape is left
-// to the 128x128 kernel, < 0 = error (the fold of pending partial tiles it had to launch first failed: kzv_last_error has it).
-int kzv_tn256_launch(const TnParams& p, hipStream_t s);
-// gemm.hip: validation of a kzv_gemm_tn call and its kernel parameter block (splits / chunk are the launcher's)
+// ---- dispatch (gemm_plan.h) ----
+KZV_LOCAL const KzvGemmSwitches& kzv_gemm_switches_tn();      // gemm_plan.cpp: the resolved switches, KZV_TN_CUS read again (as at every launch)
+// gemm_plan.cpp: the argument validation of a kzv_gemm_tn call, no device needed; gemm.hip: the parameter block of a validated call
+// (needs the zero page; splits / chunk come from the plan)
 struct kzv_gemm_tn_args;
-int kzv_tn_params(const kzv_gemm_tn_args* a, TnParams& p);
+KZV_LOCAL int kzv_tn_validate(const kzv_gemm_tn_args* a, KzvTnShape* out);
+KZV_LOCAL int kzv_tn_params(const kzv_gemm_tn_args* a, const KzvTnShape& sh, TnParams& p);
+// gemm_tn256.hip: launches a TN256F / TN256 plan and the fold of its partial tiles (or leaves the fold pending, below).  1 = launched;
+// 0 = no workspace could be had, nothing was launched: the caller falls back to the 128x128 kernel; < 0 = error (the fold of pending
+// partial tiles it had to launch first failed: kzv_last_error has it).
+KZV_LOCAL int kzv_tn256_launch(const TnParams& p, const KzvTnPlan& pl, hipStream_t s);
 
 // While one of these is alive, kzv_tn256_launch leaves the fold of its partial tiles pending (each launch gets a workspace region of
 // its own, up to 5); closing the outermost scope folds all of them in ONE launch on `stream` (the launches must be on it too;
@@ -39,5 +41,5 @@ struct KzvTnFoldScope {
 // weight-gradient tile sized so that all workgroups finish together.  1 = launched, 0 = not taken (issue the two GEMMs separately), < 0 = error.
 // Same results as the separate launches: the gemm_nt part bit for bit, the weight gradient up to the bf16 rounding of its partial tiles
 // (the token splits differ).  KZV_PAIR=0 turns it off.
-struct kzv_gemm_nt_args; struct kzv_gemm_tn_args;
+struct kzv_gemm_nt_args;
 int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gemm_tn_args* ta, hipStream_t s);

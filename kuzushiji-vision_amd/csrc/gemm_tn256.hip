@@ -34,7 +34,7 @@
 #include "gemm_nt.h"
 #include "gemm256_common.h"
 #include "gemm_nt256p_body.h"      // the persistent gemm_nt kernel's body: first phase of the dgrad + wgrad pair kernel below
-#include <vector>
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -583,46 +583,20 @@ float* tn_claim(size_t need, const float* OUT, hipStream_t s, bool* deferred, in
     return *rc == KZV_OK ? tn_partials(need, region) : nullptr;
 }
 
-// stage schedule: 0 = eight-phase ping-pong (gemm_tn256_kernel), 1 = free-running (gemm_tn256f_kernel); kzv_set_tn_schedule / KZV_TN_FREE
-int g_tn_schedule = -1;
-int tn_schedule() {
-    if (g_tn_schedule < 0) g_tn_schedule = kzv_env_int("KZV_TN_FREE", 1) != 0;      // default: free-running (+10..13 % per launch, same-box A/B, bit-identical partial tiles)
-    return g_tn_schedule;
-}
-int tn256_min_tiles() {
-    static int v = -1;
-    // 9: the 768 x 768 outputs (attention output projection, patch embedding) take this kernel too -- 28 token splits each,
-    // 83 -> ~70 us against the 128 x 128 kernel (-0.13 ms per step, same-box A/B; round 2's threshold was 24)
-    if (v < 0) v = kzv_env_int("KZV_TN256_MIN_TILES", 9);
-    return v;
-}
-
 }  // namespace
 
-int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
-    const int tiles = ((p0.N + 255) / 256) * ((p0.K + 255) / 256);
-    const int tok_tiles = p0.Mtok / 64;
-    if (tiles < tn256_min_tiles() || p0.Mtok % 64 || tok_tiles < 2 || p0.N < 8 || p0.K < 8) return 0;
-    if (!tn_dma_offsets_fit(p0)) return 0;
+// TN256F (free-running stages) or TN256 (eight-phase ping-pong) as planned; the workspace is claimed, and pending folds are folded, only here,
+// once the plan has taken the shape
+int kzv_tn256_launch(const TnParams& p0, const KzvTnPlan& pl, hipStream_t s) {
     TnParams p = p0;
-    // one workgroup per CU in total; every split keeps >= 8 reduction stages (and at least 2: the prologue stages two)
-    int cus = kzv_device_cus() - kzv_cu_reserve();
-    { const int g = kzv_env_int("KZV_TN_CUS", 0); if (g > 0 && g < cus) cus = g; }   // dev: two-stream experiment (read at every launch)
-    int splits = cus / tiles;      // leave the reserved CUs to a concurrent collective
-    if (splits > tok_tiles / 8) splits = tok_tiles / 8;
-    if (splits < 1) splits = 1;
-    int chunk_tiles = (tok_tiles + splits - 1) / splits;
-    if (chunk_tiles < 2) chunk_tiles = 2;
-    splits = (tok_tiles + chunk_tiles - 1) / chunk_tiles;
-    if (tok_tiles - (splits - 1) * chunk_tiles < 2) return 0;         // a one-stage last split: leave it to the 128x128 kernel
-    p.splits = splits; p.chunk = chunk_tiles * 64;
-    if (p.K % 4 || p.ldo % 4 || ((uintptr_t)p.OUT & 15)) return 0;
+    p.splits = pl.splits; p.chunk = pl.chunk;
+    const int tiles = pl.tiles, splits = pl.splits;
     const size_t need = (size_t)tiles * splits * PART_FLOATS;
     bool deferred; int rc;
     float* ws = tn_claim(need, p.OUT, s, &deferred, &rc);
     if (!ws) return rc;                          // the pending folds' error, or 0: no workspace, not taken
-    if (tn_schedule()) kzv_launch_lds<gemm_tn256f_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
-    else kzv_launch_lds<gemm_tn256_kernel>(dim3(tiles * splits), dim3(512), LDS_BYTES, s, p, ws);
+    if (pl.kernel == KZV_GEMM_TN256F) kzv_launch_lds<gemm_tn256f_kernel>(dim3(pl.grid), dim3(512), LDS_BYTES, s, p, ws);
+    else kzv_launch_lds<gemm_tn256_kernel>(dim3(pl.grid), dim3(512), LDS_BYTES, s, p, ws);
     if (deferred) {
         g_tn_folds.push(TnFold{ws, p.OUT, p.ldo, p.n_store, p.K, (p.K + 255) / 256, tiles, splits, 0});
         return 1;
@@ -632,104 +606,36 @@ int kzv_tn256_launch(const TnParams& p0, hipStream_t s) {
     return 1;
 }
 
-// gemm.hip: the parameter block of a kzv_gemm_nt call (validated there; kzv_tn_params, its kzv_gemm_tn twin: gemm_tn.h)
-int kzv_nt_params(const kzv_gemm_nt_args* a, int epilogue, NtParams* out);
-
-namespace {
-int g_pair = -1;
-int pair_enabled() {
-    // default OFF: measured on the step's four encoder pairs (tools/dev/r4_pair.py, same-box A/B): -23 us per layer at best (one kernel
-    // boundary per pair), +0.4 % img/s on the whole step -- and NO gain from sizing the token ranges to the gemm_nt tile counts (the
-    // workgroups that leave the gemm_nt phase early then run their weight-gradient stages beside the others' gemm_nt tiles, and the
-    // two loops slow each other as they do on two streams).  DESIGN.md section 8.
-    if (g_pair < 0) g_pair = kzv_env_int("KZV_PAIR", 0) != 0;
-    return g_pair;
-}
-// stages of the weight-gradient loop one gemm_nt tile is worth: (K-tiles x 1.45 us + drain) / 1.55 us per stage; KZV_PAIR_R overrides (x 0.01)
-double pair_ratio(int nk, int epilogue) {
-    static int ov = -2;
-    if (ov == -2) ov = kzv_env_int("KZV_PAIR_R", -1);
-    const double drain = (epilogue == KZV_EPI_DGELU || epilogue == KZV_EPI_RESID) ? 5.0 : 2.5;
-    const double r = 0.6 * (nk * 1.45 + drain) / 1.55;          // 0.6: the best of a sweep over 0 / 0.6 / 1 / 1.4 / 2 (flat between 0 and 0.6)
-    return ov >= 0 ? r * ov * 0.01 / 0.6 : r;
-}
-}  // namespace
-
 // 1 = launched as one kernel; 0 = not taken (the caller issues the two GEMMs separately); < 0 = error
 int kzv_gemm_pair_launch(const kzv_gemm_nt_args* na, int epilogue, const kzv_gemm_tn_args* ta, hipStream_t s) {
-    if (!pair_enabled() || kzv_cu_reserve() != 0 || !tn_schedule() || kzv_device_cus() != 256) return 0;
-    if (epilogue != KZV_EPI_BF16 && epilogue != KZV_EPI_F32 && epilogue != KZV_EPI_DGELU && epilogue != KZV_EPI_RESID) return 0;
-    NtParams pn;
-    if (kzv_nt_params(na, epilogue, &pn) != KZV_OK) return 0;
-    // the conditions of kzv_nt256p_launch ...
-    const int tilesN = (pn.N + 255) / 256, tiles = ((pn.M + 255) / 256) * tilesN;
-    if (pn.K < 128 || pn.K % 128 || tiles < 256) return 0;
-    if (!nt_dma_offsets_fit(pn, 2)) return 0;
-    // ... and of kzv_tn256_launch
-    TnParams pt{};
-    if (kzv_tn_params(ta, pt) != KZV_OK) return 0;
-    const int tilesKw = (pt.K + 255) / 256, tilesNw = (pt.N + 255) / 256, per = tilesNw * tilesKw;
-    const int stages = pt.Mtok / 64;
-    if (per < tn256_min_tiles() || per > 128 || pt.Mtok % 64) return 0;      // (sizes, strides and alignment: kzv_tn_params)
-    if (!tn_dma_offsets_fit(pt)) return 0;
-    const int G = 256, S = G / per;
-    if (S < 1 || stages < 8 * S || stages > 65000) return 0;
-    // ---- the plan ----
+    const KzvGemmSwitches& sw = kzv_gemm_switches();
+    const KzvGemmEnv env = kzv_gemm_env();
+    if (!kzv_pair_enabled(epilogue, sw, env)) return 0;        // (off by default: nothing below runs in the training step)
+    KzvNtShape shn; KzvTnShape sht;
+    NtParams pn; TnParams pt{};
+    if (kzv_nt_validate(na, epilogue, &shn) != KZV_OK || kzv_nt_params(na, shn, &pn) != KZV_OK) return 0;
+    if (kzv_tn_validate(ta, &sht) != KZV_OK || kzv_tn_params(ta, sht, pt) != KZV_OK) return 0;
+    KzvPairPlan pl;
+    if (!kzv_pair_plan(shn, sht, sw, env, &pl)) return 0;
     PairPlan plan;
-    int cb[256], idb[256];
-    const int nwg = per * S;
-    for (int b = 0; b < G; ++b) {
-        const int vblk = (b & 7) * (G >> 3) + (b >> 3);
-        cb[b] = vblk < tiles ? (tiles - 1 - vblk) / G + 1 : 0;
-        idb[b] = -1;
-        plan.tile[b] = plan.split[b] = plan.t0[b] = plan.cnt[b] = 0;
-        if (b < nwg) {
-            const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;                      // kzv_common.h xcd_remap
-            idb[b] = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-        }
-    }
-    const double r = pair_ratio(pn.K / 64, epilogue);
-    std::vector<int> cg((size_t)tilesNw * S, 0);                                    // gemm_nt tiles of the group (tile row, split): the largest of its members
-    for (int b = 0; b < nwg; ++b) { const int sp = idb[b] / per, tl = idb[b] % per; int& c = cg[(size_t)(tl / tilesKw) * S + sp]; c = cb[b] > c ? cb[b] : c; }
-    std::vector<int> t0((size_t)tilesNw * S), cnt((size_t)tilesNw * S);
-    for (int tn = 0; tn < tilesNw; ++tn) {
-        double csum = 0;
-        for (int sp = 0; sp < S; ++sp) csum += cg[(size_t)tn * S + sp];
-        const double level = (stages + r * csum) / S;                               // the common finishing time, in stages
-        double acc = 0; int prev = 0;
-        for (int sp = 0; sp < S; ++sp) {
-            double n = level - r * cg[(size_t)tn * S + sp];
-            if (n < 2) n = 2;
-            acc += n;
-            int end = sp == S - 1 ? stages : (int)(acc + 0.5);
-            const int left = S - 1 - sp;                                             // every later split keeps >= 2 stages
-            if (end > stages - 2 * left) end = stages - 2 * left;
-            if (end < prev + 2) end = prev + 2;
-            t0[(size_t)tn * S + sp] = prev; cnt[(size_t)tn * S + sp] = end - prev; prev = end;
-        }
-        if (prev != stages) return 0;
-    }
-    for (int b = 0; b < nwg; ++b) {
-        const int sp = idb[b] / per, tl = idb[b] % per; const size_t gi = (size_t)(tl / tilesKw) * S + sp;
-        plan.tile[b] = (unsigned short)tl; plan.split[b] = (unsigned short)sp; plan.t0[b] = (unsigned short)t0[gi]; plan.cnt[b] = (unsigned short)cnt[gi];
-    }
+    static_assert(sizeof(PairPlan) == sizeof(KzvPairTable), "the kernel argument is the planner's table");
+    std::memcpy(&plan, &pl.table, sizeof(plan));
+    const int per = pl.per, S = pl.splits;
     pt.splits = S; pt.chunk = 0;
     bool deferred; int rc;
     float* ws = tn_claim((size_t)per * S * PART_FLOATS, pt.OUT, s, &deferred, &rc);
     if (!ws) return rc;                          // the pending folds' error, or 0: no workspace, not taken
     KzvProfScope prof(5, 2.0 * pn.M * pn.n_valid * pn.K + 2.0 * pt.Mtok * pt.N * pt.K, s);
-#define KZV_PAIR_CASE(E) case E: kzv_launch_lds<gemm_pair_kernel<E>>(dim3(G), dim3(512), NT256P_LDS_BYTES, s, pn, tiles, tilesN, kzv_nt_strip(), pt, ws, per, plan); break;
+#define KZV_PAIR_CASE(E) case E: kzv_launch_lds<gemm_pair_kernel<E>>(dim3(pl.grid), dim3(512), NT256P_LDS_BYTES, s, pn, pl.tiles, pl.tilesN, pl.strip, pt, ws, per, plan); break;
     switch (epilogue) {
         KZV_PAIR_CASE(KZV_EPI_BF16) KZV_PAIR_CASE(KZV_EPI_F32) KZV_PAIR_CASE(KZV_EPI_DGELU) KZV_PAIR_CASE(KZV_EPI_RESID)
-        default: return 0;
     }
 #undef KZV_PAIR_CASE
-    if (deferred) g_tn_folds.push(TnFold{ws, pt.OUT, pt.ldo, pt.n_store, pt.K, tilesKw, per, S, 0});
-    else hipLaunchKernelGGL(gemm_tn256_fold_kernel, dim3(per * 64), dim3(256), 0, s, ws, pt.OUT, pt.ldo, pt.n_store, pt.K, tilesKw, per, S);
+    if (deferred) g_tn_folds.push(TnFold{ws, pt.OUT, pt.ldo, pt.n_store, pt.K, pl.tilesKw, per, S, 0});
+    else hipLaunchKernelGGL(gemm_tn256_fold_kernel, dim3(per * 64), dim3(256), 0, s, ws, pt.OUT, pt.ldo, pt.n_store, pt.K, pl.tilesKw, per, S);
     return kzv_check_launch("gemm_pair") == KZV_OK ? 1 : -1;
 }
 
-extern "C" int kzv_set_pair(int n) { g_pair = n < 0 ? -1 : (n != 0); return KZV_OK; }
 extern "C" int kzv_gemm_dgrad_wgrad(const kzv_gemm_nt_args* na, int epilogue, const kzv_gemm_tn_args* ta, void* stream) {
     if (!na || !ta) return kzv_fail(KZV_E_ARG, "gemm_dgrad_wgrad: null");
     const int rc = kzv_gemm_pair_launch(na, epilogue, ta, (hipStream_t)stream);
@@ -738,7 +644,6 @@ extern "C" int kzv_gemm_dgrad_wgrad(const kzv_gemm_nt_args* na, int epilogue, co
     const int r2 = kzv_gemm_tn(ta, stream);
     return r2 != KZV_OK ? r2 : kzv_gemm_nt(na, epilogue, stream);
 }
-extern "C" int kzv_set_tn_schedule(int n) { g_tn_schedule = n < 0 ? -1 : (n != 0); return KZV_OK; }
 
 KzvTnFoldScope::KzvTnFoldScope(hipStream_t stream) : s(stream) { g_tn_folds.open(); }
 int KzvTnFoldScope::close() { if (closed) return KZV_OK; closed = true; return g_tn_folds.close(s); }

@@ -132,6 +132,11 @@ class kzv_gemm_tn_args(C.Structure):
                 ("dbias", C.c_void_p)]
 
 
+class kzv_gemm_plan_info(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("grid", C.c_int32), ("grid_y", C.c_int32), ("block", C.c_int32), ("tiles", C.c_int32),
+                ("splits", C.c_int32), ("chunk", C.c_int32), ("pair", C.c_int32)]
+
+
 class kzv_attn_args(C.Structure):
     _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("LSE", C.c_void_p),
                 ("dO", C.c_void_p), ("dQ", C.c_void_p), ("dK", C.c_void_p), ("dV", C.c_void_p),
@@ -168,6 +173,8 @@ class kzv_cast_desc(C.Structure):
 
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU = range(5)
+(GEMM_ROWS, GEMM_NT256H, GEMM_NT256F, GEMM_NT256P, GEMM_NT256, GEMM_NT128, GEMM_NT256P_F8,
+ GEMM_TN256F, GEMM_TN256, GEMM_TN128) = range(10)      # kzv_gemm_nt_plan / kzv_gemm_tn_plan: kzv_gemm_plan_info.kernel
 ATTN_MFMA64, ATTN_MFMA96, ATTN_VALU = 1, 2, 3          # kzv_attn_impl
 ATTN_STREAM64, ATTN_STREAM96 = 4, 5                    # kzv_attn_impl_ex with MODEL_LONG_SEQ
 ATTN_IMPL_NAMES = {ATTN_MFMA64: "mfma64", ATTN_MFMA96: "mfma96", ATTN_VALU: "valu", ATTN_STREAM64: "stream64", ATTN_STREAM96: "stream96"}
@@ -267,6 +274,8 @@ SYMBOLS = {
     # ---- ocr_lightning/model.py path (csrc/ocr.hip)
     "kzv_gemm_dgrad_wgrad": (C.c_int, [C.POINTER(kzv_gemm_nt_args), C.c_int, C.POINTER(kzv_gemm_tn_args), _P]),
     "kzv_set_pair": (C.c_int, [C.c_int]),
+    "kzv_gemm_nt_plan": (C.c_int, [C.POINTER(kzv_gemm_nt_args), C.c_int, C.c_int, C.c_int, C.POINTER(kzv_gemm_plan_info)]),
+    "kzv_gemm_tn_plan": (C.c_int, [C.POINTER(kzv_gemm_tn_args), C.c_int, C.POINTER(kzv_gemm_plan_info)]),
     "kzv_gemm_nt_f32": (C.c_int, [C.POINTER(kzv_gemm_nt_args), C.c_int, _P]),
     "kzv_gemm_tn_f32": (C.c_int, [C.POINTER(kzv_gemm_tn_args), _P]),
     "kzv_ocr_set_precision": (C.c_int, [C.c_int]),

@@ -33,6 +33,21 @@ def _gemm_nt(lib, A, B, epi, bias=None, n_store=None, resid=None, aux=None, drop
     return out
 
 
+def _nt_kernel(lib, M, N, K, nv, epi):
+    """the kernel kzv_gemm_nt runs this call on (kzv_gemm_nt_plan: the launching entry's own planner; the operands are never read)"""
+    a = L.kzv_gemm_nt_args(A=256, lda=K, B=256, ldb=K, C=256, ldc=N, bias=None, resid=256, ldr=N, aux=256, ldaux=N, M=M, N=N, K=K, n_valid=nv, drop_p=0.0, drop_key=0)
+    info = L.kzv_gemm_plan_info()
+    L.check(lib.kzv_gemm_nt_plan(C.byref(a), epi, 0, 0, C.byref(info)), "gemm_nt_plan")
+    return info
+
+
+def _tn_kernel(lib, Mt, N, K):
+    a = L.kzv_gemm_tn_args(P=256, ldp=N, Q=256, ldq=K, OUT=256, ldo=K, Mtok=Mt, N=N, K=K, n_store=N, dbias=None)
+    info = L.kzv_gemm_plan_info()
+    L.check(lib.kzv_gemm_tn_plan(C.byref(a), 0, C.byref(info)), "gemm_tn_plan")
+    return info
+
+
 @pytest.fixture(params=["rows", "tiled"])
 def small_gemm_kernel(request, lib):
     """threshold 1024: the few-rows kernel of the generation step (gemm_rows.hip); threshold 0 (the default): the same
@@ -78,6 +93,11 @@ def test_gemm_nt_large_shapes_take_the_256x256_kernel(lib, M, N, K, nv):
     """>= 384 tiles of 256x256 -> the eight-phase kernels (persistent gemm_nt256p.hip for an even K-tile count and
     one-store epilogues, else gemm_nt256.hip): ragged M, odd and minimal K-tile counts, n_valid < N (clamped B rows,
     zeroed columns), all epilogue families."""
+    # the docstring's rule, asked of the planner that launches (tests/test_configs_gpu.py runs this test with a CU reserve too: no persistent kernel then)
+    persistent = K % 128 == 0 and lib.kzv_get_cu_reserve() == 0
+    for epi in (L.EPI_F32, L.EPI_BF16, L.EPI_RESID):
+        assert _nt_kernel(lib, M, N, K, nv, epi).kernel == (L.GEMM_NT256P if persistent else L.GEMM_NT256)
+    assert _nt_kernel(lib, M, N, K, nv, L.EPI_GELU).kernel == L.GEMM_NT256
     torch.manual_seed(K)
     A = torch.randn(M, K, device=DEV).bfloat16()
     B = (torch.randn(nv, K, device=DEV) * 0.1).bfloat16()
@@ -121,8 +141,10 @@ def test_gemm_nt_free_running_schedule_is_bit_identical_to_the_ping_pong(lib, M,
     kw = dict(bias=None if epi == "dgelu" else bias, n_store=N, resid=res, aux=aux, drop_p=0.1 if epi == "resid" else 0.0, key=11)
     try:
         L.check(lib.kzv_set_nt_schedule(0), "set_nt_schedule")
+        assert _nt_kernel(lib, M, N, K, nv, code).kernel == L.GEMM_NT256P
         ref = _gemm_nt(lib, A, B, code, **kw)
         L.check(lib.kzv_set_nt_schedule(1), "set_nt_schedule")
+        assert _nt_kernel(lib, M, N, K, nv, code).kernel == L.GEMM_NT256F
         for _ in range(6):
             assert torch.equal(_gemm_nt(lib, A, B, code, **kw), ref)
     finally:
@@ -146,9 +168,11 @@ def test_gemm_nt_four_wave_kernel_is_bit_identical_to_the_256x256_kernels(lib, M
     kw = dict(bias=None if epi == "dgelu" else bias, n_store=N, resid=res, aux=aux, drop_p=0.1 if epi == "resid" else 0.0, key=11)
     try:
         L.check(lib.kzv_set_nt_schedule(0), "set_nt_schedule")
+        assert _nt_kernel(lib, M, N, K, nv, code).kernel == (L.GEMM_NT256 if epi == "gelu" else L.GEMM_NT256P)
         ref = _gemm_nt(lib, A, B, code, **kw)
         ref_aux = aux.clone() if epi == "gelu" else None
         L.check(lib.kzv_set_nt_schedule(2), "set_nt_schedule")
+        assert _nt_kernel(lib, M, N, K, nv, code).kernel == L.GEMM_NT256H
         for _ in range(6):
             if epi == "gelu":
                 aux.zero_()
@@ -208,6 +232,7 @@ def test_gemm_tn(lib, Mt, N, K):
 def test_gemm_tn_large_outputs_take_the_256x256_kernel(lib, Mt, N, K):
     """>= 9 output tiles of 256x256 and Mtok % 64 == 0 -> gemm_tn256.hip (eight-phase schedule, token splits, atomics
     epilogue, VALU bias sums); ragged N / K (clamped columns, guarded stores) in the last case; accumulates INTO out."""
+    assert _tn_kernel(lib, Mt, N, K).kernel == L.GEMM_TN256F
     torch.manual_seed(Mt + N)
     Pm = torch.randn(Mt, N, device=DEV).bfloat16()
     Q = torch.randn(Mt, K, device=DEV).bfloat16()
@@ -254,6 +279,9 @@ def test_dgrad_wgrad_pair_launch_equals_the_two_launches(lib, Nout, Kin, epi):
                                 aux=L.ptr(aux), ldaux=Kin, M=M, N=Kin, K=Nout, n_valid=Kin, drop_p=0.0, drop_key=0)
         ta = L.kzv_gemm_tn_args(P=dY.data_ptr(), ldp=Nout, Q=X.data_ptr(), ldq=Kin, OUT=dW.data_ptr(), ldo=Kin, Mtok=M, N=Nout, K=Kin, n_store=Nout, dbias=db.data_ptr())
         L.check(lib.kzv_set_pair(pair), "set_pair")
+        half_nt, half_tn = _nt_kernel(lib, M, Kin, Nout, Kin, code), _tn_kernel(lib, M, Nout, Kin)
+        assert (half_nt.kernel, half_tn.kernel) == (L.GEMM_NT256P, L.GEMM_TN256F)      # what the two launches run on ...
+        assert (half_nt.pair, half_tn.pair) == (pair, pair)                             # ... and both halves accept the one-launch form when it is on
         dX.zero_()
         L.check(lib.kzv_gemm_dgrad_wgrad(C.byref(na), code, C.byref(ta), _st()), "dgrad_wgrad")
         torch.cuda.synchronize()
